@@ -14,9 +14,11 @@ Workload (BASELINE.json configs[1]): 1920x1080, 64 spp, full spectral Rayleigh+M
 (21600x10800 / 16200x8100, synthetic stand-ins: the reference ships no maps), default camera and sun.
 
 `--config cfg2|cfg3|cfg4|cfg5` runs any BASELINE config by name (size, sample count, the reference's camera preset, cloud-heavy maps, progressive interval;
-the line's `metric` names it).  The default 1-GPU run adds, after the timed region: `other_configs` (cfg3 / cfg4 / cfg5 for two steps each, the frame at the
-config's full sample count checked against the oracle on sparse tiles), `cpu_baseline` (the oracle on a bounded sample, all host threads) and `parity` (the
-full-size frame against the oracle's at matched seed).  One-GPU experiments for the N-rank path: `--simulate-world N` (rank 0's share, no collective),
+the line's `metric` names it).  A plain run sets up, warms up, times --steps frames and prints the line (`--dump-outputs DIR`: the last timed frame as .npy
+files first).  `--full` adds everything else, after the timed region: the single-frame, roofline and VALU figures (untimed frames of their own), with N > 1
+the other launch setting (`alt`), the parity check of the assembled frame and the in-library communicator's frame, and on the default 1-GPU run
+`other_configs` (cfg3 / cfg4 / cfg5 for two steps each, the frame at the config's full sample count checked against the oracle on sparse tiles),
+`cpu_baseline` (the oracle on a bounded sample, all host threads) and `parity` (the full-size frame against the oracle's at matched seed).  One-GPU experiments for the N-rank path: `--simulate-world N` (rank 0's share, no collective),
 `--standin-collective COPIES` (a stand-in for the frame's collective where the reduce goes), `--cu-withhold n` (CUs per XCD left to the small kernels).
 """
 import argparse
@@ -46,6 +48,8 @@ CONFIGS = {
 }
 # sparse-tile oracle check of a config at its FULL sample count: every `stride`-th 8x8 tile in raster order (spread over the whole frame), ~0.5 M paths on the host
 SPARSE_CHECK = {"cfg2": (5, 251), "cfg3": (11, 997), "cfg4": (23, 2003), "cfg5": (41, 4051)}
+# --dump-outputs writes at most this many bytes: cfg2's two whole frames (49.8 MB) fit, larger frames are sampled
+DUMP_LIMIT_BYTES = 64 * 10**6
 
 
 def metric_name(width, height, spp, preset, cloud_heavy, progressive):
@@ -105,6 +109,12 @@ def parse():
                          "+ COPIES device-to-device copies of it (7 = the ingress of an 8-rank gather) — and report its queue-to-finish latency (`standin_collective`)")
     ap.add_argument("--cu-withhold", type=int, default=0, help="CUs per XCD withheld from the render launches' streams (de_tuning.v6_cu_withhold)")
     ap.add_argument("--dump-hdr", default=None, help="rank 0: save the assembled HDR frame of the LAST step as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0, after the timed steps: what the last step handed its caller, as DIR/hdr.npy (the assembled HDR frame) and DIR/image.npy "
+                         "(its display transform), float32 (W, H, 3); above %d MB in all, the same fixed seeded sample of pixels of both, (n, 3)" % (DUMP_LIMIT_BYTES // 10**6))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline figure (module docstring); without it the run only sets up, warms up, "
+                         "times --steps frames and prints the line")
     ap.add_argument("--check-spp", type=int, default=2, help="N > 1: spp of the untimed parity check of the assembled frame against a 1-rank render on rank 0 (0 = skip)")
     args = ap.parse_args()
     args.crf_name = None
@@ -213,6 +223,21 @@ def sparse_oracle_check(name, rk, maps, seed):
     lit = float((c[mask] != 0).any(axis=-1).mean())
     del o
     return {"bit_identical_vs_oracle_on_sparse_tiles": same, "sparse_tiles": "every %dth 8x8 tile in raster order (from tile %d), %d pixels x %d spp, %.0f %% of them lit, oracle %.1f s" % (stride, first, int(mask.sum()), rk.current_spp, 100.0 * lit, dt)}
+
+
+def write_outputs(path, frame):
+    """--dump-outputs: the assembled HDR frame and its display image as the step left them (fetch_image re-runs the display transform, which is
+    deterministic, on the same accumulation).  Above DUMP_LIMIT_BYTES a fixed seeded sample of pixels, the same for both arrays and every run."""
+    import numpy as np
+    arrays = {"hdr": frame.fetch_hdr(), "image": frame.r.fetch_image()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n_pix = arrays["hdr"].shape[0] * arrays["hdr"].shape[1]
+        idx = np.sort(np.random.default_rng(0).choice(n_pix, n_pix * DUMP_LIMIT_BYTES // total, replace=False))
+        arrays = {k: a.reshape(n_pix, 3)[idx] for k, a in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a.astype(np.float32, copy=False))
 
 
 def run_other_config(name, r_main, maps, device_index, steps=2):
@@ -384,7 +409,7 @@ def main():
     # the CPU-baseline leg (after the timed region) needs the maps as uploaded: take them to the host now, then release the
     # 2.1 GB of as-uploaded device copies — the kernels read the packed copies only
     maps = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         maps = [r.download_texture(s) for s in range(7)]
     r.trim_textures()
 
@@ -395,15 +420,16 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # algorithmic work per sample, measured by the kernel's own counters on this camera/seed (untimed)
-    r.enable_counters(True)
-    r.reset_framebuffer()
-    r.accumulate(2)
-    r.synchronize()
-    cnt = r.counters()
-    r.enable_counters(False)
-    n_r8 = cnt["taps_r8"] / max(cnt["samples"], 1)
-    n_rgb = cnt["taps_rgb8"] / max(cnt["samples"], 1)
+    if args.full:
+        # algorithmic work per sample, measured by the kernel's own counters on this camera/seed (untimed)
+        r.enable_counters(True)
+        r.reset_framebuffer()
+        r.accumulate(2)
+        r.synchronize()
+        cnt = r.counters()
+        r.enable_counters(False)
+        n_r8 = cnt["taps_r8"] / max(cnt["samples"], 1)
+        n_rgb = cnt["taps_rgb8"] / max(cnt["samples"], 1)
 
     # every context in flight allocates its per-sample buffer at its first full-size launch: prime them all (untimed), whatever
     # --warmup says, so that no allocation can fall into the timed region
@@ -442,6 +468,48 @@ def main():
     last = frames[(args.steps - 1) % len(frames)]
     if args.dump_hdr and rank == 0:
         np.save(args.dump_hdr, last.r.fetch_hdr())
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, last)
+    if world > 1:
+        # the line's rate is the slowest rank's
+        dev_t = torch.device("cuda", device_index) if backend == "nccl" else torch.device("cpu")
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev_t)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    total_samples = W * H * spp * args.steps
+    value = total_samples / elapsed / 1e6
+    ms_per_step = elapsed / args.steps * 1e3
+    out = {
+        "metric": "Msamples/sec (1920x1080, 64 spp) spectral path tracing" if args.config_name == "cfg2" else metric_name(W, H, spp, args.preset, args.cloud_heavy, args.progressive), "value": value, "unit": "Msamples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "ranks_seen": ranks_seen, "devices_seen": devices_seen,
+        "config": {"workload": "%dx%d, %d spp, full spectral Rayleigh+Mie+O3+clouds, quality-%d synthetic maps%s, %s, "
+                               "%s" % (W, H, spp, args.tex_quality, " (%dx%d)" % tuple(args.tex_size) if args.tex_size else "",
+                                                         (args.preset or "default camera") + (" + film curve %s" % args.crf_name if args.crf_name else "") + (", cloud-heavy maps" if args.cloud_heavy else ""),
+                                                         "ray_marcher integrator (not the BASELINE metric)" if args.integrator != "path_tracer" else
+                                                         ("BASELINE configs[%d]" % CONFIGS[args.config_name]["index"] if args.config_name else "not a BASELINE config")),
+                   "parallelism": ((("tile-partition x%d + %s reduce (%s)" if args.collective == "reduce" else "tile-partition x%d + %s gather of the owned pixels (%s)") if args.split == "tiles" else "sample-partition x%d + %s rank-ordered gather-sum (%s)") % (world, "RCCL" if backend == "nccl" else backend, args.reduce)) if world > 1
+                                  else ("single GPU" if args.simulate_world <= 1 else "single GPU rendering rank 0's share of a %s partition x%d (no collective)" % (args.split, args.simulate_world)),
+                   "frames_in_flight": len(frames), "launch_slots": 1 if serial else 3,
+                   "waves_per_cu": 24 if timed_info["variant"] == 6 else wpc,      # render_kernel_v6: two workgroups of 12 waves per CU (80 VGPRs); the wave budget knob belongs to the state machine
+                   "primed_frames": n_prime,
+                   "kernel": timed_info["kernel"], "launches_per_call": timed_info["launches"],
+                   "progressive_every": args.progressive if args.progressive > 0 else None,
+                   "samples_per_step": W * H * spp},
+    }
+    if args.cu_withhold > 0:
+        out["config"]["cu_withhold_per_xcd"] = args.cu_withhold
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            for f in frames:
+                f.close()
+            dist.destroy_process_group()
+        return
 
     # untimed: one frame at a time (latency of a single frame), with the HIP-event duration of its render launch
     per_launch, per_frame, per_reduce, per_drain = [], [], [], []
@@ -513,10 +581,6 @@ def main():
             except Exception as exc:          # noqa: BLE001 - reported, not swallowed
                 multi = {"spp": args.check_spp, "error": "%s: %s" % (type(exc).__name__, exc)}
 
-    total_samples = W * H * spp * args.steps
-    value = total_samples / elapsed / 1e6
-    ms_per_step = elapsed / args.steps * 1e3
-
     # roofline of the dominant kernel: algorithmic bytes per launch / measured launch duration.
     # B_sample = 8 B contribution record + 4 B per r8 tap + 16 B per colour tap (render_kernel_v2 writes one
     # 8-byte (radiance, wavelength node) record per sample, the HDR read-modify-write of 24 B per pixel per launch happens
@@ -563,26 +627,9 @@ def main():
             pass
 
     steps_per_sample = (cnt["sphere_steps"] + cnt["tracking_steps"]) / max(cnt["samples"], 1)
-    out = {
-        "metric": "Msamples/sec (1920x1080, 64 spp) spectral path tracing" if args.config_name == "cfg2" else metric_name(W, H, spp, args.preset, args.cloud_heavy, args.progressive), "value": value, "unit": "Msamples/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "ranks_seen": ranks_seen, "devices_seen": devices_seen,
+    out.update({
         "single_frame_ms": single_frame_ms, "single_frame_value": W * H * spp / (single_frame_ms * 1e-3) / 1e6,
         "drain_ms": my_drain_ms,
-        "config": {"workload": "%dx%d, %d spp, full spectral Rayleigh+Mie+O3+clouds, quality-%d synthetic maps%s, %s, "
-                               "%s" % (W, H, spp, args.tex_quality, " (%dx%d)" % tuple(args.tex_size) if args.tex_size else "",
-                                                         (args.preset or "default camera") + (" + film curve %s" % args.crf_name if args.crf_name else "") + (", cloud-heavy maps" if args.cloud_heavy else ""),
-                                                         "ray_marcher integrator (not the BASELINE metric)" if args.integrator != "path_tracer" else
-                                                         ("BASELINE configs[%d]" % CONFIGS[args.config_name]["index"] if args.config_name else "not a BASELINE config")),
-                   "parallelism": ((("tile-partition x%d + %s reduce (%s)" if args.collective == "reduce" else "tile-partition x%d + %s gather of the owned pixels (%s)") if args.split == "tiles" else "sample-partition x%d + %s rank-ordered gather-sum (%s)") % (world, "RCCL" if backend == "nccl" else backend, args.reduce)) if world > 1
-                                  else ("single GPU" if args.simulate_world <= 1 else "single GPU rendering rank 0's share of a %s partition x%d (no collective)" % (args.split, args.simulate_world)),
-                   "frames_in_flight": len(frames), "launch_slots": 1 if serial else 3,
-                   "waves_per_cu": 24 if timed_info["variant"] == 6 else wpc,      # render_kernel_v6: two workgroups of 12 waves per CU (80 VGPRs); the wave budget knob belongs to the state machine
-                   "primed_frames": n_prime,
-                   "kernel": timed_info["kernel"], "launches_per_call": timed_info["launches"],
-                   "progressive_every": args.progressive if args.progressive > 0 else None,
-                   "samples_per_step": W * H * spp},
         # `bound` names the roof that BINDS this kernel (VALU issue: `valu.issue` below); achieved / peak / unit / frac keep SURVEY §8(d)'s definition —
         # algorithmic bytes over the launch's duration against the HBM peak — and `hbm_frac` repeats that fraction under its own name
         "roofline": {"bound": "valu_issue", "achieved": achieved_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -600,13 +647,11 @@ def main():
                  "sphere_steps_per_sample": cnt["sphere_steps"] / max(cnt["samples"], 1),
                  "tracking_steps_per_sample": cnt["tracking_steps"] / max(cnt["samples"], 1),
                  "vertices_per_sample": cnt["vertices"] / max(cnt["samples"], 1)},
-    }
+    })
     if args.standin_collective >= 0 and world == 1:
         out["standin_collective"] = {"extra_copies": args.standin_collective, "queue_to_finish_ms_mean_of_last_16": r.last_reduce_ms(),
                                      "bytes": (3 + 2 * args.standin_collective) * W * H * 12,
                                      "note": "one-GPU stand-in for an N-rank run's per-frame collective, enqueued on the context stream where the reduce goes (include/digital_earth_debug.h)"}
-    if args.cu_withhold > 0:
-        out["config"]["cu_withhold_per_xcd"] = args.cu_withhold
     if multi is not None:
         out["multi_gpu_parity"] = multi
     if world > 1:

@@ -14,8 +14,9 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# --full: the assertions below read what only the full line holds (per_rank, alt, multi_gpu_parity, lib_reduce, roofline)
 COMMON = ["--steps", "2", "--warmup", "1", "--width", "256", "--height", "128", "--spp", "3", "--tex-size", "1024", "512",
-          "--no-cpu-baseline"]
+          "--no-cpu-baseline", "--full"]
 
 
 def _run(cmd, env_extra=None, timeout=900):
@@ -68,6 +69,26 @@ def test_ranks_on_one_gpu_match_one_rank(tmp_path, world):
     assert all(pr["kernel"] == "per-CU stage scheduler" for pr in j2["per_rank"])
     assert j2["alt"]["serial_frames"] is True and j2["alt"]["value"] > 0
     assert j1["config"]["waves_per_cu"] == 24 and "alt" not in j1
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line holds the headline figure and what ran, nothing measured outside the timed steps; --dump-outputs writes the last
+    timed frame (the HDR accumulation the caller reads and its display image), and the HDR equals --dump-hdr's bit for bit."""
+    out_dir, hdr = tmp_path / "outputs", str(tmp_path / "hdr.npy")
+    plain = [a for a in COMMON if a != "--full"]
+    p = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(out_dir), "--dump-hdr", hdr] + plain)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = _json_line(p.stdout)
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "Msamples/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+    assert abs(j["value"] - 256 * 128 * 3 / (j["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * j["value"]
+    assert not {"single_frame_ms", "roofline", "valu", "cpu_baseline", "parity", "other_configs"} & set(j)
+    assert sorted(os.listdir(out_dir)) == ["hdr.npy", "image.npy"]
+    h, img = np.load(out_dir / "hdr.npy"), np.load(out_dir / "image.npy")
+    assert h.dtype == img.dtype == np.float32 and h.shape == img.shape == (256, 128, 3)
+    assert (h.view(np.uint32) == np.load(hdr).view(np.uint32)).all() and h.max() > 0
+    assert np.isfinite(img).all() and img.min() >= 0.0 and img.max() <= 1.0 and img.max() > 0
 
 
 def test_tile_ownership_is_balanced_at_eight_ranks():

@@ -133,3 +133,35 @@ def test_bench_names_the_baseline_configs():
         # spread over the frame: tiles in every quarter of the image
         w2, h2 = c["width"] // 2, c["height"] // 2
         assert all(q.any() for q in (mask[:w2, :h2], mask[w2:, :h2], mask[:w2, h2:], mask[w2:, h2:])), name
+
+
+def test_bench_dump_outputs_are_bounded_and_reproducible(tmp_path):
+    """`bench.py --dump-outputs DIR` (plain runs are lean: `--full` is off by default): whole frames where they fit, above the limit the same
+    seeded sample of pixels from run to run and from array to array, float32, never more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    bench, a = _bench_args(["--dump-outputs", str(tmp_path)])
+    assert a.dump_outputs == str(tmp_path) and a.full is False and _bench_args(["--full"])[1].full is True
+
+    class Frame:
+        def __init__(self, w, h):
+            self.hdr = np.random.default_rng(1).random((w, h, 3), dtype=np.float32)
+            self.r = self
+
+        def fetch_hdr(self):
+            return self.hdr
+
+        def fetch_image(self):
+            return self.hdr / 2
+
+    def dumped(frame, d):
+        bench.write_outputs(str(d), frame)
+        return {k: np.load(d / (k + ".npy")) for k in ("hdr", "image")}
+
+    whole = dumped(Frame(1920, 1080), tmp_path / "cfg2")                  # 49.8 MB: written whole
+    assert whole["hdr"].shape == (1920, 1080, 3) and (whole["image"] == whole["hdr"] / 2).all()
+    big = Frame(3840, 2160)                                                 # cfg4: 199 MB, sampled
+    one, two = dumped(big, tmp_path / "a"), dumped(big, tmp_path / "b")
+    assert one["hdr"].dtype == np.float32 and one["hdr"].ndim == 2 and one["hdr"].shape[1] == 3
+    assert sum(x.nbytes for x in one.values()) <= bench.DUMP_LIMIT_BYTES
+    assert one["hdr"].shape[0] > 0.9 * bench.DUMP_LIMIT_BYTES / 24
+    assert all((one[k] == two[k]).all() for k in one) and (one["image"] == one["hdr"] / 2).all()

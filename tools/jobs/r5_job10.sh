@@ -6,15 +6,15 @@ SUN="config - sunset hurricane.txt"
 ms() { python3 -c "import json,sys; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%.2f ms/step  single %.2f  kernel %.2f' % (j['ms_per_step'], j['single_frame_ms'], j['roofline']['kernel_ms']))"; }
 timeout 1200 python3 -m pytest tests/test_gpu_block_scheduler.py tests/test_gpu_round5.py -x -q -m gpu > $OUT/pytest_quick.txt 2>&1
 for b in 8 1 8 1; do
-  echo -n "bands $b cfg2: " >> $OUT/ab.txt; DE_V6_BANDS=$b python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "bands $b cfg2: " >> $OUT/ab.txt; DE_V6_BANDS=$b python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
 done
 for cam in "$SUN" "config - florida.txt" "config - Apollo 11.txt"; do
   for b in 8 1; do
-    echo -n "bands $b $cam: " >> $OUT/ab.txt; DE_V6_BANDS=$b python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
+    echo -n "bands $b $cam: " >> $OUT/ab.txt; DE_V6_BANDS=$b python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
   done
 done
 for b in 8 1; do
-  echo -n "bands $b cfg2 1/8 share: " >> $OUT/ab.txt; DE_V6_BANDS=$b python3 bench.py --no-cpu-baseline --steps 12 --warmup 3 --simulate-world 8 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "bands $b cfg2 1/8 share: " >> $OUT/ab.txt; DE_V6_BANDS=$b python3 bench.py --full --no-cpu-baseline --steps 12 --warmup 3 --simulate-world 8 2>/dev/null | ms >> $OUT/ab.txt
 done
 export TMPDIR=/tmp; cd /tmp
 for b in 8 1; do

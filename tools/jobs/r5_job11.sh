@@ -6,8 +6,8 @@ SUN="config - sunset hurricane.txt"
 ms() { python3 -c "import json,sys; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%.2f ms/step  single %.2f  kernel %.2f' % (j['ms_per_step'], j['single_frame_ms'], j['roofline']['kernel_ms']))"; }
 both() {  # label, env...
   label=$1; shift
-  echo -n "$label cfg2: " >> $OUT/sweep.txt; env "$@" python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | ms >> $OUT/sweep.txt
-  echo -n "$label sunset: " >> $OUT/sweep.txt; env "$@" python3 bench.py --no-cpu-baseline --steps 5 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/sweep.txt
+  echo -n "$label cfg2: " >> $OUT/sweep.txt; env "$@" python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 2>/dev/null | ms >> $OUT/sweep.txt
+  echo -n "$label sunset: " >> $OUT/sweep.txt; env "$@" python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/sweep.txt
 }
 both "default" DE_X=0
 both "gas table" DE_LIB_PATH=$PWD/build/ab/gas_table.so

@@ -9,19 +9,19 @@ tail -3 $OUT/pytest_st2.txt
 DE_V6_ST2=1 python3 tools/v6_try.py > $OUT/try_st2.txt 2>&1
 for rep in 1 2; do
   for v in 0 1; do
-    echo -n "st2=$v cfg2: " >> $OUT/ab.txt; DE_V6_ST2=$v python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+    echo -n "st2=$v cfg2: " >> $OUT/ab.txt; DE_V6_ST2=$v python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
   done
 done
 for cam in "$SUN" "config - florida.txt" "config - Apollo 11.txt"; do
   for v in 0 1; do
-    echo -n "st2=$v $cam: " >> $OUT/ab.txt; DE_V6_ST2=$v python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
+    echo -n "st2=$v $cam: " >> $OUT/ab.txt; DE_V6_ST2=$v python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
   done
 done
 for v in 0 1; do
-  echo -n "st2=$v cfg2 1/8 share: " >> $OUT/ab.txt; DE_V6_ST2=$v python3 bench.py --no-cpu-baseline --steps 12 --warmup 3 --simulate-world 8 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "st2=$v cfg2 1/8 share: " >> $OUT/ab.txt; DE_V6_ST2=$v python3 bench.py --full --no-cpu-baseline --steps 12 --warmup 3 --simulate-world 8 2>/dev/null | ms >> $OUT/ab.txt
 done
 for a in 60 100 150; do
-  echo -n "st2=1 area_st $a cfg2: " >> $OUT/ab.txt; DE_V6_ST2=1 DE_V6_AREA_ST=$a python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "st2=1 area_st $a cfg2: " >> $OUT/ab.txt; DE_V6_ST2=1 DE_V6_AREA_ST=$a python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
 done
 DE_V6_ST2=1 python3 tools/v6_lanes.py --out $OUT/lanes_cfg2_st2.md > /dev/null 2> $OUT/lanes.err
 cat $OUT/ab.txt

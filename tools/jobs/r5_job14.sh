@@ -8,12 +8,12 @@ timeout 900 python3 -m pytest tests/test_gpu_block_scheduler.py tests/test_gpu_r
 grep -E "passed|failed" $OUT/pytest.txt
 B=$PWD/build/ab/branchy_tail.so
 for rep in 1 2; do
-  echo -n "select tail cfg2: " >> $OUT/ab.txt; python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
-  echo -n "branchy tail cfg2: " >> $OUT/ab.txt; DE_LIB_PATH=$B python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "select tail cfg2: " >> $OUT/ab.txt; python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "branchy tail cfg2: " >> $OUT/ab.txt; DE_LIB_PATH=$B python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
 done
 for cam in "$SUN" "config - florida.txt" "config - Apollo 11.txt"; do
-  echo -n "select tail $cam: " >> $OUT/ab.txt; python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
-  echo -n "branchy tail $cam: " >> $OUT/ab.txt; DE_LIB_PATH=$B python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "select tail $cam: " >> $OUT/ab.txt; python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "branchy tail $cam: " >> $OUT/ab.txt; DE_LIB_PATH=$B python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$cam" 2>/dev/null | ms >> $OUT/ab.txt
 done
 export TMPDIR=/tmp; cd /tmp
 for t in select branchy; do

@@ -9,9 +9,9 @@ timeout 900 python3 -m pytest tests/test_gpu_block_scheduler.py tests/test_gpu_r
 tail -3 $OUT/pytest_quick.txt
 three() {
   label=$1; shift
-  echo -n "$label cfg2: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 2>$OUT/err.txt | ms >> $OUT/ab.txt
-  echo -n "$label cfg2 1/8 share: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 --simulate-world 8 2>>$OUT/err.txt | ms >> $OUT/ab.txt
-  echo -n "$label sunset: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --no-cpu-baseline --steps 5 --warmup 2 --preset "$SUN" 2>>$OUT/err.txt | ms >> $OUT/ab.txt
+  echo -n "$label cfg2: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 2>$OUT/err.txt | ms >> $OUT/ab.txt
+  echo -n "$label cfg2 1/8 share: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 --simulate-world 8 2>>$OUT/err.txt | ms >> $OUT/ab.txt
+  echo -n "$label sunset: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --preset "$SUN" 2>>$OUT/err.txt | ms >> $OUT/ab.txt
 }
 three "tail 0" DE_V6_TAIL=0
 three "tail 1 (96 -> 64 wg)" DE_V6_TAIL=1

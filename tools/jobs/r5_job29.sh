@@ -7,8 +7,8 @@ timeout 900 python3 -m pytest tests/test_gpu_round5.py tests/test_gpu_block_sche
 tail -3 $OUT/pytest.txt
 two() {
   label=$1; shift
-  echo -n "$label cfg2 1/8 share: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 --simulate-world 8 2>>$OUT/err.txt | ms >> $OUT/ab.txt
-  echo -n "$label cfg2: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 2>>$OUT/err.txt | ms >> $OUT/ab.txt
+  echo -n "$label cfg2 1/8 share: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 --simulate-world 8 2>>$OUT/err.txt | ms >> $OUT/ab.txt
+  echo -n "$label cfg2: " >> $OUT/ab.txt; env "$@" timeout 300 python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 2>>$OUT/err.txt | ms >> $OUT/ab.txt
 }
 two "export 128 -> 64 wg" DE_X=0
 two "export 160 -> 64 wg" DE_V6_TAIL_EXPORT0=160

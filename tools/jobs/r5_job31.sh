@@ -9,11 +9,11 @@ timeout 1200 python3 -m pytest tests/test_gpu_block_scheduler.py tests/test_gpu_
 grep -E "passed|failed" $OUT/pytest.txt
 for lib in main prev_r56 main prev_r56; do
   if [ $lib = main ]; then unset DE_LIB_PATH; else export DE_LIB_PATH=$GRAFT_REPO_ROOT/build/ab/$lib.so; fi
-  echo -n "$lib cfg2: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 2>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib sunset: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 5 --warmup 2 --preset "$SUN" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib florida: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 5 --warmup 2 --preset "config - florida.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib Apollo: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 --preset "config - Apollo 11.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib cfg2 1/8 share: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 8 --warmup 2 --simulate-world 8 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib cfg2: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 2>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib sunset: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --preset "$SUN" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib florida: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --preset "config - florida.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib Apollo: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 --preset "config - Apollo 11.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib cfg2 1/8 share: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 8 --warmup 2 --simulate-world 8 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
 done
 unset DE_LIB_PATH
 cat $OUT/ab.txt

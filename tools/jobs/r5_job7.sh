@@ -5,17 +5,17 @@ OUT=gpurun_out/r5_job7; mkdir -p $OUT
 SUN="config - sunset hurricane.txt"
 ms() { python3 -c "import json,sys; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%.2f ms/step  single %.2f  kernel %.2f' % (j['ms_per_step'], j['single_frame_ms'], j['roofline']['kernel_ms']))"; }
 timeout 900 python3 -m pytest tests/test_gpu_block_scheduler.py -x -q -m gpu > $OUT/pytest.txt 2>&1
-echo -n "r4 tree cfg2: " >> $OUT/ab.txt; (cd build/r4_tree && python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms) >> $OUT/ab.txt
-echo -n "r5 tree cfg2: " >> $OUT/ab.txt; python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
-echo -n "r5 gas table cfg2: " >> $OUT/ab.txt; DE_LIB_PATH=$PWD/build/ab/gas_table.so python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+echo -n "r4 tree cfg2: " >> $OUT/ab.txt; (cd build/r4_tree && python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms) >> $OUT/ab.txt
+echo -n "r5 tree cfg2: " >> $OUT/ab.txt; python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+echo -n "r5 gas table cfg2: " >> $OUT/ab.txt; DE_LIB_PATH=$PWD/build/ab/gas_table.so python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
 for fa in 8 16 24 32 48; do
-  echo -n "r5 flat_again $fa cfg2: " >> $OUT/ab.txt; DE_V6_FLAT_AGAIN=$fa python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+  echo -n "r5 flat_again $fa cfg2: " >> $OUT/ab.txt; DE_V6_FLAT_AGAIN=$fa python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
 done
-echo -n "r5 area 100 72 90 flat_again 24 cfg2: " >> $OUT/ab.txt; DE_V6_FLAT_AGAIN=24 DE_V6_AREA_ST=100 DE_V6_AREA_GAS=72 DE_V6_AREA_CLOUD=90 python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
-echo -n "r4 tree sunset: " >> $OUT/ab.txt; (cd build/r4_tree && python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms) >> $OUT/ab.txt
-echo -n "r5 tree sunset: " >> $OUT/ab.txt; python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/ab.txt
-echo -n "r5 gas table sunset: " >> $OUT/ab.txt; DE_LIB_PATH=$PWD/build/ab/gas_table.so python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/ab.txt
-echo -n "r5 tree sunset area 100 72 90: " >> $OUT/ab.txt; DE_V6_AREA_ST=100 DE_V6_AREA_GAS=72 DE_V6_AREA_CLOUD=90 python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/ab.txt
+echo -n "r5 area 100 72 90 flat_again 24 cfg2: " >> $OUT/ab.txt; DE_V6_FLAT_AGAIN=24 DE_V6_AREA_ST=100 DE_V6_AREA_GAS=72 DE_V6_AREA_CLOUD=90 python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>/dev/null | ms >> $OUT/ab.txt
+echo -n "r4 tree sunset: " >> $OUT/ab.txt; (cd build/r4_tree && python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms) >> $OUT/ab.txt
+echo -n "r5 tree sunset: " >> $OUT/ab.txt; python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/ab.txt
+echo -n "r5 gas table sunset: " >> $OUT/ab.txt; DE_LIB_PATH=$PWD/build/ab/gas_table.so python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/ab.txt
+echo -n "r5 tree sunset area 100 72 90: " >> $OUT/ab.txt; DE_V6_AREA_ST=100 DE_V6_AREA_GAS=72 DE_V6_AREA_CLOUD=90 python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "$SUN" 2>/dev/null | ms >> $OUT/ab.txt
 export TMPDIR=/tmp; cd /tmp
 for t in r4 r5 gastab; do
   R=$GRAFT_REPO_ROOT; L=""

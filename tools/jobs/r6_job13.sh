@@ -6,6 +6,6 @@ ms() { python3 -c "import json,sys; j=json.loads([l for l in sys.stdin if l.star
 for rep in 1 2 3; do for lib in head nobackoff backoff2 main; do
   if [ $lib = main ]; then unset DE_LIB_PATH; else export DE_LIB_PATH=$GRAFT_REPO_ROOT/build/ab/$lib.so; fi
   echo -n "$lib window loop: "; python3 tools/pipelined_trace.py run 120 3 2>&1 | tail -1
-  echo -n "$lib share 1/8: "; timeout 300 python3 bench.py --no-cpu-baseline --steps 100 --warmup 5 --simulate-world 8 2>/dev/null | ms
-  echo -n "$lib cfg2: "; timeout 300 python3 bench.py --no-cpu-baseline --no-other-configs --steps 30 --warmup 5 2>/dev/null | ms
+  echo -n "$lib share 1/8: "; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 100 --warmup 5 --simulate-world 8 2>/dev/null | ms
+  echo -n "$lib cfg2: "; timeout 300 python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 30 --warmup 5 2>/dev/null | ms
 done; done | tee $OUT/ab.txt

@@ -21,12 +21,12 @@ s=j.get('standin_collective',{})
 print('%.2f ms/step  single %.2f  kernel %.2f  standin queue-to-finish %s ms' % (j['ms_per_step'], j['single_frame_ms'], j['roofline']['kernel_ms'], ('%.3f' % s['queue_to_finish_ms_mean_of_last_16']) if s else '-'))"; }
 for wh in 0 1 2; do
   for st in -1 0 7; do
-    echo -n "cfg2 share 1/8, cu_withhold $wh, standin $st: "; python3 bench.py --no-cpu-baseline --steps 30 --warmup 5 --simulate-world 8 --standin-collective $st --cu-withhold $wh 2>/dev/null | line
+    echo -n "cfg2 share 1/8, cu_withhold $wh, standin $st: "; python3 bench.py --full --no-cpu-baseline --steps 30 --warmup 5 --simulate-world 8 --standin-collective $st --cu-withhold $wh 2>/dev/null | line
   done
 done | tee $OUT/standin.txt
 for wh in 0 1; do for st in -1 0; do
-  echo -n "cfg2 whole frame, cu_withhold $wh, standin $st: "; python3 bench.py --no-cpu-baseline --no-other-configs --steps 12 --warmup 3 --standin-collective $st --cu-withhold $wh 2>/dev/null | line
+  echo -n "cfg2 whole frame, cu_withhold $wh, standin $st: "; python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 12 --warmup 3 --standin-collective $st --cu-withhold $wh 2>/dev/null | line
 done; done | tee -a $OUT/standin.txt
 for st in -1 0; do
-  echo -n "cfg4, standin $st: "; python3 bench.py --no-cpu-baseline --config cfg4 --steps 3 --warmup 1 --standin-collective $st 2>/dev/null | line
+  echo -n "cfg4, standin $st: "; python3 bench.py --full --no-cpu-baseline --config cfg4 --steps 3 --warmup 1 --standin-collective $st 2>/dev/null | line
 done | tee -a $OUT/standin.txt

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r6_job20; mkdir -p $OUT
 timeout 2400 python3 -m pytest tests -x -q -m gpu > $OUT/pytest_all.txt 2>&1; tail -4 $OUT/pytest_all.txt | head -2
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-( time python3 bench.py ) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err
+( time python3 bench.py --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -3 $OUT/bench_default.err
 python3 -c "
 import json
 j=json.loads([l for l in open('$OUT/bench_default.json') if l.startswith('{')][-1])

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r6_job21; mkdir -p $OUT
 timeout 2400 python3 -m pytest tests -x -q -m gpu > $OUT/pytest_all.txt 2>&1; tail -4 $OUT/pytest_all.txt | head -2
 bash tools/profile_gpu.sh r6f > $OUT/prof_r6f.log 2>&1
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_r6f.json 2> $OUT/bench_r6f.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_r6f.json 2> $OUT/bench_r6f.err
 python3 -c "
 import json
 j=json.loads([l for l in open('$OUT/bench_r6f.json') if l.startswith('{')][-1])

@@ -8,10 +8,10 @@ ms() { python3 -c "import json,sys; j=json.loads([l for l in sys.stdin if l.star
 for lib in head main head main; do
   if [ $lib = main ]; then unset DE_LIB_PATH; else export DE_LIB_PATH=$GRAFT_REPO_ROOT/build/ab/$lib.so; fi
   if [ $lib = main ]; then echo -n "$lib bits (of 5 cameras): " >> $OUT/ab.txt; python3 tools/v6_try.py --small 2>&1 | grep -c "fraction 1.000000" >> $OUT/ab.txt; fi
-  echo -n "$lib cfg2: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --no-other-configs --steps 20 --warmup 3 2>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib sunset: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 6 --warmup 2 --preset "config - sunset hurricane.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib Apollo: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 10 --warmup 2 --preset "config - Apollo 11.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
-  echo -n "$lib cfg2 share 1/8: " >> $OUT/ab.txt; timeout 300 python3 bench.py --no-cpu-baseline --steps 60 --warmup 5 --simulate-world 8 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib cfg2: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 20 --warmup 3 2>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib sunset: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 2 --preset "config - sunset hurricane.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib Apollo: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 2 --preset "config - Apollo 11.txt" 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
+  echo -n "$lib cfg2 share 1/8: " >> $OUT/ab.txt; timeout 300 python3 bench.py --full --no-cpu-baseline --steps 60 --warmup 5 --simulate-world 8 2>>$OUT/err_$lib.txt | ms >> $OUT/ab.txt
   echo -n "$lib window loop: " >> $OUT/ab.txt; python3 tools/pipelined_trace.py run 90 3 2>&1 | tail -1 >> $OUT/ab.txt
 done
 unset DE_LIB_PATH

@@ -11,7 +11,7 @@ for w in ${WORLDS:-2 4 8}; do for p in "" "config - florida.txt" "config - sunse
   echo -n "world $w | ${p:-default camera} | pipeline / state machine / persistent : "
   for m in ${MODES:-1 2 5}; do
     if [ $m = 5 ] || [ $m = 6 ]; then export DE_KERNEL=$m; unset DE_AUTO_MID; else export DE_KERNEL=4 DE_AUTO_MID=$m; fi
-    if [ -z "$p" ]; then python3 bench.py --no-cpu-baseline --warmup 3 --steps 12 --simulate-world $w > /tmp/b.json 2>/tmp/b.err; else python3 bench.py --no-cpu-baseline --warmup 3 --steps 12 --simulate-world $w --preset "$p" > /tmp/b.json 2>/tmp/b.err; fi
+    if [ -z "$p" ]; then python3 bench.py --full --no-cpu-baseline --warmup 3 --steps 12 --simulate-world $w > /tmp/b.json 2>/tmp/b.err; else python3 bench.py --full --no-cpu-baseline --warmup 3 --steps 12 --simulate-world $w --preset "$p" > /tmp/b.json 2>/tmp/b.err; fi
     echo -n "$(line /tmp/b.json) | "
   done; echo
 done; done

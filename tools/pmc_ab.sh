@@ -5,9 +5,9 @@ export DE_BIG_SLOTS=1          # one launch at a time: clean kernel durations
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 for LIB in "$@"; do
   export DE_LIB_PATH=$REPO/$LIB
-  MS=$(python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.read()); print('%.2f %.2f' % (j['roofline']['kernel_ms'], j['ms_per_step']))")
+  MS=$(python3 $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.read()); print('%.2f %.2f' % (j['roofline']['kernel_ms'], j['ms_per_step']))")
   rm -rf /tmp/pmcab_$$
-  rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum --kernel-include-regex "render_kernel_v2" --output-format csv -d /tmp/pmcab_$$ -o pmc -- python3 $REPO/bench.py --steps 2 --warmup 0 --no-cpu-baseline > /tmp/pmcab_$$.log 2>&1
+  rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum --kernel-include-regex "render_kernel_v2" --output-format csv -d /tmp/pmcab_$$ -o pmc -- python3 $REPO/bench.py --full --steps 2 --warmup 0 --no-cpu-baseline > /tmp/pmcab_$$.log 2>&1
   python3 - "$LIB" "$MS" /tmp/pmcab_$$ <<'PY'
 import csv, glob, collections, sys, os
 acc = collections.defaultdict(list)

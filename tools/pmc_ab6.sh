@@ -5,10 +5,10 @@ export DE_BIG_SLOTS=1
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 for LIB in "$@"; do
   if [ "$LIB" = main ]; then unset DE_LIB_PATH; else export DE_LIB_PATH=$REPO/$LIB; fi
-  MS=$(python3 $REPO/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-other-configs 2>/dev/null | python3 -c "import sys,json; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%.2f %.2f' % (j['roofline']['kernel_ms'], j['ms_per_step']))")
+  MS=$(python3 $REPO/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-other-configs 2>/dev/null | python3 -c "import sys,json; j=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('%.2f %.2f' % (j['roofline']['kernel_ms'], j['ms_per_step']))")
   D=/tmp/pmcab6_$$; rm -rf $D
   for PASS in "WRITE_SIZE" "FETCH_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU"; do
-    rocprofv3 --pmc $PASS --kernel-include-regex "v6_kernel" --output-format csv -d $D/$(echo $PASS | cut -c1-8) -o pmc -- python3 $REPO/bench.py --steps 2 --warmup 0 --no-cpu-baseline --no-other-configs --sync-frames > $D.log 2>&1
+    rocprofv3 --pmc $PASS --kernel-include-regex "v6_kernel" --output-format csv -d $D/$(echo $PASS | cut -c1-8) -o pmc -- python3 $REPO/bench.py --full --steps 2 --warmup 0 --no-cpu-baseline --no-other-configs --sync-frames > $D.log 2>&1
   done
   python3 - "$LIB" "$MS" $D <<'PY'
 import csv, glob, collections, sys

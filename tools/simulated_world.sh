@@ -28,7 +28,7 @@ for name, extra in CFG.items():
             steps = str(max(4, min(120, int((24 if "cfg2" in name else 6) * n * (0.4 if heavy else 1.0)))))
             warm = "2" if not heavy else "1"
             def run(extra2):
-                cmd = [sys.executable, "bench.py", "--no-cpu-baseline", "--warmup", warm, "--steps", steps, "--split", split] + extra + (["--simulate-world", str(n)] if n > 1 else []) + extra2
+                cmd = [sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--warmup", warm, "--steps", steps, "--split", split] + extra + (["--simulate-world", str(n)] if n > 1 else []) + extra2
                 p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
                 return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
             j = run([])

@@ -3,8 +3,8 @@
 cd $GRAFT_REPO_ROOT
 run() {
   echo -n "$1 : "
-  if [ -n "$PRESET_NAME" ]; then env $1 python3 bench.py --no-cpu-baseline --warmup 3 --steps 12 --simulate-world ${WORLD:-8} --preset "$PRESET_NAME" 2>/dev/null > /tmp/w8.json
-  else env $1 python3 bench.py --no-cpu-baseline --warmup 3 --steps 12 --simulate-world ${WORLD:-8} 2>/dev/null > /tmp/w8.json; fi
+  if [ -n "$PRESET_NAME" ]; then env $1 python3 bench.py --full --no-cpu-baseline --warmup 3 --steps 12 --simulate-world ${WORLD:-8} --preset "$PRESET_NAME" 2>/dev/null > /tmp/w8.json
+  else env $1 python3 bench.py --full --no-cpu-baseline --warmup 3 --steps 12 --simulate-world ${WORLD:-8} 2>/dev/null > /tmp/w8.json; fi
   python3 -c "import sys,json; j=json.loads([l for l in open('/tmp/w8.json') if l.startswith('{')][-1]); print('%.1f ms/step, single %.1f' % (j['ms_per_step'], j['single_frame_ms']))"
 }
 for cfg in "$@"; do run "$cfg"; done
