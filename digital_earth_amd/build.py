@@ -55,9 +55,10 @@ def build_legacy(force=False, verbose=False):
     return OUT_LEGACY
 
 
-# Geometry variants of render_kernel_v6 for tests/test_gpu_round5.py::test_ring_protocol_on_small_pools: the same sources with -D flags
+# Variants of render_kernel_v6 for tests/test_gpu_round5.py::test_ring_protocol_on_small_pools (geometry) and tests/test_gpu_cloud_bound.py (no bound): the same sources with -D flags
 # (tiny slot pools, a ring with no slack), loaded through DE_LIB_PATH by a child process; never the product library.
-TEST_VARIANTS = (("v6_p64", ["-DDE_V6_P=64u", "-DDE_V6_CAP=65u"]), ("v6_p128", ["-DDE_V6_P=128u", "-DDE_V6_CAP=129u"]), ("v6_cap_p1", ["-DDE_V6_CAP=1121u"]))
+TEST_VARIANTS = (("v6_p64", ["-DDE_V6_P=64u", "-DDE_V6_CAP=65u"]), ("v6_p128", ["-DDE_V6_P=128u", "-DDE_V6_CAP=129u"]), ("v6_cap_p1", ["-DDE_V6_CAP=1121u"]),
+                 ("v6_no_cloud_bound", ["-DDE_NO_CLOUD_BOUND"]))      # tests/test_gpu_cloud_bound.py: the cloud stage without its occupancy bound
 
 
 def build_test_variants(force=False, verbose=False):

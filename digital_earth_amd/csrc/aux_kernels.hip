@@ -318,6 +318,95 @@ __global__ void pack_r8_kernel(const uint8_t* src, uint32_t* dst, int w, int h, 
     size_t idx = ((size_t)(j >> 2) * tiles_x + (size_t)(i >> 3)) * 32u + (size_t)(((j & 3) << 3) | (i & 7));
     dst[idx] = q;
 }
+// ------------------------------------------------------------------------------------------------ the cloud map's occupancy bound (de_kernels.h: DE_CLOUD_BOUND_*)
+// Two gathers, no atomics: the result is a pure function of the packed map.  (1) the largest byte of each 8 x 4 tile of footprint dwords
+// (the entries that exist: i < w, j < h); (2) per cell of the cube map, the largest tile byte over every tile holding a footprint the exact
+// tap can read from a direction within the cell's reach.
+__global__ void tile_max_kernel(const uint32_t* packed, uint8_t* out, int w, int h, int tiles_x, int tiles_y) {
+    const int ti = (int)(blockIdx.x * blockDim.x + threadIdx.x), tj = (int)blockIdx.y;
+    if (ti >= tiles_x || tj >= tiles_y) return;
+    uint32_t m = 0;
+    for (int k = 0; k < 32; ++k) {
+        const int i = ti * 8 + (k & 7), j = tj * 4 + (k >> 3);
+        if (i >= w || j >= h) continue;
+        const uint32_t q = packed[((size_t)tj * tiles_x + ti) * 32u + (uint32_t)k];
+        m = max(m, max(max(q & 255u, (q >> 8) & 255u), max((q >> 16) & 255u, q >> 24)));
+    }
+    out[(size_t)tj * tiles_x + ti] = (uint8_t)m;
+}
+// One wave per cell, in double precision.  The cell's region: every direction whose computed face / ratios land in it — the true ratios within
+// 1e-5 of the cell's range (the lookup's reciprocal and products err by a few 1e-7) — as a spherical cap around the cell's centre (the farthest
+// point of a convex spherical polygon from a point is a vertex), widened by the angle the travel budget can reach from the shell's lower radius.
+// The cap's latitude / longitude extent is turned into footprint rows / columns with one footprint of margin on every side (the exact tap's
+// atan2 / asin / fract rounding), wrapped across the u seam; rows that touch a pole take the first and the last footprint row too (fract_ turns
+// v = 1 into 0, and a footprint row -1 is row h - 1 (REPEAT) or 0 (CLAMP)), columns that touch the seam take the first and the last column.
+__global__ void cloud_bound_kernel(const uint8_t* tmax, uint8_t* out, int w, int h, int tiles_x, int tiles_y, double reach) {
+    const int cell = (int)blockIdx.x, lane = (int)threadIdx.x;
+    const int N = DE_CLOUD_BOUND_N, f = cell / (N * N), j = (cell / N) % N, i = cell % N;
+    const double eps = 1e-5;
+    auto dir = [&](double a, double b, double* v) {
+        double x, y, z;
+        const double sgn = (f & 1) ? -1.0 : 1.0;
+        if (f < 2) { x = sgn; y = a; z = b; } else if (f < 4) { x = a; y = sgn; z = b; } else { x = a; y = b; z = sgn; }
+        const double l = sqrt(x * x + y * y + z * z);
+        v[0] = x / l; v[1] = y / l; v[2] = z / l;
+    };
+    const double a0 = 2.0 * i / N - 1.0 - eps, a1 = 2.0 * (i + 1) / N - 1.0 + eps, b0 = 2.0 * j / N - 1.0 - eps, b1 = 2.0 * (j + 1) / N - 1.0 + eps;
+    double c[3], q[3];
+    dir(0.5 * (a0 + a1), 0.5 * (b0 + b1), c);
+    double rho = 0.0;
+    for (int k = 0; k < 4; ++k) {
+        dir((k & 1) ? a1 : a0, (k & 2) ? b1 : b0, q);
+        const double cx = c[1] * q[2] - c[2] * q[1], cy = c[2] * q[0] - c[0] * q[2], cz = c[0] * q[1] - c[1] * q[0];
+        rho = fmax(rho, atan2(sqrt(cx * cx + cy * cy + cz * cz), c[0] * q[0] + c[1] * q[1] + c[2] * q[2]));
+    }
+    const double lower = (double)DE_CLOUDS_LOWER;      // the shell's lower radius as the cloud stage tests it (de_device.h)
+    const double r = rho + 2.0 * asin(fmin(1.0, reach / (2.0 * lower))) + 1e-6;
+    const double lat = asin(fmax(-1.0, fmin(1.0, c[1]))), lon = atan2(c[2], -c[0]);
+    const double PI = 3.14159265358979323846;
+    bool full = (lat + r >= 0.5 * PI) || (lat - r <= -0.5 * PI);
+    double dl = 0.0;
+    if (!full) {
+        const double s = sin(r) / cos(lat);
+        if (s >= 1.0) full = true; else dl = asin(s);
+    }
+    // footprint columns
+    int cp[3][2], ncp = 0;
+    if (full) { cp[0][0] = 0; cp[0][1] = w - 1; ncp = 1; }
+    else {
+        const long long lo = (long long)floor(((lon - dl) / (2.0 * PI) + 0.5) * w - 0.5) - 1, hi = (long long)floor(((lon + dl) / (2.0 * PI) + 0.5) * w - 0.5) + 1;
+        if (hi - lo + 1 >= w) { cp[0][0] = 0; cp[0][1] = w - 1; ncp = 1; }
+        else {
+            const int l = (int)(((lo % w) + w) % w), u = (int)(((hi % w) + w) % w);
+            if (l <= u) {
+                cp[0][0] = l; cp[0][1] = u; ncp = 1;
+                if (lo <= 0 || hi >= w - 1) { cp[1][0] = 0; cp[1][1] = 0; cp[2][0] = w - 1; cp[2][1] = w - 1; ncp = 3; }
+            } else { cp[0][0] = l; cp[0][1] = w - 1; cp[1][0] = 0; cp[1][1] = u; ncp = 2; }      // across the seam: both ends are in
+        }
+    }
+    // footprint rows
+    int rp[3][2], nrp = 0;
+    {
+        const long long lo = (long long)floor(((lat - r) / PI + 0.5) * h - 0.5) - 1, hi = (long long)floor(((lat + r) / PI + 0.5) * h - 0.5) + 1;
+        rp[0][0] = (int)max(lo, 0ll); rp[0][1] = (int)min(hi, (long long)h - 1); nrp = 1;
+        if (lo <= 0 || hi >= h - 1) { rp[1][0] = 0; rp[1][1] = 0; rp[2][0] = h - 1; rp[2][1] = h - 1; nrp = 3; }
+    }
+    uint32_t m = 0;
+    for (int pr = 0; pr < nrp; ++pr)
+        for (int pc = 0; pc < ncp; ++pc) {
+            if (rp[pr][0] > rp[pr][1]) continue;
+            const int tr0 = rp[pr][0] >> 2, tr1 = rp[pr][1] >> 2, tc0 = cp[pc][0] >> 3, tc1 = cp[pc][1] >> 3;
+            const int nc = tc1 - tc0 + 1;
+            const long long n = (long long)(tr1 - tr0 + 1) * nc;
+            for (long long k = lane; k < n; k += 64) {
+                const int tr = tr0 + (int)(k / nc), tc = tc0 + (int)(k % nc);
+                m = max(m, (uint32_t)tmax[(size_t)tr * tiles_x + tc]);
+            }
+        }
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if (lane == 0) out[cell] = (uint8_t)m;
+    (void)tiles_y;
+}
 __global__ void pack_rgb_kernel(const uint8_t* src, uint32_t* dst, size_t n) {
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;

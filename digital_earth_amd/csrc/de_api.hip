@@ -98,7 +98,7 @@ int de_destroy(de_ctx* c) {
     hipStreamSynchronize(c->stream);
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
-    for (auto& t : c->tex) { if (t.borrowed) continue; if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); }
+    for (auto& t : c->tex) { if (t.borrowed) continue; if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); if (t.bound) hipFree(t.bound); }
     if (c->luts_borrowed) { c->d_cie = nullptr; c->d_srgb2spec = nullptr; c->d_o3 = nullptr; c->d_crf = nullptr; }
     void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin};
     for (void* p : ptrs) if (p) hipFree(p);
@@ -174,8 +174,8 @@ int de_share_textures(de_ctx* dst, de_ctx* src) {
     release_loan(dst);
     for (int i = 0; i < DE_TEX_COUNT; ++i) {
         DevTexture& t = dst->tex[i];
-        if (!t.borrowed) { if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); }
-        t = src->tex[i];
+        if (!t.borrowed) { if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); if (t.bound) hipFree(t.bound); }
+        t = src->tex[i];          // (the cloud map's occupancy bound with it)
         t.linear = nullptr;       // the as-uploaded copy stays the lender's alone: de_download_texture on the borrower fails cleanly
         t.borrowed = true;
     }
@@ -671,6 +671,20 @@ int de_debug_v6_stats(de_ctx* c, uint64_t* out, int n) {
         for (int k = 64; k < n && k < 128; ++k) { uint64_t v; memcpy(&v, &h[(size_t)(bs::G_STAT2 + k - 64) * DE_V6_CTL_STRIDE], 8); out[k] += v; }      // region statistics
         for (int k = 128; k < n && k < 192; ++k) { uint64_t v; memcpy(&v, &h[(size_t)(bs::G_DRAIN + k - 128) * DE_V6_CTL_STRIDE], 8); out[k] += v; }      // the drain's population histogram
     }
+    return DE_OK;
+}
+
+int de_debug_cloud_bound(de_ctx* c, uint8_t* out, uint64_t out_bytes, int* cells_per_edge, uint32_t* budget_m) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (cells_per_edge) *cells_per_edge = DE_CLOUD_BOUND_N;
+    if (budget_m) *budget_m = DE_CLOUD_BOUND_R;
+    if (!out) return DE_OK;
+    if (out_bytes < DE_CLOUD_BOUND_BYTES) return fail(DE_ERR_INVALID, "output buffer too small");
+    if (!c->tex[DE_TEX_CLOUDS].set) return fail(DE_ERR_STATE, "no cloud map");
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = ensure_packed(c, DE_TEX_CLOUDS, (c->p.flags & DE_FLAG_CLAMP_SAMPLER) != 0); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(out, c->tex[DE_TEX_CLOUDS].bound, DE_CLOUD_BOUND_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return DE_OK;
 }
 

@@ -53,6 +53,7 @@ struct DevTexture {
     uint32_t* packed = nullptr;   // footprint tiles (ch == 1) or rgbx dwords (ch == 3)
     int tiles_x = 0, tiles_y = 0;
     int packed_clamp = -1;        // address mode the packed copy was built with
+    uint8_t* bound = nullptr;     // the cloud map only: its occupancy bound (DE_CLOUD_BOUND_BYTES), rebuilt with the packed copy
     bool set = false;
     bool borrowed = false;        // the allocations belong to another context (de_share_textures)
 };

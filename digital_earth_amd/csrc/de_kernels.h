@@ -90,7 +90,33 @@ struct RenderArgs {
     const uint32_t* resume_count;
     const float* resume_cold;     // 16 floats per path: thr, Ls, ...
     uint32_t resume_capacity;
+    const uint8_t* cloud_bound;   // the cloud map's occupancy bound (aux_kernels.hip: cloud_bound_kernel), read by render_kernel_v6's cloud stage
 };
+
+// Occupancy bound of the cloud map: a cube map over directions, DE_CLOUD_BOUND_N x DE_CLOUD_BOUND_N cells per face, one byte per cell =
+// at least the largest byte of every footprint the exact tap can read at any point of the cloud shell within DE_CLOUD_BOUND_R metres of
+// travel (plus rounding drift) from a point whose lookup lands in the cell.  Cell of a position C: the face of the major axis (ties in
+// x, y, z order; + then - side), the two other coordinates divided by the major one.  Layout: [face][j][i].
+#ifndef DE_CLOUD_BOUND_N
+#define DE_CLOUD_BOUND_N 128
+#endif
+#ifndef DE_CLOUD_BOUND_R
+#define DE_CLOUD_BOUND_R 24576u
+#endif
+#define DE_CLOUD_BOUND_BYTES (6u * DE_CLOUD_BOUND_N * DE_CLOUD_BOUND_N)
+DE_DEV uint32_t cloud_bound_cell(float x, float y, float z) {
+    const float ax = de_abs(x), ay = de_abs(y), az = de_abs(z);
+    float s, t, m;
+    uint32_t f;
+    if (ax >= ay && ax >= az) { f = x < 0.0f ? 1u : 0u; s = y; t = z; m = ax; }
+    else if (ay >= az) { f = y < 0.0f ? 3u : 2u; s = x; t = z; m = ay; }
+    else { f = z < 0.0f ? 5u : 4u; s = x; t = y; m = az; }
+    const float r = __builtin_amdgcn_rcpf(m);
+    const float hn = (float)(DE_CLOUD_BOUND_N / 2);
+    const int i = (int)((s * r + 1.0f) * hn), j = (int)((t * r + 1.0f) * hn);
+    const uint32_t ic = (uint32_t)min(max(i, 0), DE_CLOUD_BOUND_N - 1), jc = (uint32_t)min(max(j, 0), DE_CLOUD_BOUND_N - 1);
+    return (f * (uint32_t)DE_CLOUD_BOUND_N + jc) * (uint32_t)DE_CLOUD_BOUND_N + ic;
+}
 
 struct SetupArgs {
     de_params p;

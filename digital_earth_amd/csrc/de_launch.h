@@ -48,6 +48,24 @@ void release_loan(de_ctx* c) {
     if (c->lender) { c->lender->loans--; c->lender = nullptr; }
 }
 
+// the cloud map's occupancy bound from its packed copy (aux_kernels.hip: tile_max_kernel, cloud_bound_kernel), on the context stream after the packing
+int build_cloud_bound(de_ctx* c, DevTexture& t) {
+    if (!t.bound) HIP_TRY(hipMalloc(&t.bound, DE_CLOUD_BOUND_BYTES));
+    uint8_t* tiles = nullptr;
+    HIP_TRY(hipMalloc(&tiles, (size_t)t.tiles_x * t.tiles_y));
+    hipLaunchKernelGGL(tile_max_kernel, dim3((unsigned)((t.tiles_x + 255) / 256), (unsigned)t.tiles_y), dim3(256), 0, c->stream, t.packed, tiles, t.w, t.h, t.tiles_x, t.tiles_y);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cloud_bound_kernel, dim3(DE_CLOUD_BOUND_BYTES), dim3(64), 0, c->stream, tiles, t.bound, t.w, t.h, t.tiles_x, t.tiles_y, 1.5 * (double)DE_CLOUD_BOUND_R + 64.0);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // upload time: the scratch tile maxima go now
+    if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);    // (a launch failed: nothing of ours may still read the scratch when it is freed)
+    hipFree(tiles);                                                 // on every path
+    if (e != hipSuccess) return fail(DE_ERR_HIP, std::string("building the cloud map's occupancy bound: ") + hipGetErrorString(e));
+    return DE_OK;
+}
+
 int ensure_packed(de_ctx* c, int slot, bool clamp) {
     DevTexture& t = c->tex[slot];
     if (t.packed_clamp == (clamp ? 1 : 0)) return DE_OK;
@@ -59,6 +77,7 @@ int ensure_packed(de_ctx* c, int slot, bool clamp) {
     if (t.ch == 1) {
         dim3 grid((unsigned)((t.w + 255) / 256), (unsigned)t.h);
         hipLaunchKernelGGL(pack_r8_kernel, grid, dim3(256), 0, c->stream, t.linear, t.packed, t.w, t.h, t.tiles_x, clamp ? 1 : 0);
+        if (slot == DE_TEX_CLOUDS) { HIP_TRY(hipGetLastError()); int rc = build_cloud_bound(c, t); if (rc) return rc; }
     } else {
         size_t n = (size_t)t.w * t.h;
         hipLaunchKernelGGL(pack_rgb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, t.linear, t.packed, n);
@@ -76,7 +95,8 @@ int alloc_texture(de_ctx* c, int slot, int w, int h, int ch) {
     { int rc = sync_all(c); if (rc) return rc; }      // no launch may still read the map that is being replaced
     if (t.linear && !t.borrowed) hipFree(t.linear);
     if (t.packed && !t.borrowed) hipFree(t.packed);
-    t.linear = nullptr; t.packed = nullptr; t.borrowed = false;
+    if (t.bound && !t.borrowed) hipFree(t.bound);
+    t.linear = nullptr; t.packed = nullptr; t.bound = nullptr; t.borrowed = false;
     {   // a borrower that now owns every map again gives the loan back
         bool any = false;
         for (int i = 0; i < DE_TEX_COUNT; ++i) any = any || (i != slot && c->tex[i].borrowed);
@@ -162,6 +182,7 @@ int fill_render_args(de_ctx* c, RenderArgs* a) {
     a->fixed_wavelength = (c->p.flags & DE_FLAG_FIXED_WAVELENGTH) ? 1 : 0;
     a->counters = c->d_counters; a->debug_out = c->d_scratch; a->work_counter = c->d_work_counter;   // work_counter / contrib: per launch slot, set by the caller
     a->resume_rec = nullptr; a->resume_count = nullptr; a->resume_cold = nullptr; a->resume_capacity = 0;
+    a->cloud_bound = c->tex[DE_TEX_CLOUDS].bound;
     a->pend_thr = c->tune_pend; a->heavy_thr = c->tune_heavy; a->tune_b = c->tune_b; a->gas_thr = c->tune_gas; a->chunk = c->tune_chunk;
     return DE_OK;
 }

@@ -469,15 +469,38 @@ struct GasStage {
 
 // ------------------------------------------------------------------------------------------------ CLOUD: tracking through the cloud shell
 // the same loops with get_clouds_density (pathtracer.py:48-65); p.x = (t, tmax, aux = rmo_t | trg, X = isect | li)
-template <bool CLAMP>
+//
+// BOUND (render_kernel_v6): the exact density lookup — normal, sphere_UV_map, the footprint tap, the filter — is skipped where the cloud map's
+// occupancy bound (de_kernels.h: DE_CLOUD_BOUND_*; aux_kernels.hip: cloud_bound_kernel) proves the density 0.  Why no bit changes:
+//   - tap_r8_finish filters exact byte values with fx, fy in [0, 1] (1.0 happens: in REPEAT mode x = u w - 0.5 = -2^-25 floors to -1 and
+//     x + 1 rounds to 1).  Each inner lerp, RN(t0 + (t1 - t0) fx), lies between its two bytes: the exact value does, and both are floats.
+//     The outer one is RN(a + d fy) with d = RN(b - a).  For b <= a, or fy < 1 (d fy <= (b - a)(1 + 2^-24)(1 - 2^-24) < b - a when b > a),
+//     the exact value is at most max(a, b).  For fy = 1 and b > a it is b + (d - (b - a)), within half an ulp of b (d's error is at most
+//     half an ulp of b - a <= b): it rounds to b, or to the float above b only on a tie — which goes to M if b = M, since an integer below
+//     256 has an even last significand bit, and is at most M if b < M.  So the filtered value E <= M, the largest byte of the footprint,
+//     and the bound's byte B >= M.
+//   - tex = RN(E / 255 as E * RN(1/255)) <= T = RN(B * RN(1/255)): rounded multiplication is monotone.  So are RN(tex * 0.8) and RN(tex * 0.2):
+//     if `resolve`'s band test fails for T it fails for tex, density is 0, es = pr = 0 — delta tracking never collides, ratio tracking
+//     multiplies trn by exactly 1, and the generator draws exactly as before.
+//   - B covers every point the lane reaches while its travel budget lasts: every step spends floor(t_step) + 1 >= its length and >= 1 m, and
+//     the accumulated position C drifts from the exact path by at most ~0.44 m per step (half an ulp of |C_i| < 2^23 m per component), so a
+//     point reached on a budget R is within 1.44 R of the lookup's point; the map is dilated by 1.5 R + 64 m (aux_kernels.hip).  A lane that
+//     leaves the shell forgets its bound: its next point in the shell looks up again.
+// The bound and the budget are a per-lane cache (one VGPR: byte | budget << 8), never part of the record: begin() and restore() empty it,
+// suspend() does not carry it.  DE_NO_CLOUD_BOUND builds render_kernel_v6 without it (A/B).
+template <bool CLAMP, bool BOUND = false>
 struct CloudStage {
+    static constexpr bool kBound = BOUND;
     const TexR8 clouds;
+    const uint8_t* bound;
     float ext_w, rmaxc, t, tmax, trn;
     vec3 C;
     int kind, cloud_event;
 #ifndef DE_NO_TAP_REUSE
     uint32_t last_idx = 0xffffffffu, last_q = 0u;      // the lane's previous cloud-map footprint (de_device.h: tap_r8_issue_cached); outlives the record
 #endif
+    uint32_t bnd = 0xffffffffu;                        // BOUND: the bound's byte | the travel left on it in metres << 8 (negative as int32: look up again)
+    bool exact = true, looked = false;                 // BOUND, statistics only: this step needed the exact lookup / looked the bound up
     DE_DEV void begin(wf::Path& p) {
         const int sc = wf::m_sc(p.meta);
         ext_w = (sc > 9) ? 0.02f : DE_CLOUDS_EXTINCT;
@@ -486,10 +509,12 @@ struct CloudStage {
         t = p.x[0]; tmax = p.x[1];
         C = p.P + t * p.W;
         trn = 1.0f; cloud_event = 0;
+        bnd = 0xffffffffu;
     }
     // issue / resolve: as in StStage (the draws keep their order: free flight in `issue`; collision test and event in `resolve`)
     struct Tok { uint32_t q; float fx, fy, h; bool shell; };
     DE_DEV bool issue(wf::Path& p, Tok& k) {                                 // true: the segment ended without a further point
+        exact = false; looked = false;
         const float neg_log = -de_log_unit(rng_next(p.rng));
         const float t_step = neg_log * rmaxc;
         C = C + t_step * p.W;
@@ -497,6 +522,25 @@ struct CloudStage {
         if (t >= tmax) return true;
         const float len = length_nr(C);
         k.shell = len > DE_CLOUDS_LOWER && len < DE_CLOUDS_UPPER;
+        k.h = (len - DE_CLOUDS_LOWER) * (1.0f / DE_CLOUDS_THICKNESS);
+        exact = k.shell;
+        if (BOUND) {
+            if (k.shell) {
+                bnd -= ((uint32_t)t_step + 1u) << 8;                         // t_step in [0, 29 km]: no wrap-around from a budget of < 2^23
+                if ((int32_t)bnd < 0) {
+                    const uint32_t cell = cloud_bound_cell(C.x, C.y, C.z);
+                    typedef const __attribute__((address_space(1))) uint8_t* de_gbytes;
+                    bnd = (uint32_t)*((de_gbytes)bound + cell) | (DE_CLOUD_BOUND_R << 8);
+                    looked = true;
+                }
+                const float T = (float)(bnd & 255u) * DE_INV_255;
+                const float split = 0.2f;
+                k.shell = (k.h - split < T * (float)(1.0 - 0.2)) & (split - k.h < T * split);      // resolve's band test on the bound
+            } else {
+                bnd = 0xffffffffu;
+            }
+            exact = k.shell;
+        }
         if (k.shell) {
             const vec3 nrm = C * de_rcp_nr(len);
             const vec2_ uv = sphere_UV_map(nrm);
@@ -505,7 +549,6 @@ struct CloudStage {
 #else
             k.q = tap_r8_issue<CLAMP>(clouds, fract_(uv.x * 1.0f), fract_(uv.y * 1.0f), &k.fx, &k.fy);
 #endif
-            k.h = (len - DE_CLOUDS_LOWER) * (1.0f / DE_CLOUDS_THICKNESS);
         }
         return false;
     }
@@ -545,5 +588,5 @@ struct CloudStage {
         return (kind == 1) ? wf::Q_SCFIN : wf::Q_SURFFIN;
     }
     DE_DEV void suspend(wf::Path& p, wf::Cold* c) const { p.x[0] = t; c->pad1 = trn; c->pad2 = C.x; c->pad3 = C.y; c->pad4 = C.z; }
-    DE_DEV void restore(const wf::Cold* c) { trn = c->pad1; C = v3(c->pad2, c->pad3, c->pad4); }
+    DE_DEV void restore(const wf::Cold* c) { trn = c->pad1; C = v3(c->pad2, c->pad3, c->pad4); bnd = 0xffffffffu; }
 };

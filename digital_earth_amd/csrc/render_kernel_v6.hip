@@ -82,7 +82,8 @@ static_assert(DE_V6_WAVES <= 31, "the lap tag of a ring cell has five bits: one 
 enum { G_WORK = 0, G_T_START = 1, G_T_EXHAUSTED = 2, G_T_END = 3, G_STAT0 = 8, G_STAT2 = 8 + 64, G_WORKX = 8 + 64 + 64, G_DRAIN = 8 + 64 + 64 + 8, G_POOL = 8 + 64 + 64 + 8 + 64, G_WORDS = 8 + 64 + 64 + 8 + 64 + 8 };
 // G_POOL + 2 l: entries written to the pool that launch level l exports to; G_POOL + 2 l + 1: entries of that pool handed out to level l + 1 (see "The tail" below)
 // statistics: 0-7 records taken per stage (7 = new paths), 8-15 wave time per stage (100 MHz ticks; 15 = new paths), 16 idle rounds,
-// 17 stage entries, 18 failed claims, 19 wave time in the scheduler, 20 yields of a loop stage, 21 records handed back by them, 22 wave time between the end of the work items and the wave's exit, 24-30 stage entries per stage (calls of the stage function), 32-38 trips of the loop stages / passes of the straight-line stages, 40-46 busy lanes summed over them
+// 17 stage entries, 18 failed claims, 19 wave time in the scheduler, 20 yields of a loop stage, 21 records handed back by them, 22 wave time between the end of the work items and the wave's exit, 24-30 stage entries per stage (calls of the stage function), 32-38 trips of the loop stages / passes of the straight-line stages, 40-46 busy lanes summed over them,
+// cloud stage's occupancy bound: 23 lane-steps that needed the exact density lookup, 31 trips in which none did, 39 lookups of the bound map
 // region statistics (G_STAT2 + k; STATS builds only): where a wave's time goes and how many lanes the region's vector code runs for.  Per loop stage q
 // (sphere trace, gas, cloud) fourteen words at 14 q: shader-clock ticks and ticks x active lanes of R_STEP (the stage's step(), lanes = busy), R_EPI (finish()
 // + the record's write-back, lanes = finished), R_PUSH (release + ring appends), R_REFILL (claim, take, record load, begin() / restore(), lanes = refilled),
@@ -90,7 +91,7 @@ enum { G_WORK = 0, G_T_START = 1, G_T_EXHAUSTED = 2, G_T_END = 3, G_STAT0 = 8, G
 // straight-line stage q (event, surface, volume finish, surface finish) four words at 42 + 4 (q - 3): ticks and ticks x lanes of the body, ticks of the
 // pass's ring work (claim, take, record load / store, appends), passes.  The same four for new paths (primary sphere trace included) at 58.
 enum { R_STEP = 0, R_EPI, R_PUSH, R_REFILL, R_YIELD, R_HEAD, R_N };
-enum { ST_RECS = 0, ST_CYC = 8, ST_IDLE = 16, ST_ENTRIES = 17, ST_CLAIMFAIL = 18, ST_SCHED = 19, ST_YIELD = 20, ST_YIELDED = 21, ST_DRAIN = 22, ST_ENTRY_Q = 24, ST_TRIPS = 32, ST_LANETRIPS = 40, ST_N = 48 };
+enum { ST_RECS = 0, ST_CYC = 8, ST_IDLE = 16, ST_ENTRIES = 17, ST_CLAIMFAIL = 18, ST_SCHED = 19, ST_YIELD = 20, ST_YIELDED = 21, ST_DRAIN = 22, ST_CLOUD_EXACT = 23, ST_ENTRY_Q = 24, ST_CLOUD_NOEXACT = 31, ST_TRIPS = 32, ST_CLOUD_LOOKUPS = 39, ST_LANETRIPS = 40, ST_N = 48 };
 enum { ERR_ENTRY_TIMEOUT = 1, ERR_CELL_BUSY_TIMEOUT = 2, ERR_IDLE_WATCHDOG = 3, ERR_POOL_FULL = 4 };
 // cell values as the 16-bit stores truncate them (the lap's high bits fall off)
 DE_DEV uint32_t cell_empty(uint32_t lap) { return (lap << 11) | DE_V6_SLOT_MASK; }
@@ -280,6 +281,17 @@ struct Wave {
         return W;
     }
 
+    // the cloud stage's occupancy bound (STATS builds): lane-steps that needed the exact density lookup, trips in which no lane of the wave did
+    // (the whole wave branched past it), lookups of the bound map
+    template <typename Stage>
+    DE_DEV void cloud_stats(const Stage& st, bool stepping) {
+        if constexpr (Stage::kBound) {
+            const unsigned long long n_exact = (unsigned long long)__popcll(__ballot(stepping && st.exact));
+            stat(ST_CLOUD_EXACT, n_exact);
+            stat(ST_CLOUD_NOEXACT, n_exact == 0ull && __ballot(stepping) != 0ull ? 1ull : 0ull);
+            stat(ST_CLOUD_LOOKUPS, (unsigned long long)__popcll(__ballot(stepping && st.looked)));
+        }
+    }
     DE_DEV void stat(int k, unsigned long long v) { if (STATS && lane_id() == 0) __hip_atomic_fetch_add(s_st + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
     template <int STAGE>
     DE_DEV void mark() {
@@ -558,9 +570,11 @@ struct Wave {
                 const unsigned long long n_step = STATS ? (unsigned long long)__popcll(__ballot(busy)) : 0ull;
                 if (STATS) { stat(ST_TRIPS + Q, 1); stat(ST_LANETRIPS + Q, n_step); r_cnt[1]++; }
                 tick<R_HEAD>(0ull);
+                const bool stepping = busy;
                 if (busy) {
                     if (st.step(p)) busy = false;
                 }
+                if constexpr (STATS && Q == Q_CLOUD) cloud_stats(st, stepping);
                 tick<R_STEP>(n_step);
                 trips++;
                 idle_acc += (uint32_t)(64 - __popcll(__ballot(busy)));
@@ -784,7 +798,11 @@ DE_V6_STAGE v6_stage_cloud() {
     using namespace bs;
     Wave<CLAMP, STATS> W = Wave<CLAMP, STATS>::enter();
     const RenderArgs& a = *W.A.ra;
+#ifndef DE_NO_CLOUD_BOUND
+    CloudStage<CLAMP, true> st{uni_tex(a.clouds), uni_ptr(a.cloud_bound)};      // exact density lookups only where the occupancy bound allows a cloud (de_stages.h)
+#else
     CloudStage<CLAMP> st{uni_tex(a.clouds)};
+#endif
     W.template run_loop<Q_CLOUD>(st, Targets<Q_EVENT, Q_SCFIN, Q_SURFFIN>{});
 }
 DE_V6_STAGE v6_stage_event() {

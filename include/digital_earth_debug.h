@@ -48,9 +48,14 @@ int de_debug_sched_stats(de_ctx* ctx, uint64_t* out, int n);
 /* The same for the per-CU stage scheduler (render_kernel_v6 with de_tuning.v6_stats = 1): [0..7] records taken per stage (sphere trace, gas, cloud, event,
  * surface, volume finish, surface finish, new paths), [8..15] wave-time per stage in 10 ns ticks, [16] idle scheduler rounds, [17] stage entries, [18] failed
  * claims of free slots, [19] wave-time in the scheduler, [20] yields of a loop stage, [21] records they handed back, [22] wave-time between the end of the work
- * items and the wave's exit, [32..38] wave-trips of the loop stages / passes of the straight-line stages, [40..46] the busy lanes summed over them;
+ * items and the wave's exit, [32..38] wave-trips of the loop stages / passes of the straight-line stages, [40..46] the busy lanes summed over them; the cloud
+ * stage's occupancy bound: [23] lane-steps that needed the exact density lookup, [31] cloud trips in which no lane did, [39] lookups of the bound map;
  * [64..127] the region statistics, [128..191] the drain's population histogram (render_kernel_v6.hip).  Profiling aid. */
 int de_debug_v6_stats(de_ctx* ctx, uint64_t* out, int n);
+/* The cloud map's occupancy bound as the cloud stage of render_kernel_v6 reads it, for the context's current address mode (built first if the map
+ * changed): 6 x N x N bytes, [face][j][i] (face = major axis x+, x-, y+, y-, z+, z-; i, j = the other two coordinates over the major one, in x, y, z
+ * order, from -1 to 1).  *cells_per_edge = N, *budget_m = the travel in metres one lookup covers.  With out = NULL only the two sizes are returned. */
+int de_debug_cloud_bound(de_ctx* ctx, uint8_t* out, uint64_t out_bytes, int* cells_per_edge, uint32_t* budget_m);
 
 /* ---- parity-test hooks
  * de_debug_samples: trace sample `sample_index` of every pixel WITHOUT accumulating; per pixel (row-major

@@ -49,6 +49,10 @@ def main():
     if any(st[24:31]):
         L += ["", "Stage entries (calls of the stage function; each re-reads its configuration from LDS; until round 6 it also saved and restored up to 24 callee-saved VGPRs through scratch): "
               + ", ".join("%s %d (%.0f records per entry)" % (STAGES[k], st[24 + k], st[k] / max(st[24 + k], 1)) for k in range(7)) + "."]
+    if st[32 + 2]:
+        L += ["", "Cloud occupancy bound: %d of %d cloud lane-steps needed the exact density lookup (%.1f %%); in %d of %d cloud trips no lane did (f = %.3f: the "
+              "whole wave branched past it); %d lookups of the bound map (one per %.1f lane-steps)."
+              % (st[23], st[42], 100.0 * st[23] / max(st[42], 1), st[31], st[34], st[31] / max(st[34], 1), st[39], st[42] / max(st[39], 1))]
     L += ["", "Yields: %d, handing back %d records (%.1f %% of the loop stages' record hops).  Drain: %.2f ms per wave between the end of the work items and the wave's exit."
           % (st[20], st[21], 100.0 * st[21] / max(st[0] + st[1] + st[2], 1), st[22] * 1e-5 / max(1, 12 * 512)), ""]
     # regions
