@@ -35,6 +35,17 @@ class DeCounters(ctypes.Structure):
         return d
 
 
+class DeAdaptive(ctypes.Structure):
+    """`de_adaptive` (include/digital_earth.h): the settings and the outputs of one round of an adaptive frame."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("threshold", ctypes.c_float), ("floor", ctypes.c_float),
+                ("min_spp", ctypes.c_int32), ("max_spp", ctypes.c_int32), ("round_spp", ctypes.c_int32),
+                ("tile_spp", ctypes.POINTER(ctypes.c_int32)), ("active_tiles", ctypes.c_int32), ("rounds", ctypes.c_int32),
+                ("pixel_samples", ctypes.c_uint64)]
+
+
+DE_ERR_INVALID = -1
+DE_ERR_STATE = -4
+
 DE_FLAG_FIXED_WAVELENGTH = 1 << 0
 DE_FLAG_CLAMP_SAMPLER = 1 << 1
 DE_FLAG_RAY_MARCHER = 1 << 2
@@ -64,6 +75,7 @@ SYMBOLS = {
     "de_upload_hdr": (ctypes.c_int, [_P, _P, ctypes.c_int]),
     "de_current_spp": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     "de_set_current_spp": (ctypes.c_int, [_P, ctypes.c_int]),
+    "de_accumulate_adaptive": (ctypes.c_int, [_P, ctypes.c_uint64, ctypes.POINTER(DeAdaptive)]),
     "de_hdr_device_ptr": (ctypes.c_int, [_P, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_uint64)]),
     "de_bind_hdr": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
     "de_set_stream": (ctypes.c_int, [_P, _P]),
@@ -88,6 +100,7 @@ SYMBOLS = {
 # measurement, experiment and test hooks: include/digital_earth_debug.h (same library)
 DEBUG_SYMBOLS = {
     "de_download_texture": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_uint64]),
+    "de_debug_adaptive_moments": (ctypes.c_int, [_P, _P]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "de_set_launch_slots": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),

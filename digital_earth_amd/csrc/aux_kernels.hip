@@ -192,6 +192,8 @@ DE_DEV vec3 agx_display_transform(const FrameConsts& k, vec3 c) {               
 }
 }  // namespace
 
+// PER_TILE (an adaptive frame, de_accumulate_adaptive): the pixel's sample count is its 8x8 tile's, not the frame's; nothing else changes
+template <bool PER_TILE>
 DE_DEV void display_pixel(const DisplayArgs& a, int i, int j, float* o) {
     const int idx = j * a.W + i;
     const FrameConsts& k = *a.fc;
@@ -200,7 +202,7 @@ DE_DEV void display_pixel(const DisplayArgs& a, int i, int j, float* o) {
     float du = u - k.vig_cx, dv = v - k.vig_cy;
     float darken = 1.0f - k.vig_strength * de_max(de_sqrt(du * du + dv * dv) - k.vig_radius, 0.0f);   // :352-354
     const float* px = a.hdr + (size_t)idx * 3;
-    float samples = (float)a.samples;
+    float samples = PER_TILE ? (float)a.tile_spp[(j >> 3) * (a.W >> 3) + (i >> 3)] : (float)a.samples;
     vec3 linear = v3(px[0] / samples, px[1] / samples, px[2] / samples) * darken * k.exposure_scale;   // :355
     if (k.use_agx) {                                                   // :356: srgb_transfer(agx.display_transform(linear))
         vec3 ax = agx_display_transform(k, linear);
@@ -222,6 +224,7 @@ DE_DEV void display_pixel(const DisplayArgs& a, int i, int j, float* o) {
 // One 256-thread block = one 32 x 32 pixel tile.  The accumulation buffer is [H][W][3] (pixels of a row contiguous), the
 // image (W, H, 3) like the reference field (pixels of a COLUMN contiguous): each thread transforms 4 pixels read along rows
 // and stages them in LDS; the tile is then written out along columns, so both sides move whole lines.
+template <bool PER_TILE>
 __global__ void __launch_bounds__(256) display_kernel(DisplayArgs a) {
     __shared__ float tile[32][32 * 3 + 1];
     const int tx = (int)threadIdx.x & 31, ty = (int)threadIdx.x >> 5;      // 32 x 8 threads
@@ -230,7 +233,7 @@ __global__ void __launch_bounds__(256) display_kernel(DisplayArgs a) {
         const int i = i0 + tx, j = j0 + ty + 8 * r;
         if (i < a.W && j < a.H) {
             float o[3];
-            display_pixel(a, i, j, o);
+            display_pixel<PER_TILE>(a, i, j, o);
             tile[ty + 8 * r][tx * 3 + 0] = o[0]; tile[ty + 8 * r][tx * 3 + 1] = o[1]; tile[ty + 8 * r][tx * 3 + 2] = o[2];
         }
     }

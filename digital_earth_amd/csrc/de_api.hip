@@ -100,11 +100,13 @@ int de_destroy(de_ctx* c) {
     release_loan(c);
     for (auto& t : c->tex) { if (t.borrowed) continue; if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); if (t.bound) hipFree(t.bound); }
     if (c->luts_borrowed) { c->d_cie = nullptr; c->d_srgb2spec = nullptr; c->d_o3 = nullptr; c->d_crf = nullptr; }
-    void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin};
+    void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin,
+                     c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
     if (c->h_issued) hipHostFree(c->h_issued);
+    if (c->h_ad_count) hipHostFree(c->h_ad_count);
 #ifdef DE_LEGACY_VARIANTS
     legacy_destroy(c);
 #endif
@@ -290,11 +292,13 @@ int de_reset(de_ctx* c) {
     note_abort(c);                         // re-arm the abort words ...
     c->frame_invalid = false;              // ... a new frame starts
     if (c->display_src == c->d_assembled) c->display_src = nullptr;    // the assembled frame of a progressive reduce is history now
+    c->frame_kind = DE_FRAME_NONE;         // the next de_accumulate or de_accumulate_adaptive starts the frame
     return DE_OK;
 }
 
 int de_accumulate(de_ctx* c, int spp, uint64_t seed, int tile_rank, int tile_world) {
     if (!c || spp < 0 || tile_world < 1 || tile_rank < 0 || tile_rank >= tile_world) return fail(DE_ERR_INVALID, "bad accumulate arguments");
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame is current (de_accumulate_adaptive): de_reset first");
     HIP_TRY(hipSetDevice(c->device));
     int rc = build_tiles(c, tile_rank, tile_world);
     if (rc) return rc;
@@ -320,6 +324,7 @@ int de_accumulate(de_ctx* c, int spp, uint64_t seed, int tile_rank, int tile_wor
 #endif
     if (rc) return rc;
     c->current_spp += frame_spp;
+    c->frame_kind = DE_FRAME_UNIFORM;
     return DE_OK;
 }
 
@@ -402,8 +407,10 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     d.fc = c->d_fc; d.hdr = c->display_src ? c->display_src : c->d_hdr; d.image = c->d_image;
     d.crf.data = c->d_crf; d.crf.w = 1024; d.crf.h = c->n_crf;
     d.W = c->W; d.H = c->H; d.samples = c->current_spp; d.clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) ? 1 : 0;
-    size_t npx = (size_t)c->W * c->H;
-    hipLaunchKernelGGL(display_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, d);
+    d.tile_spp = c->d_tile_spp;
+    const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
+    else hipLaunchKernelGGL(display_kernel<false>, grid, dim3(256), 0, c->stream, d);
     HIP_TRY(hipGetLastError());
     // what the next accumulate_kernel must wait for ends HERE (the display has read the HDR buffer): recorded now, not lazily at the next de_accumulate, so that
     // a device-to-host copy of the image enqueued behind the display (de_fetch_image_begin) does not hold the next frame's sums back
@@ -475,6 +482,7 @@ int de_fetch_hdr(de_ctx* c, float* out) {
 
 int de_upload_hdr(de_ctx* c, const float* hdr, int spp) {
     if (!c || !hdr || spp < 0) return fail(DE_ERR_INVALID, "bad arguments");
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame is current (de_accumulate_adaptive): de_reset first");
     HIP_TRY(hipSetDevice(c->device));
     size_t npx = (size_t)c->W * c->H;
     std::vector<float> t(npx * 3);
@@ -486,10 +494,107 @@ int de_upload_hdr(de_ctx* c, const float* hdr, int spp) {
     HIP_TRY(hipMemcpyAsync(c->d_hdr, t.data(), npx * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->current_spp = spp;
+    c->frame_kind = DE_FRAME_UNIFORM;
     return DE_OK;
 }
 int de_current_spp(de_ctx* c, int* spp) { if (!c || !spp) return fail(DE_ERR_INVALID, "null argument"); *spp = c->current_spp; return DE_OK; }
-int de_set_current_spp(de_ctx* c, int spp) { if (!c || spp < 0) return fail(DE_ERR_INVALID, "bad spp"); c->current_spp = spp; return DE_OK; }
+int de_set_current_spp(de_ctx* c, int spp) {
+    if (!c || spp < 0) return fail(DE_ERR_INVALID, "bad spp");
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame keeps a sample count per tile: de_reset first");
+    c->current_spp = spp;
+    return DE_OK;
+}
+
+/* One round of an adaptive frame (include/digital_earth.h).  The round is one accumulate_default call over the active list — sample indices
+ * n .. n + r - 1, spp_stride 1, accumulate_moments_kernel instead of accumulate_kernel — then, on the context stream, the convergence test and the
+ * compaction into the other list, and one host wait for the new number of active tiles (it sizes the next round's launch). */
+int de_accumulate_adaptive(de_ctx* c, uint64_t seed, de_adaptive* io) {
+    if (!c || !io) return fail(DE_ERR_INVALID, "null argument");
+    if (io->struct_bytes != (uint32_t)sizeof(de_adaptive)) return fail(DE_ERR_INVALID, "de_adaptive.struct_bytes does not match this library's struct");
+    if (io->min_spp < 2 || io->round_spp < 1 || io->min_spp > io->max_spp || !(io->threshold >= 0.0f) || !(io->floor >= 0.0f))
+        return fail(DE_ERR_INVALID, "adaptive settings: 2 <= min_spp <= max_spp, round_spp >= 1, threshold >= 0, floor >= 0");
+    if (c->frame_kind == DE_FRAME_UNIFORM) return fail(DE_ERR_STATE, "the current frame was started by de_accumulate / de_upload_hdr: de_reset first");
+    if (c->sample_world > 1) return fail(DE_ERR_STATE, "an adaptive frame does not run under a sample partition");
+    if (c->p.flags & DE_FLAG_RAY_MARCHER) return fail(DE_ERR_STATE, "the ray marcher writes the HDR buffer without per-sample records: no adaptive frame");
+    const int n_tiles = (c->W / 8) * (c->H / 8);
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->frame_kind != DE_FRAME_ADAPTIVE) {
+        // frame start: S2 zeroed, every tile active with count 0
+        if (!c->d_s2) HIP_TRY(hipMalloc(&c->d_s2, (size_t)c->W * c->H * 3 * sizeof(float)));
+        for (int k = 0; k < 2; ++k) if (!c->d_alist[k]) HIP_TRY(hipMalloc(&c->d_alist[k], (size_t)n_tiles * sizeof(uint32_t)));
+        if (!c->d_tile_spp) HIP_TRY(hipMalloc(&c->d_tile_spp, (size_t)n_tiles * sizeof(int32_t)));
+        if (!c->d_keep) HIP_TRY(hipMalloc(&c->d_keep, (size_t)n_tiles * sizeof(uint32_t)));
+        if (!c->d_ad_count) HIP_TRY(hipMalloc(&c->d_ad_count, sizeof(int32_t)));
+        if (!c->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_ad_count), sizeof(int32_t), hipHostMallocDefault));
+        { int rc = join_slots(c); if (rc) return rc; }
+        touched_hdr(c); touched_render_inputs(c);      // the launches read the list and read-modify-write S2 after this
+        HIP_TRY(hipMemsetAsync(c->d_s2, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
+        hipLaunchKernelGGL(adaptive_start_kernel, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, c->stream, c->d_alist[0], c->d_tile_spp, n_tiles);
+        HIP_TRY(hipGetLastError());
+        c->ad_cur = 0; c->ad_active = n_tiles; c->ad_n = 0; c->ad_rounds = 0; c->ad_pixel_samples = 0;
+        c->ad_seed = seed; c->ad_threshold = io->threshold; c->ad_floor = io->floor;
+        c->ad_min = io->min_spp; c->ad_max = io->max_spp; c->ad_round = io->round_spp;
+        c->current_spp = 0;
+        c->frame_kind = DE_FRAME_ADAPTIVE;
+    } else if (seed != c->ad_seed || memcmp(&io->threshold, &c->ad_threshold, sizeof(float)) != 0 || memcmp(&io->floor, &c->ad_floor, sizeof(float)) != 0 ||
+               io->min_spp != c->ad_min || io->max_spp != c->ad_max || io->round_spp != c->ad_round) {
+        return fail(DE_ERR_INVALID, "the seed and the settings of an adaptive frame are fixed until de_reset");
+    }
+    if (c->ad_active > 0) {
+        const int r = std::min(c->ad_round, c->ad_max - c->ad_n);
+        RenderArgs a;
+        int rc = fill_render_args(c, &a);
+        if (rc) return rc;
+        a.tiles = c->d_alist[c->ad_cur]; a.n_tiles = c->ad_active;
+        a.tiles_identity = c->ad_active == n_tiles ? 1 : 0;      // the list is stable and ascending: all tiles = the identity
+        a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+        a.spp_stride = 1;
+        rc = accumulate_default(c, a, r, c->ad_n);
+        if (rc) return rc;
+        // the test reads S1 / S2 and rewrites the counts; the compaction writes the list that no launch of this round reads
+        rc = join_slots(c);
+        if (rc) return rc;
+        touched_hdr(c); touched_render_inputs(c);
+        AdaptiveArgs t;
+        t.hdr = c->d_hdr; t.s2 = c->d_s2; t.list = c->d_alist[c->ad_cur]; t.n_active = c->ad_active;
+        t.tile_spp = c->d_tile_spp; t.keep = c->d_keep; t.W = c->W; t.tiles_x = c->W / 8;
+        t.n = c->ad_n + r; t.round = r; t.stop = t.n >= c->ad_max ? 1 : 0;
+        t.test = (t.n >= c->ad_min && c->ad_threshold > 0.0f) ? 1 : 0;      // threshold 0: no tile converges
+        t.tau2 = c->ad_threshold * c->ad_threshold; t.floor2 = c->ad_floor * c->ad_floor;
+        hipLaunchKernelGGL(adaptive_test_kernel, dim3((unsigned)(((size_t)c->ad_active * 64 + 255) / 256)), dim3(256), 0, c->stream, t);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(adaptive_compact_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_alist[c->ad_cur], c->d_keep, c->ad_active, c->d_alist[c->ad_cur ^ 1], c->d_ad_count);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->h_ad_count, c->d_ad_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));      // one wait per round: the next round's launch is sized by the count
+        rc = frame_status(c);
+        if (rc) return rc;
+        c->ad_pixel_samples += 64ull * (unsigned long long)c->ad_active * (unsigned long long)r;
+        c->ad_n += r; c->ad_rounds++;
+        c->ad_active = *c->h_ad_count;
+        c->ad_cur ^= 1;
+        c->current_spp = c->ad_n;      // de_current_spp: the largest tile count (the active tiles always hold it)
+    }
+    if (io->tile_spp) {
+        HIP_TRY(hipMemcpyAsync(io->tile_spp, c->d_tile_spp, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    io->active_tiles = c->ad_active;
+    io->rounds = c->ad_rounds;
+    io->pixel_samples = (uint64_t)c->ad_pixel_samples;
+    return DE_OK;
+}
+
+int de_debug_adaptive_moments(de_ctx* c, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (!c->d_s2) return fail(DE_ERR_STATE, "no adaptive frame has run on this context");
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = join_slots(c); if (rc) return rc; }
+    touched_hdr(c);
+    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, c->d_s2, c->d_scratch, c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    return copy_out(c, out, c->d_scratch);
+}
 
 int de_hdr_device_ptr(de_ctx* c, void** ptr, uint64_t* n_floats) {
     if (!c || !ptr) return fail(DE_ERR_INVALID, "null argument");

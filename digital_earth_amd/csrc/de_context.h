@@ -21,6 +21,7 @@
 #endif
 #include "render_kernel_v6.hip"
 #include "aux_kernels.hip"
+#include "adaptive_kernels.hip"
 
 namespace {
 
@@ -33,6 +34,8 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(DE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+enum { DE_FRAME_NONE = 0, DE_FRAME_UNIFORM = 1, DE_FRAME_ADAPTIVE = 2 };   // de_ctx::frame_kind
 
 #define DE_MAX_SLOTS 8
 #define DE_FETCH_RING 4      // de_fetch_image_begin / _end: fetches in flight (a lone one-sample launch takes ~10 ms, its longest path: 2 / 3 / 4 frames in flight run at 5.1 / 4.1 / ~3.5 ms per frame)
@@ -164,6 +167,20 @@ struct de_ctx {
 #ifdef DE_LEGACY_VARIANTS
 #include "legacy/de_ctx_legacy_members.inc"
 #endif
+    // What started the current frame (cleared by de_reset): de_accumulate / de_upload_hdr, or de_accumulate_adaptive — the two do not mix.
+    int frame_kind = 0;          // DE_FRAME_*
+    // Adaptive frame (de_accumulate_adaptive).  Allocated on first use: S2 12 B per pixel, two active lists, the tile counts and the keep flags 4 B per tile.
+    float* d_s2 = nullptr;           // [H][W][3] per-pixel sums of squares, accumulated by accumulate_moments_kernel
+    uint32_t* d_alist[2] = {nullptr, nullptr};   // active tile lists, ascending; a round's launches read alist[ad_cur], its compaction writes the other one
+    int32_t* d_tile_spp = nullptr;   // [H/8][W/8] samples per tile (the per-tile display reads it)
+    uint32_t* d_keep = nullptr;      // [active] flags of the convergence test
+    int32_t* d_ad_count = nullptr;   // tiles still active after the compaction ...
+    int32_t* h_ad_count = nullptr;   // ... and its pinned host copy: the host sizes the next round's launch with it
+    int ad_cur = 0, ad_active = 0, ad_n = 0, ad_rounds = 0;      // list in use, tiles active, samples of every active tile, rounds so far
+    unsigned long long ad_pixel_samples = 0;
+    uint64_t ad_seed = 0;
+    float ad_threshold = 0.f, ad_floor = 0.f;
+    int ad_min = 0, ad_max = 0, ad_round = 0;
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

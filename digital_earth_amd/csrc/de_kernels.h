@@ -140,4 +140,5 @@ struct DisplayArgs {
     float* image;       // (W, H, 3)
     TexF3 crf;
     int W, H, samples, clamp;
+    const int32_t* tile_spp;   // display_kernel<true> (an adaptive frame): per-tile sample counts [H/8][W/8] instead of `samples`
 };

@@ -308,6 +308,14 @@ int frame_status(de_ctx* c) {
     return c->frame_invalid ? fail(DE_ERR_HIP, c->invalid_msg) : DE_OK;
 }
 
+// The second half of a records launch: accumulate_kernel, or inside an adaptive frame accumulate_moments_kernel — the same sums, plus the frame's
+// sums of squares (adaptive_kernels.hip).  Ordered like the other through `pre_acc` and the slot events.
+hipError_t launch_accumulate(de_ctx* c, const RenderArgs& a, dim3 grid, dim3 block, hipStream_t stream) {
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) hipLaunchKernelGGL(accumulate_moments_kernel, grid, block, 0, stream, a, c->d_s2);
+    else hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
 // One launch on `stream`.  v2 (the default path tracer): render_kernel_v2 writes the per-sample records, then — after `pre_acc`
 // has made the stream wait for the previous launch's accumulate_kernel and for context-stream work on the HDR buffer — accumulate_kernel
 // adds them to the HDR buffer.  The other kernels read-modify-write the HDR buffer themselves: `pre_acc` runs before them.
@@ -322,8 +330,7 @@ hipError_t launch_render(de_ctx* c, const RenderArgs& a, hipStream_t stream, Pre
         if (el != hipSuccess) return el;
         hipError_t pe = pre_acc();
         if (pe != hipSuccess) return pe;
-        hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, stream, a);
-        return hipGetLastError();
+        return launch_accumulate(c, a, grid, block, stream);
     }
 #endif
     if (!march && c->launch_variant == 6 && MODE == 0) {
@@ -331,8 +338,7 @@ hipError_t launch_render(de_ctx* c, const RenderArgs& a, hipStream_t stream, Pre
         if (e6 != hipSuccess) return e6;
         hipError_t pe = pre_acc();
         if (pe != hipSuccess) return pe;
-        hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, stream, a);
-        return hipGetLastError();
+        return launch_accumulate(c, a, grid, block, stream);
     }
     if (!march && c->launch_variant != 1) {
         // persistent waves pulling pixels from a device-wide counter: size the grid to the machine, not to the image
@@ -354,7 +360,7 @@ hipError_t launch_render(de_ctx* c, const RenderArgs& a, hipStream_t stream, Pre
         if (MODE != 2) {
             hipError_t pe = pre_acc();
             if (pe != hipSuccess) return pe;
-            hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, stream, a);
+            return launch_accumulate(c, a, grid, block, stream);
         }
         return hipGetLastError();
     }

@@ -104,6 +104,7 @@ int de_comm_destroy(de_ctx* c) {
 namespace {
 int reduce_impl(de_ctx* c, void* comm, int root, bool progressive) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame is one GPU's (de_accumulate_adaptive): nothing to reduce");
     void* use = comm ? comm : c->comm;
     if (!use) return fail(DE_ERR_STATE, "no communicator: pass an ncclComm_t or call de_comm_init");
     if (root < 0 || (!comm && root >= c->comm_world)) return fail(DE_ERR_INVALID, "root out of range");
@@ -175,6 +176,7 @@ int launch_ordered_sum(de_ctx* c, int world, int root, bool out_of_place) {
 }
 int reduce_ordered_impl(de_ctx* c, void* comm, int root, bool out_of_place) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame is one GPU's (de_accumulate_adaptive): nothing to reduce");
     void* use = comm ? comm : c->comm;
     if (!use) return fail(DE_ERR_STATE, "no communicator: pass an ncclComm_t or call de_comm_init");
     int rc = load_rccl();

@@ -212,6 +212,17 @@ class EarthViewer:
         self._image = self.renderer.fetch_image()
         return self._image
 
+    def render_to_noise(self, threshold, max_spp, min_spp=16, round_spp=16, floor=None):
+        """Adaptive sampling (Renderer.render_adaptive): a NEW frame in which every 8x8 tile is rendered until its noise converges — its standard error
+        below `threshold` times the luminance, floored at `floor` (default Renderer's ADAPTIVE_FLOOR) — or until `max_spp`.  Returns the image;
+        self.last_adaptive holds dict(rounds, pixel_samples, mean_spp)."""
+        r = self.renderer
+        r.reset_framebuffer()
+        kw = {} if floor is None else {"floor": floor}
+        self.last_adaptive = r.render_adaptive(threshold, max_spp, min_spp=min_spp, round_spp=round_spp, **kw)
+        self._image = r.fetch_image()
+        return self._image
+
     def frame(self, spp=1, copy=True, pipelined=False, **sliders):
         """ONE iteration of the reference's window loop (earth_viewer.py:203-317), with the GUI sliders passed as keywords
         (sun_angle, sun_path_rot, fov, aspect_scale, exposure, selected_crf, gamma):
@@ -276,9 +287,13 @@ class EarthViewer:
         a = (np.clip(self._image, 0.0, 1.0) * 255).astype(np.uint8)        # Renderer.to_vec3u
         Image.fromarray(a.transpose(1, 0, 2)[::-1]).save(path)
 
-    def start(self, spp=64, out="screenshot/earth.png"):
-        """Reference entry point (main.py:4).  Headless: render one frame and save it."""
+    def start(self, spp=64, out="screenshot/earth.png", noise=None):
+        """Reference entry point (main.py:4).  Headless: render one frame and save it.  noise=None: `spp` samples per pixel; noise = a threshold:
+        adaptive sampling up to `spp` per pixel (render_to_noise)."""
         os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
-        self.render(spp)
+        if noise is not None:
+            self.render_to_noise(float(noise), int(spp))
+        else:
+            self.render(spp)
         self.save(out)
         return out

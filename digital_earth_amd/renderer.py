@@ -19,7 +19,14 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, check
+from ._native import DeParams, DeCounters, DeAdaptive, DigitalEarthError, check
+
+# Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
+# with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
+# pixels that show the Earth or its atmosphere has its 10th percentile at 0.018 / 0.013 / 0.0027 / 0.0085 (default camera, florida, sunset hurricane,
+# Apollo 11; median 0.011) and its median at 0.033 / 0.022 / 0.016 / 0.024.  0.01 sits at about the dark tenth of the lit pixels: darker pixels (night
+# side, deep shadow, space) are held to an absolute standard error of threshold x 0.01 instead of a relative one that would never be reached near zero.
+ADAPTIVE_FLOOR = 0.01
 
 
 class _ScalarField:
@@ -116,6 +123,7 @@ class Renderer:
                                                  cloud_heavy, synth_seed)
         self._textures_copied = False
         self._bound = None           # (tensor, stream) kept alive while the context points at them (parallel.DistributedFrame)
+        self._adaptive = None        # the current adaptive frame's outputs after its last round (accumulate_adaptive); None in a uniform frame
 
         # LUTs (renderer.py:96-134)
         self.crf_names = []
@@ -380,6 +388,7 @@ class Renderer:
     def reset_framebuffer(self):
         self.current_spp = 0
         check(self._lib.de_reset(self._h))
+        self._adaptive = None
 
     def accumulate(self, spp=1):
         """renderer.py:371-380, `spp` times in one launch (the reference's accumulate() is spp = 1)."""
@@ -387,6 +396,53 @@ class Renderer:
             self.copy_textures()
         check(self._lib.de_accumulate(self._h, int(spp), self.seed, self.tile_rank, self.tile_world))
         self.current_spp += int(spp)
+
+    # ------------------------------------------------------------------ adaptive sampling (include/digital_earth.h: de_accumulate_adaptive)
+    def accumulate_adaptive(self, threshold, max_spp, min_spp=16, round_spp=16, floor=ADAPTIVE_FLOOR):
+        """One round of an adaptive frame: every 8x8 tile still active gets `round_spp` more samples (never past `max_spp`), then the tiles whose
+        noise has converged leave.  A tile stays while some pixel's standard error, in some channel, exceeds `threshold` times the pixel's luminance
+        floored at `floor` (HDR units); it stops at `max_spp` at the latest.  A tile that stopped at n samples holds the bits of a uniform n-spp frame.
+        The first call after reset_framebuffer() starts the frame; threshold, spp settings, floor and seed stay fixed until the next reset.
+        Returns the number of tiles still active (0: the frame is finished; further calls render nothing).  current_spp follows the largest tile
+        count; tile_spp() has every tile's."""
+        if not self._textures_copied:
+            self.copy_textures()
+        if self.tile_world > 1:
+            raise DigitalEarthError(_native.DE_ERR_STATE, "an adaptive frame covers the whole image: no tile partition")
+        W, H = self.image_res
+        counts = np.empty((H // 8, W // 8), dtype=np.int32)
+        io = DeAdaptive()
+        io.struct_bytes = ctypes.sizeof(DeAdaptive)
+        io.threshold, io.floor = float(threshold), float(floor)
+        io.min_spp, io.max_spp, io.round_spp = int(min_spp), int(max_spp), int(round_spp)
+        io.tile_spp = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        check(self._lib.de_accumulate_adaptive(self._h, ctypes.c_uint64(self.seed), ctypes.byref(io)))
+        self._adaptive = dict(active_tiles=int(io.active_tiles), rounds=int(io.rounds), pixel_samples=int(io.pixel_samples), tile_spp=counts)
+        spp = ctypes.c_int()
+        check(self._lib.de_current_spp(self._h, ctypes.byref(spp)))
+        self.current_spp = int(spp.value)
+        return int(io.active_tiles)
+
+    def render_adaptive(self, threshold, max_spp, min_spp=16, round_spp=16, floor=ADAPTIVE_FLOOR):
+        """accumulate_adaptive() until no tile is active.  Returns dict(rounds, pixel_samples, mean_spp) — mean_spp = pixel_samples / (W H)."""
+        while self.accumulate_adaptive(threshold, max_spp, min_spp=min_spp, round_spp=round_spp, floor=floor) > 0:
+            pass
+        a = self._adaptive
+        return dict(rounds=a["rounds"], pixel_samples=a["pixel_samples"], mean_spp=a["pixel_samples"] / float(self.image_res[0] * self.image_res[1]))
+
+    def tile_spp(self):
+        """Samples per 8x8 tile, int32 (W/8, H/8) in fetch_image's (u, v) orientation: the adaptive frame's counts after its last round, or
+        current_spp everywhere in a uniform frame."""
+        W, H = self.image_res
+        if getattr(self, "_adaptive", None) is None:
+            return np.full((W // 8, H // 8), self.current_spp, dtype=np.int32)
+        return np.ascontiguousarray(self._adaptive["tile_spp"].T)
+
+    def adaptive_moments(self):
+        """Per-pixel sums of squares of the last adaptive frame, (W, H, 3) float32 (include/digital_earth_debug.h)."""
+        out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
+        check(self._lib.de_debug_adaptive_moments(self._h, out.ctypes.data))
+        return out
 
     def _staging_view(self, ptr):
         view = np.ctypeslib.as_array(ptr, shape=(self.image_res[0], self.image_res[1], 3)).view(_StagingView)
@@ -626,7 +682,10 @@ class Renderer:
 
     def save_checkpoint(self, path):
         """Persist the progressive state — HDR sums, sample count, RNG base seed and the scalar parameters — so that a long
-        render (BASELINE cfg5: 1024 spp) can be resumed.  The reference keeps this state in memory only (renderer.py:23,25)."""
+        render (BASELINE cfg5: 1024 spp) can be resumed.  The reference keeps this state in memory only (renderer.py:23,25).
+        An adaptive frame (accumulate_adaptive) has no checkpoint: its state is a sample count per tile."""
+        if getattr(self, "_adaptive", None) is not None:
+            raise RuntimeError("an adaptive frame cannot be checkpointed: finish it, or reset_framebuffer()")
         np.savez(path, hdr=self.fetch_hdr(), spp=np.int64(self.current_spp), seed=np.uint64(self.seed),
                  params=np.frombuffer(bytes(self._params), dtype=np.uint8), image_res=np.array(self.image_res))
 

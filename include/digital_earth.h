@@ -31,7 +31,7 @@ extern "C" {
  * legacy library (digital_earth_legacy.h); an abort of a persistent launch is sticky until de_reset.  6 (round 6): the measurement, experiment and test hooks
  * (timers, counters, statistics, de_debug_*, map read-back, de_set_kernel_variant / _launch_slots / _wave_budget / _memory_budget) are declared in
  * digital_earth_debug.h — still exported, no longer in the binder's header; de_fetch_image_begin / _end (the window loop pipelined), de_tuning.v6_cu_withhold,
- * de_debug_ordered_sum, de_debug_standin_reduce added. */
+ * de_debug_ordered_sum, de_debug_standin_reduce added; later additions only, still 6: de_accumulate_adaptive, de_debug_adaptive_moments. */
 #define DE_ABI_VERSION 6
 /* version of the arithmetic contract the kernels and the oracle implement: golden vectors are tied to it */
 #define DE_ARITHMETIC_CONTRACT 2
@@ -165,6 +165,34 @@ int de_fetch_hdr(de_ctx* ctx, float* out);
 int de_upload_hdr(de_ctx* ctx, const float* hdr, int spp);
 int de_current_spp(de_ctx* ctx, int* spp);
 int de_set_current_spp(de_ctx* ctx, int spp);
+
+/* ADAPTIVE SAMPLING: stop rendering an 8x8 tile once its noise has converged.  An adaptive frame runs in rounds; each call is one round:
+ * every tile still ACTIVE gets round_spp more samples (the last round is clamped so that no tile passes max_spp), then each active tile is tested and
+ * the converged ones leave for good.  So the active tiles always share one count n, a round renders sample indices n .. n + r - 1 of exactly those
+ * tiles, and a tile that stopped at n samples holds the same bits — HDR sums and displayed image — as a uniform n-spp frame of the same seed.
+ * Test, per pixel and channel c, once n >= min_spp:  mean_c = S1_c / n,  var_c = max(0, (S2_c - S1_c mean_c) / (n - 1)),
+ * Y = 0.2126 mean_r + 0.7152 mean_g + 0.0722 mean_b (S1 = the HDR sums, S2 = the sums of squares of the same per-sample RGB).  The tile stays active iff
+ * some pixel and channel has var_c > threshold^2 n (Y^2 + floor^2) — the standard error exceeds `threshold` times the luminance floored at `floor` —
+ * and n < max_spp.  threshold = 0: the test never runs, no tile converges, the frame equals the uniform max_spp frame.
+ *   Frame start: the first call after de_reset (or de_create) starts the frame: every tile active, counts 0, S2 zeroed.  The seed and the settings are
+ * the frame's: another seed or other settings before the next de_reset give DE_ERR_INVALID.  A call after the frame has finished renders nothing and
+ * returns the same outputs.  Each round waits for its result on the host (one synchronisation per round: rounds do not overlap).
+ *   Inside an adaptive frame de_current_spp answers the largest tile count and the display (de_fetch_image, _view, _begin, de_render_to_image) divides
+ * every tile by its own count; de_fetch_hdr is unchanged (the sums).  DE_ERR_STATE: this call in a frame that de_accumulate or de_upload_hdr started,
+ * with a sample partition (world > 1) or DE_FLAG_RAY_MARCHER; de_accumulate, de_upload_hdr, de_set_current_spp, de_reduce, de_reduce_progressive and
+ * de_reduce_ordered inside an adaptive frame.  The frame covers the whole image (no tile partition) and runs the product's kernels.
+ * Memory, allocated on first use: 12 bytes per pixel + 16 bytes per tile. */
+typedef struct de_adaptive {
+    uint32_t struct_bytes;   /* sizeof(de_adaptive) of the caller; checked like de_tuning */
+    float threshold;         /* tau >= 0: relative standard error at which a tile stops */
+    float floor;             /* >= 0: luminance floor, HDR units (dark pixels stop at an absolute error of threshold x floor) */
+    int32_t min_spp, max_spp, round_spp;   /* 2 <= min_spp <= max_spp, round_spp >= 1 */
+    int32_t* tile_spp;       /* optional host array [H/8][W/8]: filled with every tile's count after the round */
+    int32_t active_tiles;    /* out: tiles still active after this round (0: the frame is finished) */
+    int32_t rounds;          /* out: rounds of this frame so far */
+    uint64_t pixel_samples;  /* out: samples rendered in this frame, summed over pixels */
+} de_adaptive;
+int de_accumulate_adaptive(de_ctx* ctx, uint64_t seed, de_adaptive* io);
 
 /* Multi-GPU plumbing (no reference counterpart): the HDR buffer's device address and element count
  * (row-major [H][W][3] f32), so that the host can wrap it as a tensor and sum it across ranks with RCCL, and the

@@ -68,6 +68,9 @@ int de_debug_samples(de_ctx* ctx, uint64_t seed, int sample_index, float* out);
 int de_debug_math(de_ctx* ctx, int fn, const float* a, const float* b, float* out, uint64_t n);
 /* Read a map back as uploaded (row-major, `channels` bytes per texel) — lets tests hand the same texels to the oracle. */
 int de_download_texture(de_ctx* ctx, int slot, uint8_t* out, uint64_t out_bytes);
+/* The per-pixel sums of squares S2 of the last adaptive frame (de_accumulate_adaptive), (W, H, 3) f32 in de_fetch_hdr's layout.  DE_ERR_STATE before the
+ * context's first adaptive frame. */
+int de_debug_adaptive_moments(de_ctx* ctx, float* out);
 int de_texture_info(de_ctx* ctx, int slot, int* width, int* height, int* channels);
 
 /* ---- the N-rank collectives' device code on ONE GPU
