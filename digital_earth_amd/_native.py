@@ -43,6 +43,11 @@ class DeAdaptive(ctypes.Structure):
                 ("pixel_samples", ctypes.c_uint64)]
 
 
+class DeDenoise(ctypes.Structure):
+    """`de_denoise` (include/digital_earth_denoise.h): the denoiser's settings."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("levels", ctypes.c_int32), ("sigma_luminance", ctypes.c_float)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -101,6 +106,7 @@ SYMBOLS = {
 DEBUG_SYMBOLS = {
     "de_download_texture": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_uint64]),
     "de_debug_adaptive_moments": (ctypes.c_int, [_P, _P]),
+    "de_debug_denoise": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_float, _P]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "de_set_launch_slots": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
@@ -120,6 +126,14 @@ DEBUG_SYMBOLS = {
     "de_debug_math": (ctypes.c_int, [_P, ctypes.c_int, _P, _P, _P, ctypes.c_uint64]),
     "de_debug_ordered_sum": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P]),
     "de_debug_standin_reduce": (ctypes.c_int, [_P, ctypes.c_int]),
+}
+
+# the denoiser: include/digital_earth_denoise.h (same library, additions only; not part of the binder's header)
+DENOISE_SYMBOLS = {
+    "de_set_denoise": (ctypes.c_int, [_P, ctypes.POINTER(DeDenoise)]),
+    "de_get_denoise": (ctypes.c_int, [_P, ctypes.POINTER(DeDenoise)]),
+    "de_fetch_denoised_hdr": (ctypes.c_int, [_P, _P]),
+    "de_fetch_guides": (ctypes.c_int, [_P, _P]),
 }
 
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
@@ -201,7 +215,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

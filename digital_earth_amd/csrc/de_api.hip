@@ -2,6 +2,7 @@
 // No CPU fallback exists: every entry point needs a HIP device.  The launches are in de_launch.h, the collectives in de_rccl.h, the context in
 // de_context.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS (legacy/).
 #include "de_rccl.h"
+#include "../../include/digital_earth_denoise.h"
 
 namespace {
 // A launch slot's stream.  withhold > 0: the stream may use every CU but the LAST `withhold` of each XCD (hipExtStreamCreateWithCUMask; bit i of the mask is
@@ -15,6 +16,75 @@ hipError_t create_slot_stream(de_ctx* c, hipStream_t* out) {
     memset(mask, 0, sizeof(mask));
     for (int i = 0; i < keep && i < 512; ++i) mask[i >> 5] |= 1u << (i & 31);
     return hipExtStreamCreateWithCUMask(out, (uint32_t)((n + 31) / 32), mask);
+}
+
+// ---- the denoiser (include/digital_earth_denoise.h, denoise_kernels.hip)
+int denoise_refusal(de_ctx* c) {
+    if (c->tiles_world > 1) return fail(DE_ERR_STATE, "the denoiser filters whole frames: not under a tile partition");
+    if (c->sample_world > 1) return fail(DE_ERR_STATE, "the denoiser filters whole frames: not under a sample partition");
+    if (c->display_src) return fail(DE_ERR_STATE, "the denoiser filters this context's own frame: not with a display source or after de_reduce_progressive");
+    return DE_OK;
+}
+int dn_alloc(de_ctx* c) {
+    const size_t npx = (size_t)c->W * c->H;
+    if (!c->d_dn_nc) HIP_TRY(hipMalloc(&c->d_dn_nc, npx * sizeof(float4)));
+    if (!c->d_dn_at) HIP_TRY(hipMalloc(&c->d_dn_at, npx * sizeof(float4)));
+    if (!c->d_dn_dist) HIP_TRY(hipMalloc(&c->d_dn_dist, npx * sizeof(float)));
+    for (int k = 0; k < 2; ++k) if (!c->d_dn_buf[k]) HIP_TRY(hipMalloc(&c->d_dn_buf[k], npx * sizeof(float4)));
+    if (!c->d_dn_out) HIP_TRY(hipMalloc(&c->d_dn_out, npx * 3 * sizeof(float)));
+    return DE_OK;
+}
+DenoiseGuides dn_guides(de_ctx* c) { DenoiseGuides g; g.nc = c->d_dn_nc; g.at = c->d_dn_at; g.dist = c->d_dn_dist; return g; }
+dim3 dn_grid(de_ctx* c) { return dim3((unsigned)((c->W + 15) / 16), (unsigned)((c->H + 15) / 16)); }
+// The guides of the current camera, maps and address mode: once per frame (de_reset, a map or a camera change clears them).
+int dn_ensure_guides(de_ctx* c) {
+    int rc = dn_alloc(c);
+    if (rc) return rc;
+    if (c->dn_guides_valid) return DE_OK;
+    RenderArgs a;
+    rc = fill_render_args(c, &a);          // packs the maps and rebuilds the frame constants if needed
+    if (rc) return rc;
+    if (c->p.flags & DE_FLAG_CLAMP_SAMPLER) hipLaunchKernelGGL(guide_kernel<true>, dn_grid(c), dim3(256), 0, c->stream, a, dn_guides(c));
+    else hipLaunchKernelGGL(guide_kernel<false>, dn_grid(c), dim3(256), 0, c->stream, a, dn_guides(c));
+    HIP_TRY(hipGetLastError());
+    c->dn_guides_valid = true;
+    return DE_OK;
+}
+// The a-trous levels over d_dn_buf[1] (colour, variance); the last one also writes the filtered mean to d_dn_out.  Returns the buffer that holds the result.
+int dn_levels(de_ctx* c, int levels, float sigma_l, float4** result) {
+    AtrousArgs t;
+    t.g = dn_guides(c); t.W = c->W; t.H = c->H; t.sigma_l = sigma_l;
+    int cur = 1;
+    for (int l = 0; l < levels; ++l) {
+        t.in = c->d_dn_buf[cur]; t.out = c->d_dn_buf[cur ^ 1]; t.step = 1 << l;
+        t.out3 = l == levels - 1 ? c->d_dn_out : nullptr;
+        hipLaunchKernelGGL(atrous_kernel, dn_grid(c), dim3(256), 0, c->stream, t);
+        HIP_TRY(hipGetLastError());
+        cur ^= 1;
+    }
+    *result = c->d_dn_buf[cur];
+    return DE_OK;
+}
+// The frame's filtered mean into d_dn_out, on the context stream (the caller has joined the launch slots and marked the HDR buffer as read).
+// Variance source: the per-pixel estimate from S2 when S2 is complete and the pixel has n >= 4 samples, else the 7x7 spatial estimate.
+int run_denoise(de_ctx* c) {
+    int rc = dn_ensure_guides(c);
+    if (rc) return rc;
+    DenoisePrepArgs pa;
+    const bool adaptive = c->frame_kind == DE_FRAME_ADAPTIVE;
+    pa.s1 = c->display_src ? c->display_src : c->d_hdr;
+    pa.s2 = (c->dn_s2_complete || adaptive) ? c->d_s2 : nullptr;
+    pa.tile_spp = adaptive ? c->d_tile_spp : nullptr;
+    pa.spp = c->current_spp; pa.W = c->W; pa.H = c->H; pa.out = c->d_dn_buf[0];
+    hipLaunchKernelGGL(prep_mean_kernel, dn_grid(c), dim3(256), 0, c->stream, pa);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prep_spatial_kernel, dn_grid(c), dim3(256), 0, c->stream, (const float4*)c->d_dn_buf[0], c->d_dn_buf[1], c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    float4* res = nullptr;
+    rc = dn_levels(c, c->dn_levels, c->dn_sigma_l, &res);
+    if (rc) return rc;
+    c->dn_out_valid = true;
+    return DE_OK;
 }
 }  // namespace
 
@@ -101,7 +171,8 @@ int de_destroy(de_ctx* c) {
     for (auto& t : c->tex) { if (t.borrowed) continue; if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); if (t.bound) hipFree(t.bound); }
     if (c->luts_borrowed) { c->d_cie = nullptr; c->d_srgb2spec = nullptr; c->d_o3 = nullptr; c->d_crf = nullptr; }
     void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin,
-                     c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count};
+                     c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
+                     c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
@@ -141,6 +212,7 @@ int de_upload_texture(de_ctx* c, int slot, const uint8_t* texels, int w, int h, 
     HIP_TRY(hipMemcpyAsync(c->tex[slot].linear, texels, (size_t)w * h * channels, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->tex[slot].set = true;
+    c->dn_guides_valid = false;
     if (slot == DE_TEX_TOPOGRAPHY) c->params_dirty = true;
     return DE_OK;
 }
@@ -155,6 +227,7 @@ int de_generate_texture(de_ctx* c, int slot, int w, int h, uint32_t seed, int va
     hipLaunchKernelGGL(synth_kernel, grid, dim3(256), 0, c->stream, c->tex[slot].linear, slot, w, h, seed, variant);
     HIP_TRY(hipGetLastError());
     c->tex[slot].set = true;
+    c->dn_guides_valid = false;
     if (slot == DE_TEX_TOPOGRAPHY) c->params_dirty = true;
     return DE_OK;
 }
@@ -190,6 +263,7 @@ int de_share_textures(de_ctx* dst, de_ctx* src) {
     dst->params_dirty = true; dst->nodes_dirty = true;
     // the loan is on record: while it lasts the lender refuses to free, replace or repack its maps and LUTs, and to be destroyed
     dst->lender = src; src->loans++;
+    dst->dn_guides_valid = false;
     touched_render_inputs(dst);
     return DE_OK;
 }
@@ -270,6 +344,9 @@ int de_upload_luts(de_ctx* c, const float* cie, const uint16_t* srgb2spec_f16, c
 int de_set_params(de_ctx* c, const de_params* p) {
     if (!c || !p) return fail(DE_ERR_INVALID, "null argument");
     if (p->flags != c->p.flags || memcmp(&p->fixed_wavelength, &c->p.fixed_wavelength, sizeof(float)) != 0) c->nodes_dirty = true;
+    // the denoiser's guides depend on the camera, the terrain scale and the address mode; exposure, CRF, gamma and the vignette do not
+    if (memcmp(p->camera_pos, c->p.camera_pos, 11 * sizeof(float)) != 0 || memcmp(&p->land_height_scale, &c->p.land_height_scale, sizeof(float)) != 0 ||
+        ((p->flags ^ c->p.flags) & DE_FLAG_CLAMP_SAMPLER) != 0u || p->topo_res_override != c->p.topo_res_override) c->dn_guides_valid = false;
     c->p = *p;
     c->params_dirty = true;
     return DE_OK;
@@ -288,6 +365,13 @@ int de_reset(de_ctx* c) {
     HIP_TRY(hipMemsetAsync(c->d_hdr, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
     HIP_TRY(hipMemsetAsync(c->d_counters, 0, DE_N_COUNTERS * sizeof(unsigned long long), c->stream));
     memset(&c->counters, 0, sizeof(c->counters));
+    c->dn_guides_valid = false; c->dn_out_valid = false;
+    c->dn_s2_complete = false;
+    if (c->dn_on) {                        // the denoiser tracks S2 from the frame's first sample on (zeroed before the first accumulate: same stream, touched_hdr above)
+        if (!c->d_s2) HIP_TRY(hipMalloc(&c->d_s2, (size_t)c->W * c->H * 3 * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(c->d_s2, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
+        c->dn_s2_complete = true;
+    }
     c->current_spp = 0;
     note_abort(c);                         // re-arm the abort words ...
     c->frame_invalid = false;              // ... a new frame starts
@@ -317,6 +401,8 @@ int de_accumulate(de_ctx* c, int spp, uint64_t seed, int tile_rank, int tile_wor
         spp = first_index < c->current_spp + frame_spp ? (c->current_spp + frame_spp - first_index + c->sample_world - 1) / c->sample_world : 0;
     }
     a.spp_stride = c->sample_world;
+    // S2 stays complete only while every sample goes through accumulate_moments_kernel (launch_accumulate): the denoiser on, no ray marcher, no per-lane loops
+    if (!c->dn_on || (c->p.flags & DE_FLAG_RAY_MARCHER) || c->kernel_variant == 1) c->dn_s2_complete = false;
 #ifdef DE_LEGACY_VARIANTS
     rc = accumulate_legacy(c, a, spp, first_index);
 #else
@@ -400,16 +486,19 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     HIP_TRY(hipSetDevice(c->device));
     int rc = run_setup(c);
     if (rc) return rc;
+    if (c->dn_on) { rc = denoise_refusal(c); if (rc) return rc; }
     rc = join_slots(c);
     if (rc) return rc;
     touched_hdr(c);              // the next accumulate_kernel must not overwrite what this reads
+    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }       // the filter reads S1 and S2: before ev_main below
     DisplayArgs d;
     d.fc = c->d_fc; d.hdr = c->display_src ? c->display_src : c->d_hdr; d.image = c->d_image;
     d.crf.data = c->d_crf; d.crf.w = 1024; d.crf.h = c->n_crf;
     d.W = c->W; d.H = c->H; d.samples = c->current_spp; d.clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) ? 1 : 0;
     d.tile_spp = c->d_tile_spp;
+    if (c->dn_on) { d.hdr = c->d_dn_out; d.samples = 1; }          // the filtered MEAN through the unchanged transform: x / 1.0f == x
     const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
-    if (c->frame_kind == DE_FRAME_ADAPTIVE) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
+    if (c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
     else hipLaunchKernelGGL(display_kernel<false>, grid, dim3(256), 0, c->stream, d);
     HIP_TRY(hipGetLastError());
     // what the next accumulate_kernel must wait for ends HERE (the display has read the HDR buffer): recorded now, not lazily at the next de_accumulate, so that
@@ -495,6 +584,7 @@ int de_upload_hdr(de_ctx* c, const float* hdr, int spp) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->current_spp = spp;
     c->frame_kind = DE_FRAME_UNIFORM;
+    c->dn_s2_complete = false;             // a checkpoint has no S2: the denoiser falls back on the spatial variance
     return DE_OK;
 }
 int de_current_spp(de_ctx* c, int* spp) { if (!c || !spp) return fail(DE_ERR_INVALID, "null argument"); *spp = c->current_spp; return DE_OK; }
@@ -502,6 +592,7 @@ int de_set_current_spp(de_ctx* c, int spp) {
     if (!c || spp < 0) return fail(DE_ERR_INVALID, "bad spp");
     if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame keeps a sample count per tile: de_reset first");
     c->current_spp = spp;
+    c->dn_s2_complete = false;
     return DE_OK;
 }
 
@@ -536,6 +627,7 @@ int de_accumulate_adaptive(de_ctx* c, uint64_t seed, de_adaptive* io) {
         c->ad_min = io->min_spp; c->ad_max = io->max_spp; c->ad_round = io->round_spp;
         c->current_spp = 0;
         c->frame_kind = DE_FRAME_ADAPTIVE;
+        c->dn_s2_complete = true;          // every round runs accumulate_moments_kernel
     } else if (seed != c->ad_seed || memcmp(&io->threshold, &c->ad_threshold, sizeof(float)) != 0 || memcmp(&io->floor, &c->ad_floor, sizeof(float)) != 0 ||
                io->min_spp != c->ad_min || io->max_spp != c->ad_max || io->round_spp != c->ad_round) {
         return fail(DE_ERR_INVALID, "the seed and the settings of an adaptive frame are fixed until de_reset");
@@ -607,6 +699,7 @@ int de_bind_hdr(de_ctx* c, void* device_ptr, uint64_t n_floats) {
     HIP_TRY(hipSetDevice(c->device));
     { int rc = sync_all(c); if (rc) return rc; }
     touched_hdr(c);
+    c->dn_s2_complete = false;
     if (!device_ptr) { c->d_hdr = c->d_hdr_own; return DE_OK; }
     if (n_floats < (uint64_t)c->W * c->H * 3) return fail(DE_ERR_INVALID, "bound HDR buffer is smaller than W*H*3 floats");
     c->d_hdr = (float*)device_ptr;
@@ -842,6 +935,118 @@ int de_debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out,
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, m.dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+
+
+/* ---- the denoiser: include/digital_earth_denoise.h */
+int de_set_denoise(de_ctx* c, const de_denoise* d) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (!d) { c->dn_on = false; c->dn_out_valid = false; return DE_OK; }
+    if (d->struct_bytes != (uint32_t)sizeof(de_denoise)) return fail(DE_ERR_INVALID, "de_denoise.struct_bytes does not match this library's struct");
+    if (d->levels < 1 || d->levels > 10 || !(d->sigma_luminance > 0.0f) || !(d->sigma_luminance < 1e30f))
+        return fail(DE_ERR_INVALID, "denoiser settings: 1 <= levels <= 10, 0 < sigma_luminance < 1e30");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->dn_on) {
+        { int rc = dn_alloc(c); if (rc) return rc; }
+        if (c->frame_kind == DE_FRAME_NONE) {
+            // no sample yet: S2 starts complete (zeroed on the context stream, ordered before the frame's first accumulate)
+            if (!c->d_s2) HIP_TRY(hipMalloc(&c->d_s2, (size_t)c->W * c->H * 3 * sizeof(float)));
+            { int rc = join_slots(c); if (rc) return rc; }
+            touched_hdr(c);
+            HIP_TRY(hipMemsetAsync(c->d_s2, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
+            c->dn_s2_complete = true;
+        } else if (c->frame_kind != DE_FRAME_ADAPTIVE) {
+            c->dn_s2_complete = false;     // enabled mid-frame: the samples so far have no S2
+        }
+    }
+    c->dn_on = true; c->dn_levels = d->levels; c->dn_sigma_l = d->sigma_luminance;
+    c->dn_out_valid = false;
+    return DE_OK;
+}
+int de_get_denoise(de_ctx* c, de_denoise* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    out->struct_bytes = (uint32_t)sizeof(de_denoise);
+    out->levels = c->dn_on ? c->dn_levels : 0;
+    out->sigma_luminance = c->dn_on ? c->dn_sigma_l : 0.0f;
+    return DE_OK;
+}
+int de_fetch_denoised_hdr(de_ctx* c, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (!c->dn_on) return fail(DE_ERR_STATE, "the denoiser is off (de_set_denoise)");
+    { int rc = denoise_refusal(c); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = run_setup(c);
+    if (rc) return rc;
+    rc = join_slots(c);
+    if (rc) return rc;
+    touched_hdr(c);
+    rc = run_denoise(c);
+    if (rc) return rc;
+    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, c->d_dn_out, c->d_scratch, c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    return copy_out(c, out, c->d_scratch);
+}
+int de_fetch_guides(de_ctx* c, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = run_setup(c);
+    if (rc) return rc;
+    rc = dn_ensure_guides(c);
+    if (rc) return rc;
+    const size_t npx = (size_t)c->W * c->H;
+    std::vector<float4> nc(npx), at(npx);
+    std::vector<float> dist(npx);
+    HIP_TRY(hipMemcpyAsync(nc.data(), c->d_dn_nc, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(at.data(), c->d_dn_at, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(dist.data(), c->d_dn_dist, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < c->W; ++i)
+        for (int j = 0; j < c->H; ++j) {
+            const size_t p = (size_t)j * c->W + i;
+            float* o = out + ((size_t)i * c->H + j) * 9;
+            o[0] = nc[p].w; o[1] = dist[p]; o[2] = nc[p].x; o[3] = nc[p].y; o[4] = nc[p].z;
+            o[5] = at[p].x; o[6] = at[p].y; o[7] = at[p].z; o[8] = at[p].w;
+        }
+    return DE_OK;
+}
+int de_debug_denoise(de_ctx* c, const float* mean, const float* var, const float* guides, int levels, float sigma_l, float* out) {
+    if (!c || !mean || !var || !guides || !out || levels < 1 || levels > 10 || !(sigma_l > 0.0f)) return fail(DE_ERR_INVALID, "bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = dn_alloc(c);
+    if (rc) return rc;
+    rc = sync_all(c);
+    if (rc) return rc;
+    const size_t npx = (size_t)c->W * c->H;
+    std::vector<float4> col(npx), nc(npx), at(npx);
+    std::vector<float> dist(npx);
+    for (int i = 0; i < c->W; ++i)
+        for (int j = 0; j < c->H; ++j) {
+            const size_t p = (size_t)j * c->W + i, h = (size_t)i * c->H + j;
+            const float* m = mean + h * 3;
+            const float* g = guides + h * 9;
+            col[p] = make_float4(m[0], m[1], m[2], var[h]);
+            nc[p] = make_float4(g[2], g[3], g[4], g[0]);
+            at[p] = make_float4(g[5], g[6], g[7], g[8]);
+            dist[p] = g[1];
+        }
+    HIP_TRY(hipMemcpyAsync(c->d_dn_buf[1], col.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_dn_nc, nc.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_dn_at, at.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_dn_dist, dist.data(), npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));      // the host vectors are reused below
+    c->dn_guides_valid = false; c->dn_out_valid = false;      // the context's guides were overwritten
+    float4* res = nullptr;
+    rc = dn_levels(c, levels, sigma_l, &res);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(col.data(), res, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < c->W; ++i)
+        for (int j = 0; j < c->H; ++j) {
+            const float4 v = col[(size_t)j * c->W + i];
+            float* o = out + ((size_t)i * c->H + j) * 4;
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+        }
     return DE_OK;
 }
 

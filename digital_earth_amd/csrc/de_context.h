@@ -22,6 +22,7 @@
 #include "render_kernel_v6.hip"
 #include "aux_kernels.hip"
 #include "adaptive_kernels.hip"
+#include "denoise_kernels.hip"
 
 namespace {
 
@@ -181,6 +182,19 @@ struct de_ctx {
     uint64_t ad_seed = 0;
     float ad_threshold = 0.f, ad_floor = 0.f;
     int ad_min = 0, ad_max = 0, ad_round = 0;
+    // Denoiser (include/digital_earth_denoise.h).  Allocated on first use: guides 36 B per pixel, two (colour, variance) buffers 32 B, the
+    // filtered mean 12 B.  S2 (d_s2 above) doubles as the temporal variance source of uniform frames.
+    bool dn_on = false;
+    int dn_levels = 5;
+    float dn_sigma_l = 4.0f;
+    bool dn_s2_complete = false;    // every sample of the current frame went through accumulate_moments_kernel since the denoiser was on at its start
+    bool dn_guides_valid = false;   // the guides belong to the current camera, maps and address mode (cleared by de_reset, map changes, camera changes)
+    bool dn_out_valid = false;      // d_dn_out holds the filtered mean of the frame as last displayed
+    float4* d_dn_nc = nullptr;      // [H][W] (normal, coverage)
+    float4* d_dn_at = nullptr;      // [H][W] (albedo, cloud transmittance)
+    float* d_dn_dist = nullptr;     // [H][W]
+    float4* d_dn_buf[2] = {nullptr, nullptr};   // [H][W] (colour, variance): the levels alternate
+    float* d_dn_out = nullptr;      // [H][W][3] the filtered mean: what the display reads with samples = 1
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

@@ -308,10 +308,10 @@ int frame_status(de_ctx* c) {
     return c->frame_invalid ? fail(DE_ERR_HIP, c->invalid_msg) : DE_OK;
 }
 
-// The second half of a records launch: accumulate_kernel, or inside an adaptive frame accumulate_moments_kernel — the same sums, plus the frame's
-// sums of squares (adaptive_kernels.hip).  Ordered like the other through `pre_acc` and the slot events.
+// The second half of a records launch: accumulate_kernel, or inside an adaptive frame or while the denoiser tracks moments accumulate_moments_kernel — the
+// same sums, plus the frame's sums of squares (adaptive_kernels.hip).  Ordered like the other through `pre_acc` and the slot events.
 hipError_t launch_accumulate(de_ctx* c, const RenderArgs& a, dim3 grid, dim3 block, hipStream_t stream) {
-    if (c->frame_kind == DE_FRAME_ADAPTIVE) hipLaunchKernelGGL(accumulate_moments_kernel, grid, block, 0, stream, a, c->d_s2);
+    if (c->frame_kind == DE_FRAME_ADAPTIVE || (c->dn_on && c->dn_s2_complete)) hipLaunchKernelGGL(accumulate_moments_kernel, grid, block, 0, stream, a, c->d_s2);
     else hipLaunchKernelGGL(accumulate_kernel, grid, block, 0, stream, a);
     return hipGetLastError();
 }

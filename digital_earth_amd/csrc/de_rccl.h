@@ -105,6 +105,7 @@ namespace {
 int reduce_impl(de_ctx* c, void* comm, int root, bool progressive) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame is one GPU's (de_accumulate_adaptive): nothing to reduce");
+    c->dn_s2_complete = false;             // the sums change, this rank's S2 does not (the denoiser's per-pixel variance: DESIGN.md §10)
     void* use = comm ? comm : c->comm;
     if (!use) return fail(DE_ERR_STATE, "no communicator: pass an ncclComm_t or call de_comm_init");
     if (root < 0 || (!comm && root >= c->comm_world)) return fail(DE_ERR_INVALID, "root out of range");
@@ -177,6 +178,7 @@ int launch_ordered_sum(de_ctx* c, int world, int root, bool out_of_place) {
 int reduce_ordered_impl(de_ctx* c, void* comm, int root, bool out_of_place) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (c->frame_kind == DE_FRAME_ADAPTIVE) return fail(DE_ERR_STATE, "an adaptive frame is one GPU's (de_accumulate_adaptive): nothing to reduce");
+    c->dn_s2_complete = false;             // the sums change, this rank's S2 does not (the denoiser's per-pixel variance: DESIGN.md §10)
     void* use = comm ? comm : c->comm;
     if (!use) return fail(DE_ERR_STATE, "no communicator: pass an ncclComm_t or call de_comm_init");
     int rc = load_rccl();
@@ -219,6 +221,7 @@ int de_reduce_ordered(de_ctx* c, void* comm, int root, int out_of_place) { retur
 /* include/digital_earth_debug.h: the root's half of de_reduce_ordered with the parts coming from the host instead of ncclRecv */
 int de_debug_ordered_sum(de_ctx* c, const float* parts, int n_parts, int root, int out_of_place, float* out) {
     if (!c || !parts || !out || n_parts < 2 || n_parts > 16 || root < 0 || root >= n_parts) return fail(DE_ERR_INVALID, "de_debug_ordered_sum: 2..16 parts, 0 <= root < n_parts");
+    c->dn_s2_complete = false;
     HIP_TRY(hipSetDevice(c->device));
     int rc = join_slots(c);
     if (rc) return rc;

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -442,6 +442,52 @@ class Renderer:
         """Per-pixel sums of squares of the last adaptive frame, (W, H, 3) float32 (include/digital_earth_debug.h)."""
         out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
         check(self._lib.de_debug_adaptive_moments(self._h, out.ctypes.data))
+        return out
+
+    # ------------------------------------------------------------------ denoiser (include/digital_earth_denoise.h, DESIGN.md §10)
+    def set_denoise(self, on=True, levels=5, sigma_luminance=4.0):
+        """Turn the denoiser of the display path on (or off).  While it is on, fetch_image (every mode, lag included) returns the denoised image: an
+        edge-avoiding a-trous filter of the HDR mean guided by noise-free first-hit features, with the per-pixel variance when the frame tracked its
+        sums of squares from its first sample (turn it on before accumulating) and the 7x7 spatial variance otherwise.  fetch_hdr() is unchanged."""
+        if not on:
+            check(self._lib.de_set_denoise(self._h, None))
+            return
+        d = DeDenoise()
+        d.struct_bytes = ctypes.sizeof(DeDenoise)
+        d.levels, d.sigma_luminance = int(levels), float(sigma_luminance)
+        check(self._lib.de_set_denoise(self._h, ctypes.byref(d)))
+
+    def denoise(self):
+        """The denoiser's settings, dict(levels, sigma_luminance), or None while it is off."""
+        d = DeDenoise()
+        check(self._lib.de_get_denoise(self._h, ctypes.byref(d)))
+        return None if d.levels == 0 else dict(levels=int(d.levels), sigma_luminance=float(d.sigma_luminance))
+
+    def fetch_denoised_hdr(self):
+        """The filtered HDR mean, (W, H, 3) float32 in fetch_hdr's layout (a mean, not a sum).  The denoiser must be on."""
+        if not self._textures_copied:
+            self.copy_textures()
+        out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
+        check(self._lib.de_fetch_denoised_hdr(self._h, out.ctypes.data))
+        return out
+
+    def fetch_guides(self):
+        """The denoiser's guides, (W, H, 9) float32: coverage, distance (m), normal xyz, albedo rgb, cloud transmittance."""
+        if not self._textures_copied:
+            self.copy_textures()
+        out = np.empty((self.image_res[0], self.image_res[1], 9), dtype=np.float32)
+        check(self._lib.de_fetch_guides(self._h, out.ctypes.data))
+        return out
+
+    def debug_denoise(self, mean, var, guides, levels=5, sigma_luminance=4.0):
+        """The filter's levels on given inputs (include/digital_earth_debug.h: de_debug_denoise): mean (W, H, 3), var (W, H), guides (W, H, 9).
+        Returns (W, H, 4): filtered rgb and the carried variance."""
+        W, H = self.image_res
+        mean = np.ascontiguousarray(mean, dtype=np.float32).reshape(W, H, 3)
+        var = np.ascontiguousarray(var, dtype=np.float32).reshape(W, H)
+        guides = np.ascontiguousarray(guides, dtype=np.float32).reshape(W, H, 9)
+        out = np.empty((W, H, 4), dtype=np.float32)
+        check(self._lib.de_debug_denoise(self._h, mean.ctypes.data, var.ctypes.data, guides.ctypes.data, int(levels), float(sigma_luminance), out.ctypes.data))
         return out
 
     def _staging_view(self, ptr):

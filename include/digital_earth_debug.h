@@ -72,6 +72,10 @@ int de_download_texture(de_ctx* ctx, int slot, uint8_t* out, uint64_t out_bytes)
  * context's first adaptive frame. */
 int de_debug_adaptive_moments(de_ctx* ctx, float* out);
 int de_texture_info(de_ctx* ctx, int slot, int* width, int* height, int* channels);
+/* The denoiser's a-trous levels (include/digital_earth_denoise.h) on host-given inputs, host layout: mean (W, H, 3), var (W, H) = variance of the mean,
+ * guides (W, H, 9) as de_fetch_guides returns them; out (W, H, 4) = filtered rgb and carried variance.  Overwrites the context's guides (recomputed at the
+ * next denoised display).  For the tests' float64 restatement (tests/denoise_f64.py). */
+int de_debug_denoise(de_ctx* ctx, const float* mean, const float* var, const float* guides, int levels, float sigma_l, float* out);
 
 /* ---- the N-rank collectives' device code on ONE GPU
  * de_debug_ordered_sum: the root's half of de_reduce_ordered without a communicator.  `parts` = n_parts host buffers of W*H*3 floats each (device
