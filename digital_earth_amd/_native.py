@@ -48,6 +48,18 @@ class DeDenoise(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("levels", ctypes.c_int32), ("sigma_luminance", ctypes.c_float)]
 
 
+class DeAutoExposure(ctypes.Structure):
+    """`de_auto_exposure` (include/digital_earth_exposure.h): the settings of the metered exposure."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("key", ctypes.c_float), ("compensation", ctypes.c_float), ("ev_min", ctypes.c_float), ("ev_max", ctypes.c_float),
+                ("low_fraction", ctypes.c_float), ("high_fraction", ctypes.c_float), ("adapt", ctypes.c_float), ("region", ctypes.c_int32 * 4)]
+
+
+class DeMetering(ctypes.Structure):
+    """`de_metering` (include/digital_earth_exposure.h): what the newest display metered."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("ev", ctypes.c_float), ("ev_target", ctypes.c_float), ("mean_log2", ctypes.c_float), ("valid", ctypes.c_uint32),
+                ("metered", ctypes.c_uint64), ("below", ctypes.c_uint64), ("clipped", ctypes.c_uint64), ("histogram", ctypes.c_uint32 * 256)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -136,6 +148,13 @@ DENOISE_SYMBOLS = {
     "de_fetch_guides": (ctypes.c_int, [_P, _P]),
 }
 
+# auto-exposure: include/digital_earth_exposure.h (same library, additions only; not part of the binder's header)
+EXPOSURE_SYMBOLS = {
+    "de_set_auto_exposure": (ctypes.c_int, [_P, ctypes.POINTER(DeAutoExposure)]),
+    "de_get_auto_exposure": (ctypes.c_int, [_P, ctypes.POINTER(DeAutoExposure)]),
+    "de_get_metering": (ctypes.c_int, [_P, ctypes.POINTER(DeMetering)]),
+}
+
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
 LEGACY_SYMBOLS = {
     "de_debug_v5_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -215,7 +234,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -86,6 +86,50 @@ int run_denoise(de_ctx* c) {
     c->dn_out_valid = true;
     return DE_OK;
 }
+// ---- auto-exposure (include/digital_earth_exposure.h, exposure_kernels.hip)
+int ae_alloc(de_ctx* c) {
+    if (!c->d_ae_partial) HIP_TRY(hipMalloc(&c->d_ae_partial, (size_t)AE_MAX_WG * AE_ROW * sizeof(uint32_t)));
+    if (!c->d_ae_state) HIP_TRY(hipMalloc(&c->d_ae_state, sizeof(MeterState)));
+    if (!c->d_fc_ae) HIP_TRY(hipMalloc(&c->d_fc_ae, sizeof(FrameConsts)));
+    if (!c->d_ae_result) HIP_TRY(hipMalloc(&c->d_ae_result, sizeof(MeterResult)));
+    if (!c->d_ae_centre) {
+        // log2 of the bins' centres: bin k = octave (k >> 3) - 24, sub-bin k & 7 of 8 linear ones; uploaded once, so that the device computes no logarithm
+        double centre[AE_BINS];
+        for (int k = 0; k < AE_BINS; ++k) centre[k] = (double)((k >> 3) - 24) + log2(1.0 + ((double)(k & 7) + 0.5) / 8.0);
+        HIP_TRY(hipMalloc(&c->d_ae_centre, sizeof(centre)));
+        HIP_TRY(hipMemcpyAsync(c->d_ae_centre, centre, sizeof(centre), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));      // the table is a local: once per context, when the feature is first turned on, never in a display
+    }
+    return DE_OK;
+}
+// The two metering kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).
+int run_meter(de_ctx* c, const DisplayArgs& d, bool per_tile) {
+    const de_auto_exposure& s = c->ae;
+    const bool whole = !(s.region[0] | s.region[1] | s.region[2] | s.region[3]);
+    MeterArgs m;
+    m.hdr = d.hdr; m.tile_spp = per_tile ? d.tile_spp : nullptr; m.samples = d.samples; m.W = c->W;
+    m.x0 = whole ? 0 : s.region[0]; m.y0 = whole ? 0 : s.region[1]; m.x1 = whole ? c->W : s.region[2]; m.y1 = whole ? c->H : s.region[3];
+    m.gx0 = m.x0 >> 2; m.gw = ((m.x1 + 3) >> 2) - m.gx0;
+    const unsigned long long items = (unsigned long long)m.gw * (unsigned long long)(m.y1 - m.y0);      // at most the region's pixels
+    if ((unsigned long long)(m.x1 - m.x0) * (unsigned long long)(m.y1 - m.y0) >= (1ull << 31))
+        return fail(DE_ERR_INVALID, "the metering region must hold fewer than 2^31 pixels (the counts and the item index are 32-bit)");
+    m.n_items = (uint32_t)items;
+    m.partial = c->d_ae_partial;
+    const unsigned n_wg = (unsigned)std::min<unsigned long long>((items + 255ull) / 256ull, (unsigned long long)AE_MAX_WG);
+    if ((reinterpret_cast<uintptr_t>(d.hdr) & 15u) == 0u) hipLaunchKernelGGL(meter_hist_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, m);
+    else hipLaunchKernelGGL(meter_hist_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, m);
+    HIP_TRY(hipGetLastError());
+    MeterSolveArgs v;
+    v.partial = c->d_ae_partial; v.n_rows = (int)n_wg;
+    v.low = s.low_fraction; v.high = s.high_fraction; v.adapt = s.adapt; v.compensation = s.compensation; v.ev_min = s.ev_min; v.ev_max = s.ev_max;
+    v.manual = c->p.exposure;
+    v.log2_key = log2((double)s.key);
+    v.centre = c->d_ae_centre; v.state = c->d_ae_state; v.fc = c->d_fc; v.fc_ae = c->d_fc_ae; v.res = c->d_ae_result;
+    hipLaunchKernelGGL(meter_solve_kernel, dim3(1), dim3(1024), 0, c->stream, v);
+    HIP_TRY(hipGetLastError());
+    c->ae_displayed = true;
+    return DE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -172,7 +216,8 @@ int de_destroy(de_ctx* c) {
     if (c->luts_borrowed) { c->d_cie = nullptr; c->d_srgb2spec = nullptr; c->d_o3 = nullptr; c->d_crf = nullptr; }
     void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin,
                      c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
-                     c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out};
+                     c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
+                     c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
@@ -497,8 +542,10 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     d.W = c->W; d.H = c->H; d.samples = c->current_spp; d.clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) ? 1 : 0;
     d.tile_spp = c->d_tile_spp;
     if (c->dn_on) { d.hdr = c->d_dn_out; d.samples = 1; }          // the filtered MEAN through the unchanged transform: x / 1.0f == x
+    const bool per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
+    if (c->ae_on) { rc = run_meter(c, d, per_tile); if (rc) return rc; d.fc = c->d_fc_ae; }      // the same transform over the metered exposure: a second FrameConsts, written on the device
     const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
-    if (c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
+    if (per_tile) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
     else hipLaunchKernelGGL(display_kernel<false>, grid, dim3(256), 0, c->stream, d);
     HIP_TRY(hipGetLastError());
     // what the next accumulate_kernel must wait for ends HERE (the display has read the HDR buffer): recorded now, not lazily at the next de_accumulate, so that
@@ -1047,6 +1094,48 @@ int de_debug_denoise(de_ctx* c, const float* mean, const float* var, const float
             float* o = out + ((size_t)i * c->H + j) * 4;
             o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
         }
+    return DE_OK;
+}
+
+/* ---- auto-exposure: include/digital_earth_exposure.h */
+int de_set_auto_exposure(de_ctx* c, const de_auto_exposure* s) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (!s) { c->ae_on = false; c->ae_displayed = false; return DE_OK; }
+    if (s->struct_bytes != (uint32_t)sizeof(de_auto_exposure)) return fail(DE_ERR_INVALID, "de_auto_exposure.struct_bytes does not match this library's struct");
+    if (!(s->key > 0.0f) || !(s->key < 1e30f) || !(fabsf(s->compensation) < 1e30f) || !(fabsf(s->ev_min) < 1e30f) || !(fabsf(s->ev_max) < 1e30f) || !(s->ev_min <= s->ev_max))
+        return fail(DE_ERR_INVALID, "auto-exposure settings: 0 < key, finite compensation, finite ev_min <= ev_max");
+    if (!(s->low_fraction >= 0.0f) || !(s->low_fraction < s->high_fraction) || !(s->high_fraction <= 1.0f) || !(s->low_fraction < 1.0f))
+        return fail(DE_ERR_INVALID, "auto-exposure settings: 0 <= low_fraction < high_fraction <= 1");
+    if (!(s->adapt > 0.0f) || !(s->adapt <= 1.0f)) return fail(DE_ERR_INVALID, "auto-exposure settings: 0 < adapt <= 1");
+    const int32_t* r = s->region;
+    if ((r[0] | r[1] | r[2] | r[3]) != 0 && (r[0] < 0 || r[1] < 0 || r[2] > c->W || r[3] > c->H || r[0] >= r[2] || r[1] >= r[3]))
+        return fail(DE_ERR_INVALID, "auto-exposure region: 0 <= x0 < x1 <= width, 0 <= y0 < y1 <= height (all 0 = the whole image)");
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = ae_alloc(c); if (rc) return rc; }
+    // every call clears the adaptation state, ordered on the context stream behind the displays already enqueued
+    HIP_TRY(hipMemsetAsync(c->d_ae_state, 0, sizeof(MeterState), c->stream));
+    c->ae = *s;
+    c->ae_on = true; c->ae_displayed = false;
+    return DE_OK;
+}
+int de_get_auto_exposure(de_ctx* c, de_auto_exposure* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (c->ae_on) *out = c->ae; else memset(out, 0, sizeof(*out));
+    out->struct_bytes = (uint32_t)sizeof(de_auto_exposure);
+    return DE_OK;
+}
+int de_get_metering(de_ctx* c, de_metering* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (out->struct_bytes != (uint32_t)sizeof(de_metering)) return fail(DE_ERR_INVALID, "de_metering.struct_bytes does not match this library's struct");
+    if (!c->ae_on) return fail(DE_ERR_STATE, "auto-exposure is off (de_set_auto_exposure)");
+    if (!c->ae_displayed) return fail(DE_ERR_STATE, "nothing has been displayed since auto-exposure was turned on");
+    HIP_TRY(hipSetDevice(c->device));
+    MeterResult r;
+    HIP_TRY(hipMemcpyAsync(&r, c->d_ae_result, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    out->ev = r.ev; out->ev_target = r.target; out->mean_log2 = r.mean; out->valid = r.valid;
+    out->metered = r.n; out->below = r.below; out->clipped = r.clipped;
+    memcpy(out->histogram, r.h, sizeof(out->histogram));
     return DE_OK;
 }
 

@@ -1,6 +1,7 @@
 // de_context.h — the context behind the C ABI (include/digital_earth.h): device memory, streams, launch slots, what the launches need to know.
 #pragma once
 #include "de_kernels.h"
+#include "../../include/digital_earth_exposure.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -23,6 +24,7 @@
 #include "aux_kernels.hip"
 #include "adaptive_kernels.hip"
 #include "denoise_kernels.hip"
+#include "exposure_kernels.hip"
 
 namespace {
 
@@ -195,6 +197,16 @@ struct de_ctx {
     float* d_dn_dist = nullptr;     // [H][W]
     float4* d_dn_buf[2] = {nullptr, nullptr};   // [H][W] (colour, variance): the levels alternate
     float* d_dn_out = nullptr;      // [H][W][3] the filtered mean: what the display reads with samples = 1
+    // Auto-exposure (include/digital_earth_exposure.h).  Allocated on first use: the workgroups' partial histograms (528 KB), the bins' centres,
+    // the adaptation state, the second FrameConsts and the result block.  Per context: a context that borrows its maps meters for itself.
+    bool ae_on = false;
+    bool ae_displayed = false;      // a display has been enqueued since the feature was turned on (de_get_metering answers)
+    de_auto_exposure ae;            // the settings
+    uint32_t* d_ae_partial = nullptr;   // [AE_MAX_WG][AE_ROW]
+    double* d_ae_centre = nullptr;      // [AE_BINS]
+    MeterState* d_ae_state = nullptr;   // previous EV: survives de_reset, cleared by de_set_auto_exposure
+    FrameConsts* d_fc_ae = nullptr;     // *d_fc with the metered exposure_scale: what the display reads (d_fc itself is never written: render launches in flight read it)
+    MeterResult* d_ae_result = nullptr;
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

@@ -287,11 +287,14 @@ class EarthViewer:
         a = (np.clip(self._image, 0.0, 1.0) * 255).astype(np.uint8)        # Renderer.to_vec3u
         Image.fromarray(a.transpose(1, 0, 2)[::-1]).save(path)
 
-    def start(self, spp=64, out="screenshot/earth.png", noise=None, denoise=False):
+    def start(self, spp=64, out="screenshot/earth.png", noise=None, denoise=False, auto_exposure=False):
         """Reference entry point (main.py:4).  Headless: render one frame and save it.  noise=None: `spp` samples per pixel; noise = a threshold:
         adaptive sampling up to `spp` per pixel (render_to_noise).  denoise=True: the saved image is the denoised one (Renderer.set_denoise, turned on
-        before the frame starts so that it has the per-pixel variance)."""
+        before the frame starts so that it has the per-pixel variance).  auto_exposure=True: the saved image is exposed by the GPU meter
+        (Renderer.set_auto_exposure, default settings) instead of the configuration's hand-set exposure."""
         os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
+        if auto_exposure:
+            self.renderer.set_auto_exposure(True)
         if denoise:
             self.renderer.set_denoise(True)
             self.renderer.reset_framebuffer()

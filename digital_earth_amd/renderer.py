@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -489,6 +489,46 @@ class Renderer:
         out = np.empty((W, H, 4), dtype=np.float32)
         check(self._lib.de_debug_denoise(self._h, mean.ctypes.data, var.ctypes.data, guides.ctypes.data, int(levels), float(sigma_luminance), out.ctypes.data))
         return out
+
+    # ------------------------------------------------------------------ auto-exposure (include/digital_earth_exposure.h)
+    def set_auto_exposure(self, on=True, key=0.18, compensation=0.0, ev_range=(-8.0, 16.0), percentiles=(0.10, 0.95), adapt=1.0, region=None):
+        """Turn the metered exposure of the display path on (or off).  While it is on, every fetch_image (lag included) first meters what it shows on the
+        GPU — a histogram of log2 luminance, 8 bins per octave; the mean of the pixels between the two `percentiles` is mapped to `key`, plus `compensation`
+        EV, clamped to `ev_range` — and displays with that exposure instead of the manual one, which is kept (set_exposure, exposure[None]) and comes
+        back when the feature is turned off.  adapt < 1 eases towards the target from display to display: ev += adapt (target - ev).  region =
+        (x0, y0, x1, y1), half-open in pixels: meter that rectangle only.  Every call restarts the adaptation; reset_framebuffer() does not."""
+        if not on:
+            check(self._lib.de_set_auto_exposure(self._h, None))
+            return
+        s = DeAutoExposure()
+        s.struct_bytes = ctypes.sizeof(DeAutoExposure)
+        s.key, s.compensation, s.adapt = float(key), float(compensation), float(adapt)
+        s.ev_min, s.ev_max = float(ev_range[0]), float(ev_range[1])
+        s.low_fraction, s.high_fraction = float(percentiles[0]), float(percentiles[1])
+        if region is not None:
+            if len(region) != 4:
+                raise ValueError("region is (x0, y0, x1, y1)")
+            s.region[:] = [int(v) for v in region]
+        check(self._lib.de_set_auto_exposure(self._h, ctypes.byref(s)))
+
+    def auto_exposure(self):
+        """The auto-exposure settings as a dict (set_auto_exposure's keywords), or None while it is off."""
+        s = DeAutoExposure()
+        check(self._lib.de_get_auto_exposure(self._h, ctypes.byref(s)))
+        if s.key == 0.0:
+            return None
+        region = tuple(int(v) for v in s.region)
+        return dict(key=float(s.key), compensation=float(s.compensation), ev_range=(float(s.ev_min), float(s.ev_max)),
+                    percentiles=(float(s.low_fraction), float(s.high_fraction)), adapt=float(s.adapt), region=region if any(region) else None)
+
+    def metering(self):
+        """What the newest display metered (waits for it): dict(ev, ev_target, mean_log2, valid, metered, below, clipped, histogram) — histogram a
+        numpy uint32 array of 256 bins, bin k = octave (k >> 3) - 24, sub-bin k & 7.  Auto-exposure must be on and a fetch_image issued since."""
+        m = DeMetering()
+        m.struct_bytes = ctypes.sizeof(DeMetering)
+        check(self._lib.de_get_metering(self._h, ctypes.byref(m)))
+        return dict(ev=float(np.float32(m.ev)), ev_target=float(np.float32(m.ev_target)), mean_log2=float(np.float32(m.mean_log2)), valid=bool(m.valid),
+                    metered=int(m.metered), below=int(m.below), clipped=int(m.clipped), histogram=np.array(m.histogram, dtype=np.uint32))
 
     def _staging_view(self, ptr):
         view = np.ctypeslib.as_array(ptr, shape=(self.image_res[0], self.image_res[1], 3)).view(_StagingView)
