@@ -60,6 +60,12 @@ class DeMetering(ctypes.Structure):
                 ("metered", ctypes.c_uint64), ("below", ctypes.c_uint64), ("clipped", ctypes.c_uint64), ("histogram", ctypes.c_uint32 * 256)]
 
 
+class DeBloom(ctypes.Structure):
+    """`de_bloom` (include/digital_earth_bloom.h): the settings of the bloom."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("intensity", ctypes.c_float), ("threshold", ctypes.c_float), ("knee", ctypes.c_float), ("clamp", ctypes.c_float),
+                ("spread", ctypes.c_float), ("levels", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -155,6 +161,13 @@ EXPOSURE_SYMBOLS = {
     "de_get_metering": (ctypes.c_int, [_P, ctypes.POINTER(DeMetering)]),
 }
 
+# bloom: include/digital_earth_bloom.h (same library, additions only; not part of the binder's header)
+BLOOM_SYMBOLS = {
+    "de_set_bloom": (ctypes.c_int, [_P, ctypes.POINTER(DeBloom)]),
+    "de_get_bloom": (ctypes.c_int, [_P, ctypes.POINTER(DeBloom)]),
+    "de_fetch_bloom_hdr": (ctypes.c_int, [_P, _P]),
+}
+
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
 LEGACY_SYMBOLS = {
     "de_debug_v5_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -234,7 +247,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -130,6 +130,73 @@ int run_meter(de_ctx* c, const DisplayArgs& d, bool per_tile) {
     c->ae_displayed = true;
     return DE_OK;
 }
+// ---- bloom (include/digital_earth_bloom.h, bloom_kernels.hip)
+// The pyramid of a W x H image: level l is ((w + 1) >> 1, (h + 1) >> 1) of level l - 1; L = `levels`, reduced so that halving stops before a level
+// whose smaller side would be below 2, never less than 1.  off[l]: where D_l (and, `total` further, U_l) starts in d_bl_pyr, in float4.
+struct BloomPlan { int L; int w[BL_MAX_LEVELS + 1], h[BL_MAX_LEVELS + 1]; size_t off[BL_MAX_LEVELS + 1]; size_t total; };
+BloomPlan bl_plan(int W, int H, int levels) {
+    BloomPlan p;
+    p.L = 0; p.w[0] = W; p.h[0] = H; p.off[0] = 0; p.total = 0;
+    while (p.L < levels) {
+        const int w = (p.w[p.L] + 1) >> 1, h = (p.h[p.L] + 1) >> 1;
+        if (p.L >= 1 && std::min(w, h) < 2) break;
+        ++p.L;
+        p.w[p.L] = w; p.h[p.L] = h; p.off[p.L] = p.total;
+        p.total += (size_t)w * (size_t)h;
+    }
+    return p;
+}
+int bl_alloc(de_ctx* c) {
+    const BloomPlan p = bl_plan(c->W, c->H, BL_MAX_LEVELS);      // room for every setting of `levels`: the offsets of a level do not depend on it
+    if (!c->d_bl_pyr) HIP_TRY(hipMalloc(&c->d_bl_pyr, 2 * p.total * sizeof(float4)));
+    if (!c->d_bl_out) HIP_TRY(hipMalloc(&c->d_bl_out, (size_t)c->W * c->H * 3 * sizeof(float)));
+    return DE_OK;
+}
+// The bloom kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).  Afterwards `d`
+// describes the composited mean: the unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).
+int run_bloom(de_ctx* c, DisplayArgs& d, bool& per_tile) {
+    const de_bloom& b = c->bl;
+    const BloomPlan p = bl_plan(c->W, c->H, b.levels);
+    float4* D = c->d_bl_pyr;
+    float4* U = c->d_bl_pyr + bl_plan(c->W, c->H, BL_MAX_LEVELS).total;
+    BloomSrc s;
+    s.hdr = d.hdr; s.tile_spp = per_tile ? d.tile_spp : nullptr; s.samples = d.samples; s.W = c->W; s.H = c->H;
+    s.threshold = b.threshold; s.knee = b.knee; s.clamp = b.clamp;
+    const bool vec = (reinterpret_cast<uintptr_t>(d.hdr) & 15u) == 0u;
+    auto tiles = [](int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); };
+    if (vec) hipLaunchKernelGGL(bloom_down0_kernel<true>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    else hipLaunchKernelGGL(bloom_down0_kernel<false>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    HIP_TRY(hipGetLastError());
+    for (int l = 1; l < p.L; ++l) {
+        hipLaunchKernelGGL(bloom_down_kernel, tiles(p.w[l + 1], p.h[l + 1]), dim3(256), 0, c->stream, (const float4*)(D + p.off[l]), p.w[l], p.h[l], D + p.off[l + 1], p.w[l + 1], p.h[l + 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    const float4* top = D + p.off[p.L];      // U_L = D_L
+    for (int l = p.L - 1; l >= 1; --l) {
+        BloomUpArgs u;
+        u.coarse = top; u.fine = D + p.off[l]; u.out = U + p.off[l];
+        u.Wc = p.w[l + 1]; u.Hc = p.h[l + 1]; u.Wf = p.w[l]; u.Hf = p.h[l];
+        u.keep = 1.0f - b.spread; u.spread = b.spread;
+        hipLaunchKernelGGL(bloom_up_kernel, tiles(p.w[l], p.h[l]), dim3(256), 0, c->stream, u);
+        HIP_TRY(hipGetLastError());
+        top = u.out;
+    }
+    // level 0 is not blended in: the glow never holds the unblurred image
+    const unsigned n_wg = (unsigned)(((size_t)(c->W >> 2) * (size_t)c->H + 255u) / 256u);
+    if (vec) hipLaunchKernelGGL(bloom_composite_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, s, top, p.w[1], p.h[1], b.intensity, c->d_bl_out);
+    else hipLaunchKernelGGL(bloom_composite_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, s, top, p.w[1], p.h[1], b.intensity, c->d_bl_out);
+    HIP_TRY(hipGetLastError());
+    d.hdr = c->d_bl_out; d.samples = 1; per_tile = false;
+    return DE_OK;
+}
+// What the display reads: the sums with the frame's or the tiles' counts, a display source, or the denoiser's filtered mean (the caller has run it).
+void display_source(de_ctx* c, DisplayArgs& d, bool& per_tile) {
+    d.hdr = c->display_src ? c->display_src : c->d_hdr;
+    d.W = c->W; d.H = c->H; d.samples = c->current_spp;
+    d.tile_spp = c->d_tile_spp;
+    if (c->dn_on) { d.hdr = c->d_dn_out; d.samples = 1; }
+    per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
+}
 }  // namespace
 
 extern "C" {
@@ -217,7 +284,7 @@ int de_destroy(de_ctx* c) {
     void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin,
                      c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
-                     c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result};
+                     c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
@@ -542,8 +609,9 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     d.W = c->W; d.H = c->H; d.samples = c->current_spp; d.clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) ? 1 : 0;
     d.tile_spp = c->d_tile_spp;
     if (c->dn_on) { d.hdr = c->d_dn_out; d.samples = 1; }          // the filtered MEAN through the unchanged transform: x / 1.0f == x
-    const bool per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
+    bool per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
     if (c->ae_on) { rc = run_meter(c, d, per_tile); if (rc) return rc; d.fc = c->d_fc_ae; }      // the same transform over the metered exposure: a second FrameConsts, written on the device
+    if (c->bl_on) { rc = run_bloom(c, d, per_tile); if (rc) return rc; }      // after the meter (the scene is metered, not the lens): the composited mean through the unchanged transform
     const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
     if (per_tile) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
     else hipLaunchKernelGGL(display_kernel<false>, grid, dim3(256), 0, c->stream, d);
@@ -1137,6 +1205,49 @@ int de_get_metering(de_ctx* c, de_metering* out) {
     out->metered = r.n; out->below = r.below; out->clipped = r.clipped;
     memcpy(out->histogram, r.h, sizeof(out->histogram));
     return DE_OK;
+}
+
+/* ---- bloom: include/digital_earth_bloom.h */
+int de_set_bloom(de_ctx* c, const de_bloom* s) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (!s) { c->bl_on = false; return DE_OK; }
+    if (s->struct_bytes != (uint32_t)sizeof(de_bloom)) return fail(DE_ERR_INVALID, "de_bloom.struct_bytes does not match this library's struct");
+    if (!(s->intensity >= 0.0f) || !(s->intensity <= 1.0f) || !(s->knee >= 0.0f) || !(s->knee <= 1.0f) || !(s->spread >= 0.0f) || !(s->spread <= 1.0f))
+        return fail(DE_ERR_INVALID, "bloom settings: intensity, knee and spread in [0, 1]");
+    if (!(s->threshold >= 0.0f) || !(s->threshold < 1e30f) || !(s->clamp >= 0.0f) || !(s->clamp < 1e30f))
+        return fail(DE_ERR_INVALID, "bloom settings: finite threshold >= 0, finite clamp >= 0 (0 = none)");
+    if (s->levels < 1 || s->levels > BL_MAX_LEVELS) return fail(DE_ERR_INVALID, "bloom settings: levels in 1 .. 10");
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = bl_alloc(c); if (rc) return rc; }
+    c->bl = *s;
+    c->bl_on = true;
+    return DE_OK;
+}
+int de_get_bloom(de_ctx* c, de_bloom* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (c->bl_on) *out = c->bl; else memset(out, 0, sizeof(*out));
+    out->struct_bytes = (uint32_t)sizeof(de_bloom);
+    return DE_OK;
+}
+int de_fetch_bloom_hdr(de_ctx* c, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (!c->bl_on) return fail(DE_ERR_STATE, "bloom is off (de_set_bloom)");
+    if (c->dn_on) { int rc = denoise_refusal(c); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = c->dn_on ? run_setup(c) : DE_OK;
+    if (rc) return rc;
+    rc = join_slots(c);
+    if (rc) return rc;
+    touched_hdr(c);
+    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }
+    DisplayArgs d;
+    bool per_tile;
+    display_source(c, d, per_tile);
+    rc = run_bloom(c, d, per_tile);
+    if (rc) return rc;
+    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, (const float*)c->d_bl_out, c->d_scratch, c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    return copy_out(c, out, c->d_scratch);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 #pragma once
 #include "de_kernels.h"
 #include "../../include/digital_earth_exposure.h"
+#include "../../include/digital_earth_bloom.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -25,6 +26,7 @@
 #include "adaptive_kernels.hip"
 #include "denoise_kernels.hip"
 #include "exposure_kernels.hip"
+#include "bloom_kernels.hip"
 
 namespace {
 
@@ -207,6 +209,12 @@ struct de_ctx {
     MeterState* d_ae_state = nullptr;   // previous EV: survives de_reset, cleared by de_set_auto_exposure
     FrameConsts* d_fc_ae = nullptr;     // *d_fc with the metered exposure_scale: what the display reads (d_fc itself is never written: render launches in flight read it)
     MeterResult* d_ae_result = nullptr;
+    // Bloom (include/digital_earth_bloom.h).  Allocated on first use: the pyramid (the levels D_1 .. D_L and U_1 .. U_{L-1} of the largest L the
+    // image admits, float4: 22 MB at 1080p) and the composited mean that the display reads with samples = 1 (25 MB at 1080p).  Per context.
+    bool bl_on = false;
+    de_bloom bl;                    // the settings
+    float4* d_bl_pyr = nullptr;
+    float* d_bl_out = nullptr;      // [H][W][3]
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

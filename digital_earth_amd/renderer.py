@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -529,6 +529,36 @@ class Renderer:
         check(self._lib.de_get_metering(self._h, ctypes.byref(m)))
         return dict(ev=float(np.float32(m.ev)), ev_target=float(np.float32(m.ev_target)), mean_log2=float(np.float32(m.mean_log2)), valid=bool(m.valid),
                     metered=int(m.metered), below=int(m.below), clipped=int(m.clipped), histogram=np.array(m.histogram, dtype=np.uint32))
+
+    # ------------------------------------------------------------------ bloom (include/digital_earth_bloom.h)
+    def set_bloom(self, on=True, intensity=0.05, threshold=0.0, knee=0.5, clamp=0.0, spread=0.7, levels=6):
+        """Turn the bloom of the display path on (or off).  While it is on, every fetch_image (lag included) first takes the fraction `intensity` of
+        the light above `threshold` (luminance of the HDR mean; soft `knee`; at most `clamp` per pixel, 0 = no bound) from every pixel and gives it
+        back through a wide, normalised point-spread function — a pyramid of `levels` levels, `spread` the weight of each coarser one — on the GPU;
+        energy is conserved.  threshold = 0 is plain veiling glare.  fetch_hdr() is unchanged; auto-exposure meters the image before the bloom."""
+        if not on:
+            check(self._lib.de_set_bloom(self._h, None))
+            return
+        s = DeBloom()
+        s.struct_bytes = ctypes.sizeof(DeBloom)
+        s.intensity, s.threshold, s.knee, s.clamp, s.spread, s.levels = float(intensity), float(threshold), float(knee), float(clamp), float(spread), int(levels)
+        check(self._lib.de_set_bloom(self._h, ctypes.byref(s)))
+
+    def bloom(self):
+        """The bloom settings as a dict (set_bloom's keywords), or None while it is off."""
+        s = DeBloom()
+        check(self._lib.de_get_bloom(self._h, ctypes.byref(s)))
+        if s.levels == 0:
+            return None
+        return dict(intensity=float(s.intensity), threshold=float(s.threshold), knee=float(s.knee), clamp=float(s.clamp), spread=float(s.spread), levels=int(s.levels))
+
+    def fetch_bloom_hdr(self):
+        """The composited HDR mean that the display transform is given, (W, H, 3) float32 in fetch_hdr's layout (a mean, not a sum).  Bloom must be on."""
+        if self.denoise() is not None and not self._textures_copied:
+            self.copy_textures()
+        out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
+        check(self._lib.de_fetch_bloom_hdr(self._h, out.ctypes.data))
+        return out
 
     def _staging_view(self, ptr):
         view = np.ctypeslib.as_array(ptr, shape=(self.image_res[0], self.image_res[1], 3)).view(_StagingView)
