@@ -66,6 +66,11 @@ class DeBloom(ctypes.Structure):
                 ("spread", ctypes.c_float), ("levels", ctypes.c_int32)]
 
 
+class DeHistory(ctypes.Structure):
+    """`de_history` (include/digital_earth_history.h): the settings of the history reprojection."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_history", ctypes.c_float), ("depth_tolerance", ctypes.c_float)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -125,6 +130,7 @@ DEBUG_SYMBOLS = {
     "de_download_texture": (ctypes.c_int, [_P, ctypes.c_int, _P, ctypes.c_uint64]),
     "de_debug_adaptive_moments": (ctypes.c_int, [_P, _P]),
     "de_debug_denoise": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_float, _P]),
+    "de_debug_history": (ctypes.c_int, [_P, _P, _P, _P, ctypes.POINTER(DeParams), _P, _P, ctypes.POINTER(DeParams), ctypes.c_float, ctypes.c_float, _P]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "de_set_launch_slots": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
@@ -166,6 +172,13 @@ BLOOM_SYMBOLS = {
     "de_set_bloom": (ctypes.c_int, [_P, ctypes.POINTER(DeBloom)]),
     "de_get_bloom": (ctypes.c_int, [_P, ctypes.POINTER(DeBloom)]),
     "de_fetch_bloom_hdr": (ctypes.c_int, [_P, _P]),
+}
+
+# history reprojection: include/digital_earth_history.h (same library, additions only; not part of the binder's header)
+HISTORY_SYMBOLS = {
+    "de_set_history": (ctypes.c_int, [_P, ctypes.POINTER(DeHistory)]),
+    "de_get_history": (ctypes.c_int, [_P, ctypes.POINTER(DeHistory)]),
+    "de_fetch_history_hdr": (ctypes.c_int, [_P, _P]),
 }
 
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
@@ -247,7 +260,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

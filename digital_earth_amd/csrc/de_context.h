@@ -3,6 +3,7 @@
 #include "de_kernels.h"
 #include "../../include/digital_earth_exposure.h"
 #include "../../include/digital_earth_bloom.h"
+#include "../../include/digital_earth_history.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -27,6 +28,7 @@
 #include "denoise_kernels.hip"
 #include "exposure_kernels.hip"
 #include "bloom_kernels.hip"
+#include "history_kernels.hip"
 
 namespace {
 
@@ -215,6 +217,17 @@ struct de_ctx {
     de_bloom bl;                    // the settings
     float4* d_bl_pyr = nullptr;
     float* d_bl_out = nullptr;      // [H][W][3]
+    // History reprojection (include/digital_earth_history.h).  Allocated on first use: the history and the candidate (a float4 and an f32 per
+    // pixel each, and a camera) and the blended mean that the display reads with samples = 1: 2 x (16 + 4) + 12 bytes per pixel (108 MB at 1080p).  Per context.
+    bool hs_on = false;
+    bool hs_valid = false;          // the history holds a displayed picture (cleared by everything that drops it)
+    bool hs_cand_valid = false;     // the candidate was written by a display since the last swap: the next de_reset makes it the history
+    de_history hs;                  // the settings
+    float4* d_hs_c[2] = {nullptr, nullptr};       // [H][W] (rgb, weight): [hs_cur] the history, [hs_cur ^ 1] the candidate
+    float* d_hs_d[2] = {nullptr, nullptr};        // [H][W] land distance
+    HistoryCam* d_hs_cam[2] = {nullptr, nullptr};
+    int hs_cur = 0;
+    float* d_hs_out = nullptr;      // [H][W][3]
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

@@ -176,12 +176,16 @@ class Camera:
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, **renderer_kwargs):
+        """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
+        in frame()'s loop instead of restarting at one sample per pixel."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
         self.renderer.set_camera_pos(*self.camera.position)
         self.renderer.copy_textures()
+        if history:
+            self.renderer.set_history(True, **(history if isinstance(history, dict) else {}))
         self.config = None
         if config is not None:
             self.load_config(config)

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -558,6 +558,58 @@ class Renderer:
             self.copy_textures()
         out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
         check(self._lib.de_fetch_bloom_hdr(self._h, out.ctypes.data))
+        return out
+
+    # ------------------------------------------------------------------ history reprojection (include/digital_earth_history.h)
+    MAX_HISTORY = 32.0          # samples: the largest weight a reprojected pixel may carry
+    DEPTH_TOLERANCE = 0.02      # a history tap is refused when its land distance is off by more than this fraction
+
+    def set_history(self, enabled=True, max_history=MAX_HISTORY, depth_tolerance=DEPTH_TOLERANCE):
+        """Turn history reprojection on (or off).  While it is on, every fetch_image (lag included) keeps what it showed, and after a
+        reset_framebuffer() — a camera move — the next images blend, pixel by pixel, the new frame's mean with the previous picture reprojected into the
+        new camera, weighted by sample counts (at most `max_history` samples for the old picture; taps whose land distance differs by more than
+        `depth_tolerance` are refused).  A change of the sun, the terrain scale, a map or the integrator drops the history; exposure, gamma and the camera
+        response keep it.  fetch_hdr() is unchanged; auto-exposure and bloom see the blended image.  Every call drops the history."""
+        if not enabled:
+            check(self._lib.de_set_history(self._h, None))
+            return
+        s = DeHistory()
+        s.struct_bytes = ctypes.sizeof(DeHistory)
+        s.max_history, s.depth_tolerance = float(max_history), float(depth_tolerance)
+        check(self._lib.de_set_history(self._h, ctypes.byref(s)))
+
+    def history(self):
+        """The history settings as a dict (set_history's keywords), or None while it is off."""
+        s = DeHistory()
+        check(self._lib.de_get_history(self._h, ctypes.byref(s)))
+        if s.max_history == 0.0:
+            return None
+        return dict(max_history=float(s.max_history), depth_tolerance=float(s.depth_tolerance))
+
+    def fetch_history_hdr(self):
+        """The blended HDR mean that the display transform is given and its weight in samples, (W, H, 4) float32 in fetch_hdr's layout.  History
+        reprojection must be on.  Counts as a display: the next reset_framebuffer() keeps this picture."""
+        if not self._textures_copied:
+            self.copy_textures()
+        out = np.empty((self.image_res[0], self.image_res[1], 4), dtype=np.float32)
+        check(self._lib.de_fetch_history_hdr(self._h, out.ctypes.data))
+        return out
+
+    def debug_history(self, mean, n, dist, params, hist_c=None, hist_d=None, hist_params=None, max_history=MAX_HISTORY, depth_tolerance=DEPTH_TOLERANCE):
+        """The blend once on given arrays (include/digital_earth_debug.h: de_debug_history): mean (W, H, 3), n (W, H) int32, dist (W, H), params the
+        current DeParams; hist_c (W, H, 4), hist_d (W, H) and hist_params the history (None: no history yet).  Returns (W, H, 4)."""
+        W, H = self.image_res
+        mean = np.ascontiguousarray(mean, dtype=np.float32).reshape(W, H, 3)
+        n = np.ascontiguousarray(n, dtype=np.int32).reshape(W, H)
+        dist = np.ascontiguousarray(dist, dtype=np.float32).reshape(W, H)
+        hc = hd = hp = None
+        if hist_c is not None:
+            hist_c = np.ascontiguousarray(hist_c, dtype=np.float32).reshape(W, H, 4)
+            hist_d = np.ascontiguousarray(hist_d, dtype=np.float32).reshape(W, H)
+            hc, hd, hp = hist_c.ctypes.data, hist_d.ctypes.data, ctypes.byref(hist_params)
+        out = np.empty((W, H, 4), dtype=np.float32)
+        check(self._lib.de_debug_history(self._h, mean.ctypes.data, n.ctypes.data, dist.ctypes.data, ctypes.byref(params), hc, hd, hp,
+                                         float(max_history), float(depth_tolerance), out.ctypes.data))
         return out
 
     def _staging_view(self, ptr):

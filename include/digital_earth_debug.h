@@ -76,6 +76,13 @@ int de_texture_info(de_ctx* ctx, int slot, int* width, int* height, int* channel
  * guides (W, H, 9) as de_fetch_guides returns them; out (W, H, 4) = filtered rgb and carried variance.  Overwrites the context's guides (recomputed at the
  * next denoised display).  For the tests' float64 restatement (tests/denoise_f64.py). */
 int de_debug_denoise(de_ctx* ctx, const float* mean, const float* var, const float* guides, int levels, float sigma_l, float* out);
+/* The history reprojection's blend (include/digital_earth_history.h) once on host-given arrays, host layout; needs no maps.  mean (W, H, 3) = the frame's
+ * HDR mean, n (W, H) int32 = every pixel's sample count, dist (W, H) = the current land distance (0: no land), cur = the current de_params (its camera
+ * fields are read); hist_c (W, H, 4) = the history's rgb and weight, hist_d (W, H) its land distance, hist = the de_params it was displayed with — or
+ * hist_c = NULL: no history yet.  out (W, H, 4) = the blended mean and its weight.  The context's own history is not touched.  For the tests' float32
+ * restatement (tests/history_ref.py). */
+int de_debug_history(de_ctx* ctx, const float* mean, const int32_t* n, const float* dist, const de_params* cur, const float* hist_c, const float* hist_d,
+                     const de_params* hist, float max_history, float depth_tolerance, float* out);
 
 /* ---- the N-rank collectives' device code on ONE GPU
  * de_debug_ordered_sum: the root's half of de_reduce_ordered without a communicator.  `parts` = n_parts host buffers of W*H*3 floats each (device

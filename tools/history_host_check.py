@@ -1,0 +1,82 @@
+"""history_blend_kernel's source on the HOST under the address and undefined-behaviour sanitizers: builds tools/history_host_check.cpp
+(a stand-alone program that includes csrc/history_kernels.hip and runs it one workgroup at a time), feeds it the inputs of
+tests/test_gpu_history.py::test_kernel_equals_the_restatement_bit_for_bit at the three sizes, and compares what it writes with the numpy float32
+restatement (tests/history_ref.py) bit for bit.  Needs a C++ compiler and no GPU.
+
+    python tools/history_host_check.py [--cxx g++] [--keep DIR]
+"""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+class _NoDevice:
+    """What the test's helpers read of a Renderer: its de_params."""
+
+    def __init__(self):
+        from digital_earth_amd import _native
+        self._params = _native.DeParams()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cxx", default=os.environ.get("CXX", "g++"))
+    ap.add_argument("--keep", metavar="DIR")
+    args = ap.parse_args()
+    import history_ref as hr
+    import test_gpu_history as t
+    work = args.keep or tempfile.mkdtemp(prefix="history_host_")
+    os.makedirs(work, exist_ok=True)
+    exe = os.path.join(work, "history_host_check")
+    subprocess.check_call([args.cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-x", "c++", os.path.join(ROOT, "tools", "history_host_check.cpp"), "-o", exe])
+    r = _NoDevice()
+    runs = pixels = 0
+    for W, H in t.SIZES:
+        x = t._inputs(r, W, H)
+        hp = t._params(r)
+        hcam = hr.camera(hp, W, H)
+        jobs = []
+        for name, p in t._cameras(r, H).items():
+            cam = hr.camera(p, W, H)
+            sphere = t._sphere(cam, W, H)
+            cases = {"mixed": (np.where(x["rng"].uniform(size=(W, H)) < 0.15, np.float32(0), sphere).astype(np.float32), x["hist_d"])}
+            if name in ("identical", "yaw 1.5 px"):
+                cases["edge"] = (sphere, t._edge(x["hsphere"], 0.02, x["rng"]))
+            if name in ("identical", "sideways"):
+                cases["step"] = (x["step"], x["step"])
+            for case, (dist, hist_d) in cases.items():
+                for kw in (dict(), dict(max_history=4.0, depth_tolerance=0.5)):
+                    jobs.append(((name, case, kw), p, cam, dist, x["hist"], hist_d, kw))
+        jobs.append((("no history",), hp, hcam, x["step"], None, None, dict()))
+        for what, p, cam, dist, hist, hist_d, kw in jobs:
+            s = dict(hr.DEFAULTS, **kw)
+            dev = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1))      # (W, H, k) -> the device layout [H][W][k]
+            with open(os.path.join(work, "in.bin"), "wb") as f:
+                f.write(np.array([W, H, hist is not None], np.int32).tobytes())
+                f.write(np.array([s["max_history"], s["depth_tolerance"]], np.float32).tobytes())
+                f.write(bytes(p) + bytes(hp))
+                for a in (x["m"], x["n"].astype(np.int32), dist) + ((hist, hist_d) if hist is not None else ()):
+                    f.write(dev(a).tobytes())
+            subprocess.check_call([exe, os.path.join(work, "in.bin"), os.path.join(work, "out.bin")])
+            raw = np.fromfile(os.path.join(work, "out.bin"), np.float32)
+            got = np.swapaxes(raw[:W * H * 4].reshape(H, W, 4), 0, 1)
+            shown = np.swapaxes(raw[W * H * 4:].reshape(H, W, 3), 0, 1)
+            want = hr.blend(x["m"], x["n"], dist, cam, hist, hist_d, hcam, **kw) if hist is not None else hr.blend(x["m"], x["n"], dist, cam)
+            t._same(got, want, what)
+            t._same(shown, want[..., :3], what)
+            runs += 1
+            pixels += W * H
+    print("history_blend_kernel on the host under -fsanitize=address,undefined: %d runs, %d pixels, no report, every bit equal to tests/history_ref.py" % (runs, pixels))
+
+
+if __name__ == "__main__":
+    main()
