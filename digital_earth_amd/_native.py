@@ -71,6 +71,11 @@ class DeHistory(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("max_history", ctypes.c_float), ("depth_tolerance", ctypes.c_float)]
 
 
+class DePixels(ctypes.Structure):
+    """`de_pixels` (include/digital_earth_pixels.h): the format of the 8-bit pixel output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("channels", ctypes.c_int32), ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("animate", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -131,6 +136,7 @@ DEBUG_SYMBOLS = {
     "de_debug_adaptive_moments": (ctypes.c_int, [_P, _P]),
     "de_debug_denoise": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_float, _P]),
     "de_debug_history": (ctypes.c_int, [_P, _P, _P, _P, ctypes.POINTER(DeParams), _P, _P, ctypes.POINTER(DeParams), ctypes.c_float, ctypes.c_float, _P]),
+    "de_debug_pixels": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePixels), ctypes.c_uint32, _P]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "de_set_launch_slots": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
@@ -179,6 +185,17 @@ HISTORY_SYMBOLS = {
     "de_set_history": (ctypes.c_int, [_P, ctypes.POINTER(DeHistory)]),
     "de_get_history": (ctypes.c_int, [_P, ctypes.POINTER(DeHistory)]),
     "de_fetch_history_hdr": (ctypes.c_int, [_P, _P]),
+}
+
+# 8-bit pixel output: include/digital_earth_pixels.h (same library, additions only; not part of the binder's header)
+PIXELS_SYMBOLS = {
+    "de_set_pixels": (ctypes.c_int, [_P, ctypes.POINTER(DePixels)]),
+    "de_get_pixels": (ctypes.c_int, [_P, ctypes.POINTER(DePixels), ctypes.POINTER(ctypes.c_uint32)]),
+    "de_render_to_pixels": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_pixels": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
+    "de_fetch_pixels_view": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
+    "de_fetch_pixels_begin": (ctypes.c_int, [_P]),
+    "de_fetch_pixels_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
 }
 
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
@@ -260,7 +277,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -333,10 +333,12 @@ int de_destroy(de_ctx* c) {
                      c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
                      c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
-                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out};
+                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
+    if (c->h_px_stage) hipHostFree(c->h_px_stage);
+    for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_px_ring[k]) hipHostFree(c->h_px_ring[k]); if (c->ev_px_ring[k]) hipEventDestroy(c->ev_px_ring[k]); }
     if (c->h_issued) hipHostFree(c->h_issued);
     if (c->h_ad_count) hipHostFree(c->h_ad_count);
 #ifdef DE_LEGACY_VARIANTS
@@ -1425,5 +1427,119 @@ int de_debug_history(de_ctx* c, const float* mean, const int32_t* n, const float
     return DE_OK;
 }
 
-}  // extern "C"
+/* ---- 8-bit pixel output: include/digital_earth_pixels.h (pixels_kernels.hip) */
+namespace {
+size_t px_size(const de_ctx* c) { return (size_t)c->W * c->H * (size_t)c->px.channels; }
+size_t px_capacity(const de_ctx* c) { return (size_t)c->W * c->H * 4; }      // every buffer holds either format: de_set_pixels frees nothing
+int px_settings_check(const de_pixels* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_pixels)) return fail(DE_ERR_INVALID, "de_pixels.struct_bytes does not match this library's struct");
+    if (s->channels != 3 && s->channels != 4) return fail(DE_ERR_INVALID, "de_pixels.channels must be 3 or 4");
+    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_pixels.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
+    return DE_OK;
+}
+int px_host_alloc(uint8_t** p, size_t bytes) {
+    if (!*p && hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the pixel staging buffers"); }
+    return DE_OK;
+}
+void px_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_pixels& s, uint32_t phase) {
+    PixelsArgs a;
+    a.image = image; a.out = out; a.W = W; a.H = H; a.channels = s.channels; a.mode = s.mode; a.seed = s.seed; a.phase = phase;
+    hipLaunchKernelGGL(pixels_pack_kernel, dim3((unsigned)((W + PX_TILE - 1) / PX_TILE), (unsigned)((H + PX_TILE - 1) / PX_TILE)), dim3(256), 0, stream, a);
+}
+}  // namespace
 
+int de_set_pixels(de_ctx* c, const de_pixels* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = px_settings_check(s); if (rc) return rc; }
+    if (c->px_begun != c->px_ended) return fail(DE_ERR_STATE, "pixel fetches are in flight: de_fetch_pixels_end first");
+    c->px = *s;
+    c->px_count = 0; c->px_last_phase = 0;
+    return DE_OK;
+}
+int de_get_pixels(de_ctx* c, de_pixels* out, uint32_t* last_phase) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->px;
+    if (last_phase) *last_phase = c->px_last_phase;
+    return DE_OK;
+}
+int de_render_to_pixels(de_ctx* c, const uint8_t** device_pixels) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_px) HIP_TRY(hipMalloc(&c->d_px, px_capacity(c)));
+    int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
+    if (rc) return rc;
+    const uint32_t phase = c->px.animate ? c->px_count : 0u;
+    px_launch(c->stream, c->d_image, c->d_px, c->W, c->H, c->px, phase);
+    HIP_TRY(hipGetLastError());
+    c->px_count++; c->px_last_phase = phase;
+    if (device_pixels) *device_pixels = c->d_px;
+    return DE_OK;
+}
+int de_fetch_pixels_view(de_ctx* c, const uint8_t** host) {
+    if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = px_host_alloc(&c->h_px_stage, px_capacity(c));
+    if (rc) return rc;
+    rc = de_render_to_pixels(c, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_px_stage, c->d_px, px_size(c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *host = c->h_px_stage;
+    return frame_status(c);
+}
+int de_fetch_pixels(de_ctx* c, uint8_t* out, uint64_t out_bytes) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (out_bytes < (uint64_t)px_size(c)) return fail(DE_ERR_INVALID, "out_bytes is smaller than W * H * channels");
+    const uint8_t* host = nullptr;
+    int rc = de_fetch_pixels_view(c, &host);
+    if (rc) return rc;
+    memcpy(out, host, px_size(c));
+    return DE_OK;
+}
+int de_fetch_pixels_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (c->px_begun - c->px_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four pixel fetches are in flight already: de_fetch_pixels_end first");
+    const int k = (int)(c->px_begun % (unsigned)DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = px_host_alloc(&c->h_px_ring[k], px_capacity(c));
+    if (rc) return rc;
+    if (!c->ev_px_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_px_ring[k], hipEventDisableTiming));
+    rc = de_render_to_pixels(c, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_px_ring[k], c->d_px, px_size(c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_px_ring[k], c->stream));
+    c->px_begun++;
+    return DE_OK;
+}
+int de_fetch_pixels_end(de_ctx* c, const uint8_t** host) {
+    if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
+    if (c->px_begun == c->px_ended) return fail(DE_ERR_STATE, "no pixel fetch in flight: de_fetch_pixels_begin first");
+    const int k = (int)(c->px_ended % (unsigned)DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->ev_px_ring[k]));
+    c->px_ended++;
+    *host = c->h_px_ring[k];
+    return frame_status(c);
+}
+/* include/digital_earth_debug.h: the conversion once on a host-given image.  Buffers of its own; the context's pixels and phase counter are not touched. */
+int de_debug_pixels(de_ctx* c, const float* image, int W, int H, const de_pixels* s, uint32_t phase, uint8_t* out) {
+    if (!c || !image || !s || !out || W <= 0 || H <= 0 || (W % 16) != 0 || (H % 8) != 0 || (long long)W * H > (1ll << 28))
+        return fail(DE_ERR_INVALID, "bad arguments (W a multiple of 16, H a multiple of 8, as de_create asks)");
+    { int rc = px_settings_check(s); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    struct Bufs {   // freed on every exit path
+        void* p[2] = {};
+        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
+    } b;
+    const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), out_bytes = (size_t)W * H * (size_t)s->channels;
+    HIP_TRY(hipMalloc(&b.p[0], in_bytes));
+    HIP_TRY(hipMalloc(&b.p[1], out_bytes));
+    HIP_TRY(hipMemcpyAsync(b.p[0], image, in_bytes, hipMemcpyHostToDevice, c->stream));
+    px_launch(c->stream, (const float*)b.p[0], (uint8_t*)b.p[1], W, H, *s, phase);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b.p[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+
+}  // extern "C"

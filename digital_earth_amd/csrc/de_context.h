@@ -4,6 +4,7 @@
 #include "../../include/digital_earth_exposure.h"
 #include "../../include/digital_earth_bloom.h"
 #include "../../include/digital_earth_history.h"
+#include "../../include/digital_earth_pixels.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -29,6 +30,7 @@
 #include "exposure_kernels.hip"
 #include "bloom_kernels.hip"
 #include "history_kernels.hip"
+#include "pixels_kernels.hip"
 
 namespace {
 
@@ -228,6 +230,17 @@ struct de_ctx {
     HistoryCam* d_hs_cam[2] = {nullptr, nullptr};
     int hs_cur = 0;
     float* d_hs_out = nullptr;      // [H][W][3]
+    // 8-bit pixel output (include/digital_earth_pixels.h).  Allocated on first use, each for 4 channels so that de_set_pixels never frees a
+    // buffer a caller may still read: W * H * 4 bytes on the device, and as much pinned per staging buffer and ring cell (five in all, W * H * channels of
+    // each in use); a ring, counters and events of its own, independent of the float image's.
+    de_pixels px = {(uint32_t)sizeof(de_pixels), 4, DE_PIXELS_TRUNCATE, 0u, 0};      // the settings
+    uint32_t px_count = 0;          // conversions since de_set_pixels
+    uint32_t px_last_phase = 0;     // the phase of the newest conversion
+    uint8_t* d_px = nullptr;        // [H][W][channels]
+    uint8_t* h_px_stage = nullptr;
+    uint8_t* h_px_ring[DE_FETCH_RING] = {};
+    hipEvent_t ev_px_ring[DE_FETCH_RING] = {};
+    unsigned px_begun = 0, px_ended = 0;
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

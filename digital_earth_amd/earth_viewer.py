@@ -173,6 +173,14 @@ class Camera:
         self._moved = True
 
 
+def _rgb_picture(px):
+    """(H, W, 3 | 4) uint8 rows top-down -> the image writer's RGB picture.  The writer's own unpacker reads the bytes (RGBA8 as RGBX: the alpha byte is
+    dropped, so the file is the one an RGB array gives whatever the channel count); no numpy pass over the pixels."""
+    from PIL import Image
+    h, w, ch = px.shape
+    return Image.frombytes("RGB", (w, h), np.ascontiguousarray(px).tobytes(), "raw", "RGBX" if ch == 4 else "RGB", 0, 1)
+
+
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
@@ -190,6 +198,7 @@ class EarthViewer:
         if config is not None:
             self.load_config(config)
         self._image = None
+        self._pixels = None                     # the picture of the last frame(pixels=True)
         self._sliders = None
 
     def load_config(self, path_or_config):
@@ -214,6 +223,7 @@ class EarthViewer:
             self.renderer.accumulate(n)
             left -= n
         self._image = self.renderer.fetch_image()
+        self._pixels = None
         return self._image
 
     def render_to_noise(self, threshold, max_spp, min_spp=16, round_spp=16, floor=None):
@@ -225,9 +235,10 @@ class EarthViewer:
         kw = {} if floor is None else {"floor": floor}
         self.last_adaptive = r.render_adaptive(threshold, max_spp, min_spp=min_spp, round_spp=round_spp, **kw)
         self._image = r.fetch_image()
+        self._pixels = None
         return self._image
 
-    def frame(self, spp=1, copy=True, pipelined=False, **sliders):
+    def frame(self, spp=1, copy=True, pipelined=False, pixels=False, **sliders):
         """ONE iteration of the reference's window loop (earth_viewer.py:203-317), with the GUI sliders passed as keywords
         (sun_angle, sun_path_rot, fov, aspect_scale, exposure, selected_crf, gamma):
           1. a moved camera is pushed to the renderer and marks the framebuffer for reset          (:206-213)
@@ -238,7 +249,9 @@ class EarthViewer:
         Returns the displayed image of step 2 (copy=False: a read-only view that the next frame() overwrites — what a canvas needs).
         pipelined=True (or 2: two frames of lag): the display and the host copy of this frame are only enqueued (Renderer.fetch_image(lag=...)) and the
         image RETURNED is the previous iteration's (None in the first): the next iteration's accumulate() renders while this frame is shown — the same images, one
-        iteration later, at a fraction of the frame time; finish() returns the last one."""
+        iteration later, at a fraction of the frame time; finish() returns the last one.
+        pixels=True: the iteration returns the packed 8-bit picture instead of the float field — (H, W, channels) uint8, rows top-down, converted on the
+        GPU in the format of Renderer.set_pixels() (Renderer.fetch_pixels) — with the same copy / pipelined rules; finish(pixels=True) ends that loop."""
         r = self.renderer
         should_reset = False
         if self.camera.update_camera(0.0):
@@ -247,7 +260,11 @@ class EarthViewer:
             r.set_up(*self.camera._up)
             should_reset = True
         r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
-        self._image = r.fetch_image(copy=copy, lag=int(pipelined))
+        if pixels:
+            self._pixels, self._image = r.fetch_pixels(copy=copy, lag=int(pipelined)), None
+        else:
+            self._image = r.fetch_image(copy=copy, lag=int(pipelined))
+            self._pixels = None
         if self._sliders is None:               # current_* of earth_viewer.py:191-199, read once when the loop starts
             self._sliders = {"sun_angle": r.sun_angle[None], "sun_path_rot": r.sun_path_rot[None], "fov": r.fov[None],
                              "aspect_scale": r.aspect_scale[None], "exposure": r.exposure[None],
@@ -265,31 +282,43 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        return self._image
+        return self._pixels if pixels else self._image
 
-    def finish(self, copy=True):
-        """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight)."""
-        img = self.renderer.fetch_pending(copy=copy)
+    def finish(self, copy=True, pixels=False):
+        """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop."""
+        img = self.renderer.fetch_pending(copy=copy, pixels=pixels)
         if img is not None:
-            self._image = img
+            if pixels:
+                self._pixels = img
+            else:
+                self._image = img
         return img
 
     def close(self):
         """Release the renderer.  A zero-copy image kept from frame(copy=False) is copied first: it lives in the renderer's staging buffer."""
         if self._image is not None and getattr(self._image, "_owner", None) is not None:
             self._image = np.array(self._image)
+        if self._pixels is not None and getattr(self._pixels, "_owner", None) is not None:
+            self._pixels = np.array(self._pixels)
         self.renderer.close()
 
     def save(self, path):
-        """'p' screenshot (:244-250): writes the displayed image; `.npy` keeps the float (W, H, 3) array."""
-        if self._image is None:
+        """'p' screenshot (:244-250): writes the displayed image; `.npy` keeps the float (W, H, 3) array.  Every other format gets packed 8-bit pixels
+        converted on the GPU in the renderer's current mode (Renderer.set_pixels; truncation by default: the reference's to_vec3u, byte for byte) and
+        handed to the image writer as they are, rows top-down — no clip, cast, transpose or flip on the host.  What is written is the picture this
+        viewer last showed, never a new display of the context: the image held goes through the pack kernel as it is (Renderer.debug_pixels), and
+        after frame(pixels=True) the picture held is written.  A slider, bloom or exposure changed since then does not reach the file."""
+        r = self.renderer
+        if self._image is None and self._pixels is None:
             self.render(1)
         if path.endswith(".npy"):
-            np.save(path, self._image)
+            np.save(path, self._image if self._image is not None else r.fetch_image())
             return
-        from PIL import Image
-        a = (np.clip(self._image, 0.0, 1.0) * 255).astype(np.uint8)        # Renderer.to_vec3u
-        Image.fromarray(a.transpose(1, 0, 2)[::-1]).save(path)
+        px = self._pixels
+        if px is None:
+            fmt = r.pixels()
+            px = r.debug_pixels(self._image, channels=fmt["channels"], mode=fmt["mode"], seed=fmt["seed"], phase=fmt["last_phase"])
+        _rgb_picture(px).save(path)
 
     def start(self, spp=64, out="screenshot/earth.png", noise=None, denoise=False, auto_exposure=False):
         """Reference entry point (main.py:4).  Headless: render one frame and save it.  noise=None: `spp` samples per pixel; noise = a threshold:

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -140,6 +140,9 @@ class Renderer:
             ref = getattr(self, "_view_ref", None)
             if ref is not None and ref() is not None:
                 raise RuntimeError("a fetch_image(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
+            ref = getattr(self, "_pixel_view_ref", None)
+            if ref is not None and ref() is not None:
+                raise RuntimeError("a fetch_pixels(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
             check(self._lib.de_destroy(self._h))
             self._h = ctypes.c_void_p()
             self._lender = None
@@ -656,15 +659,98 @@ class Renderer:
         view = self._staging_view(ptr)
         return np.array(view) if copy else view
 
-    def fetch_pending(self, copy=True, all_images=False):
+    def fetch_pending(self, copy=True, all_images=False, pixels=False):
         """End the pipelined window loop: wait for the fetches still in flight and return the newest image (None when there is none);
-        all_images=True: the list of all of them, oldest first (copies)."""
+        all_images=True: the list of all of them, oldest first (copies).  pixels=True: the same for the lagged fetch_pixels() calls, which have a
+        ring of their own; the float fetches are left alone, as the pixel fetches are without it."""
         imgs = []
-        while getattr(self, "_fetches", 0) > 0:
-            imgs.append(self._fetch_end(copy or all_images))
+        if pixels:
+            while getattr(self, "_pixel_fetches", 0) > 0:
+                imgs.append(self._fetch_pixels_end(copy or all_images))
+        else:
+            while getattr(self, "_fetches", 0) > 0:
+                imgs.append(self._fetch_end(copy or all_images))
         if all_images:
             return imgs
         return imgs[-1] if imgs else None
+
+    # ------------------------------------------------------------------ 8-bit pixel output (include/digital_earth_pixels.h, DESIGN.md §14)
+    PIXEL_MODES = ("truncate", "round", "dither")
+
+    def set_pixels(self, channels=4, mode="truncate", seed=0, animate=False):
+        """The format of fetch_pixels(): 3 (RGB8) or 4 (RGBA8, alpha 255) channels; mode "truncate" (to_vec3u: what screenshots have always held),
+        "round", or "dither" (a two-LSB triangular dither from a hash of `seed`, the pixel and the channel, fading out at 0 and 255 so that black
+        and clipped white stay exact).  animate=False: a frame always gives the same bytes; True: the pattern changes with every conversion.  Every
+        call resets the phase counter; refused (DE_ERR_STATE) while lagged pixel fetches are in flight.  fetch_image() is not affected."""
+        if mode not in self.PIXEL_MODES:
+            raise ValueError("mode must be one of %s" % (self.PIXEL_MODES,))
+        s = DePixels()
+        s.struct_bytes = ctypes.sizeof(DePixels)
+        s.channels, s.mode, s.seed, s.animate = int(channels), self.PIXEL_MODES.index(mode), int(seed) & 0xffffffff, 1 if animate else 0
+        check(self._lib.de_set_pixels(self._h, ctypes.byref(s)))
+
+    def pixels(self):
+        """The pixel format as a dict (set_pixels' keywords) plus last_phase, the dither phase of the newest conversion."""
+        s, phase = DePixels(), ctypes.c_uint32()
+        check(self._lib.de_get_pixels(self._h, ctypes.byref(s), ctypes.byref(phase)))
+        return dict(channels=int(s.channels), mode=self.PIXEL_MODES[s.mode], seed=int(s.seed), animate=bool(s.animate), last_phase=int(phase.value))
+
+    def _pixel_view(self, ptr, channels):
+        view = np.ctypeslib.as_array(ptr, shape=(self.image_res[1], self.image_res[0], channels)).view(_StagingView)
+        view.flags.writeable = False
+        view._owner = self
+        self._pixel_view_ref = weakref.ref(view)
+        return view
+
+    def fetch_pixels(self, copy=True, lag=0):
+        """The displayed image as packed 8-bit pixels, converted on the GPU behind the display transform: (H, W, channels) uint8, rows top-down — what
+        a canvas, an image writer or an encoder takes as it is — in the format of set_pixels().  A quarter or a third of fetch_image()'s bytes cross the
+        link and the host converts nothing.  copy=False: a read-only view of the library's pinned pixel staging buffer, valid until the next
+        fetch_pixels call.  lag=1, 2 or 3: pipelined like fetch_image(lag=...), through a ring of its own — the call returns the pixels of the
+        lag-th previous call (None until there is one); fetch_pending(pixels=True) hands out the rest."""
+        if not self._textures_copied:
+            self.copy_textures()
+        if lag not in (0, 1, 2, 3):
+            raise ValueError("lag must be 0 ... 3")
+        if lag:
+            channels = self.pixels()["channels"]
+            check(self._lib.de_fetch_pixels_begin(self._h))
+            self._pixel_fetches = getattr(self, "_pixel_fetches", 0) + 1
+            self._pixel_channels = channels
+            if self._pixel_fetches <= lag:
+                return None
+            return self._fetch_pixels_end(copy)
+        if getattr(self, "_pixel_fetches", 0):
+            raise RuntimeError("lagged pixel fetches are in flight: fetch_pending(pixels=True) first")
+        channels = self.pixels()["channels"]
+        if not copy:
+            ptr = ctypes.POINTER(ctypes.c_uint8)()
+            check(self._lib.de_fetch_pixels_view(self._h, ctypes.byref(ptr)))
+            return self._pixel_view(ptr, channels)
+        out = np.empty((self.image_res[1], self.image_res[0], channels), dtype=np.uint8)
+        check(self._lib.de_fetch_pixels(self._h, out.ctypes.data, ctypes.c_uint64(out.nbytes)))
+        return out
+
+    def _fetch_pixels_end(self, copy):
+        ptr = ctypes.POINTER(ctypes.c_uint8)()
+        self._pixel_fetches -= 1
+        check(self._lib.de_fetch_pixels_end(self._h, ctypes.byref(ptr)))
+        view = self._pixel_view(ptr, self._pixel_channels)      # set_pixels is refused while fetches are in flight: the format is the begin's
+        return np.array(view) if copy else view
+
+    def debug_pixels(self, image, channels=4, mode="truncate", seed=0, phase=0):
+        """The conversion once on a given (W, H, 3) float32 image (include/digital_earth_debug.h: de_debug_pixels), W a multiple of 16 and H of 8 but
+        free of this renderer's size; returns (H, W, channels) uint8.  The renderer's own pixels and phase counter are not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (W, H, 3)")
+        W, H = image.shape[:2]
+        s = DePixels()
+        s.struct_bytes = ctypes.sizeof(DePixels)
+        s.channels, s.mode, s.seed, s.animate = int(channels), self.PIXEL_MODES.index(mode), int(seed) & 0xffffffff, 0
+        out = np.empty((H, W, int(channels) if channels in (3, 4) else 4), dtype=np.uint8)
+        check(self._lib.de_debug_pixels(self._h, image.ctypes.data, W, H, ctypes.byref(s), ctypes.c_uint32(int(phase) & 0xffffffff), out.ctypes.data))
+        return out
 
     def fetch_hdr(self):
         out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)

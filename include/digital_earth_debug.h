@@ -83,6 +83,11 @@ int de_debug_denoise(de_ctx* ctx, const float* mean, const float* var, const flo
  * restatement (tests/history_ref.py). */
 int de_debug_history(de_ctx* ctx, const float* mean, const int32_t* n, const float* dist, const de_params* cur, const float* hist_c, const float* hist_d,
                      const de_params* hist, float max_history, float depth_tolerance, float* out);
+/* The 8-bit pixel conversion (include/digital_earth_pixels.h) once on a host-given image: image (W, H, 3) floats as de_fetch_image returns them, W a
+ * multiple of 16 and H of 8 but otherwise free of the context's size; settings as de_set_pixels takes them, `phase` given; out [H][W][channels] bytes,
+ * row 0 at the top.  Buffers of its own: the context's pixels and its phase counter are not touched.  For the tests' restatement (tests/pixels_ref.py). */
+struct de_pixels;
+int de_debug_pixels(de_ctx* ctx, const float* image, int W, int H, const struct de_pixels* settings, uint32_t phase, uint8_t* out);
 
 /* ---- the N-rank collectives' device code on ONE GPU
  * de_debug_ordered_sum: the root's half of de_reduce_ordered without a communicator.  `parts` = n_parts host buffers of W*H*3 floats each (device
