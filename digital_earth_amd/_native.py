@@ -76,6 +76,12 @@ class DePixels(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("channels", ctypes.c_int32), ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("animate", ctypes.c_int32)]
 
 
+class DeLocalExposure(ctypes.Structure):
+    """`de_local_exposure` (include/digital_earth_local_exposure.h): the settings of the local exposure."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("on", ctypes.c_int32), ("highlights", ctypes.c_float), ("shadows", ctypes.c_float), ("sigma", ctypes.c_float),
+                ("max_ev", ctypes.c_float), ("key", ctypes.c_float), ("levels", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -198,6 +204,14 @@ PIXELS_SYMBOLS = {
     "de_fetch_pixels_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
 }
 
+# local exposure: include/digital_earth_local_exposure.h (same library, additions only; not part of the binder's header)
+LOCAL_EXPOSURE_SYMBOLS = {
+    "de_set_local_exposure": (ctypes.c_int, [_P, ctypes.POINTER(DeLocalExposure)]),
+    "de_get_local_exposure": (ctypes.c_int, [_P, ctypes.POINTER(DeLocalExposure)]),
+    "de_fetch_local_exposure_hdr": (ctypes.c_int, [_P, _P]),
+    "de_debug_local_exposure": (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.POINTER(DeLocalExposure), _P]),
+}
+
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
 LEGACY_SYMBOLS = {
     "de_debug_v5_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -277,7 +291,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

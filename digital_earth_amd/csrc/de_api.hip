@@ -237,6 +237,62 @@ int run_history(de_ctx* c, DisplayArgs& d, bool& per_tile) {
     d.hdr = c->d_hs_out; d.samples = 1; per_tile = false;
     return DE_OK;
 }
+// ---- local exposure (include/digital_earth_local_exposure.h, local_exposure_kernels.hip)
+int lx_alloc(de_ctx* c) {
+    const BloomPlan p = bl_plan(c->W, c->H, LX_MAX_LEVELS);      // the bloom's pyramid plan; room for every setting of `levels`: the offsets of a level do not depend on it
+    if (!c->d_lx_pyr) HIP_TRY(hipMalloc(&c->d_lx_pyr, p.total * sizeof(float2)));
+    if (!c->d_lx_base) HIP_TRY(hipMalloc(&c->d_lx_base, p.total * sizeof(float)));
+    if (!c->d_lx_out) HIP_TRY(hipMalloc(&c->d_lx_out, (size_t)c->W * c->H * 3 * sizeof(float)));
+    return DE_OK;
+}
+int lx_settings_check(const de_local_exposure* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_local_exposure)) return fail(DE_ERR_INVALID, "de_local_exposure.struct_bytes does not match this library's struct");
+    if (!(s->highlights >= 0.0f) || !(s->highlights <= 1.0f) || !(s->shadows >= 0.0f) || !(s->shadows <= 1.0f))
+        return fail(DE_ERR_INVALID, "local exposure settings: highlights and shadows in [0, 1]");
+    if (!(s->sigma > 0.0f) || !(s->sigma < 1e30f) || !(s->max_ev >= 0.0f) || !(s->max_ev < 1e30f) || !(s->key > 0.0f) || !(s->key < 1e30f))
+        return fail(DE_ERR_INVALID, "local exposure settings: finite sigma > 0, finite max_ev >= 0, finite key > 0");
+    if (s->levels < 1 || s->levels > LX_MAX_LEVELS) return fail(DE_ERR_INVALID, "local exposure settings: levels in 1 .. 10");
+    return DE_OK;
+}
+// The kernels on the context stream with the settings `x`, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>)
+// and with the anchor from d.fc (the metered FrameConsts while auto-exposure is on: no host round trip).  Afterwards `d` describes the dodged mean: the
+// unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).
+int lx_run(de_ctx* c, const de_local_exposure& x, DisplayArgs& d, bool& per_tile) {
+    const BloomPlan p = bl_plan(c->W, c->H, x.levels);
+    float2* D = c->d_lx_pyr;
+    float* B = c->d_lx_base;
+    LxSrc s;
+    s.hdr = d.hdr; s.tile_spp = per_tile ? d.tile_spp : nullptr; s.samples = d.samples; s.W = c->W; s.H = c->H;
+    const bool vec = (reinterpret_cast<uintptr_t>(d.hdr) & 15u) == 0u;
+    const float inv_sigma = 1.0f / x.sigma;
+    auto tiles = [](int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); };
+    if (vec) hipLaunchKernelGGL(lx_down0_kernel<true>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    else hipLaunchKernelGGL(lx_down0_kernel<false>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    HIP_TRY(hipGetLastError());
+    for (int l = 1; l < p.L; ++l) {
+        hipLaunchKernelGGL(lx_down_kernel, tiles(p.w[l + 1], p.h[l + 1]), dim3(256), 0, c->stream, (const float2*)(D + p.off[l]), p.w[l], p.h[l], D + p.off[l + 1], p.w[l + 1], p.h[l + 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    const float* top = nullptr;      // B_L is the top level's guide: not stored
+    for (int l = p.L - 1; l >= 1; --l) {
+        LxUpArgs u;
+        u.fine = D + p.off[l]; u.coarse = D + p.off[l + 1]; u.coarse_b = top; u.out = B + p.off[l];
+        u.Wc = p.w[l + 1]; u.Hc = p.h[l + 1]; u.Wf = p.w[l]; u.Hf = p.h[l]; u.inv_sigma = inv_sigma;
+        hipLaunchKernelGGL(lx_up_kernel, dim3((unsigned)(((size_t)u.Wf * (size_t)u.Hf + 255u) / 256u)), dim3(256), 0, c->stream, u);
+        HIP_TRY(hipGetLastError());
+        top = u.out;
+    }
+    LxApplyArgs a;
+    a.s = s; a.d1 = D + p.off[1]; a.b1 = top; a.W1 = p.w[1]; a.H1 = p.h[1]; a.fc = d.fc;
+    a.highlights = x.highlights; a.shadows = x.shadows; a.inv_sigma = inv_sigma; a.max_ev = x.max_ev; a.key = x.key; a.out = c->d_lx_out;
+    const unsigned n_wg = (unsigned)(((size_t)(c->W >> 2) * (size_t)c->H + 255u) / 256u);
+    if (vec) hipLaunchKernelGGL(lx_apply_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(lx_apply_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    d.hdr = c->d_lx_out; d.samples = 1; per_tile = false;
+    return DE_OK;
+}
+int run_local_exposure(de_ctx* c, DisplayArgs& d, bool& per_tile) { return lx_run(c, c->lx, d, per_tile); }
 // What the display reads: the sums with the frame's or the tiles' counts, a display source, or the denoiser's filtered mean (the caller has run it).
 void display_source(de_ctx* c, DisplayArgs& d, bool& per_tile) {
     d.hdr = c->display_src ? c->display_src : c->d_hdr;
@@ -333,7 +389,7 @@ int de_destroy(de_ctx* c) {
                      c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
                      c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
-                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px};
+                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px, c->d_lx_pyr, c->d_lx_base, c->d_lx_out};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
@@ -672,6 +728,7 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     if (c->hs_on) { rc = run_history(c, d, per_tile); if (rc) return rc; }      // ahead of the meter and the bloom: they see the stabilised image
     if (c->ae_on) { rc = run_meter(c, d, per_tile); if (rc) return rc; d.fc = c->d_fc_ae; }      // the same transform over the metered exposure: a second FrameConsts, written on the device
     if (c->bl_on) { rc = run_bloom(c, d, per_tile); if (rc) return rc; }      // after the meter (the scene is metered, not the lens): the composited mean through the unchanged transform
+    if (c->lx_on) { rc = run_local_exposure(c, d, per_tile); if (rc) return rc; }      // last: the scene is metered, the lens glares, the print is dodged; the anchor is d.fc's exposure
     const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
     if (per_tile) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
     else hipLaunchKernelGGL(display_kernel<false>, grid, dim3(256), 0, c->stream, d);
@@ -1424,6 +1481,90 @@ int de_debug_history(de_ctx* c, const float* mean, const int32_t* n, const float
             float* o = out + ((size_t)i * H + j) * 4;
             o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
         }
+    return DE_OK;
+}
+
+/* ---- local exposure: include/digital_earth_local_exposure.h */
+int de_set_local_exposure(de_ctx* c, const de_local_exposure* s) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (!s) { c->lx_on = false; return DE_OK; }
+    if (s->struct_bytes != (uint32_t)sizeof(de_local_exposure)) return fail(DE_ERR_INVALID, "de_local_exposure.struct_bytes does not match this library's struct");
+    if (!s->on) { c->lx_on = false; return DE_OK; }
+    { int rc = lx_settings_check(s); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = lx_alloc(c); if (rc) return rc; }
+    c->lx = *s;
+    c->lx.on = 1;
+    c->lx_on = true;
+    return DE_OK;
+}
+int de_get_local_exposure(de_ctx* c, de_local_exposure* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (c->lx_on) *out = c->lx; else memset(out, 0, sizeof(*out));
+    out->struct_bytes = (uint32_t)sizeof(de_local_exposure);
+    return DE_OK;
+}
+int de_fetch_local_exposure_hdr(de_ctx* c, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (!c->lx_on) return fail(DE_ERR_STATE, "local exposure is off (de_set_local_exposure)");
+    if (!c->luts_set) return fail(DE_ERR_STATE, "LUTs must be uploaded before fetch_local_exposure_hdr");
+    if (c->dn_on) { int rc = denoise_refusal(c); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = run_setup(c);      // the anchor is read from the frame constants
+    if (rc) return rc;
+    rc = join_slots(c);
+    if (rc) return rc;
+    touched_hdr(c);
+    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }
+    DisplayArgs d;
+    bool per_tile;
+    display_source(c, d, per_tile);
+    d.fc = c->d_fc;
+    // as the display does
+    if (c->hs_on) { rc = run_history(c, d, per_tile); if (rc) return rc; }
+    if (c->ae_on) { rc = run_meter(c, d, per_tile); if (rc) return rc; d.fc = c->d_fc_ae; }
+    if (c->bl_on) { rc = run_bloom(c, d, per_tile); if (rc) return rc; }
+    rc = run_local_exposure(c, d, per_tile);
+    if (rc) return rc;
+    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, (const float*)c->d_lx_out, c->d_scratch, c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    return copy_out(c, out, c->d_scratch);
+}
+/* The stage once on a host-given mean.  A source and a FrameConsts of its own; the pyramid and the output are the context's (nothing between displays
+ * lives in them). */
+int de_debug_local_exposure(de_ctx* c, const float* mean, float exposure_scale, const de_local_exposure* s, float* out) {
+    if (!c || !mean || !s || !out) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = lx_settings_check(s); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = lx_alloc(c); if (rc) return rc; }
+    const int W = c->W, H = c->H;
+    const size_t npx = (size_t)W * H;
+    struct Bufs {   // freed on every exit path
+        void* p[2] = {};
+        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
+    } b;
+    HIP_TRY(hipMalloc(&b.p[0], npx * 3 * sizeof(float)));
+    HIP_TRY(hipMalloc(&b.p[1], sizeof(FrameConsts)));
+    std::vector<float> m(npx * 3);      // host layout (W, H, 3) -> device layout [H][W][3]
+    for (int i = 0; i < W; ++i)
+        for (int j = 0; j < H; ++j)
+            for (int ch = 0; ch < 3; ++ch) m[((size_t)j * W + i) * 3 + ch] = mean[((size_t)i * H + j) * 3 + ch];
+    FrameConsts fc;
+    memset(&fc, 0, sizeof(fc));
+    fc.exposure_scale = exposure_scale;      // the only field the stage reads
+    HIP_TRY(hipMemcpyAsync(b.p[0], m.data(), npx * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b.p[1], &fc, sizeof(fc), hipMemcpyHostToDevice, c->stream));
+    DisplayArgs d;
+    memset(&d, 0, sizeof(d));
+    d.fc = (const FrameConsts*)b.p[1]; d.hdr = (const float*)b.p[0]; d.W = W; d.H = H; d.samples = 1;
+    bool per_tile = false;
+    int rc = lx_run(c, *s, d, per_tile);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(m.data(), c->d_lx_out, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < W; ++i)
+        for (int j = 0; j < H; ++j)
+            for (int ch = 0; ch < 3; ++ch) out[((size_t)i * H + j) * 3 + ch] = m[((size_t)j * W + i) * 3 + ch];
     return DE_OK;
 }
 

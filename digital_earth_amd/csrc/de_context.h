@@ -5,6 +5,7 @@
 #include "../../include/digital_earth_bloom.h"
 #include "../../include/digital_earth_history.h"
 #include "../../include/digital_earth_pixels.h"
+#include "../../include/digital_earth_local_exposure.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -31,6 +32,7 @@
 #include "bloom_kernels.hip"
 #include "history_kernels.hip"
 #include "pixels_kernels.hip"
+#include "local_exposure_kernels.hip"
 
 namespace {
 
@@ -241,6 +243,14 @@ struct de_ctx {
     uint8_t* h_px_ring[DE_FETCH_RING] = {};
     hipEvent_t ev_px_ring[DE_FETCH_RING] = {};
     unsigned px_begun = 0, px_ended = 0;
+    // Local exposure (include/digital_earth_local_exposure.h).  Allocated on first use: the float2 pyramid D_1 .. D_L (l w, w) and the f32
+    // bases B_1 .. B_{L-1} of the largest L the image admits (5.5 + 2.8 MB at 1080p) and the dodged mean that the display reads with samples = 1 (25 MB
+    // at 1080p).  Per context.
+    bool lx_on = false;
+    de_local_exposure lx;           // the settings
+    float2* d_lx_pyr = nullptr;
+    float* d_lx_base = nullptr;
+    float* d_lx_out = nullptr;      // [H][W][3]
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

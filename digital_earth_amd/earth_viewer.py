@@ -184,9 +184,10 @@ def _rgb_picture(px):
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, **renderer_kwargs):
         """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
-        in frame()'s loop instead of restarting at one sample per pixel."""
+        in frame()'s loop instead of restarting at one sample per pixel.  local_exposure: the same for Renderer.set_local_exposure — every frame is
+        dodged and burned on the GPU ahead of the display transform."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
@@ -194,6 +195,8 @@ class EarthViewer:
         self.renderer.copy_textures()
         if history:
             self.renderer.set_history(True, **(history if isinstance(history, dict) else {}))
+        if local_exposure:
+            self.renderer.set_local_exposure(True, **(local_exposure if isinstance(local_exposure, dict) else {}))
         self.config = None
         if config is not None:
             self.load_config(config)

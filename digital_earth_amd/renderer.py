@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeLocalExposure, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -613,6 +613,53 @@ class Renderer:
         out = np.empty((W, H, 4), dtype=np.float32)
         check(self._lib.de_debug_history(self._h, mean.ctypes.data, n.ctypes.data, dist.ctypes.data, ctypes.byref(params), hc, hd, hp,
                                          float(max_history), float(depth_tolerance), out.ctypes.data))
+        return out
+
+    # ------------------------------------------------------------------ local exposure (include/digital_earth_local_exposure.h)
+    def _local_exposure_settings(self, highlights, shadows, sigma, max_ev, key, levels):
+        s = DeLocalExposure()
+        s.struct_bytes = ctypes.sizeof(DeLocalExposure)
+        s.on = 1
+        s.highlights, s.shadows, s.sigma, s.max_ev, s.key, s.levels = float(highlights), float(shadows), float(sigma), float(max_ev), float(key), int(levels)
+        return s
+
+    def set_local_exposure(self, on=True, highlights=0.5, shadows=0.25, sigma=1.0, max_ev=2.0, key=0.18, levels=6):
+        """Turn the local exposure of the display path on (or off): an edge-aware dodge and burn.  While it is on, every fetch_image / fetch_pixels (lag
+        included) first multiplies every pixel of the HDR mean by 2^ev on the GPU, ev = -strength (B - mid) clamped to +-`max_ev` stops: B a smooth base
+        of log2 luminance that stops at edges (a pyramid of `levels` levels, `sigma` stops wide in range), mid the scene luminance that the exposure in
+        use (the metered one under auto-exposure) maps to `key`, strength `highlights` above mid and `shadows` below.  Detail and chroma are kept: the
+        gain depends on the base only.  It runs last, behind the meter and the bloom.  fetch_hdr() is unchanged."""
+        if not on:
+            check(self._lib.de_set_local_exposure(self._h, None))
+            return
+        check(self._lib.de_set_local_exposure(self._h, ctypes.byref(self._local_exposure_settings(highlights, shadows, sigma, max_ev, key, levels))))
+
+    @property
+    def local_exposure(self):
+        """The local exposure settings as a dict (set_local_exposure's keywords), or None while it is off."""
+        s = DeLocalExposure()
+        check(self._lib.de_get_local_exposure(self._h, ctypes.byref(s)))
+        if not s.on:
+            return None
+        return dict(highlights=float(s.highlights), shadows=float(s.shadows), sigma=float(s.sigma), max_ev=float(s.max_ev), key=float(s.key), levels=int(s.levels))
+
+    def fetch_local_exposure_hdr(self):
+        """The dodged HDR mean that the display transform is given, (W, H, 3) float32 in fetch_hdr's layout (a mean, not a sum): the display chain up to
+        and including this stage.  Local exposure must be on.  Under auto-exposure it counts as a display for the meter's adaptation."""
+        if not self._textures_copied:
+            self.copy_textures()
+        out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
+        check(self._lib.de_fetch_local_exposure_hdr(self._h, out.ctypes.data))
+        return out
+
+    def debug_local_exposure(self, mean, exposure_scale, highlights=0.5, shadows=0.25, sigma=1.0, max_ev=2.0, key=0.18, levels=6):
+        """The stage once on a given (W, H, 3) float32 mean of this renderer's size, the anchor taken from `exposure_scale` = 2^exposure
+        (include/digital_earth_local_exposure.h: de_debug_local_exposure).  Returns (W, H, 3); the renderer's settings and frame are not touched."""
+        W, H = self.image_res
+        mean = np.ascontiguousarray(mean, dtype=np.float32).reshape(W, H, 3)
+        out = np.empty((W, H, 3), dtype=np.float32)
+        s = self._local_exposure_settings(highlights, shadows, sigma, max_ev, key, levels)
+        check(self._lib.de_debug_local_exposure(self._h, mean.ctypes.data, ctypes.c_float(float(exposure_scale)), ctypes.byref(s), out.ctypes.data))
         return out
 
     def _staging_view(self, ptr):
