@@ -82,6 +82,11 @@ class DeLocalExposure(ctypes.Structure):
                 ("max_ev", ctypes.c_float), ("key", ctypes.c_float), ("levels", ctypes.c_int32)]
 
 
+class DeOutputScale(ctypes.Structure):
+    """`de_output_scale` (include/digital_earth_output_scale.h): the size and the filter of the resampled output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("enabled", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("filter", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -143,6 +148,8 @@ DEBUG_SYMBOLS = {
     "de_debug_denoise": (ctypes.c_int, [_P, _P, _P, _P, ctypes.c_int, ctypes.c_float, _P]),
     "de_debug_history": (ctypes.c_int, [_P, _P, _P, _P, ctypes.POINTER(DeParams), _P, _P, ctypes.POINTER(DeParams), ctypes.c_float, ctypes.c_float, _P]),
     "de_debug_pixels": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePixels), ctypes.c_uint32, _P]),
+    "de_debug_output_scale": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeOutputScale), _P]),
+    "de_debug_output_scale_weights": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_int)]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "de_set_launch_slots": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
@@ -210,6 +217,13 @@ LOCAL_EXPOSURE_SYMBOLS = {
     "de_get_local_exposure": (ctypes.c_int, [_P, ctypes.POINTER(DeLocalExposure)]),
     "de_fetch_local_exposure_hdr": (ctypes.c_int, [_P, _P]),
     "de_debug_local_exposure": (ctypes.c_int, [_P, _P, ctypes.c_float, ctypes.POINTER(DeLocalExposure), _P]),
+}
+
+# output scaling: include/digital_earth_output_scale.h (same library, additions only; not part of the binder's header)
+OUTPUT_SCALE_SYMBOLS = {
+    "de_set_output_scale": (ctypes.c_int, [_P, ctypes.POINTER(DeOutputScale)]),
+    "de_get_output_scale": (ctypes.c_int, [_P, ctypes.POINTER(DeOutputScale)]),
+    "de_output_size": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
 }
 
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
@@ -291,7 +305,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

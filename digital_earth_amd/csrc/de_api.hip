@@ -389,7 +389,8 @@ int de_destroy(de_ctx* c) {
                      c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
                      c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
-                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px, c->d_lx_pyr, c->d_lx_base, c->d_lx_out};
+                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px, c->d_lx_pyr, c->d_lx_base, c->d_lx_out,
+                     c->os_tab[0].first, c->os_tab[0].w, c->os_tab[1].first, c->os_tab[1].w, c->d_os_mid, c->d_os_out};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
@@ -707,6 +708,87 @@ int de_flush(de_ctx* c) {
     return frame_status(c);  // an abort already known (the words are host-visible): a host framework's own collective must not ship that frame
 }
 
+/* ---- output scaling: include/digital_earth_output_scale.h (output_scale_kernels.hip).  The helpers stand here because every call that
+ * hands out the displayed image sizes itself from them; the entry points are at the end of the file. */
+namespace {
+bool os_active(const de_ctx* c) { return c->os.enabled && c->os.width > 0 && (c->os.width != c->W || c->os.height != c->H); }      // on at W x H is the identity: nothing runs
+int out_w(const de_ctx* c) { return os_active(c) ? c->os.width : c->W; }
+int out_h(const de_ctx* c) { return os_active(c) ? c->os.height : c->H; }
+size_t out_image_bytes(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3 * sizeof(float); }
+const float* shown_image(const de_ctx* c) { return os_active(c) ? c->d_os_out : c->d_image; }
+// The settings against a source size; *ow, *oh = the output size they ask for (0, 0: the source's).
+int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_output_scale)) return fail(DE_ERR_INVALID, "de_output_scale.struct_bytes does not match this library's struct");
+    if (s->filter < DE_SCALE_BOX || s->filter > DE_SCALE_LANCZOS3) return fail(DE_ERR_INVALID, "de_output_scale.filter must be DE_SCALE_BOX, _TRIANGLE, _MITCHELL or _LANCZOS3");
+    const int w = (s->width == 0 && s->height == 0) ? W : s->width, h = (s->width == 0 && s->height == 0) ? H : s->height;
+    if (w <= 0 || h <= 0 || (w % 16) != 0 || (h % 8) != 0) return fail(DE_ERR_INVALID, "de_output_scale: width must be a positive multiple of 16 and height of 8");
+    if ((long long)w * 8 < W || (long long)W * 8 < w || (long long)h * 8 < H || (long long)H * 8 < h) return fail(DE_ERR_INVALID, "de_output_scale: each axis' ratio out / source must lie in [1/8, 8]");
+    if ((long long)w * h > (1ll << 28)) return fail(DE_ERR_INVALID, "de_output_scale: width * height must not exceed 2^28");
+    *ow = w; *oh = h;
+    return DE_OK;
+}
+// A device buffer of at least `bytes`: one that is too small is replaced (hipFree waits for the work that reads it).
+int os_device_ensure(void** p, size_t* have, size_t bytes) {
+    if (*p && *have >= bytes) return DE_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no device memory for the output scaling's buffers"); }
+    *have = bytes;
+    return DE_OK;
+}
+// One axis' table on the device, rebuilt only when the axis or the filter changed.  The upload reads pageable host memory that dies with this call: waited for.
+int os_table_ensure(hipStream_t stream, de_ctx::ScaleDev& d, int n_src, int n_dst, int filter) {
+    if (d.first && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
+    ScaleTable T;
+    if (!os_build_table(n_src, n_dst, filter, &T)) return fail(DE_ERR_INVALID, "output scaling: no table for this pair of sizes");
+    size_t fb = d.first_cap * sizeof(int32_t), wb = d.w_cap * sizeof(float);
+    int rc = os_device_ensure((void**)&d.first, &fb, T.first.size() * sizeof(int32_t));
+    d.first_cap = fb / sizeof(int32_t);
+    if (rc) return rc;
+    rc = os_device_ensure((void**)&d.w, &wb, T.w.size() * sizeof(float));
+    d.w_cap = wb / sizeof(float);
+    if (rc) return rc;
+    d.filter = -1;
+    HIP_TRY(hipMemcpyAsync(d.first, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d.w, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    d.n_src = n_src; d.n_dst = n_dst; d.filter = filter; d.taps = T.taps;
+    return DE_OK;
+}
+// The passes of (W, H, 3) -> (ow, oh, 3), not both sizes equal: along v into `mid` (or straight into `out` when the other axis is a copy), then along u.
+int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh, const de_ctx::ScaleDev& tv, const de_ctx::ScaleDev& tu, float* mid, float* out) {
+    const float* in = src;
+    if (oh != H) {
+        ScaleArgs a;
+        a.src = in; a.dst = ow != W ? mid : out; a.first = tv.first; a.w = tv.w; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
+        const unsigned long long blocks = (unsigned long long)W * (unsigned long long)os_v_tiles(oh);
+        if (blocks * OS_V_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the image has too many columns for one launch");
+        hipLaunchKernelGGL(output_scale_v_kernel, dim3((unsigned)blocks), dim3(OS_V_THREADS), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+        in = a.dst;
+    }
+    if (ow != W) {
+        ScaleArgs a;
+        a.src = in; a.dst = out; a.first = tu.first; a.w = tu.w; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
+        const unsigned long long blocks = (unsigned long long)ow * (unsigned long long)os_u_chunks(oh * 3);
+        if (blocks * OS_U_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the output has too many columns for one launch");
+        hipLaunchKernelGGL(output_scale_u_kernel, dim3((unsigned)blocks), dim3(OS_U_THREADS), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return DE_OK;
+}
+// Behind the display on the context stream: d_image -> d_os_out.
+int run_output_scale(de_ctx* c) {
+    const int W = c->W, H = c->H, ow = c->os.width, oh = c->os.height;
+    int rc = DE_OK;
+    if (oh != H) { rc = os_table_ensure(c->stream, c->os_tab[0], H, oh, c->os.filter); if (rc) return rc; }
+    if (ow != W) { rc = os_table_ensure(c->stream, c->os_tab[1], W, ow, c->os.filter); if (rc) return rc; }
+    if (oh != H && ow != W) { rc = os_device_ensure((void**)&c->d_os_mid, &c->os_mid_bytes, (size_t)W * (size_t)oh * 3 * sizeof(float)); if (rc) return rc; }
+    rc = os_device_ensure((void**)&c->d_os_out, &c->os_out_bytes, (size_t)ow * (size_t)oh * 3 * sizeof(float));
+    if (rc) return rc;
+    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], c->d_os_mid, c->d_os_out);
+}
+}  // namespace
+
 int de_render_to_image(de_ctx* c, const float** device_image) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (!c->luts_set) return fail(DE_ERR_STATE, "LUTs must be uploaded before fetch_image");
@@ -737,7 +819,8 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     // a device-to-host copy of the image enqueued behind the display (de_fetch_image_begin) does not hold the next frame's sums back
     HIP_TRY(hipEventRecord(c->ev_main, c->stream));
     c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
-    if (device_image) *device_image = c->d_image;
+    if (os_active(c)) { rc = run_output_scale(c); if (rc) return rc; }      // behind ev_main: the next frame's sums do not wait for the resampling
+    if (device_image) *device_image = shown_image(c);
     return DE_OK;
 }
 
@@ -745,16 +828,16 @@ int de_fetch_image(de_ctx* c, float* out) {
     if (!out) return fail(DE_ERR_INVALID, "out is null");
     int rc = de_render_to_image(c, nullptr);
     if (rc) return rc;
-    return copy_out(c, out, c->d_image);
+    return copy_out(c, out, shown_image(c), out_image_bytes(c));
 }
 
 int de_fetch_image_view(de_ctx* c, const float** host_image) {
     if (!host_image) return fail(DE_ERR_INVALID, "host_image is null");
     int rc = de_render_to_image(c, nullptr);
     if (rc) return rc;
-    const size_t bytes = (size_t)c->W * c->H * 3 * sizeof(float);
-    if (!c->h_stage && hipHostMalloc((void**)&c->h_stage, bytes, hipHostMallocDefault) != hipSuccess) { c->h_stage = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the staging buffer"); }
-    HIP_TRY(hipMemcpyAsync(c->h_stage, c->d_image, bytes, hipMemcpyDeviceToHost, c->stream));
+    const size_t bytes = out_image_bytes(c);
+    if (stage_ensure(c, bytes) != hipSuccess) return fail(DE_ERR_NOMEM, "no pinned host memory for the staging buffer");
+    HIP_TRY(hipMemcpyAsync(c->h_stage, shown_image(c), bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *host_image = c->h_stage;
     return frame_status(c);
@@ -767,15 +850,17 @@ int de_fetch_image_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (c->fetch_begun - c->fetch_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four fetches are in flight already: de_fetch_image_end first");
     const int k = (int)(c->fetch_begun % (unsigned)DE_FETCH_RING);
-    const size_t bytes = (size_t)c->W * c->H * 3 * sizeof(float);
+    const size_t bytes = out_image_bytes(c);
     HIP_TRY(hipSetDevice(c->device));
+    if (c->h_ring[k] && c->h_ring_bytes[k] < bytes) { (void)hipHostFree(c->h_ring[k]); c->h_ring[k] = nullptr; c->h_ring_bytes[k] = 0; }      // the output size grew; cell k is not in flight
     if (!c->h_ring[k]) {
         if (hipHostMalloc((void**)&c->h_ring[k], bytes, hipHostMallocDefault) != hipSuccess) { c->h_ring[k] = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the staging buffers"); }
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_ring[k], hipEventDisableTiming));
+        c->h_ring_bytes[k] = bytes;
     }
+    if (!c->ev_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_ring[k], hipEventDisableTiming));
     int rc = de_render_to_image(c, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_ring[k], c->d_image, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_ring[k], shown_image(c), bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(c->ev_ring[k], c->stream));
     c->fetch_begun++;
     return DE_OK;
@@ -1570,16 +1655,20 @@ int de_debug_local_exposure(de_ctx* c, const float* mean, float exposure_scale, 
 
 /* ---- 8-bit pixel output: include/digital_earth_pixels.h (pixels_kernels.hip) */
 namespace {
-size_t px_size(const de_ctx* c) { return (size_t)c->W * c->H * (size_t)c->px.channels; }
-size_t px_capacity(const de_ctx* c) { return (size_t)c->W * c->H * 4; }      // every buffer holds either format: de_set_pixels frees nothing
+size_t px_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (size_t)c->px.channels; }      // of the output size (include/digital_earth_output_scale.h): W x H while that stage is off
+size_t px_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 4; }      // every buffer holds either format: de_set_pixels frees nothing
 int px_settings_check(const de_pixels* s) {
     if (s->struct_bytes != (uint32_t)sizeof(de_pixels)) return fail(DE_ERR_INVALID, "de_pixels.struct_bytes does not match this library's struct");
     if (s->channels != 3 && s->channels != 4) return fail(DE_ERR_INVALID, "de_pixels.channels must be 3 or 4");
     if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_pixels.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
     return DE_OK;
 }
-int px_host_alloc(uint8_t** p, size_t bytes) {
-    if (!*p && hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the pixel staging buffers"); }
+int px_host_alloc(uint8_t** p, size_t* have, size_t bytes) {      // one that is too small for a new output size is replaced: no copy into it is in flight
+    if (*p && *have < bytes) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
+    if (!*p) {
+        if (hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the pixel staging buffers"); }
+        *have = bytes;
+    }
     return DE_OK;
 }
 void px_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_pixels& s, uint32_t phase) {
@@ -1606,11 +1695,12 @@ int de_get_pixels(de_ctx* c, de_pixels* out, uint32_t* last_phase) {
 int de_render_to_pixels(de_ctx* c, const uint8_t** device_pixels) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_px) HIP_TRY(hipMalloc(&c->d_px, px_capacity(c)));
+    if (c->d_px && c->d_px_bytes < px_capacity(c)) { (void)hipFree(c->d_px); c->d_px = nullptr; c->d_px_bytes = 0; }      // the output size grew (hipFree waits for the work that reads it)
+    if (!c->d_px) { HIP_TRY(hipMalloc(&c->d_px, px_capacity(c))); c->d_px_bytes = px_capacity(c); }
     int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
     if (rc) return rc;
     const uint32_t phase = c->px.animate ? c->px_count : 0u;
-    px_launch(c->stream, c->d_image, c->d_px, c->W, c->H, c->px, phase);
+    px_launch(c->stream, shown_image(c), c->d_px, out_w(c), out_h(c), c->px, phase);
     HIP_TRY(hipGetLastError());
     c->px_count++; c->px_last_phase = phase;
     if (device_pixels) *device_pixels = c->d_px;
@@ -1619,7 +1709,7 @@ int de_render_to_pixels(de_ctx* c, const uint8_t** device_pixels) {
 int de_fetch_pixels_view(de_ctx* c, const uint8_t** host) {
     if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_px_stage, px_capacity(c));
+    int rc = px_host_alloc(&c->h_px_stage, &c->h_px_stage_bytes, px_capacity(c));
     if (rc) return rc;
     rc = de_render_to_pixels(c, nullptr);
     if (rc) return rc;
@@ -1642,7 +1732,7 @@ int de_fetch_pixels_begin(de_ctx* c) {
     if (c->px_begun - c->px_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four pixel fetches are in flight already: de_fetch_pixels_end first");
     const int k = (int)(c->px_begun % (unsigned)DE_FETCH_RING);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_px_ring[k], px_capacity(c));
+    int rc = px_host_alloc(&c->h_px_ring[k], &c->h_px_ring_bytes[k], px_capacity(c));
     if (rc) return rc;
     if (!c->ev_px_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_px_ring[k], hipEventDisableTiming));
     rc = de_render_to_pixels(c, nullptr);
@@ -1680,6 +1770,70 @@ int de_debug_pixels(de_ctx* c, const float* image, int W, int H, const de_pixels
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, b.p[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+
+/* ---- output scaling: include/digital_earth_output_scale.h (the helpers stand ahead of de_render_to_image) */
+int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    int ow = 0, oh = 0;
+    { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
+    if (c->fetch_begun != c->fetch_ended) return fail(DE_ERR_STATE, "image fetches are in flight: de_fetch_image_end first");
+    if (c->px_begun != c->px_ended) return fail(DE_ERR_STATE, "pixel fetches are in flight: de_fetch_pixels_end first");
+    c->os = *s;
+    c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
+    return DE_OK;
+}
+int de_get_output_scale(de_ctx* c, de_output_scale* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->os;
+    if (out->width == 0 && out->height == 0) { out->width = c->W; out->height = c->H; }
+    return DE_OK;
+}
+int de_output_size(de_ctx* c, int* width, int* height) {
+    if (!c || !width || !height) return fail(DE_ERR_INVALID, "null argument");
+    *width = out_w(c); *height = out_h(c);
+    return DE_OK;
+}
+/* include/digital_earth_debug.h: the stage once on a host-given image.  Buffers and tables of its own; the context's setting is not touched. */
+int de_debug_output_scale(de_ctx* c, const float* image, int W, int H, const de_output_scale* s, float* out) {
+    if (!c || !image || !s || !out || W <= 0 || H <= 0 || (W % 16) != 0 || (H % 8) != 0 || (long long)W * H > (1ll << 28))
+        return fail(DE_ERR_INVALID, "bad arguments (W a multiple of 16, H a multiple of 8, as de_create asks)");
+    int ow = 0, oh = 0;
+    { int rc = os_settings_check(s, W, H, &ow, &oh); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    struct Bufs {   // freed on every exit path
+        void* p[3] = {};
+        de_ctx::ScaleDev t[2];
+        ~Bufs() { for (void* q : p) if (q) hipFree(q); for (auto& d : t) { if (d.first) hipFree(d.first); if (d.w) hipFree(d.w); } }
+    } b;
+    const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), mid_bytes = (size_t)W * oh * 3 * sizeof(float), out_bytes = (size_t)ow * oh * 3 * sizeof(float);
+    HIP_TRY(hipMalloc(&b.p[0], in_bytes));
+    HIP_TRY(hipMalloc(&b.p[1], mid_bytes));
+    HIP_TRY(hipMalloc(&b.p[2], out_bytes));
+    int rc = DE_OK;
+    if (oh != H) { rc = os_table_ensure(c->stream, b.t[0], H, oh, s->filter); if (rc) return rc; }
+    if (ow != W) { rc = os_table_ensure(c->stream, b.t[1], W, ow, s->filter); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(b.p[0], image, in_bytes, hipMemcpyHostToDevice, c->stream));
+    const void* result = b.p[0];      // both axes copies: the identity, nothing runs
+    if (ow != W || oh != H) {
+        rc = os_launch(c->stream, (const float*)b.p[0], W, H, ow, oh, b.t[0], b.t[1], (float*)b.p[1], (float*)b.p[2]);
+        if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+        result = b.p[2];
+    }
+    HIP_TRY(hipMemcpyAsync(out, result, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+int de_debug_output_scale_weights(de_ctx* c, int n_src, int n_dst, int filter, int32_t* first, float* weights, int* taps) {
+    if (!c || !taps) return fail(DE_ERR_INVALID, "null argument");
+    ScaleTable T;
+    if (!os_build_table(n_src, n_dst, filter, &T)) return fail(DE_ERR_INVALID, "de_debug_output_scale_weights: sizes must be positive with n_dst / n_src in [1/8, 8], the filter DE_SCALE_*");
+    *taps = T.taps;
+    if (first) memcpy(first, T.first.data(), T.first.size() * sizeof(int32_t));
+    if (weights)
+        for (int j = 0; j < n_dst; ++j)
+            for (int t = 0; t < T.taps; ++t) weights[(size_t)j * (size_t)T.taps + (size_t)t] = T.w[(size_t)t * (size_t)n_dst + (size_t)j];      // the kernels' [tap][j], transposed
     return DE_OK;
 }
 

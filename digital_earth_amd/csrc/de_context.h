@@ -6,6 +6,7 @@
 #include "../../include/digital_earth_history.h"
 #include "../../include/digital_earth_pixels.h"
 #include "../../include/digital_earth_local_exposure.h"
+#include "../../include/digital_earth_output_scale.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -32,6 +33,7 @@
 #include "bloom_kernels.hip"
 #include "history_kernels.hip"
 #include "pixels_kernels.hip"
+#include "output_scale_kernels.hip"
 #include "local_exposure_kernels.hip"
 
 namespace {
@@ -119,9 +121,11 @@ struct de_ctx {
     float* d_image = nullptr;    // (W, H, 3)
     float* d_scratch = nullptr;  // (W, H, 3) / debug [H][W][4]
     float* h_stage = nullptr;     // pinned host staging for fetch_image / fetch_hdr (a pageable destination copies at a fraction of the link rate)
+    size_t h_stage_bytes = 0;     // its size: W * H * 3 floats, or the output size's when that is larger (include/digital_earth_output_scale.h)
     // de_fetch_image_begin / _end: the window loop pipelined — display + device-to-host copy of frame k run on the context stream while launch k + 1 renders.
     // DE_FETCH_RING pinned buffers and events; fetch_begun / fetch_ended count the calls (begun - ended = fetches in flight, at most DE_FETCH_RING).
     float* h_ring[DE_FETCH_RING] = {};
+    size_t h_ring_bytes[DE_FETCH_RING] = {};
     hipEvent_t ev_ring[DE_FETCH_RING] = {};
     unsigned fetch_begun = 0, fetch_ended = 0;
     uint32_t* d_tiles = nullptr;
@@ -243,6 +247,7 @@ struct de_ctx {
     uint8_t* h_px_ring[DE_FETCH_RING] = {};
     hipEvent_t ev_px_ring[DE_FETCH_RING] = {};
     unsigned px_begun = 0, px_ended = 0;
+    size_t d_px_bytes = 0, h_px_stage_bytes = 0, h_px_ring_bytes[DE_FETCH_RING] = {};      // sized from the output size: a buffer too small for a new one is re-allocated
     // Local exposure (include/digital_earth_local_exposure.h).  Allocated on first use: the float2 pyramid D_1 .. D_L (l w, w) and the f32
     // bases B_1 .. B_{L-1} of the largest L the image admits (5.5 + 2.8 MB at 1080p) and the dodged mean that the display reads with samples = 1 (25 MB
     // at 1080p).  Per context.
@@ -251,6 +256,18 @@ struct de_ctx {
     float2* d_lx_pyr = nullptr;
     float* d_lx_base = nullptr;
     float* d_lx_out = nullptr;      // [H][W][3]
+    // Output scaling (include/digital_earth_output_scale.h).  Allocated on first use: the tables of the two axes (first[n_dst] and
+    // w[taps][n_dst] each), the intermediate (W, oh, 3) and the output (ow, oh, 3); re-allocated when a new size needs more.  Per context.
+    de_output_scale os = {(uint32_t)sizeof(de_output_scale), 0, 0, 0, DE_SCALE_LANCZOS3};      // the settings; width = height = 0 until the first set: W, H
+    struct ScaleDev {               // one axis' table on the device, and what it was built for
+        int32_t* first = nullptr;
+        float* w = nullptr;
+        size_t first_cap = 0, w_cap = 0;      // elements
+        int n_src = 0, n_dst = 0, filter = -1, taps = 0;
+    } os_tab[2];                    // [0] along v, [1] along u
+    float* d_os_mid = nullptr;
+    float* d_os_out = nullptr;
+    size_t os_mid_bytes = 0, os_out_bytes = 0;
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

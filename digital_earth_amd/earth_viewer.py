@@ -184,10 +184,11 @@ def _rgb_picture(px):
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", **renderer_kwargs):
         """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
         in frame()'s loop instead of restarting at one sample per pixel.  local_exposure: the same for Renderer.set_local_exposure — every frame is
-        dodged and burned on the GPU ahead of the display transform."""
+        dodged and burned on the GPU ahead of the display transform.  output_res: None, or the (width, height) at which frames are delivered and
+        saved while screen_res is rendered (Renderer.set_output_scale with `output_filter`): a supersampled still, or a window larger than the render."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
@@ -197,6 +198,8 @@ class EarthViewer:
             self.renderer.set_history(True, **(history if isinstance(history, dict) else {}))
         if local_exposure:
             self.renderer.set_local_exposure(True, **(local_exposure if isinstance(local_exposure, dict) else {}))
+        if output_res is not None:
+            self.renderer.set_output_scale(tuple(output_res), filter=output_filter)
         self.config = None
         if config is not None:
             self.load_config(config)
@@ -306,7 +309,7 @@ class EarthViewer:
         self.renderer.close()
 
     def save(self, path):
-        """'p' screenshot (:244-250): writes the displayed image; `.npy` keeps the float (W, H, 3) array.  Every other format gets packed 8-bit pixels
+        """'p' screenshot (:244-250): writes the displayed image, at the output size when output_res is set; `.npy` keeps the float (W, H, 3) array.  Every other format gets packed 8-bit pixels
         converted on the GPU in the renderer's current mode (Renderer.set_pixels; truncation by default: the reference's to_vec3u, byte for byte) and
         handed to the image writer as they are, rows top-down — no clip, cast, transpose or flip on the host.  What is written is the picture this
         viewer last showed, never a new display of the context: the image held goes through the pack kernel as it is (Renderer.debug_pixels), and

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeLocalExposure, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -662,8 +662,68 @@ class Renderer:
         check(self._lib.de_debug_local_exposure(self._h, mean.ctypes.data, ctypes.c_float(float(exposure_scale)), ctypes.byref(s), out.ctypes.data))
         return out
 
+    # ------------------------------------------------------------------ output scaling (include/digital_earth_output_scale.h)
+    SCALE_FILTERS = ("box", "triangle", "mitchell", "lanczos3")
+
+    def _output_scale_settings(self, size, filter, on):
+        if filter not in self.SCALE_FILTERS:
+            raise ValueError("filter must be one of %s" % (self.SCALE_FILTERS,))
+        s = DeOutputScale()
+        s.struct_bytes = ctypes.sizeof(DeOutputScale)
+        s.enabled = 1 if on else 0
+        s.width, s.height = (0, 0) if size is None else (int(size[0]), int(size[1]))      # 0, 0: the source's own size
+        s.filter = self.SCALE_FILTERS.index(filter)
+        return s
+
+    def set_output_scale(self, size=None, filter="lanczos3", on=True):
+        """Deliver the displayed image at `size` = (width, height) instead of image_res: while this is on, fetch_image, fetch_pixels (lag included) and
+        render_to_image_device hand out the image of the unchanged display transform resampled on the GPU by a separable polyphase filter — "box",
+        "triangle", "mitchell" or "lanczos3", antialiased when it shrinks — and the pixels packed from it.  Render 3840 x 2160 and deliver 1920 x 1080
+        (a quarter of the bytes cross the link), or render at half size while the camera moves.  width a multiple of 16, height of 8, each within
+        [1/8, 8] of image_res; size=None is image_res (the identity, bit for bit).  Black and clipped white survive exactly.  Everything ahead of the
+        display runs at image_res; fetch_hdr() is unchanged.  Refused (DE_ERR_STATE) while lagged fetches are in flight; a view from a fetch with
+        copy=False does not outlive a change of size.  on=False: every fetch returns the bytes it returned before."""
+        check(self._lib.de_set_output_scale(self._h, ctypes.byref(self._output_scale_settings(size, filter, on))))
+
+    def output_scale(self):
+        """The output scaling as a dict (set_output_scale's keywords; size is image_res until one is set)."""
+        s = DeOutputScale()
+        check(self._lib.de_get_output_scale(self._h, ctypes.byref(s)))
+        return dict(size=(int(s.width), int(s.height)), filter=self.SCALE_FILTERS[s.filter], on=bool(s.enabled))
+
+    def output_size(self):
+        """(width, height) of what fetch_image and fetch_pixels deliver now: image_res while the output scaling is off."""
+        w, h = ctypes.c_int(), ctypes.c_int()
+        check(self._lib.de_output_size(self._h, ctypes.byref(w), ctypes.byref(h)))
+        return int(w.value), int(h.value)
+
+    def debug_output_scale(self, image, size, filter="lanczos3"):
+        """The stage once on a given (W, H, 3) float32 image (include/digital_earth_debug.h: de_debug_output_scale), W a multiple of 16 and H of 8 but
+        free of this renderer's size; returns (width, height, 3) float32.  The renderer's own setting is not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (W, H, 3)")
+        W, H = image.shape[:2]
+        s = self._output_scale_settings(size, filter, True)
+        ow, oh = (W, H) if size is None else (int(size[0]), int(size[1]))
+        out = np.empty((max(ow, 0), max(oh, 0), 3), dtype=np.float32)
+        check(self._lib.de_debug_output_scale(self._h, image.ctypes.data, W, H, ctypes.byref(s), out.ctypes.data))
+        return out
+
+    def debug_output_scale_weights(self, n_src, n_dst, filter):
+        """The table of one axis exactly as the kernels read it (de_debug_output_scale_weights): (first, weights) — first (n_dst,) int32, the first
+        source index of every output sample, unclamped; weights (n_dst, taps) float32."""
+        if filter not in self.SCALE_FILTERS:
+            raise ValueError("filter must be one of %s" % (self.SCALE_FILTERS,))
+        f, taps = self.SCALE_FILTERS.index(filter), ctypes.c_int()
+        check(self._lib.de_debug_output_scale_weights(self._h, int(n_src), int(n_dst), f, None, None, ctypes.byref(taps)))
+        first, w = np.empty(int(n_dst), np.int32), np.empty((int(n_dst), int(taps.value)), np.float32)
+        check(self._lib.de_debug_output_scale_weights(self._h, int(n_src), int(n_dst), f, first.ctypes.data, w.ctypes.data, ctypes.byref(taps)))
+        return first, w
+
     def _staging_view(self, ptr):
-        view = np.ctypeslib.as_array(ptr, shape=(self.image_res[0], self.image_res[1], 3)).view(_StagingView)
+        ow, oh = self.output_size()
+        view = np.ctypeslib.as_array(ptr, shape=(ow, oh, 3)).view(_StagingView)
         view.flags.writeable = False
         view._owner = self                      # the memory belongs to the context: the view keeps its Renderer alive ...
         self._view_ref = weakref.ref(view)      # ... and close() refuses while the view is
@@ -695,7 +755,8 @@ class Renderer:
             ptr = ctypes.POINTER(ctypes.c_float)()
             check(self._lib.de_fetch_image_view(self._h, ctypes.byref(ptr)))
             return self._staging_view(ptr)
-        out = np.empty((self.image_res[0], self.image_res[1], 3), dtype=np.float32)
+        ow, oh = self.output_size()
+        out = np.empty((ow, oh, 3), dtype=np.float32)
         check(self._lib.de_fetch_image(self._h, out.ctypes.data))
         return out
 
@@ -743,7 +804,8 @@ class Renderer:
         return dict(channels=int(s.channels), mode=self.PIXEL_MODES[s.mode], seed=int(s.seed), animate=bool(s.animate), last_phase=int(phase.value))
 
     def _pixel_view(self, ptr, channels):
-        view = np.ctypeslib.as_array(ptr, shape=(self.image_res[1], self.image_res[0], channels)).view(_StagingView)
+        ow, oh = self.output_size()
+        view = np.ctypeslib.as_array(ptr, shape=(oh, ow, channels)).view(_StagingView)
         view.flags.writeable = False
         view._owner = self
         self._pixel_view_ref = weakref.ref(view)
@@ -774,7 +836,8 @@ class Renderer:
             ptr = ctypes.POINTER(ctypes.c_uint8)()
             check(self._lib.de_fetch_pixels_view(self._h, ctypes.byref(ptr)))
             return self._pixel_view(ptr, channels)
-        out = np.empty((self.image_res[1], self.image_res[0], channels), dtype=np.uint8)
+        ow, oh = self.output_size()
+        out = np.empty((oh, ow, channels), dtype=np.uint8)
         check(self._lib.de_fetch_pixels(self._h, out.ctypes.data, ctypes.c_uint64(out.nbytes)))
         return out
 
@@ -957,7 +1020,8 @@ class Renderer:
         check(self._lib.de_set_wave_budget(self._h, int(waves_per_cu)))
 
     def render_to_image_device(self):
-        """Run the display transform and leave the (W, H, 3) image on the device; returns its address."""
+        """Run the display transform and leave the image on the device, (W, H, 3) float32 — (width, height, 3) of output_size() while the output scaling
+        is on; returns its address."""
         if not self._textures_copied:
             self.copy_textures()
         p = ctypes.c_void_p()

@@ -88,6 +88,16 @@ int de_debug_history(de_ctx* ctx, const float* mean, const int32_t* n, const flo
  * row 0 at the top.  Buffers of its own: the context's pixels and its phase counter are not touched.  For the tests' restatement (tests/pixels_ref.py). */
 struct de_pixels;
 int de_debug_pixels(de_ctx* ctx, const float* image, int W, int H, const struct de_pixels* settings, uint32_t phase, uint8_t* out);
+/* The output scaling (include/digital_earth_output_scale.h) once on a host-given image: image (W, H, 3) floats as de_fetch_image returns them, W a
+ * multiple of 16 and H of 8 but otherwise free of the context's size; settings as de_set_output_scale takes them (`enabled` is not read, and 0, 0
+ * stands for W, H), checked against W and H; out (width, height, 3) floats.  Buffers of its own: the context's setting is not touched.
+ * de_debug_output_scale_weights: the table of one axis exactly as the kernels read it.  first[n_dst] = the first source index of every output
+ * sample, unclamped and possibly negative; weights[n_dst][taps] float32, row by row (the kernels hold the transpose, [tap][j]); *taps = the axis'
+ * tap count.  `first` and `weights` may be NULL to ask for the tap count alone (at most 49).  n_dst / n_src must lie in [1/8, 8].  For the tests'
+ * restatement (tests/output_scale_ref.py). */
+struct de_output_scale;
+int de_debug_output_scale(de_ctx* ctx, const float* image, int W, int H, const struct de_output_scale* settings, float* out);
+int de_debug_output_scale_weights(de_ctx* ctx, int n_src, int n_dst, int filter, int32_t* first, float* weights, int* taps);
 
 /* ---- the N-rank collectives' device code on ONE GPU
  * de_debug_ordered_sum: the root's half of de_reduce_ordered without a communicator.  `parts` = n_parts host buffers of W*H*3 floats each (device
