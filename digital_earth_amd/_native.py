@@ -87,6 +87,12 @@ class DeOutputScale(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("enabled", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("filter", ctypes.c_int32)]
 
 
+class DeHdrOutput(ctypes.Structure):
+    """`de_hdr_output` (include/digital_earth_hdr_output.h): the HDR display output — peak luminance, gamut, transfer, and the format of its pixels."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("on", ctypes.c_int32), ("peak_nits", ctypes.c_float), ("gamut", ctypes.c_int32), ("transfer", ctypes.c_int32),
+                ("pixel_format", ctypes.c_int32), ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("animate", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -150,6 +156,7 @@ DEBUG_SYMBOLS = {
     "de_debug_pixels": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePixels), ctypes.c_uint32, _P]),
     "de_debug_output_scale": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeOutputScale), _P]),
     "de_debug_output_scale_weights": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_int)]),
+    "de_debug_hdr_consts": (ctypes.c_int, [_P, ctypes.POINTER(DeHdrOutput), _P]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
     "de_set_launch_slots": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
@@ -224,6 +231,15 @@ OUTPUT_SCALE_SYMBOLS = {
     "de_set_output_scale": (ctypes.c_int, [_P, ctypes.POINTER(DeOutputScale)]),
     "de_get_output_scale": (ctypes.c_int, [_P, ctypes.POINTER(DeOutputScale)]),
     "de_output_size": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+}
+
+# HDR display output: include/digital_earth_hdr_output.h (same library, additions only; not part of the binder's header)
+HDR_OUTPUT_SYMBOLS = {
+    "de_set_hdr_output": (ctypes.c_int, [_P, ctypes.POINTER(DeHdrOutput)]),
+    "de_get_hdr_output": (ctypes.c_int, [_P, ctypes.POINTER(DeHdrOutput), ctypes.POINTER(ctypes.c_uint32)]),
+    "de_render_to_hdr_pixels": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_hdr_pixels": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
+    "de_debug_hdr_transform": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.POINTER(DeHdrOutput), _P]),
 }
 
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
@@ -305,7 +321,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

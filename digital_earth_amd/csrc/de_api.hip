@@ -25,6 +25,11 @@ int denoise_refusal(de_ctx* c) {
     if (c->display_src) return fail(DE_ERR_STATE, "the denoiser filters this context's own frame: not with a display source or after de_reduce_progressive");
     return DE_OK;
 }
+// ---- the HDR display output (include/digital_earth_hdr_output.h, hdr_output_kernels.hip)
+int hdr_output_refusal(de_ctx* c) {
+    if (c->p.flags & DE_FLAG_AGX) return fail(DE_ERR_STATE, "the HDR display output runs OpenDRT: not with DE_FLAG_AGX, an SDR transform");
+    return DE_OK;
+}
 // the guides alone: what guide_kernel writes (the history reprojection reads their distance without the denoiser's other buffers)
 int dn_alloc_guides(de_ctx* c) {
     const size_t npx = (size_t)c->W * c->H;
@@ -390,11 +395,12 @@ int de_destroy(de_ctx* c) {
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
                      c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
                      c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px, c->d_lx_pyr, c->d_lx_base, c->d_lx_out,
-                     c->os_tab[0].first, c->os_tab[0].w, c->os_tab[1].first, c->os_tab[1].w, c->d_os_mid, c->d_os_out};
+                     c->os_tab[0].first, c->os_tab[0].w, c->os_tab[1].first, c->os_tab[1].w, c->d_os_mid, c->d_os_out, c->d_hpx};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
     if (c->h_px_stage) hipHostFree(c->h_px_stage);
+    if (c->h_hpx_stage) hipHostFree(c->h_hpx_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_px_ring[k]) hipHostFree(c->h_px_ring[k]); if (c->ev_px_ring[k]) hipEventDestroy(c->ev_px_ring[k]); }
     if (c->h_issued) hipHostFree(c->h_issued);
     if (c->h_ad_count) hipHostFree(c->h_ad_count);
@@ -796,6 +802,7 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     int rc = run_setup(c);
     if (rc) return rc;
     if (c->dn_on) { rc = denoise_refusal(c); if (rc) return rc; }
+    if (c->ho.on) { rc = hdr_output_refusal(c); if (rc) return rc; }
     rc = join_slots(c);
     if (rc) return rc;
     touched_hdr(c);              // the next accumulate_kernel must not overwrite what this reads
@@ -812,7 +819,11 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     if (c->bl_on) { rc = run_bloom(c, d, per_tile); if (rc) return rc; }      // after the meter (the scene is metered, not the lens): the composited mean through the unchanged transform
     if (c->lx_on) { rc = run_local_exposure(c, d, per_tile); if (rc) return rc; }      // last: the scene is metered, the lens glares, the print is dodged; the anchor is d.fc's exposure
     const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
-    if (per_tile) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
+    if (c->ho.on) {              // the HDR display output: the same launch over the same arguments, the settings' constants by value
+        if (per_tile) hipLaunchKernelGGL(hdr_display_kernel<true>, grid, dim3(256), 0, c->stream, d, c->ho_consts);
+        else hipLaunchKernelGGL(hdr_display_kernel<false>, grid, dim3(256), 0, c->stream, d, c->ho_consts);
+    }
+    else if (per_tile) hipLaunchKernelGGL(display_kernel<true>, grid, dim3(256), 0, c->stream, d);    // every tile divided by its own count
     else hipLaunchKernelGGL(display_kernel<false>, grid, dim3(256), 0, c->stream, d);
     HIP_TRY(hipGetLastError());
     // what the next accumulate_kernel must wait for ends HERE (the display has read the HDR buffer): recorded now, not lazily at the next de_accumulate, so that
@@ -1834,6 +1845,108 @@ int de_debug_output_scale_weights(de_ctx* c, int n_src, int n_dst, int filter, i
     if (weights)
         for (int j = 0; j < n_dst; ++j)
             for (int t = 0; t < T.taps; ++t) weights[(size_t)j * (size_t)T.taps + (size_t)t] = T.w[(size_t)t * (size_t)n_dst + (size_t)j];      // the kernels' [tap][j], transposed
+    return DE_OK;
+}
+
+/* ---- HDR display output: include/digital_earth_hdr_output.h (hdr_output_kernels.hip) */
+namespace {
+size_t hpx_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (c->ho.pixel_format == DE_HDR_PIXELS_RGB16 ? 6u : 4u); }
+size_t hpx_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 6; }      // every buffer holds either format
+int ho_settings_check(const de_hdr_output* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_hdr_output)) return fail(DE_ERR_INVALID, "de_hdr_output.struct_bytes does not match this library's struct");
+    if (!(s->peak_nits >= 100.0f && s->peak_nits <= 10000.0f)) return fail(DE_ERR_INVALID, "de_hdr_output.peak_nits must lie in [100, 10000]");      // NaN fails both
+    if (s->gamut < DE_HDR_GAMUT_REC709 || s->gamut > DE_HDR_GAMUT_REC2020) return fail(DE_ERR_INVALID, "de_hdr_output.gamut must be DE_HDR_GAMUT_REC709, _P3D65 or _REC2020");
+    if (s->transfer < DE_HDR_TRANSFER_LINEAR || s->transfer > DE_HDR_TRANSFER_HLG) return fail(DE_ERR_INVALID, "de_hdr_output.transfer must be DE_HDR_TRANSFER_LINEAR, _PQ or _HLG");
+    if (s->pixel_format < DE_HDR_PIXELS_RGB10A2 || s->pixel_format > DE_HDR_PIXELS_RGB16) return fail(DE_ERR_INVALID, "de_hdr_output.pixel_format must be DE_HDR_PIXELS_RGB10A2 or _RGB16");
+    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_hdr_output.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
+    return DE_OK;
+}
+}  // namespace
+
+int de_set_hdr_output(de_ctx* c, const de_hdr_output* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ho_settings_check(s); if (rc) return rc; }
+    c->ho = *s;
+    c->ho.on = s->on ? 1 : 0;
+    hdr_output_consts((double)s->peak_nits, s->gamut, s->transfer, &c->ho_consts);
+    c->ho_count = 0; c->ho_last_phase = 0;
+    return DE_OK;
+}
+int de_get_hdr_output(de_ctx* c, de_hdr_output* out, uint32_t* last_phase) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->ho;
+    if (last_phase) *last_phase = c->ho_last_phase;
+    return DE_OK;
+}
+int de_render_to_hdr_pixels(de_ctx* c, const void** device_pixels) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (!c->ho.on) return fail(DE_ERR_STATE, "the HDR display output is off: de_set_hdr_output first");
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->d_hpx && c->d_hpx_bytes < hpx_capacity(c)) { (void)hipFree(c->d_hpx); c->d_hpx = nullptr; c->d_hpx_bytes = 0; }      // the output size grew (hipFree waits for the work that reads it)
+    if (!c->d_hpx) { HIP_TRY(hipMalloc(&c->d_hpx, hpx_capacity(c))); c->d_hpx_bytes = hpx_capacity(c); }
+    int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
+    if (rc) return rc;
+    const uint32_t phase = c->ho.animate ? c->ho_count : 0u;
+    HdrPackArgs a;
+    a.image = shown_image(c); a.out = c->d_hpx; a.W = out_w(c); a.H = out_h(c); a.format = c->ho.pixel_format; a.mode = c->ho.mode; a.seed = c->ho.seed; a.phase = phase;
+    hipLaunchKernelGGL(hdr_pack_kernel, dim3((unsigned)((a.W + HPX_TILE - 1) / HPX_TILE), (unsigned)((a.H + HPX_TILE - 1) / HPX_TILE)), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    c->ho_count++; c->ho_last_phase = phase;
+    if (device_pixels) *device_pixels = c->d_hpx;
+    return DE_OK;
+}
+int de_fetch_hdr_pixels(de_ctx* c, void* out, uint64_t out_bytes) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (!c->ho.on) return fail(DE_ERR_STATE, "the HDR display output is off: de_set_hdr_output first");
+    if (out_bytes < (uint64_t)hpx_size(c)) return fail(DE_ERR_INVALID, "out_bytes is smaller than width * height * 4 (RGB10A2) or * 6 (RGB16)");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = px_host_alloc(&c->h_hpx_stage, &c->h_hpx_stage_bytes, hpx_capacity(c));
+    if (rc) return rc;
+    rc = de_render_to_hdr_pixels(c, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_hpx_stage, c->d_hpx, hpx_size(c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rc = frame_status(c);
+    if (rc) return rc;
+    memcpy(out, c->h_hpx_stage, hpx_size(c));
+    return DE_OK;
+}
+/* the transform alone on n colours.  Buffers of its own; the context's setting is not touched. */
+int de_debug_hdr_transform(de_ctx* c, const float* rgb, uint64_t n, const de_hdr_output* s, float* out) {
+    if (!c || !rgb || !s || !out || n == 0 || n > (1ull << 28)) return fail(DE_ERR_INVALID, "bad arguments (1 <= n <= 2^28)");
+    { int rc = ho_settings_check(s); if (rc) return rc; }
+    HdrConsts h;
+    hdr_output_consts((double)s->peak_nits, s->gamut, s->transfer, &h);
+    HIP_TRY(hipSetDevice(c->device));
+    struct Bufs {   // freed on every exit path
+        void* p[2] = {};
+        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
+    } b;
+    const size_t bytes = (size_t)n * 3 * sizeof(float);
+    HIP_TRY(hipMalloc(&b.p[0], bytes));
+    HIP_TRY(hipMalloc(&b.p[1], bytes));
+    HIP_TRY(hipMemcpyAsync(b.p[0], rgb, bytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(hdr_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b.p[0], (float*)b.p[1], (size_t)n, h);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b.p[1], bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+/* include/digital_earth_debug.h: the constants alone, on the host.  settings = NULL: the six constants setup_kernel is handed for the SDR display
+ * (opendrt_consts), the other thirteen 0 — so that a test can put the two host functions side by side. */
+int de_debug_hdr_consts(de_ctx* c, const de_hdr_output* s, float* out19) {
+    (void)c;      // host only: the context is not read and may be NULL
+    if (!out19) return fail(DE_ERR_INVALID, "null argument");
+    if (!s) {
+        memset(out19, 0, 19 * sizeof(float));
+        opendrt_consts(&out19[0], &out19[1], &out19[2], &out19[3], &out19[4], &out19[5]);
+        return DE_OK;
+    }
+    { int rc = ho_settings_check(s); if (rc) return rc; }
+    HdrConsts h;
+    hdr_output_consts((double)s->peak_nits, s->gamut, s->transfer, &h);
+    const float first[6] = {h.m, h.s, h.fl, h.ds, h.clamp_max, h.dch_s}, last[4] = {h.h_a, h.h_b, h.h_c, h.h_e};
+    memcpy(out19, first, sizeof(first)); memcpy(out19 + 6, h.xyz_to_display, sizeof(h.xyz_to_display)); memcpy(out19 + 15, last, sizeof(last));
     return DE_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "../../include/digital_earth_pixels.h"
 #include "../../include/digital_earth_local_exposure.h"
 #include "../../include/digital_earth_output_scale.h"
+#include "../../include/digital_earth_hdr_output.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -35,6 +36,7 @@
 #include "pixels_kernels.hip"
 #include "output_scale_kernels.hip"
 #include "local_exposure_kernels.hip"
+#include "hdr_output_kernels.hip"
 
 namespace {
 
@@ -268,6 +270,16 @@ struct de_ctx {
     float* d_os_mid = nullptr;
     float* d_os_out = nullptr;
     size_t os_mid_bytes = 0, os_out_bytes = 0;
+    // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
+    // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
+    // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.
+    de_hdr_output ho = {(uint32_t)sizeof(de_hdr_output), 0, 1000.0f, DE_HDR_GAMUT_REC2020, DE_HDR_TRANSFER_PQ, DE_HDR_PIXELS_RGB10A2, DE_PIXELS_TRUNCATE, 0u, 0};
+    HdrConsts ho_consts = {};       // of `ho`; valid while ho.on
+    uint32_t ho_count = 0;          // conversions since de_set_hdr_output
+    uint32_t ho_last_phase = 0;
+    void* d_hpx = nullptr;
+    uint8_t* h_hpx_stage = nullptr;
+    size_t d_hpx_bytes = 0, h_hpx_stage_bytes = 0;
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

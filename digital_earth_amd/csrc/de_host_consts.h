@@ -57,6 +57,32 @@ void opendrt_consts(float* m, float* s, float* fl, float* ds, float* clamp_max, 
     *m = (float)m_d; *s = (float)s_d; *fl = (float)flare; *ds = (float)ds_d; *clamp_max = (float)cm; *dch_s = (float)(dch / s_d);
 }
 
+// The same for the HDR display output (include/digital_earth_hdr_output.h): openDR_transform's parameter setup in its general form, over
+// the peak luminance Lp and the inverse EOTF (lib/OpenDRT.py:270-271, 306-319, 404), the XYZ -> display matrix of the gamut (:72-74, :245-247) and the
+// constants of eotf_hlg (:140-146: HLG_Lw = 1000, HLG_Ls = 5, so h_g = 1.2).  Evaluated once per de_set_hdr_output in double and rounded to f32; at
+// Lp = 100 under the linear transfer the first six equal opendrt_consts' (the same expressions).  transfer: 0 linear, 1 PQ, 2 HLG; gamut: 0 Rec.709,
+// 1 P3-D65, 2 Rec.2020.
+void hdr_output_consts(double Lp, int gamut, int transfer, HdrConsts* h) {
+    const double gb = 0.12, c = 1.0, flare = 0.005, dch = 0.35;
+    double ds_d = transfer == 1 ? 0.01 : (transfer == 2 ? 0.1 : 100.0 / Lp), cm = ds_d * Lp / 100.0;
+    double px = 128.0 * log10(Lp) / log10(100.0) - 64.0, py = Lp / 100.0, gx = 0.18;
+    double gy = 11.696 / 100.0 * (1.0 + gb * log10(py) / log10(2.0));
+    double s0 = (gy + sqrt(gy * (4.0 * flare + gy))) / 2.0, m0 = (py + sqrt(py * (4.0 * flare + py))) / 2.0;
+    double ip = 1.0 / c;
+    double s_d = (px * gx * (pow(m0, ip) - pow(s0, ip))) / (px * pow(s0, ip) - gx * pow(m0, ip));
+    double m_d = pow(m0, ip) * (s_d + px) / px;
+    h->m = (float)m_d; h->s = (float)s_d; h->fl = (float)flare; h->ds = (float)ds_d; h->clamp_max = (float)cm; h->dch_s = (float)(dch / s_d);
+    static const double xyz_to[3][9] = {
+        {3.2409699419, -1.53738317757, -0.498610760293, -0.969243636281, 1.87596750151, 0.041555057407, 0.055630079697, -0.203976958889, 1.05697151424},
+        {2.49349691194, -0.931383617919, -0.402710784451, -0.829488969562, 1.76266406032, 0.023624685842, 0.035845830244, -0.076172389268, 0.956884524008},
+        {1.71665118797, -0.355670783776, -0.253366281374, -0.666684351832, 1.61648123664, 0.015768545814, 0.017639857445, -0.042770613258, 0.942103121235}};
+    for (int i = 0; i < 9; ++i) h->xyz_to_display[i] = (float)xyz_to[gamut][i];
+    const double h_a = 0.17883277, h_b = 1.0 - 4.0 * 0.17883277, h_c = 0.5 - h_a * log10(4.0 * h_a);
+    const double h_g = 1.2 * pow(1.111, log2(1000.0 / 1000.0)) * pow(0.98, log2(fmax(1e-6, 5.0) / 5.0));
+    h->h_a = (float)h_a; h->h_b = (float)h_b; h->h_c = (float)h_c; h->h_e = (float)((1.0 - h_g) / h_g);
+    h->transfer = transfer;
+}
+
 // lib/AgX.py:22-85, 99-101, 133-150: matrices and curve scales of the AgX display transform — constant expressions of
 // module constants (primaries, COMPRESSION = 0.15, SLOPE = 2.3, TOE_POWER = 1.9, SHOULDER_POWER = 3.1, EV range
 // [-10, 6.5]), evaluated in double and rounded to f32.

@@ -13,7 +13,7 @@ import os
 
 import numpy as np
 
-from . import luts
+from . import luts, png16
 from .renderer import Renderer
 
 SCREEN_RES = (1920, 1080)      # earth_viewer.py:12
@@ -184,11 +184,13 @@ def _rgb_picture(px):
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, **renderer_kwargs):
         """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
         in frame()'s loop instead of restarting at one sample per pixel.  local_exposure: the same for Renderer.set_local_exposure — every frame is
         dodged and burned on the GPU ahead of the display transform.  output_res: None, or the (width, height) at which frames are delivered and
-        saved while screen_res is rendered (Renderer.set_output_scale with `output_filter`): a supersampled still, or a window larger than the render."""
+        saved while screen_res is rendered (Renderer.set_output_scale with `output_filter`): a supersampled still, or a window larger than the render.
+        hdr_output: None / False, True (Renderer.set_hdr_output's defaults: 1000-nit Rec.2020 PQ) or a dict of its keywords — frames are then the HDR
+        signal, frame(hdr_pixels=True) hands out 10 / 16-bit pixels and save() writes a 16-bit PNG that names its colour space."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
@@ -200,11 +202,15 @@ class EarthViewer:
             self.renderer.set_local_exposure(True, **(local_exposure if isinstance(local_exposure, dict) else {}))
         if output_res is not None:
             self.renderer.set_output_scale(tuple(output_res), filter=output_filter)
+        if hdr_output:
+            self.renderer.set_hdr_output(True, **(hdr_output if isinstance(hdr_output, dict) else {}))
         self.config = None
         if config is not None:
             self.load_config(config)
         self._image = None
         self._pixels = None                     # the picture of the last frame(pixels=True)
+        self._held_hdr = None                   # Renderer.hdr_output when the picture held was taken: what save() labels it with
+        self._hdr_in_flight = {False: [], True: []}      # the same per lagged fetch in flight (float ring, pixel ring), oldest first
         self._sliders = None
 
     def load_config(self, path_or_config):
@@ -229,7 +235,7 @@ class EarthViewer:
             self.renderer.accumulate(n)
             left -= n
         self._image = self.renderer.fetch_image()
-        self._pixels = None
+        self._pixels, self._held_hdr = None, self.renderer.hdr_output
         return self._image
 
     def render_to_noise(self, threshold, max_spp, min_spp=16, round_spp=16, floor=None):
@@ -241,7 +247,7 @@ class EarthViewer:
         kw = {} if floor is None else {"floor": floor}
         self.last_adaptive = r.render_adaptive(threshold, max_spp, min_spp=min_spp, round_spp=round_spp, **kw)
         self._image = r.fetch_image()
-        self._pixels = None
+        self._pixels, self._held_hdr = None, r.hdr_output
         return self._image
 
     def frame(self, spp=1, copy=True, pipelined=False, pixels=False, **sliders):
@@ -257,8 +263,13 @@ class EarthViewer:
         image RETURNED is the previous iteration's (None in the first): the next iteration's accumulate() renders while this frame is shown — the same images, one
         iteration later, at a fraction of the frame time; finish() returns the last one.
         pixels=True: the iteration returns the packed 8-bit picture instead of the float field — (H, W, channels) uint8, rows top-down, converted on the
-        GPU in the format of Renderer.set_pixels() (Renderer.fetch_pixels) — with the same copy / pipelined rules; finish(pixels=True) ends that loop."""
+        GPU in the format of Renderer.set_pixels() (Renderer.fetch_pixels) — with the same copy / pipelined rules; finish(pixels=True) ends that loop.
+        hdr_pixels=True (a keyword beside the sliders, none of them): the iteration returns the packed HDR pixels of Renderer.fetch_hdr_pixels() — uint32
+        (H, W) or uint16 (H, W, 3) — always a copy, never pipelined: these pixels have no ring.  The HDR display output must be on."""
         r = self.renderer
+        hdr_pixels = bool(sliders.pop("hdr_pixels", False))
+        if hdr_pixels and (pixels or pipelined):
+            raise ValueError("hdr_pixels=True goes with neither pixels=True nor pipelined")
         should_reset = False
         if self.camera.update_camera(0.0):
             r.set_camera_pos(*self.camera.position)
@@ -266,11 +277,22 @@ class EarthViewer:
             r.set_up(*self.camera._up)
             should_reset = True
         r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
-        if pixels:
+        if hdr_pixels:
+            self._pixels, self._image = r.fetch_hdr_pixels(), None
+        elif pixels:
             self._pixels, self._image = r.fetch_pixels(copy=copy, lag=int(pipelined)), None
         else:
             self._image = r.fetch_image(copy=copy, lag=int(pipelined))
             self._pixels = None
+        # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
+        # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
+        shown = self._pixels if (pixels or hdr_pixels) else self._image
+        if pipelined:
+            self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
+            if shown is not None:
+                self._held_hdr = self._hdr_in_flight[bool(pixels)].pop(0)
+        else:
+            self._held_hdr = r.hdr_output
         if self._sliders is None:               # current_* of earth_viewer.py:191-199, read once when the loop starts
             self._sliders = {"sun_angle": r.sun_angle[None], "sun_path_rot": r.sun_path_rot[None], "fov": r.fov[None],
                              "aspect_scale": r.aspect_scale[None], "exposure": r.exposure[None],
@@ -288,11 +310,15 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        return self._pixels if pixels else self._image
+        return self._pixels if (pixels or hdr_pixels) else self._image
 
     def finish(self, copy=True, pixels=False):
         """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop."""
         img = self.renderer.fetch_pending(copy=copy, pixels=pixels)
+        queue = self._hdr_in_flight[bool(pixels)]
+        if img is not None and queue:
+            self._held_hdr = queue[-1]          # the newest fetch's picture is the one handed out
+        del queue[:]
         if img is not None:
             if pixels:
                 self._pixels = img
@@ -313,12 +339,23 @@ class EarthViewer:
         converted on the GPU in the renderer's current mode (Renderer.set_pixels; truncation by default: the reference's to_vec3u, byte for byte) and
         handed to the image writer as they are, rows top-down — no clip, cast, transpose or flip on the host.  What is written is the picture this
         viewer last showed, never a new display of the context: the image held goes through the pack kernel as it is (Renderer.debug_pixels), and
-        after frame(pixels=True) the picture held is written.  A slider, bloom or exposure changed since then does not reach the file."""
+        after frame(pixels=True) the picture held is written.  A slider, bloom or exposure changed since then does not reach the file.
+        A picture taken while the HDR display output was on (render, frame, frame(hdr_pixels=True)) is written, for every format but `.npy`, as a
+        16-bit RGB PNG with a cICP chunk naming the gamut and the transfer it was TAKEN with (colour primaries 1 / 12 / 9, transfer 8 / 16 / 18 for
+        linear / PQ / HLG, RGB, full range; digital_earth_amd/png16.py).  Here too nothing is displayed again and no setting or dither phase of the
+        renderer is touched: "rgb16" pixels are written as they are, "rgb10a2" codes widened to 16 bits by bit replication, and a float signal held
+        from render() / frame() is quantised on the host by rounding (png16.to_rgb16) — the setting's mode and dither belong to fetch_hdr_pixels().
+        Under the P3-D65 and Rec.2020 gamuts the label names the container, not a colorimetric picture: see Renderer.set_hdr_output."""
         r = self.renderer
         if self._image is None and self._pixels is None:
             self.render(1)
         if path.endswith(".npy"):
             np.save(path, self._image if self._image is not None else r.fetch_image())
+            return
+        hdr = self._held_hdr
+        if hdr is not None:
+            held = self._pixels if self._pixels is not None else np.asarray(self._image, dtype=np.float32)
+            png16.write_png16(path, png16.to_rgb16(held), png16.cicp_of(hdr["gamut"], hdr["transfer"]))
             return
         px = self._pixels
         if px is None:

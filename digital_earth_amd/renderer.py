@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -860,6 +860,80 @@ class Renderer:
         s.channels, s.mode, s.seed, s.animate = int(channels), self.PIXEL_MODES.index(mode), int(seed) & 0xffffffff, 0
         out = np.empty((H, W, int(channels) if channels in (3, 4) else 4), dtype=np.uint8)
         check(self._lib.de_debug_pixels(self._h, image.ctypes.data, W, H, ctypes.byref(s), ctypes.c_uint32(int(phase) & 0xffffffff), out.ctypes.data))
+        return out
+
+    # ------------------------------------------------------------------ HDR display output (include/digital_earth_hdr_output.h)
+    HDR_GAMUTS = ("rec709", "p3d65", "rec2020")
+    HDR_TRANSFERS = ("linear", "pq", "hlg")
+    HDR_PIXEL_FORMATS = ("rgb10a2", "rgb16")
+
+    def _hdr_output_settings(self, on, peak_nits, gamut, transfer, pixel_format, mode, seed, animate):
+        for value, names, what in ((gamut, self.HDR_GAMUTS, "gamut"), (transfer, self.HDR_TRANSFERS, "transfer"), (pixel_format, self.HDR_PIXEL_FORMATS, "pixel_format"),
+                                   (mode, self.PIXEL_MODES, "mode")):
+            if value not in names:
+                raise ValueError("%s must be one of %s" % (what, names))
+        s = DeHdrOutput()
+        s.struct_bytes = ctypes.sizeof(DeHdrOutput)
+        s.on, s.peak_nits = 1 if on else 0, float(peak_nits)
+        s.gamut, s.transfer, s.pixel_format = self.HDR_GAMUTS.index(gamut), self.HDR_TRANSFERS.index(transfer), self.HDR_PIXEL_FORMATS.index(pixel_format)
+        s.mode, s.seed, s.animate = self.PIXEL_MODES.index(mode), int(seed) & 0xffffffff, 1 if animate else 0
+        return s
+
+    def set_hdr_output(self, on=True, peak_nits=1000.0, gamut="rec2020", transfer="pq", pixel_format="rgb10a2", mode="truncate", seed=0, animate=False):
+        """Turn the HDR display output on (or off).  While it is on, the display transform is OpenDRT in its general form instead of the 100-nit sRGB
+        picture: rendered for a display of `peak_nits` (100 ... 10000) in the `gamut` "rec709", "p3d65" or "rec2020" and encoded by the `transfer`
+        "linear" (1.0 = the peak), "pq" (ST 2084) or "hlg".  The camera response curve, gamma and the sRGB OETF are NOT applied in this mode: an SDR film
+        curve and an SDR encoding.  fetch_image() then returns that signal as floats in [0, 1], output scaling resamples it, fetch_pixels() keeps working on
+        it (8 bits of PQ: legal but coarse), and fetch_hdr_pixels() packs it to `pixel_format` "rgb10a2" or "rgb16" in `mode` "truncate", "round" or
+        "dither" (set_pixels' modes, seed and animate).  Everything ahead of the display — adaptive counts, the denoiser, history, auto-exposure, bloom,
+        local exposure — is inherited.  Refused (DE_ERR_STATE at the next display) together with the AgX display transform.
+        KNOWN LIMIT, kept from the reference: only gamut="rec709" is colorimetrically meaningful.  The reference's two gamut products multiply by the
+        transposed matrices, which cancels for Rec.709 only; under "p3d65" and "rec2020" — the default — every neutral comes out strongly green (0.18
+        grey gives the signal (0.256, 0.383, 0.339) at 1000-nit Rec.2020 PQ).  This method reproduces the reference; pass gamut="rec709" for a
+        picture meant for a panel.  Whether 1000-nit PQ at the
+        default exposure looks right on a panel has not been judged: the defaults are starting values.  fetch_hdr() is unchanged."""
+        check(self._lib.de_set_hdr_output(self._h, ctypes.byref(self._hdr_output_settings(on, peak_nits, gamut, transfer, pixel_format, mode, seed, animate))))
+
+    @property
+    def hdr_output(self):
+        """The HDR display output as a dict (set_hdr_output's keywords) plus last_phase, or None while it is off."""
+        s, phase = DeHdrOutput(), ctypes.c_uint32()
+        check(self._lib.de_get_hdr_output(self._h, ctypes.byref(s), ctypes.byref(phase)))
+        if not s.on:
+            return None
+        return dict(on=True, peak_nits=float(s.peak_nits), gamut=self.HDR_GAMUTS[s.gamut], transfer=self.HDR_TRANSFERS[s.transfer],
+                    pixel_format=self.HDR_PIXEL_FORMATS[s.pixel_format], mode=self.PIXEL_MODES[s.mode], seed=int(s.seed), animate=bool(s.animate),
+                    last_phase=int(phase.value))
+
+    def fetch_hdr_pixels(self):
+        """The displayed HDR signal as packed pixels of the output size, converted on the GPU, rows top-down: uint32 (H, W) for "rgb10a2" (R in bits
+        0-9, G in 10-19, B in 20-29, alpha 3 in 30-31) or uint16 (H, W, 3) for "rgb16".  The HDR display output must be on."""
+        if not self._textures_copied:
+            self.copy_textures()
+        s = DeHdrOutput()
+        check(self._lib.de_get_hdr_output(self._h, ctypes.byref(s), None))
+        ow, oh = self.output_size()
+        out = np.empty((oh, ow, 3), dtype=np.uint16) if s.pixel_format == 1 else np.empty((oh, ow), dtype=np.uint32)
+        check(self._lib.de_fetch_hdr_pixels(self._h, out.ctypes.data, ctypes.c_uint64(out.nbytes)))
+        return out
+
+    def render_to_hdr_pixels_device(self):
+        """Run the display and the HDR pack and leave the pixels on the device (de_render_to_hdr_pixels); returns their address."""
+        if not self._textures_copied:
+            self.copy_textures()
+        p = ctypes.c_void_p()
+        check(self._lib.de_render_to_hdr_pixels(self._h, ctypes.byref(p)))
+        return p.value
+
+    def debug_hdr_transform(self, rgb, peak_nits=1000.0, gamut="rec2020", transfer="pq"):
+        """The HDR display transform alone on (..., 3) float32 scene-linear Rec.709 colours, already exposed (de_debug_hdr_transform); returns the
+        signal in the same shape.  The renderer's own setting is not touched."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim < 1 or rgb.shape[-1] != 3:
+            raise ValueError("rgb must have shape (..., 3)")
+        out = np.empty_like(rgb)
+        s = self._hdr_output_settings(True, peak_nits, gamut, transfer, "rgb10a2", "truncate", 0, False)
+        check(self._lib.de_debug_hdr_transform(self._h, rgb.ctypes.data, ctypes.c_uint64(rgb.size // 3), ctypes.byref(s), out.ctypes.data))
         return out
 
     def fetch_hdr(self):

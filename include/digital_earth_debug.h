@@ -98,6 +98,13 @@ int de_debug_pixels(de_ctx* ctx, const float* image, int W, int H, const struct 
 struct de_output_scale;
 int de_debug_output_scale(de_ctx* ctx, const float* image, int W, int H, const struct de_output_scale* settings, float* out);
 int de_debug_output_scale_weights(de_ctx* ctx, int n_src, int n_dst, int filter, int32_t* first, float* weights, int* taps);
+/* de_debug_hdr_consts: the constants the HDR display kernel is handed for `settings` (include/digital_earth_hdr_output.h), evaluated on
+ * the host in double and rounded to f32 exactly as de_set_hdr_output does — no device work, `ctx` is not read and may be NULL.  out19 = m, s, fl, ds,
+ * clamp_max, dch_s, the nine entries of the XYZ -> display matrix (row-major, as lib/OpenDRT.py:72-74 writes them), h_a, h_b, h_c, (1 - h_g) / h_g.
+ * DE_ERR_INVALID as de_set_hdr_output.  settings = NULL: out19[0 .. 5] = the same six constants as the SDR display is handed them today (the host function
+ * behind setup_kernel), the other thirteen 0 — at peak_nits = 100 under the linear transfer the two must agree in every bit. */
+struct de_hdr_output;
+int de_debug_hdr_consts(de_ctx* ctx, const struct de_hdr_output* settings, float* out19);
 
 /* ---- the N-rank collectives' device code on ONE GPU
  * de_debug_ordered_sum: the root's half of de_reduce_ordered without a communicator.  `parts` = n_parts host buffers of W*H*3 floats each (device
