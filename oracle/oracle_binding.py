@@ -74,6 +74,7 @@ def lib():
         L.deo_eval.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.deo_eval_transmittance.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                              ctypes.c_float, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
+        L.deo_probe.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -198,3 +199,14 @@ class Oracle:
         out = ctypes.c_float()
         _check(lib().deo_eval_transmittance(self._h, seed, pos.ctypes.data, direction.ctypes.data, wavelength, n, ctypes.byref(out)))
         return out.value
+
+    _PROBES = {"intersect_land": (6, 2), "land_sdf": (3, 1), "land_normal": (3, 3), "land_material": (3, 4), "clouds_density": (3, 1)}
+
+    def probe(self, kind, x):
+        """The restatement's scene functions at rows of x, on this instance's maps, land_height_scale, topo resolution and address mode (deo_probe):
+        intersect_land (pos, dir) -> (t or -1, steps); land_sdf, land_normal, land_material (albedo_srgb, ocean), clouds_density (pos)."""
+        n_in, n_out = self._PROBES[kind]
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, n_in)
+        out = np.zeros((x.shape[0], n_out), dtype=np.float32)
+        _check(lib().deo_probe(self._h, kind.encode(), x.ctypes.data, out.ctypes.data, x.shape[0]))
+        return out

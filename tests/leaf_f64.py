@@ -68,10 +68,12 @@ def earth_brdf(albedo, ocean, bathy, v, n, l):
 
 
 def grade_land_albedo(tex, ocean):
+    """tex (..., 3), ocean (...): one texel or any array of them."""
     tex = np.asarray(tex, np.float64)
-    grey = lambda c: np.full(3, c @ LUMA)
+    ocean = np.asarray(ocean, np.float64)[..., None]
+    grey = lambda c: np.broadcast_to(np.asarray(c @ LUMA)[..., None], c.shape)
     land = _mix(grey(tex), tex, 6.5)
-    green = _smoothstep(1.5, 1.9, (land[1] / (land @ LUMA)) ** 2)
+    green = np.asarray(_smoothstep(1.5, 1.9, (land[..., 1] / (land @ LUMA)) ** 2))[..., None]
     land = tex / (green * 0.7 + 1.0)
     land = _mix(grey(land), land, 1.4 - green * 0.45)
     land = _mix(land, land * np.array([255.0, 128.0, 64.0]) / 255.0, 0.2 * (1.0 - green))
