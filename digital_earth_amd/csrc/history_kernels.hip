@@ -68,12 +68,15 @@ DE_DEV bool history_reproject(const HistoryArgs& a, int u, int v, float t, float
     const float fv = 2.0f * fc.fov * ((float)v + 0.5f) / Hf - fc.fov - 1e-5f;
     const vec3 dir = normalized_ieee(fc.d + fu * fc.du + fv * fc.dv);
     const bool land = t > 0.0f;
+    // the camera's step first: it is small and near-exact, and dir * t is rounded relative to itself.  (cam + dir * t) - cam_h would round the world
+    // point at planet scale (0.25 - 0.5 m) and leave that absolute error in q however short the ray is.
+    const vec3 step = fc.cam_pos - hc.cam_pos;
     vec3 q;
     if (land) {
-        q = (fc.cam_pos + dir * t) - hc.cam_pos;
+        q = step + dir * t;
     } else {
         const float s = -dot(fc.cam_pos, dir);            // the planet is centred at the origin: the tangent point, where the limb's glow sits
-        q = s > 0.0f ? (fc.cam_pos + dir * s) - hc.cam_pos : dir;      // behind the camera: the pixel is at infinity, only its direction reprojects
+        q = s > 0.0f ? step + dir * s : dir;              // behind the camera: the pixel is at infinity, only its direction reprojects
     }
     const float z = dot(q, hc.d);
     if (!(z > 0.0f)) return false;

@@ -56,7 +56,7 @@ def project(q, hcam, W, H):
 
 
 def reproject(dist, cam, hist_c, hist_d, hcam, max_history=32.0, depth_tolerance=0.02):
-    """Steps 2 - 6 for every pixel.  Returns dict(have, h (W, H, 3), w, B, xo, yo, z)."""
+    """Steps 2 - 6 for every pixel.  Returns dict(have, h (W, H, 3), w, B, xo, yo, z, r, x0, y0, valid (4, W, H): the taps (x0 + (k & 1), y0 + (k >> 1)))."""
     dist = np.asarray(dist, np.float32)
     hist_c, hist_d = np.asarray(hist_c, np.float32), np.asarray(hist_d, np.float32)
     W, H = dist.shape
@@ -65,9 +65,10 @@ def reproject(dist, cam, hist_c, hist_d, hcam, max_history=32.0, depth_tolerance
         land = dist > 0
         s = -_dot(cam["cam"], dr)
         t = np.where(land, dist, s)
-        P = [cam["cam"][k] + dr[k] * t for k in range(3)]
+        # the camera's step first: (cam + dir t) - cam_h would round the world point at planet scale and keep that error however short the ray
+        step = [cam["cam"][k] - hcam["cam"][k] for k in range(3)]
         at_infinity = ~land & ~(s > 0)
-        q = [np.where(at_infinity, dr[k], P[k] - hcam["cam"][k]) for k in range(3)]
+        q = [np.where(at_infinity, dr[k], step[k] + dr[k] * t) for k in range(3)]
         z, xo, yo = project(q, hcam, W, H)
         ok = (z > 0) & (xo >= F(-1.0)) & (xo < F(W)) & (yo >= F(-1.0)) & (yo < F(H))
         xs, ys = np.where(ok, xo, F(0)), np.where(ok, yo, F(0))
@@ -77,7 +78,7 @@ def reproject(dist, cam, hist_c, hist_d, hcam, max_history=32.0, depth_tolerance
         r = np.sqrt(_dot(q, q))
         tol = F(depth_tolerance) * r
         zero = np.zeros((W, H), np.float32)
-        terms = []
+        terms, valids = [], []
         for k in range(4):
             xi, yi = x0 + (k & 1), y0 + (k >> 1)
             inside = (xi >= 0) & (xi < W) & (yi >= 0) & (yi < H)
@@ -86,6 +87,7 @@ def reproject(dist, cam, hist_c, hist_d, hcam, max_history=32.0, depth_tolerance
             finite = (np.abs(c[..., 0]) <= FLT_MAX) & (np.abs(c[..., 1]) <= FLT_MAX) & (np.abs(c[..., 2]) <= FLT_MAX)
             surface = np.where(land, (hd > 0) & (np.abs(hd - r) <= tol), hd == 0)
             valid = ok & inside & (c[..., 3] > 0) & finite & surface
+            valids.append(valid)
             b = ((bx if k & 1 else F(1.0) - bx) * (by if k >> 1 else F(1.0) - by)).astype(np.float32)
             # an invalid tap contributes +0 to every sum
             terms.append([np.where(valid, b, F(0))] + [np.where(valid, b * c[..., ch], F(0)) for ch in (3, 0, 1, 2)])
@@ -97,7 +99,7 @@ def reproject(dist, cam, hist_c, hist_d, hcam, max_history=32.0, depth_tolerance
         wm = Ws / B
         mh = F(max_history)
         w = np.where(wm < mh, wm, mh) * B
-    return dict(have=have, h=np.where(have[..., None], h, F(0)).astype(np.float32), w=np.where(have, w, F(0)).astype(np.float32), B=B, xo=xo, yo=yo, z=z)
+    return dict(have=have, h=np.where(have[..., None], h, F(0)).astype(np.float32), w=np.where(have, w, F(0)).astype(np.float32), B=B, xo=xo, yo=yo, z=z, r=r, x0=x0, y0=y0, valid=np.stack(valids))
 
 
 def blend(m, n, dist, cam, hist_c=None, hist_d=None, hcam=None, max_history=32.0, depth_tolerance=0.02, details=False):

@@ -12,6 +12,8 @@ import pytest
 
 import bloom_ref as bl
 import exposure_f64 as ae
+import history_cases as hc
+import history_f64 as h64
 import history_ref as hr
 
 pytestmark = pytest.mark.gpu
@@ -173,6 +175,44 @@ def test_kernel_equals_the_restatement_bit_for_bit(contexts, size):
     _same(got[..., :3], x["m"])
 
 
+# ---------------------------------------------------------------- 1b. low cameras: the restatement bit for bit, the float64 statement within its budgets
+def _low(r, key):
+    """The device on one case of tests/history_cases.py against both references.  Returns the number of conditioned pixels compared with float64."""
+    x = hc.case(*key)
+    f = x["f64"]
+    p = _params(r, x["p"].camera_pos, x["p"].look_at, x["p"].fov)
+    hp = _params(r, x["hp"].camera_pos, x["hp"].look_at, x["hp"].fov)
+    got = r.debug_history(x["m"], x["n"], x["dist"], p, x["hist"], x["hist_d"], hp)
+    _same(got, hr.blend(x["m"], x["n"], x["dist"], x["cam"], x["hist"], x["hist_d"], x["hcam"]), key)
+    ill = f["ill"]
+    cond = ~(ill["depth"] | ill["z"] | ill["s"] | ill["B"]) if key[4] == "identical" else ~ill["any"]      # tests/test_history_f64.py: a still camera is on the grid
+    err = np.abs(got[..., :3].astype(np.float64) - f["out"])
+    bound = hc.blend_bound(x)
+    assert (err[cond] <= bound[cond]).all(), (key, float((err[cond] / np.maximum(bound[cond], 1e-300)).max()))
+    weight = min(float(x["hist"][0, 0, 3]), hr.DEFAULTS["max_history"])
+    wb = np.where(f["full"], 0.0, 4.0 * f["pos"] * weight) + hc.K_BLEND * h64.EPS * f["Wout"]
+    assert (np.abs(got[..., 3].astype(np.float64) - f["Wout"])[cond] <= wb[cond]).all(), key
+    return int((cond & f["have"]).sum())
+
+
+@pytest.mark.parametrize("size", hc.SIZES)
+def test_kernel_at_low_cameras_equals_the_restatement_and_float64(contexts, size):
+    r = contexts(*size)
+    compared = 0
+    for altitude in ("2 m", "100 m", "10 km", "100 m, oblique"):
+        for fov in hc.FOVS:
+            for view in ("horizon", "down"):
+                for history in ("identical", "step 1 %", "step 30 % zoom 1.2"):
+                    compared += _low(r, (size, altitude, fov, view, history))
+    assert compared > 24 * size[0] * size[1]
+
+
+def test_kernel_at_the_lowest_camera_with_partial_edge_tiles(contexts):
+    """2 m, fov 0.05, a still camera: where the former expression was worst (2 px)."""
+    r = contexts(208, 120)
+    assert _low(r, ((208, 120), "2 m", 0.05, "horizon", "identical")) > 208 * 120 // 2
+
+
 # ---------------------------------------------------------------- 2. the whole pipeline
 def _start(r, p=None, **kw):
     """A fresh frame at camera p with the feature on and no history."""
@@ -220,6 +260,59 @@ def test_pipeline_equals_the_restatement(contexts, size):
     assert (_bits(r.fetch_hdr()) == _bits(hdr)).all()                      # the sums are never written
     r.set_history(False)
     assert (_bits(r.fetch_image()) == _bits(_display_elsewhere(other, r, hr.mean_of(hdr, 1)))).all()      # off: the plain display again
+
+
+@pytest.mark.parametrize("moved", [False, True])
+def test_pipeline_at_a_low_camera(contexts, moved):
+    """100 m above the sphere, looking at the horizon: the restatement bit for bit and the float64 statement within its budgets; a still camera keeps
+    its picture in place (what it shows again is what it showed, to within G N S: the position budget of each axis times the first picture's steepest
+    neighbour difference along that axis, G = Gx + Gy, which is at most twice the largest neighbour difference)."""
+    W, H = 80, 56
+    r = contexts(W, H)
+    a, b = hc.camera_pair("100 m", FOV, "horizon", "step 1 %" if moved else "identical", H)
+    pa, pb = _params(r, a.camera_pos, a.look_at, a.fov), _params(r, b.camera_pos, b.look_at, b.fov)
+    _start(r, pa)
+    r.accumulate(7)
+    r.fetch_image()
+    hist = r.fetch_history_hdr()
+    da = r.fetch_guides()[..., 1]
+    _move(r, pb)
+    r.reset_framebuffer()
+    r.accumulate(1)
+    got = r.fetch_history_hdr()
+    m = hr.mean_of(r.fetch_hdr(), 1)
+    db = r.fetch_guides()[..., 1]
+    r.set_history(False)
+    cam, hcam = hr.camera(pb, W, H), hr.camera(pa, W, H)
+    _same(got, hr.blend(m, 1, db, cam, hist, da, hcam))
+    assert 0.2 < (db > 0).mean() < 0.8                                       # land and sky
+    f = h64.history(cam, db, hist, da, hcam, hr.DEFAULTS["max_history"], hr.DEFAULTS["depth_tolerance"], m, 1, hc.N_POS, hc.N_LEN, hc.N_S)
+    ill = f["ill"]
+    cond = ~ill["any"] if moved else ~(ill["depth"] | ill["z"] | ill["s"] | ill["B"])
+    assert cond.mean() >= 0.99
+    # the first picture's steepest step between neighbours, in float64: what a pixel of position error can cost
+    c = hist[..., :3].astype(np.float64)
+    finite = np.isfinite(c).all()
+    assert finite
+    # a position error of e px in each axis moves a bilinear sample by at most (Gx + Gy) e: the steepest step along x plus the steepest along y
+    G = float(np.abs(np.diff(c, axis=0)).max() + np.abs(np.diff(c, axis=1)).max())
+    bound = hc.blend_bound(dict(f64=f, m=m), gradient=G)
+    err = np.abs(got[..., :3].astype(np.float64) - f["out"])
+    assert (err[cond] <= bound[cond]).all(), float((err[cond] / np.maximum(bound[cond], 1e-300)).max())
+    assert (cond & f["have"]).mean() > 0.5
+    if not moved:
+        inner = np.zeros((W, H), bool)
+        inner[1:-1, 1:-1] = True
+        keep = cond & inner & f["land"] & f["have"]
+        assert keep.sum() >= 100
+        out, wout = got[..., :3].astype(np.float64), got[..., 3].astype(np.float64)
+        w = wout - 1.0
+        with np.errstate(all="ignore"):
+            h = (out * wout[..., None] - m.astype(np.float64)) / w[..., None]
+        # out's own roundings (K_BLEND of them, tests/history_cases.py) come back multiplied by Wout / w
+        rounding = hc.K_BLEND * h64.EPS * np.maximum(np.abs(m.astype(np.float64)), np.abs(c)) * (wout / w)[..., None]
+        moved_by = np.abs(h - c)
+        assert (moved_by[keep] <= (G * f["pos"] + rounding)[keep]).all(), float((moved_by[keep] / (G * f["pos"] + rounding)[keep]).max())
 
 
 def _two_frames(r, W, H, first, second):

@@ -1,6 +1,6 @@
 """history_blend_kernel's source on the HOST under the address and undefined-behaviour sanitizers: builds tools/history_host_check.cpp
 (a stand-alone program that includes csrc/history_kernels.hip and runs it one workgroup at a time), feeds it the inputs of
-tests/test_gpu_history.py::test_kernel_equals_the_restatement_bit_for_bit at the three sizes, and compares what it writes with the numpy float32
+tests/test_gpu_history.py::test_kernel_equals_the_restatement_bit_for_bit at the three sizes and the low-camera cases of tests/history_cases.py, and compares what it writes with the numpy float32
 restatement (tests/history_ref.py) bit for bit.  Needs a C++ compiler and no GPU.
 
     python tools/history_host_check.py [--cxx g++] [--keep DIR]
@@ -39,7 +39,27 @@ def main():
     subprocess.check_call([args.cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fno-fast-math", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            "-x", "c++", os.path.join(ROOT, "tools", "history_host_check.cpp"), "-o", exe])
     r = _NoDevice()
-    runs = pixels = 0
+    done = [0, 0]                                                           # runs, pixels
+
+    def run(what, W, H, p, hp, m, n, dist, hist, hist_d, want, kw):
+        """One job through the program: the candidate and the display's mean against `want`, bit for bit."""
+        s = dict(hr.DEFAULTS, **kw)
+        dev = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1))          # (W, H, k) -> the device layout [H][W][k]
+        with open(os.path.join(work, "in.bin"), "wb") as f:
+            f.write(np.array([W, H, hist is not None], np.int32).tobytes())
+            f.write(np.array([s["max_history"], s["depth_tolerance"]], np.float32).tobytes())
+            f.write(bytes(p) + bytes(hp))
+            for a in (m, n.astype(np.int32), dist) + ((hist, hist_d) if hist is not None else ()):
+                f.write(dev(a).tobytes())
+        subprocess.check_call([exe, os.path.join(work, "in.bin"), os.path.join(work, "out.bin")])
+        raw = np.fromfile(os.path.join(work, "out.bin"), np.float32)
+        got = np.swapaxes(raw[:W * H * 4].reshape(H, W, 4), 0, 1)
+        shown = np.swapaxes(raw[W * H * 4:].reshape(H, W, 3), 0, 1)
+        t._same(got, want, what)
+        t._same(shown, want[..., :3], what)
+        done[0] += 1
+        done[1] += W * H
+
     for W, H in t.SIZES:
         x = t._inputs(r, W, H)
         hp = t._params(r)
@@ -58,23 +78,17 @@ def main():
                     jobs.append(((name, case, kw), p, cam, dist, x["hist"], hist_d, kw))
         jobs.append((("no history",), hp, hcam, x["step"], None, None, dict()))
         for what, p, cam, dist, hist, hist_d, kw in jobs:
-            s = dict(hr.DEFAULTS, **kw)
-            dev = lambda a: np.ascontiguousarray(np.swapaxes(a, 0, 1))      # (W, H, k) -> the device layout [H][W][k]
-            with open(os.path.join(work, "in.bin"), "wb") as f:
-                f.write(np.array([W, H, hist is not None], np.int32).tobytes())
-                f.write(np.array([s["max_history"], s["depth_tolerance"]], np.float32).tobytes())
-                f.write(bytes(p) + bytes(hp))
-                for a in (x["m"], x["n"].astype(np.int32), dist) + ((hist, hist_d) if hist is not None else ()):
-                    f.write(dev(a).tobytes())
-            subprocess.check_call([exe, os.path.join(work, "in.bin"), os.path.join(work, "out.bin")])
-            raw = np.fromfile(os.path.join(work, "out.bin"), np.float32)
-            got = np.swapaxes(raw[:W * H * 4].reshape(H, W, 4), 0, 1)
-            shown = np.swapaxes(raw[W * H * 4:].reshape(H, W, 3), 0, 1)
             want = hr.blend(x["m"], x["n"], dist, cam, hist, hist_d, hcam, **kw) if hist is not None else hr.blend(x["m"], x["n"], dist, cam)
-            t._same(got, want, what)
-            t._same(shown, want[..., :3], what)
-            runs += 1
-            pixels += W * H
+            run(what, W, H, p, hp, x["m"], x["n"], dist, hist, hist_d, want, kw)
+    # the low cameras of tests/history_cases.py, as tests/test_gpu_history.py runs them on the device
+    import history_cases as hc
+    low = [(size, altitude, fov, view, history) for size in hc.SIZES for altitude in ("2 m", "100 m", "10 km", "100 m, oblique") for fov in hc.FOVS
+           for view in ("horizon", "down") for history in ("identical", "step 1 %", "step 30 % zoom 1.2")] + [((208, 120), "2 m", 0.05, "horizon", "identical")]
+    for key in low:
+        (W, H), x = key[0], hc.case(*key)
+        p, hp = t._params(r, x["p"].camera_pos, x["p"].look_at, x["p"].fov), t._params(r, x["hp"].camera_pos, x["hp"].look_at, x["hp"].fov)
+        run(key, W, H, p, hp, x["m"], x["n"], x["dist"], x["hist"], x["hist_d"], hr.blend(x["m"], x["n"], x["dist"], x["cam"], x["hist"], x["hist_d"], x["hcam"]), dict())
+    runs, pixels = done
     print("history_blend_kernel on the host under -fsanitize=address,undefined: %d runs, %d pixels, no report, every bit equal to tests/history_ref.py" % (runs, pixels))
 
 
