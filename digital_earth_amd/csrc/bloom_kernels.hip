@@ -7,49 +7,27 @@
 //   bloom_up_kernel         U_l = (1 - spread) D_l + spread up(U_{l+1})
 //   bloom_composite_kernel  full resolution: out = m + intensity (up(U_1) - b), m and b recomputed (a pure function: the same bits), written [H][W][3]
 // All arithmetic is f32 with + - * / min max and compares in the order DESIGN.md §12 states (no contraction: -ffp-contract=off), so a numpy float32
-// restatement (tests/bloom_ref.py) is bit-exact.  No global atomics, nothing to clear between displays.  Included into de_api.hip's translation unit;
+// restatement (tests/bloom_ref.py) is bit-exact.  No global atomics, nothing to clear between displays.  The two passes of a level down are the
+// shared pyramid's (pyramid.h), the source is read as every stage reads it (display_source.h).  Included into de_api.hip's translation unit;
 // display_kernel is untouched.
 #include "de_kernels.h"
+#include "display_source.h"
+#include "pyramid.h"
 
 #include <float.h>
 
-#define BL_MAX_LEVELS 10
-#define BL_SRC_COLS 40      // down0: the 34 source columns 32 bx - 1 .. 32 bx + 32 lie in the ten groups of 4 pixels from 32 bx - 4 on
-#define BL_SRC_STRIDE 41    // odd row strides: the 16 lanes of the next row start on an odd bank, so the stride-2 reads of the row pass do not collide
-#define BL_LVL_STRIDE 35
-#define BL_H_STRIDE 24      // two rows down is 48 = 16 mod 32 banks on: the column pass of lanes (x, y) and (x, y + 1) covers all 32 banks once
+#define BL_MAX_LEVELS PYR_MAX_LEVELS
 
 // What the display launch is about to read, and the settings of the bright part.
-struct BloomSrc {
-    const float* hdr;           // [H][W][3]: DisplayArgs::hdr
-    const int32_t* tile_spp;    // [H/8][W/8] when the display divides every tile by its own count (display_kernel<true>), else null
-    int samples;                // DisplayArgs::samples
-    int W, H;
+struct BloomSrc : DisplaySrc {
     float threshold, knee, clamp;
 };
-
-// Twelve floats = 4 pixels of a row.  VEC: the buffer is 16-byte aligned (the context's own always are; a bound buffer or a display source may not be).
-template <bool VEC>
-DE_DEV void bloom_load4(const float* p, float* px) {
-    if (VEC) {
-        const float4 v0 = reinterpret_cast<const float4*>(p)[0], v1 = reinterpret_cast<const float4*>(p)[1], v2 = reinterpret_cast<const float4*>(p)[2];
-        px[0] = v0.x; px[1] = v0.y; px[2] = v0.z; px[3] = v0.w; px[4] = v1.x; px[5] = v1.y; px[6] = v1.z; px[7] = v1.w;
-        px[8] = v2.x; px[9] = v2.y; px[10] = v2.z; px[11] = v2.w;
-    } else {
-        for (int k = 0; k < 12; ++k) px[k] = p[k];
-    }
-}
-
-// display_pixel's own sample count (a group of 4 pixels lies in one 8x8 tile)
-DE_DEV float bloom_samples(const BloomSrc& s, int i, int j) {
-    return s.tile_spp ? (float)s.tile_spp[(j >> 3) * (s.W >> 3) + (i >> 3)] : (float)s.samples;
-}
 
 // Steps 1 and 2: the mean m (display_pixel's own division) and its bright part b.  A pixel whose luminance is not in (0, FLT_MAX] — zero, negative,
 // NaN, Inf — gives nothing and cannot spread.  With threshold = 0, w == 1 exactly and b == m bit for bit.
 DE_DEV void bloom_bright(const BloomSrc& s, const float* px, float samples, float* m, float* b) {
     m[0] = px[0] / samples; m[1] = px[1] / samples; m[2] = px[2] / samples;
-    const float Y = (0.2126f * m[0] + 0.7152f * m[1]) + 0.0722f * m[2];      // the meter's expression
+    const float Y = src_luminance(m[0], m[1], m[2]);
     if (!(Y > 0.0f && Y <= FLT_MAX)) { b[0] = 0.0f; b[1] = 0.0f; b[2] = 0.0f; return; }
     const float t = s.threshold, tk = t * s.knee;
     const float q = de_min(de_max((Y - t) + tk, 0.0f), 2.0f * tk);
@@ -60,74 +38,50 @@ DE_DEV void bloom_bright(const BloomSrc& s, const float* px, float samples, floa
     b[0] = m[0] * w; b[1] = m[1] * w; b[2] = m[2] * w;
 }
 
-DE_DEV int bl_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-DE_DEV float bl_tent4(float p0, float p1, float p2, float p3) { return (0.125f * p0 + 0.375f * p1) + (0.375f * p2 + 0.125f * p3); }
-
-// The two passes of one level down, from a staged source tile.  src: three planes of 34 rows; plane row r is source row r0 + r, plane column k is
-// source column c0 + k; only rows and columns inside the level were staged, and the clamped indices read only those.  The row pass makes 34 x 16
-// values, the column pass 16 x 16 outputs (Wd, Hd) = ((Ws + 1) >> 1, (Hs + 1) >> 1).
-template <int STRIDE>
-DE_DEV void bloom_down_passes(float (*src)[34][STRIDE], float (*hb)[34][BL_H_STRIDE], int c0, int r0, int Ws, int Hs, int Wd, int Hd, float4* out) {
-    const int X0 = (int)blockIdx.x * 16, Y0 = (int)blockIdx.y * 16;
-    for (int it = (int)threadIdx.x; it < 34 * 16; it += 256) {
-        const int row = it >> 4, x = it & 15, X = X0 + x, j = r0 + row;
-        if (j < 0 || j >= Hs || X >= Wd) continue;
-        const int k0 = bl_clampi(2 * X - 1, 0, Ws - 1) - c0, k1 = 2 * X - c0, k2 = bl_clampi(2 * X + 1, 0, Ws - 1) - c0, k3 = bl_clampi(2 * X + 2, 0, Ws - 1) - c0;
-        for (int c = 0; c < 3; ++c) hb[c][row][x] = bl_tent4(src[c][row][k0], src[c][row][k1], src[c][row][k2], src[c][row][k3]);
-    }
-    __syncthreads();
-    const int x = (int)threadIdx.x & 15, y = (int)threadIdx.x >> 4, X = X0 + x, Y = Y0 + y;
-    if (X >= Wd || Y >= Hd) return;
-    const int q0 = bl_clampi(2 * Y - 1, 0, Hs - 1) - r0, q1 = 2 * Y - r0, q2 = bl_clampi(2 * Y + 1, 0, Hs - 1) - r0, q3 = bl_clampi(2 * Y + 2, 0, Hs - 1) - r0;
-    float4 o;
-    o.x = bl_tent4(hb[0][q0][x], hb[0][q1][x], hb[0][q2][x], hb[0][q3][x]);
-    o.y = bl_tent4(hb[1][q0][x], hb[1][q1][x], hb[1][q2][x], hb[1][q3][x]);
-    o.z = bl_tent4(hb[2][q0][x], hb[2][q1][x], hb[2][q2][x], hb[2][q3][x]);
-    o.w = 0.0f;
-    out[(size_t)Y * Wd + X] = o;
-}
-
-// Source -> level 1.  Grid: 16 x 16 output tiles of level 1.  W is a multiple of 16, so a group of 4 source pixels is inside the image or outside it.
+// Source -> the staged tile of level 0: every source pixel's bright part.  W is a multiple of 16, so a group of 4 source pixels is inside the image
+// or outside it.
 template <bool VEC>
-__global__ void __launch_bounds__(256) bloom_down0_kernel(BloomSrc s, float4* out, int Wd, int Hd) {
-    __shared__ float src[3][34][BL_SRC_STRIDE];
-    __shared__ float hb[3][34][BL_H_STRIDE];
-    const int c0 = (int)blockIdx.x * 32 - 4, r0 = (int)blockIdx.y * 32 - 1;
-    for (int it = (int)threadIdx.x; it < 34 * (BL_SRC_COLS / 4); it += 256) {
-        const int row = it / (BL_SRC_COLS / 4), g = it - row * (BL_SRC_COLS / 4);
+DE_DEV void bloom_stage0(const BloomSrc& s, float (*src)[34][PYR_SRC_STRIDE], int t, int bx, int by) {
+    const int c0 = bx * 32 - 4, r0 = by * 32 - 1;
+    for (int it = t; it < 34 * (PYR_SRC_COLS / 4); it += 256) {
+        const int row = it / (PYR_SRC_COLS / 4), g = it - row * (PYR_SRC_COLS / 4);
         const int j = r0 + row, i0 = c0 + 4 * g;
         if (j < 0 || j >= s.H || i0 < 0 || i0 >= s.W) continue;
         float px[12];
-        bloom_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
-        const float samples = bloom_samples(s, i0, j);
+        src_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
+        const float samples = src_samples(s, i0, j);
         for (int k = 0; k < 4; ++k) {
             float m[3], b[3];
             bloom_bright(s, px + 3 * k, samples, m, b);
             src[0][row][4 * g + k] = b[0]; src[1][row][4 * g + k] = b[1]; src[2][row][4 * g + k] = b[2];
         }
     }
+}
+
+// Source -> level 1.  Grid: 16 x 16 output tiles of level 1.
+template <bool VEC>
+__global__ void __launch_bounds__(256) bloom_down0_kernel(BloomSrc s, float4* out, int Wd, int Hd) {
+    __shared__ float src[3][34][PYR_SRC_STRIDE];
+    __shared__ float hb[3][34][PYR_H_STRIDE];
+    const int t = (int)threadIdx.x, bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    bloom_stage0<VEC>(s, src, t, bx, by);
     __syncthreads();
-    bloom_down_passes<BL_SRC_STRIDE>(src, hb, c0, r0, s.W, s.H, Wd, Hd, out);
+    pyr_row_pass<3, PYR_SRC_STRIDE>(src, hb, t, bx, by, bx * 32 - 4, s.W, s.H, Wd);
+    __syncthreads();
+    pyr_col_pass<3>(hb, t, bx, by, s.H, Wd, Hd, out);
 }
 
 // Level l -> level l + 1.  Grid: 16 x 16 output tiles.
 __global__ void __launch_bounds__(256) bloom_down_kernel(const float4* in, int Ws, int Hs, float4* out, int Wd, int Hd) {
-    __shared__ float src[3][34][BL_LVL_STRIDE];
-    __shared__ float hb[3][34][BL_H_STRIDE];
-    const int c0 = (int)blockIdx.x * 32 - 1, r0 = (int)blockIdx.y * 32 - 1;
-    for (int it = (int)threadIdx.x; it < 34 * 34; it += 256) {
-        const int row = it / 34, col = it - row * 34;
-        const int j = r0 + row, i = c0 + col;
-        if (j < 0 || j >= Hs || i < 0 || i >= Ws) continue;
-        const float4 v = in[(size_t)j * Ws + i];
-        src[0][row][col] = v.x; src[1][row][col] = v.y; src[2][row][col] = v.z;
-    }
+    __shared__ float src[3][34][PYR_LVL_STRIDE];
+    __shared__ float hb[3][34][PYR_H_STRIDE];
+    const int t = (int)threadIdx.x, bx = (int)blockIdx.x, by = (int)blockIdx.y;
+    pyr_stage_level<3>(in, Ws, Hs, src, t, bx, by);
     __syncthreads();
-    bloom_down_passes<BL_LVL_STRIDE>(src, hb, c0, r0, Ws, Hs, Wd, Hd, out);
+    pyr_row_pass<3, PYR_LVL_STRIDE>(src, hb, t, bx, by, bx * 32 - 1, Ws, Hs, Wd);
+    __syncthreads();
+    pyr_col_pass<3>(hb, t, bx, by, Hs, Wd, Hd, out);
 }
-
-// far neighbour of fine index x on the coarse level of n entries: near - 1 for even x, near + 1 for odd x, clamped
-DE_DEV int bl_far(int x, int n) { return bl_clampi((x & 1) ? (x >> 1) + 1 : (x >> 1) - 1, 0, n - 1); }
 
 // U_l = (1 - spread) D_l + spread up(U_{l+1}).  Grid: 16 x 16 tiles of level l (Wf, Hf); a tile needs a 10 x 10 tile of the coarse level (Wc, Hc).
 struct BloomUpArgs {
@@ -154,14 +108,14 @@ __global__ void __launch_bounds__(256) bloom_up_kernel(BloomUpArgs a) {
     if (threadIdx.x < 160u) {
         const int row = (int)threadIdx.x >> 4, x = (int)threadIdx.x & 15, X = X0 + x, j = r0 + row;
         if (j >= 0 && j < a.Hc && X < a.Wf) {
-            const int kn = (X >> 1) - c0, kf = bl_far(X, a.Wc) - c0;
+            const int kn = (X >> 1) - c0, kf = pyr_far(X, a.Wc) - c0;
             for (int c = 0; c < 3; ++c) hb[c][row][x] = 0.75f * cs[c][row][kn] + 0.25f * cs[c][row][kf];
         }
     }
     __syncthreads();
     const int x = (int)threadIdx.x & 15, y = (int)threadIdx.x >> 4, X = X0 + x, Y = Y0 + y;
     if (X >= a.Wf || Y >= a.Hf) return;
-    const int qn = (Y >> 1) - r0, qf = bl_far(Y, a.Hc) - r0;
+    const int qn = (Y >> 1) - r0, qf = pyr_far(Y, a.Hc) - r0;
     const float4 d = a.fine[(size_t)Y * a.Wf + X];
     float4 o;
     o.x = a.keep * d.x + a.spread * (0.75f * hb[0][qn][x] + 0.25f * hb[0][qf][x]);
@@ -179,13 +133,13 @@ __global__ void __launch_bounds__(256) bloom_composite_kernel(BloomSrc s, const 
     if (item >= gw * (uint32_t)s.H) return;
     const int j = (int)(item / gw), i0 = (int)(item - (uint32_t)j * gw) * 4;
     float px[12];
-    bloom_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
-    const float samples = bloom_samples(s, i0, j);
-    const int cx = i0 >> 1, rn = j >> 1, rf = bl_far(j, H1);
+    src_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
+    const float samples = src_samples(s, i0, j);
+    const int cx = i0 >> 1, rn = j >> 1, rf = pyr_far(j, H1);
     float4 un[4], uf[4];      // columns cx - 1 .. cx + 2, clamped, of the near and the far row
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int col = bl_clampi(cx - 1 + k, 0, W1 - 1);
+        const int col = pyr_clampi(cx - 1 + k, 0, W1 - 1);
         un[k] = u1[(size_t)rn * W1 + col];
         uf[k] = u1[(size_t)rf * W1 + col];
     }

@@ -1,8 +1,9 @@
 // de_api.hip — the C ABI of libdigitalearth_hip.so (include/digital_earth.h): context life cycle, uploads, parameters, the frame loop, fetches.
-// No CPU fallback exists: every entry point needs a HIP device.  The launches are in de_launch.h, the collectives in de_rccl.h, the context in
-// de_context.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS (legacy/).
+// No CPU fallback exists: every entry point needs a HIP device.  The launches are in de_launch.h, the collectives in de_rccl.h, the display path's stages
+// and their one chain in de_display.h, the context in de_context.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS
+// (legacy/).  This file holds entry points only.
 #include "de_rccl.h"
-#include "../../include/digital_earth_denoise.h"
+#include "de_display.h"
 
 namespace {
 // A launch slot's stream.  withhold > 0: the stream may use every CU but the LAST `withhold` of each XCD (hipExtStreamCreateWithCUMask; bit i of the mask is
@@ -18,294 +19,6 @@ hipError_t create_slot_stream(de_ctx* c, hipStream_t* out) {
     return hipExtStreamCreateWithCUMask(out, (uint32_t)((n + 31) / 32), mask);
 }
 
-// ---- the denoiser (include/digital_earth_denoise.h, denoise_kernels.hip)
-int denoise_refusal(de_ctx* c) {
-    if (c->tiles_world > 1) return fail(DE_ERR_STATE, "the denoiser filters whole frames: not under a tile partition");
-    if (c->sample_world > 1) return fail(DE_ERR_STATE, "the denoiser filters whole frames: not under a sample partition");
-    if (c->display_src) return fail(DE_ERR_STATE, "the denoiser filters this context's own frame: not with a display source or after de_reduce_progressive");
-    return DE_OK;
-}
-// ---- the HDR display output (include/digital_earth_hdr_output.h, hdr_output_kernels.hip)
-int hdr_output_refusal(de_ctx* c) {
-    if (c->p.flags & DE_FLAG_AGX) return fail(DE_ERR_STATE, "the HDR display output runs OpenDRT: not with DE_FLAG_AGX, an SDR transform");
-    return DE_OK;
-}
-// the guides alone: what guide_kernel writes (the history reprojection reads their distance without the denoiser's other buffers)
-int dn_alloc_guides(de_ctx* c) {
-    const size_t npx = (size_t)c->W * c->H;
-    if (!c->d_dn_nc) HIP_TRY(hipMalloc(&c->d_dn_nc, npx * sizeof(float4)));
-    if (!c->d_dn_at) HIP_TRY(hipMalloc(&c->d_dn_at, npx * sizeof(float4)));
-    if (!c->d_dn_dist) HIP_TRY(hipMalloc(&c->d_dn_dist, npx * sizeof(float)));
-    return DE_OK;
-}
-int dn_alloc(de_ctx* c) {
-    const size_t npx = (size_t)c->W * c->H;
-    { int rc = dn_alloc_guides(c); if (rc) return rc; }
-    for (int k = 0; k < 2; ++k) if (!c->d_dn_buf[k]) HIP_TRY(hipMalloc(&c->d_dn_buf[k], npx * sizeof(float4)));
-    if (!c->d_dn_out) HIP_TRY(hipMalloc(&c->d_dn_out, npx * 3 * sizeof(float)));
-    return DE_OK;
-}
-DenoiseGuides dn_guides(de_ctx* c) { DenoiseGuides g; g.nc = c->d_dn_nc; g.at = c->d_dn_at; g.dist = c->d_dn_dist; return g; }
-dim3 dn_grid(de_ctx* c) { return dim3((unsigned)((c->W + 15) / 16), (unsigned)((c->H + 15) / 16)); }
-// The guides of the current camera, maps and address mode: once per frame (de_reset, a map or a camera change clears them).
-int dn_ensure_guides(de_ctx* c) {
-    int rc = dn_alloc_guides(c);
-    if (rc) return rc;
-    if (c->dn_guides_valid) return DE_OK;
-    RenderArgs a;
-    rc = fill_render_args(c, &a);          // packs the maps and rebuilds the frame constants if needed
-    if (rc) return rc;
-    if (c->p.flags & DE_FLAG_CLAMP_SAMPLER) hipLaunchKernelGGL(guide_kernel<true>, dn_grid(c), dim3(256), 0, c->stream, a, dn_guides(c));
-    else hipLaunchKernelGGL(guide_kernel<false>, dn_grid(c), dim3(256), 0, c->stream, a, dn_guides(c));
-    HIP_TRY(hipGetLastError());
-    c->dn_guides_valid = true;
-    return DE_OK;
-}
-// The a-trous levels over d_dn_buf[1] (colour, variance); the last one also writes the filtered mean to d_dn_out.  Returns the buffer that holds the result.
-int dn_levels(de_ctx* c, int levels, float sigma_l, float4** result) {
-    AtrousArgs t;
-    t.g = dn_guides(c); t.W = c->W; t.H = c->H; t.sigma_l = sigma_l;
-    int cur = 1;
-    for (int l = 0; l < levels; ++l) {
-        t.in = c->d_dn_buf[cur]; t.out = c->d_dn_buf[cur ^ 1]; t.step = 1 << l;
-        t.out3 = l == levels - 1 ? c->d_dn_out : nullptr;
-        hipLaunchKernelGGL(atrous_kernel, dn_grid(c), dim3(256), 0, c->stream, t);
-        HIP_TRY(hipGetLastError());
-        cur ^= 1;
-    }
-    *result = c->d_dn_buf[cur];
-    return DE_OK;
-}
-// The frame's filtered mean into d_dn_out, on the context stream (the caller has joined the launch slots and marked the HDR buffer as read).
-// Variance source: the per-pixel estimate from S2 when S2 is complete and the pixel has n >= 4 samples, else the 7x7 spatial estimate.
-int run_denoise(de_ctx* c) {
-    int rc = dn_alloc(c);
-    if (rc) return rc;
-    rc = dn_ensure_guides(c);
-    if (rc) return rc;
-    DenoisePrepArgs pa;
-    const bool adaptive = c->frame_kind == DE_FRAME_ADAPTIVE;
-    pa.s1 = c->display_src ? c->display_src : c->d_hdr;
-    pa.s2 = (c->dn_s2_complete || adaptive) ? c->d_s2 : nullptr;
-    pa.tile_spp = adaptive ? c->d_tile_spp : nullptr;
-    pa.spp = c->current_spp; pa.W = c->W; pa.H = c->H; pa.out = c->d_dn_buf[0];
-    hipLaunchKernelGGL(prep_mean_kernel, dn_grid(c), dim3(256), 0, c->stream, pa);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prep_spatial_kernel, dn_grid(c), dim3(256), 0, c->stream, (const float4*)c->d_dn_buf[0], c->d_dn_buf[1], c->W, c->H);
-    HIP_TRY(hipGetLastError());
-    float4* res = nullptr;
-    rc = dn_levels(c, c->dn_levels, c->dn_sigma_l, &res);
-    if (rc) return rc;
-    c->dn_out_valid = true;
-    return DE_OK;
-}
-// ---- auto-exposure (include/digital_earth_exposure.h, exposure_kernels.hip)
-int ae_alloc(de_ctx* c) {
-    if (!c->d_ae_partial) HIP_TRY(hipMalloc(&c->d_ae_partial, (size_t)AE_MAX_WG * AE_ROW * sizeof(uint32_t)));
-    if (!c->d_ae_state) HIP_TRY(hipMalloc(&c->d_ae_state, sizeof(MeterState)));
-    if (!c->d_fc_ae) HIP_TRY(hipMalloc(&c->d_fc_ae, sizeof(FrameConsts)));
-    if (!c->d_ae_result) HIP_TRY(hipMalloc(&c->d_ae_result, sizeof(MeterResult)));
-    if (!c->d_ae_centre) {
-        // log2 of the bins' centres: bin k = octave (k >> 3) - 24, sub-bin k & 7 of 8 linear ones; uploaded once, so that the device computes no logarithm
-        double centre[AE_BINS];
-        for (int k = 0; k < AE_BINS; ++k) centre[k] = (double)((k >> 3) - 24) + log2(1.0 + ((double)(k & 7) + 0.5) / 8.0);
-        HIP_TRY(hipMalloc(&c->d_ae_centre, sizeof(centre)));
-        HIP_TRY(hipMemcpyAsync(c->d_ae_centre, centre, sizeof(centre), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));      // the table is a local: once per context, when the feature is first turned on, never in a display
-    }
-    return DE_OK;
-}
-// The two metering kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).
-int run_meter(de_ctx* c, const DisplayArgs& d, bool per_tile) {
-    const de_auto_exposure& s = c->ae;
-    const bool whole = !(s.region[0] | s.region[1] | s.region[2] | s.region[3]);
-    MeterArgs m;
-    m.hdr = d.hdr; m.tile_spp = per_tile ? d.tile_spp : nullptr; m.samples = d.samples; m.W = c->W;
-    m.x0 = whole ? 0 : s.region[0]; m.y0 = whole ? 0 : s.region[1]; m.x1 = whole ? c->W : s.region[2]; m.y1 = whole ? c->H : s.region[3];
-    m.gx0 = m.x0 >> 2; m.gw = ((m.x1 + 3) >> 2) - m.gx0;
-    const unsigned long long items = (unsigned long long)m.gw * (unsigned long long)(m.y1 - m.y0);      // at most the region's pixels
-    if ((unsigned long long)(m.x1 - m.x0) * (unsigned long long)(m.y1 - m.y0) >= (1ull << 31))
-        return fail(DE_ERR_INVALID, "the metering region must hold fewer than 2^31 pixels (the counts and the item index are 32-bit)");
-    m.n_items = (uint32_t)items;
-    m.partial = c->d_ae_partial;
-    const unsigned n_wg = (unsigned)std::min<unsigned long long>((items + 255ull) / 256ull, (unsigned long long)AE_MAX_WG);
-    if ((reinterpret_cast<uintptr_t>(d.hdr) & 15u) == 0u) hipLaunchKernelGGL(meter_hist_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, m);
-    else hipLaunchKernelGGL(meter_hist_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, m);
-    HIP_TRY(hipGetLastError());
-    MeterSolveArgs v;
-    v.partial = c->d_ae_partial; v.n_rows = (int)n_wg;
-    v.low = s.low_fraction; v.high = s.high_fraction; v.adapt = s.adapt; v.compensation = s.compensation; v.ev_min = s.ev_min; v.ev_max = s.ev_max;
-    v.manual = c->p.exposure;
-    v.log2_key = log2((double)s.key);
-    v.centre = c->d_ae_centre; v.state = c->d_ae_state; v.fc = c->d_fc; v.fc_ae = c->d_fc_ae; v.res = c->d_ae_result;
-    hipLaunchKernelGGL(meter_solve_kernel, dim3(1), dim3(1024), 0, c->stream, v);
-    HIP_TRY(hipGetLastError());
-    c->ae_displayed = true;
-    return DE_OK;
-}
-// ---- bloom (include/digital_earth_bloom.h, bloom_kernels.hip)
-// The pyramid of a W x H image: level l is ((w + 1) >> 1, (h + 1) >> 1) of level l - 1; L = `levels`, reduced so that halving stops before a level
-// whose smaller side would be below 2, never less than 1.  off[l]: where D_l (and, `total` further, U_l) starts in d_bl_pyr, in float4.
-struct BloomPlan { int L; int w[BL_MAX_LEVELS + 1], h[BL_MAX_LEVELS + 1]; size_t off[BL_MAX_LEVELS + 1]; size_t total; };
-BloomPlan bl_plan(int W, int H, int levels) {
-    BloomPlan p;
-    p.L = 0; p.w[0] = W; p.h[0] = H; p.off[0] = 0; p.total = 0;
-    while (p.L < levels) {
-        const int w = (p.w[p.L] + 1) >> 1, h = (p.h[p.L] + 1) >> 1;
-        if (p.L >= 1 && std::min(w, h) < 2) break;
-        ++p.L;
-        p.w[p.L] = w; p.h[p.L] = h; p.off[p.L] = p.total;
-        p.total += (size_t)w * (size_t)h;
-    }
-    return p;
-}
-int bl_alloc(de_ctx* c) {
-    const BloomPlan p = bl_plan(c->W, c->H, BL_MAX_LEVELS);      // room for every setting of `levels`: the offsets of a level do not depend on it
-    if (!c->d_bl_pyr) HIP_TRY(hipMalloc(&c->d_bl_pyr, 2 * p.total * sizeof(float4)));
-    if (!c->d_bl_out) HIP_TRY(hipMalloc(&c->d_bl_out, (size_t)c->W * c->H * 3 * sizeof(float)));
-    return DE_OK;
-}
-// The bloom kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).  Afterwards `d`
-// describes the composited mean: the unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).
-int run_bloom(de_ctx* c, DisplayArgs& d, bool& per_tile) {
-    const de_bloom& b = c->bl;
-    const BloomPlan p = bl_plan(c->W, c->H, b.levels);
-    float4* D = c->d_bl_pyr;
-    float4* U = c->d_bl_pyr + bl_plan(c->W, c->H, BL_MAX_LEVELS).total;
-    BloomSrc s;
-    s.hdr = d.hdr; s.tile_spp = per_tile ? d.tile_spp : nullptr; s.samples = d.samples; s.W = c->W; s.H = c->H;
-    s.threshold = b.threshold; s.knee = b.knee; s.clamp = b.clamp;
-    const bool vec = (reinterpret_cast<uintptr_t>(d.hdr) & 15u) == 0u;
-    auto tiles = [](int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); };
-    if (vec) hipLaunchKernelGGL(bloom_down0_kernel<true>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
-    else hipLaunchKernelGGL(bloom_down0_kernel<false>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
-    HIP_TRY(hipGetLastError());
-    for (int l = 1; l < p.L; ++l) {
-        hipLaunchKernelGGL(bloom_down_kernel, tiles(p.w[l + 1], p.h[l + 1]), dim3(256), 0, c->stream, (const float4*)(D + p.off[l]), p.w[l], p.h[l], D + p.off[l + 1], p.w[l + 1], p.h[l + 1]);
-        HIP_TRY(hipGetLastError());
-    }
-    const float4* top = D + p.off[p.L];      // U_L = D_L
-    for (int l = p.L - 1; l >= 1; --l) {
-        BloomUpArgs u;
-        u.coarse = top; u.fine = D + p.off[l]; u.out = U + p.off[l];
-        u.Wc = p.w[l + 1]; u.Hc = p.h[l + 1]; u.Wf = p.w[l]; u.Hf = p.h[l];
-        u.keep = 1.0f - b.spread; u.spread = b.spread;
-        hipLaunchKernelGGL(bloom_up_kernel, tiles(p.w[l], p.h[l]), dim3(256), 0, c->stream, u);
-        HIP_TRY(hipGetLastError());
-        top = u.out;
-    }
-    // level 0 is not blended in: the glow never holds the unblurred image
-    const unsigned n_wg = (unsigned)(((size_t)(c->W >> 2) * (size_t)c->H + 255u) / 256u);
-    if (vec) hipLaunchKernelGGL(bloom_composite_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, s, top, p.w[1], p.h[1], b.intensity, c->d_bl_out);
-    else hipLaunchKernelGGL(bloom_composite_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, s, top, p.w[1], p.h[1], b.intensity, c->d_bl_out);
-    HIP_TRY(hipGetLastError());
-    d.hdr = c->d_bl_out; d.samples = 1; per_tile = false;
-    return DE_OK;
-}
-// ---- history reprojection (include/digital_earth_history.h, history_kernels.hip)
-int hs_alloc(de_ctx* c) {
-    const size_t npx = (size_t)c->W * c->H;
-    for (int k = 0; k < 2; ++k) {
-        if (!c->d_hs_c[k]) HIP_TRY(hipMalloc(&c->d_hs_c[k], npx * sizeof(float4)));
-        if (!c->d_hs_d[k]) HIP_TRY(hipMalloc(&c->d_hs_d[k], npx * sizeof(float)));
-        if (!c->d_hs_cam[k]) HIP_TRY(hipMalloc(&c->d_hs_cam[k], sizeof(HistoryCam)));
-    }
-    if (!c->d_hs_out) HIP_TRY(hipMalloc(&c->d_hs_out, npx * 3 * sizeof(float)));
-    return DE_OK;
-}
-// All weights 0: neither the history nor a candidate written before this point is read again (host flags: the buffers need no clearing).
-void hs_drop(de_ctx* c) { c->hs_valid = false; c->hs_cand_valid = false; }
-// Does the step from de_params a to b change radiance?  Camera fields reproject; exposure, gamma, CRF, vignette and DE_FLAG_AGX are display-only.
-bool hs_radiance_changed(const de_params& a, const de_params& b) {
-    return memcmp(&a.sun_angle, &b.sun_angle, sizeof(float)) != 0 || memcmp(&a.sun_path_rot, &b.sun_path_rot, sizeof(float)) != 0 ||
-           memcmp(&a.land_height_scale, &b.land_height_scale, sizeof(float)) != 0 || memcmp(&a.fixed_wavelength, &b.fixed_wavelength, sizeof(float)) != 0 ||
-           a.topo_res_override != b.topo_res_override || ((a.flags ^ b.flags) & ~(uint32_t)DE_FLAG_AGX) != 0u;
-}
-// The blend on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).  Afterwards `d` describes
-// the blended mean: the unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).  The same launch writes the next history candidate.
-int run_history(de_ctx* c, DisplayArgs& d, bool& per_tile) {
-    int rc = hs_alloc(c);
-    if (rc) return rc;
-    rc = dn_ensure_guides(c);      // the distance of the current camera: once per frame, shared with the denoiser
-    if (rc) return rc;
-    const int cur = c->hs_cur, cand = cur ^ 1;
-    HistoryArgs a;
-    a.hdr = d.hdr; a.tile_spp = per_tile ? d.tile_spp : nullptr; a.samples = d.samples;
-    a.n_tile = c->frame_kind == DE_FRAME_ADAPTIVE ? c->d_tile_spp : nullptr; a.n_pixel = nullptr; a.n_frame = c->current_spp;
-    a.dist = c->d_dn_dist; a.fc = c->d_fc;
-    a.hist_c = c->hs_valid ? c->d_hs_c[cur] : nullptr; a.hist_d = c->d_hs_d[cur]; a.hist_cam = c->d_hs_cam[cur];
-    a.out = c->d_hs_out; a.cand_c = c->d_hs_c[cand]; a.cand_d = c->d_hs_d[cand]; a.cand_cam = c->d_hs_cam[cand];
-    a.W = c->W; a.H = c->H; a.max_history = c->hs.max_history; a.depth_tolerance = c->hs.depth_tolerance;
-    hipLaunchKernelGGL(history_blend_kernel, dn_grid(c), dim3(256), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    c->hs_cand_valid = true;
-    d.hdr = c->d_hs_out; d.samples = 1; per_tile = false;
-    return DE_OK;
-}
-// ---- local exposure (include/digital_earth_local_exposure.h, local_exposure_kernels.hip)
-int lx_alloc(de_ctx* c) {
-    const BloomPlan p = bl_plan(c->W, c->H, LX_MAX_LEVELS);      // the bloom's pyramid plan; room for every setting of `levels`: the offsets of a level do not depend on it
-    if (!c->d_lx_pyr) HIP_TRY(hipMalloc(&c->d_lx_pyr, p.total * sizeof(float2)));
-    if (!c->d_lx_base) HIP_TRY(hipMalloc(&c->d_lx_base, p.total * sizeof(float)));
-    if (!c->d_lx_out) HIP_TRY(hipMalloc(&c->d_lx_out, (size_t)c->W * c->H * 3 * sizeof(float)));
-    return DE_OK;
-}
-int lx_settings_check(const de_local_exposure* s) {
-    if (s->struct_bytes != (uint32_t)sizeof(de_local_exposure)) return fail(DE_ERR_INVALID, "de_local_exposure.struct_bytes does not match this library's struct");
-    if (!(s->highlights >= 0.0f) || !(s->highlights <= 1.0f) || !(s->shadows >= 0.0f) || !(s->shadows <= 1.0f))
-        return fail(DE_ERR_INVALID, "local exposure settings: highlights and shadows in [0, 1]");
-    if (!(s->sigma > 0.0f) || !(s->sigma < 1e30f) || !(s->max_ev >= 0.0f) || !(s->max_ev < 1e30f) || !(s->key > 0.0f) || !(s->key < 1e30f))
-        return fail(DE_ERR_INVALID, "local exposure settings: finite sigma > 0, finite max_ev >= 0, finite key > 0");
-    if (s->levels < 1 || s->levels > LX_MAX_LEVELS) return fail(DE_ERR_INVALID, "local exposure settings: levels in 1 .. 10");
-    return DE_OK;
-}
-// The kernels on the context stream with the settings `x`, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>)
-// and with the anchor from d.fc (the metered FrameConsts while auto-exposure is on: no host round trip).  Afterwards `d` describes the dodged mean: the
-// unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).
-int lx_run(de_ctx* c, const de_local_exposure& x, DisplayArgs& d, bool& per_tile) {
-    const BloomPlan p = bl_plan(c->W, c->H, x.levels);
-    float2* D = c->d_lx_pyr;
-    float* B = c->d_lx_base;
-    LxSrc s;
-    s.hdr = d.hdr; s.tile_spp = per_tile ? d.tile_spp : nullptr; s.samples = d.samples; s.W = c->W; s.H = c->H;
-    const bool vec = (reinterpret_cast<uintptr_t>(d.hdr) & 15u) == 0u;
-    const float inv_sigma = 1.0f / x.sigma;
-    auto tiles = [](int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); };
-    if (vec) hipLaunchKernelGGL(lx_down0_kernel<true>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
-    else hipLaunchKernelGGL(lx_down0_kernel<false>, tiles(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
-    HIP_TRY(hipGetLastError());
-    for (int l = 1; l < p.L; ++l) {
-        hipLaunchKernelGGL(lx_down_kernel, tiles(p.w[l + 1], p.h[l + 1]), dim3(256), 0, c->stream, (const float2*)(D + p.off[l]), p.w[l], p.h[l], D + p.off[l + 1], p.w[l + 1], p.h[l + 1]);
-        HIP_TRY(hipGetLastError());
-    }
-    const float* top = nullptr;      // B_L is the top level's guide: not stored
-    for (int l = p.L - 1; l >= 1; --l) {
-        LxUpArgs u;
-        u.fine = D + p.off[l]; u.coarse = D + p.off[l + 1]; u.coarse_b = top; u.out = B + p.off[l];
-        u.Wc = p.w[l + 1]; u.Hc = p.h[l + 1]; u.Wf = p.w[l]; u.Hf = p.h[l]; u.inv_sigma = inv_sigma;
-        hipLaunchKernelGGL(lx_up_kernel, dim3((unsigned)(((size_t)u.Wf * (size_t)u.Hf + 255u) / 256u)), dim3(256), 0, c->stream, u);
-        HIP_TRY(hipGetLastError());
-        top = u.out;
-    }
-    LxApplyArgs a;
-    a.s = s; a.d1 = D + p.off[1]; a.b1 = top; a.W1 = p.w[1]; a.H1 = p.h[1]; a.fc = d.fc;
-    a.highlights = x.highlights; a.shadows = x.shadows; a.inv_sigma = inv_sigma; a.max_ev = x.max_ev; a.key = x.key; a.out = c->d_lx_out;
-    const unsigned n_wg = (unsigned)(((size_t)(c->W >> 2) * (size_t)c->H + 255u) / 256u);
-    if (vec) hipLaunchKernelGGL(lx_apply_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, a);
-    else hipLaunchKernelGGL(lx_apply_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    d.hdr = c->d_lx_out; d.samples = 1; per_tile = false;
-    return DE_OK;
-}
-int run_local_exposure(de_ctx* c, DisplayArgs& d, bool& per_tile) { return lx_run(c, c->lx, d, per_tile); }
-// What the display reads: the sums with the frame's or the tiles' counts, a display source, or the denoiser's filtered mean (the caller has run it).
-void display_source(de_ctx* c, DisplayArgs& d, bool& per_tile) {
-    d.hdr = c->display_src ? c->display_src : c->d_hdr;
-    d.W = c->W; d.H = c->H; d.samples = c->current_spp;
-    d.tile_spp = c->d_tile_spp;
-    if (c->dn_on) { d.hdr = c->d_dn_out; d.samples = 1; }
-    per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
-}
 }  // namespace
 
 extern "C" {
@@ -714,111 +427,13 @@ int de_flush(de_ctx* c) {
     return frame_status(c);  // an abort already known (the words are host-visible): a host framework's own collective must not ship that frame
 }
 
-/* ---- output scaling: include/digital_earth_output_scale.h (output_scale_kernels.hip).  The helpers stand here because every call that
- * hands out the displayed image sizes itself from them; the entry points are at the end of the file. */
-namespace {
-bool os_active(const de_ctx* c) { return c->os.enabled && c->os.width > 0 && (c->os.width != c->W || c->os.height != c->H); }      // on at W x H is the identity: nothing runs
-int out_w(const de_ctx* c) { return os_active(c) ? c->os.width : c->W; }
-int out_h(const de_ctx* c) { return os_active(c) ? c->os.height : c->H; }
-size_t out_image_bytes(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3 * sizeof(float); }
-const float* shown_image(const de_ctx* c) { return os_active(c) ? c->d_os_out : c->d_image; }
-// The settings against a source size; *ow, *oh = the output size they ask for (0, 0: the source's).
-int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) {
-    if (s->struct_bytes != (uint32_t)sizeof(de_output_scale)) return fail(DE_ERR_INVALID, "de_output_scale.struct_bytes does not match this library's struct");
-    if (s->filter < DE_SCALE_BOX || s->filter > DE_SCALE_LANCZOS3) return fail(DE_ERR_INVALID, "de_output_scale.filter must be DE_SCALE_BOX, _TRIANGLE, _MITCHELL or _LANCZOS3");
-    const int w = (s->width == 0 && s->height == 0) ? W : s->width, h = (s->width == 0 && s->height == 0) ? H : s->height;
-    if (w <= 0 || h <= 0 || (w % 16) != 0 || (h % 8) != 0) return fail(DE_ERR_INVALID, "de_output_scale: width must be a positive multiple of 16 and height of 8");
-    if ((long long)w * 8 < W || (long long)W * 8 < w || (long long)h * 8 < H || (long long)H * 8 < h) return fail(DE_ERR_INVALID, "de_output_scale: each axis' ratio out / source must lie in [1/8, 8]");
-    if ((long long)w * h > (1ll << 28)) return fail(DE_ERR_INVALID, "de_output_scale: width * height must not exceed 2^28");
-    *ow = w; *oh = h;
-    return DE_OK;
-}
-// A device buffer of at least `bytes`: one that is too small is replaced (hipFree waits for the work that reads it).
-int os_device_ensure(void** p, size_t* have, size_t bytes) {
-    if (*p && *have >= bytes) return DE_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no device memory for the output scaling's buffers"); }
-    *have = bytes;
-    return DE_OK;
-}
-// One axis' table on the device, rebuilt only when the axis or the filter changed.  The upload reads pageable host memory that dies with this call: waited for.
-int os_table_ensure(hipStream_t stream, de_ctx::ScaleDev& d, int n_src, int n_dst, int filter) {
-    if (d.first && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
-    ScaleTable T;
-    if (!os_build_table(n_src, n_dst, filter, &T)) return fail(DE_ERR_INVALID, "output scaling: no table for this pair of sizes");
-    size_t fb = d.first_cap * sizeof(int32_t), wb = d.w_cap * sizeof(float);
-    int rc = os_device_ensure((void**)&d.first, &fb, T.first.size() * sizeof(int32_t));
-    d.first_cap = fb / sizeof(int32_t);
-    if (rc) return rc;
-    rc = os_device_ensure((void**)&d.w, &wb, T.w.size() * sizeof(float));
-    d.w_cap = wb / sizeof(float);
-    if (rc) return rc;
-    d.filter = -1;
-    HIP_TRY(hipMemcpyAsync(d.first, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d.w, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    d.n_src = n_src; d.n_dst = n_dst; d.filter = filter; d.taps = T.taps;
-    return DE_OK;
-}
-// The passes of (W, H, 3) -> (ow, oh, 3), not both sizes equal: along v into `mid` (or straight into `out` when the other axis is a copy), then along u.
-int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh, const de_ctx::ScaleDev& tv, const de_ctx::ScaleDev& tu, float* mid, float* out) {
-    const float* in = src;
-    if (oh != H) {
-        ScaleArgs a;
-        a.src = in; a.dst = ow != W ? mid : out; a.first = tv.first; a.w = tv.w; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
-        const unsigned long long blocks = (unsigned long long)W * (unsigned long long)os_v_tiles(oh);
-        if (blocks * OS_V_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the image has too many columns for one launch");
-        hipLaunchKernelGGL(output_scale_v_kernel, dim3((unsigned)blocks), dim3(OS_V_THREADS), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-        in = a.dst;
-    }
-    if (ow != W) {
-        ScaleArgs a;
-        a.src = in; a.dst = out; a.first = tu.first; a.w = tu.w; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
-        const unsigned long long blocks = (unsigned long long)ow * (unsigned long long)os_u_chunks(oh * 3);
-        if (blocks * OS_U_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the output has too many columns for one launch");
-        hipLaunchKernelGGL(output_scale_u_kernel, dim3((unsigned)blocks), dim3(OS_U_THREADS), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    return DE_OK;
-}
-// Behind the display on the context stream: d_image -> d_os_out.
-int run_output_scale(de_ctx* c) {
-    const int W = c->W, H = c->H, ow = c->os.width, oh = c->os.height;
-    int rc = DE_OK;
-    if (oh != H) { rc = os_table_ensure(c->stream, c->os_tab[0], H, oh, c->os.filter); if (rc) return rc; }
-    if (ow != W) { rc = os_table_ensure(c->stream, c->os_tab[1], W, ow, c->os.filter); if (rc) return rc; }
-    if (oh != H && ow != W) { rc = os_device_ensure((void**)&c->d_os_mid, &c->os_mid_bytes, (size_t)W * (size_t)oh * 3 * sizeof(float)); if (rc) return rc; }
-    rc = os_device_ensure((void**)&c->d_os_out, &c->os_out_bytes, (size_t)ow * (size_t)oh * 3 * sizeof(float));
-    if (rc) return rc;
-    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], c->d_os_mid, c->d_os_out);
-}
-}  // namespace
-
 int de_render_to_image(de_ctx* c, const float** device_image) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
-    if (!c->luts_set) return fail(DE_ERR_STATE, "LUTs must be uploaded before fetch_image");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = run_setup(c);
-    if (rc) return rc;
-    if (c->dn_on) { rc = denoise_refusal(c); if (rc) return rc; }
-    if (c->ho.on) { rc = hdr_output_refusal(c); if (rc) return rc; }
-    rc = join_slots(c);
-    if (rc) return rc;
-    touched_hdr(c);              // the next accumulate_kernel must not overwrite what this reads
-    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }       // the filter reads S1 and S2: before ev_main below
     DisplayArgs d;
-    d.fc = c->d_fc; d.hdr = c->display_src ? c->display_src : c->d_hdr; d.image = c->d_image;
-    d.crf.data = c->d_crf; d.crf.w = 1024; d.crf.h = c->n_crf;
-    d.W = c->W; d.H = c->H; d.samples = c->current_spp; d.clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) ? 1 : 0;
-    d.tile_spp = c->d_tile_spp;
-    if (c->dn_on) { d.hdr = c->d_dn_out; d.samples = 1; }          // the filtered MEAN through the unchanged transform: x / 1.0f == x
-    bool per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
-    if (c->hs_on) { rc = run_history(c, d, per_tile); if (rc) return rc; }      // ahead of the meter and the bloom: they see the stabilised image
-    if (c->ae_on) { rc = run_meter(c, d, per_tile); if (rc) return rc; d.fc = c->d_fc_ae; }      // the same transform over the metered exposure: a second FrameConsts, written on the device
-    if (c->bl_on) { rc = run_bloom(c, d, per_tile); if (rc) return rc; }      // after the meter (the scene is metered, not the lens): the composited mean through the unchanged transform
-    if (c->lx_on) { rc = run_local_exposure(c, d, per_tile); if (rc) return rc; }      // last: the scene is metered, the lens glares, the print is dodged; the anchor is d.fc's exposure
-    const dim3 grid((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32));
+    bool per_tile;
+    int rc = display_chain(c, STOP_IMAGE, &d, &per_tile);
+    if (rc) return rc;
+    const dim3 grid = tiles32(c);
     if (c->ho.on) {              // the HDR display output: the same launch over the same arguments, the settings' constants by value
         if (per_tile) hipLaunchKernelGGL(hdr_display_kernel<true>, grid, dim3(256), 0, c->stream, d, c->ho_consts);
         else hipLaunchKernelGGL(hdr_display_kernel<false>, grid, dim3(256), 0, c->stream, d, c->ho_consts);
@@ -892,9 +507,7 @@ int de_fetch_hdr(de_ctx* c, float* out) {
     HIP_TRY(hipSetDevice(c->device));
     { int rc = join_slots(c); if (rc) return rc; }
     touched_hdr(c);
-    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, c->display_src ? c->display_src : c->d_hdr, c->d_scratch, c->W, c->H);
-    HIP_TRY(hipGetLastError());
-    return copy_out(c, out, c->d_scratch);
+    return fetch_transposed(c, c->display_src ? c->display_src : c->d_hdr, out);
 }
 
 int de_upload_hdr(de_ctx* c, const float* hdr, int spp) {
@@ -903,9 +516,7 @@ int de_upload_hdr(de_ctx* c, const float* hdr, int spp) {
     HIP_TRY(hipSetDevice(c->device));
     size_t npx = (size_t)c->W * c->H;
     std::vector<float> t(npx * 3);
-    for (int i = 0; i < c->W; ++i)
-        for (int j = 0; j < c->H; ++j)
-            for (int ch = 0; ch < 3; ++ch) t[((size_t)j * c->W + i) * 3 + ch] = hdr[((size_t)i * c->H + j) * 3 + ch];
+    to_device_layout(hdr, t.data(), c->W, c->H, 3);
     { int rc = join_slots(c); if (rc) return rc; }
     touched_hdr(c);
     HIP_TRY(hipMemcpyAsync(c->d_hdr, t.data(), npx * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1011,9 +622,7 @@ int de_debug_adaptive_moments(de_ctx* c, float* out) {
     HIP_TRY(hipSetDevice(c->device));
     { int rc = join_slots(c); if (rc) return rc; }
     touched_hdr(c);
-    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, c->d_s2, c->d_scratch, c->W, c->H);
-    HIP_TRY(hipGetLastError());
-    return copy_out(c, out, c->d_scratch);
+    return fetch_transposed(c, c->d_s2, out);
 }
 
 int de_hdr_device_ptr(de_ctx* c, void** ptr, uint64_t* n_floats) {
@@ -1250,18 +859,15 @@ int de_debug_samples(de_ctx* c, uint64_t seed, int sample_index, float* out) {
 int de_debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n) {
     if (!c || !a || !out || fn < 0 || fn > 31) return fail(DE_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(c->device));
-    struct Bufs {   // freed on every exit path
-        float *da = nullptr, *db = nullptr, *dout = nullptr;
-        ~Bufs() { if (da) hipFree(da); if (db) hipFree(db); if (dout) hipFree(dout); }
-    } m;
-    HIP_TRY(hipMalloc(&m.da, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&m.dout, n * sizeof(float)));
-    if (b) HIP_TRY(hipMalloc(&m.db, n * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(m.da, a, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (b) HIP_TRY(hipMemcpyAsync(m.db, b, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, m.da, m.db, m.dout, (size_t)n);
+    DeviceBufs<3> m;      // a, b (null without one), out
+    HIP_TRY(hipMalloc(&m.p[0], n * sizeof(float)));
+    HIP_TRY(hipMalloc(&m.p[2], n * sizeof(float)));
+    if (b) HIP_TRY(hipMalloc(&m.p[1], n * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(m.p[0], a, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (b) HIP_TRY(hipMemcpyAsync(m.p[1], b, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m.p[0], (const float*)m.p[1], (float*)m.p[2], (size_t)n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, m.dout, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out, m.p[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DE_OK;
 }
@@ -1301,19 +907,11 @@ int de_get_denoise(de_ctx* c, de_denoise* out) {
 }
 int de_fetch_denoised_hdr(de_ctx* c, float* out) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (!c->dn_on) return fail(DE_ERR_STATE, "the denoiser is off (de_set_denoise)");
-    { int rc = denoise_refusal(c); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = run_setup(c);
+    DisplayArgs d;
+    bool per_tile;
+    int rc = display_chain(c, STOP_DENOISE, &d, &per_tile);
     if (rc) return rc;
-    rc = join_slots(c);
-    if (rc) return rc;
-    touched_hdr(c);
-    rc = run_denoise(c);
-    if (rc) return rc;
-    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, c->d_dn_out, c->d_scratch, c->W, c->H);
-    HIP_TRY(hipGetLastError());
-    return copy_out(c, out, c->d_scratch);
+    return fetch_transposed(c, d.hdr, out);
 }
 int de_fetch_guides(de_ctx* c, float* out) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
@@ -1329,13 +927,13 @@ int de_fetch_guides(de_ctx* c, float* out) {
     HIP_TRY(hipMemcpyAsync(at.data(), c->d_dn_at, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(dist.data(), c->d_dn_dist, npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < c->W; ++i)
-        for (int j = 0; j < c->H; ++j) {
-            const size_t p = (size_t)j * c->W + i;
-            float* o = out + ((size_t)i * c->H + j) * 9;
-            o[0] = nc[p].w; o[1] = dist[p]; o[2] = nc[p].x; o[3] = nc[p].y; o[4] = nc[p].z;
-            o[5] = at[p].x; o[6] = at[p].y; o[7] = at[p].z; o[8] = at[p].w;
-        }
+    std::vector<float> g(npx * 9);      // the nine guides of a pixel side by side, still [H][W]
+    for (size_t p = 0; p < npx; ++p) {
+        float* o = &g[p * 9];
+        o[0] = nc[p].w; o[1] = dist[p]; o[2] = nc[p].x; o[3] = nc[p].y; o[4] = nc[p].z;
+        o[5] = at[p].x; o[6] = at[p].y; o[7] = at[p].z; o[8] = at[p].w;
+    }
+    to_host_layout(g.data(), out, c->W, c->H, 9);
     return DE_OK;
 }
 int de_debug_denoise(de_ctx* c, const float* mean, const float* var, const float* guides, int levels, float sigma_l, float* out) {
@@ -1347,17 +945,18 @@ int de_debug_denoise(de_ctx* c, const float* mean, const float* var, const float
     if (rc) return rc;
     const size_t npx = (size_t)c->W * c->H;
     std::vector<float4> col(npx), nc(npx), at(npx);
-    std::vector<float> dist(npx);
-    for (int i = 0; i < c->W; ++i)
-        for (int j = 0; j < c->H; ++j) {
-            const size_t p = (size_t)j * c->W + i, h = (size_t)i * c->H + j;
-            const float* m = mean + h * 3;
-            const float* g = guides + h * 9;
-            col[p] = make_float4(m[0], m[1], m[2], var[h]);
-            nc[p] = make_float4(g[2], g[3], g[4], g[0]);
-            at[p] = make_float4(g[5], g[6], g[7], g[8]);
-            dist[p] = g[1];
-        }
+    std::vector<float> dist(npx), m3(npx * 3), v1(npx), g9(npx * 9);
+    to_device_layout(mean, m3.data(), c->W, c->H, 3);
+    to_device_layout(var, v1.data(), c->W, c->H, 1);
+    to_device_layout(guides, g9.data(), c->W, c->H, 9);
+    for (size_t p = 0; p < npx; ++p) {
+        const float* m = &m3[p * 3];
+        const float* g = &g9[p * 9];
+        col[p] = make_float4(m[0], m[1], m[2], v1[p]);
+        nc[p] = make_float4(g[2], g[3], g[4], g[0]);
+        at[p] = make_float4(g[5], g[6], g[7], g[8]);
+        dist[p] = g[1];
+    }
     HIP_TRY(hipMemcpyAsync(c->d_dn_buf[1], col.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_dn_nc, nc.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_dn_at, at.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
@@ -1369,12 +968,7 @@ int de_debug_denoise(de_ctx* c, const float* mean, const float* var, const float
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(col.data(), res, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < c->W; ++i)
-        for (int j = 0; j < c->H; ++j) {
-            const float4 v = col[(size_t)j * c->W + i];
-            float* o = out + ((size_t)i * c->H + j) * 4;
-            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-        }
+    to_host_layout(reinterpret_cast<const float*>(col.data()), out, c->W, c->H, 4);
     return DE_OK;
 }
 
@@ -1399,12 +993,7 @@ int de_set_auto_exposure(de_ctx* c, const de_auto_exposure* s) {
     c->ae_on = true; c->ae_displayed = false;
     return DE_OK;
 }
-int de_get_auto_exposure(de_ctx* c, de_auto_exposure* out) {
-    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (c->ae_on) *out = c->ae; else memset(out, 0, sizeof(*out));
-    out->struct_bytes = (uint32_t)sizeof(de_auto_exposure);
-    return DE_OK;
-}
+int de_get_auto_exposure(de_ctx* c, de_auto_exposure* out) { return get_settings(c, &de_ctx::ae_on, &de_ctx::ae, out); }
 int de_get_metering(de_ctx* c, de_metering* out) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
     if (out->struct_bytes != (uint32_t)sizeof(de_metering)) return fail(DE_ERR_INVALID, "de_metering.struct_bytes does not match this library's struct");
@@ -1436,32 +1025,14 @@ int de_set_bloom(de_ctx* c, const de_bloom* s) {
     c->bl_on = true;
     return DE_OK;
 }
-int de_get_bloom(de_ctx* c, de_bloom* out) {
-    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (c->bl_on) *out = c->bl; else memset(out, 0, sizeof(*out));
-    out->struct_bytes = (uint32_t)sizeof(de_bloom);
-    return DE_OK;
-}
+int de_get_bloom(de_ctx* c, de_bloom* out) { return get_settings(c, &de_ctx::bl_on, &de_ctx::bl, out); }
 int de_fetch_bloom_hdr(de_ctx* c, float* out) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (!c->bl_on) return fail(DE_ERR_STATE, "bloom is off (de_set_bloom)");
-    if (c->dn_on) { int rc = denoise_refusal(c); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = (c->dn_on || c->hs_on) ? run_setup(c) : DE_OK;
-    if (rc) return rc;
-    rc = join_slots(c);
-    if (rc) return rc;
-    touched_hdr(c);
-    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }
     DisplayArgs d;
     bool per_tile;
-    display_source(c, d, per_tile);
-    if (c->hs_on) { rc = run_history(c, d, per_tile); if (rc) return rc; }      // as the display does: the bloom sees the stabilised image
-    rc = run_bloom(c, d, per_tile);
+    int rc = display_chain(c, STOP_BLOOM, &d, &per_tile);
     if (rc) return rc;
-    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, (const float*)c->d_bl_out, c->d_scratch, c->W, c->H);
-    HIP_TRY(hipGetLastError());
-    return copy_out(c, out, c->d_scratch);
+    return fetch_transposed(c, d.hdr, out);
 }
 
 /* ---- history reprojection: include/digital_earth_history.h */
@@ -1478,41 +1049,19 @@ int de_set_history(de_ctx* c, const de_history* s) {
     hs_drop(c);      // every call drops the history
     return DE_OK;
 }
-int de_get_history(de_ctx* c, de_history* out) {
-    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (c->hs_on) *out = c->hs; else memset(out, 0, sizeof(*out));
-    out->struct_bytes = (uint32_t)sizeof(de_history);
-    return DE_OK;
-}
+int de_get_history(de_ctx* c, de_history* out) { return get_settings(c, &de_ctx::hs_on, &de_ctx::hs, out); }
 int de_fetch_history_hdr(de_ctx* c, float* out) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (!c->hs_on) return fail(DE_ERR_STATE, "history reprojection is off (de_set_history)");
-    for (int i = 0; i < DE_TEX_COUNT; ++i)
-        if (!c->tex[i].set) return fail(DE_ERR_STATE, "history reprojection takes its distances from the maps: all 7 must be uploaded or generated first");
-    if (!c->luts_set) return fail(DE_ERR_STATE, "LUTs must be uploaded before fetch_history_hdr");
-    if (c->dn_on) { int rc = denoise_refusal(c); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = run_setup(c);
-    if (rc) return rc;
-    rc = join_slots(c);
-    if (rc) return rc;
-    touched_hdr(c);
-    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }
     DisplayArgs d;
     bool per_tile;
-    display_source(c, d, per_tile);
-    rc = run_history(c, d, per_tile);
+    int rc = display_chain(c, STOP_HISTORY, &d, &per_tile);
     if (rc) return rc;
+    // the candidate the blend just wrote: the mean the display reads and its weight in samples
     const size_t npx = (size_t)c->W * c->H;
     std::vector<float4> px(npx);
     HIP_TRY(hipMemcpyAsync(px.data(), c->d_hs_c[c->hs_cur ^ 1], npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < c->W; ++i)
-        for (int j = 0; j < c->H; ++j) {
-            const float4 v = px[(size_t)j * c->W + i];
-            float* o = out + ((size_t)i * c->H + j) * 4;
-            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-        }
+    to_host_layout(reinterpret_cast<const float*>(px.data()), out, c->W, c->H, 4);
     return frame_status(c);
 }
 /* include/digital_earth_debug.h: the blend on host-given arrays.  Buffers of its own; the context's history is not touched. */
@@ -1523,24 +1072,20 @@ int de_debug_history(de_ctx* c, const float* mean, const int32_t* n, const float
     HIP_TRY(hipSetDevice(c->device));
     const int W = c->W, H = c->H;
     const size_t npx = (size_t)W * H;
-    struct Bufs {   // freed on every exit path
-        void* p[10] = {};
-        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
-    } b;
+    DeviceBufs<10> b;
     const size_t bytes[10] = {npx * 3 * sizeof(float), npx * sizeof(int32_t), npx * sizeof(float), npx * sizeof(float4), npx * sizeof(float),
                               sizeof(FrameConsts), 2 * sizeof(HistoryCam), npx * 3 * sizeof(float), npx * sizeof(float4), npx * sizeof(float)};
     for (int k = 0; k < 10; ++k) HIP_TRY(hipMalloc(&b.p[k], bytes[k]));
-    // host layout (W, H, k) -> device layout [H][W][k]
     std::vector<float> m(npx * 3), t(npx), hd(npx);
     std::vector<int32_t> nn(npx);
     std::vector<float4> hcol(npx);
-    for (int i = 0; i < W; ++i)
-        for (int j = 0; j < H; ++j) {
-            const size_t p = (size_t)j * W + i, h = (size_t)i * H + j;
-            for (int ch = 0; ch < 3; ++ch) m[p * 3 + ch] = mean[h * 3 + ch];
-            nn[p] = n[h]; t[p] = dist[h];
-            if (hist_c) { hcol[p] = make_float4(hist_c[h * 4], hist_c[h * 4 + 1], hist_c[h * 4 + 2], hist_c[h * 4 + 3]); hd[p] = hist_d[h]; }
-        }
+    to_device_layout(mean, m.data(), W, H, 3);
+    to_device_layout(n, nn.data(), W, H, 1);
+    to_device_layout(dist, t.data(), W, H, 1);
+    if (hist_c) {
+        to_device_layout(hist_c, reinterpret_cast<float*>(hcol.data()), W, H, 4);
+        to_device_layout(hist_d, hd.data(), W, H, 1);
+    }
     HIP_TRY(hipMemcpyAsync(b.p[0], m.data(), bytes[0], hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(b.p[1], nn.data(), bytes[1], hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(b.p[2], t.data(), bytes[2], hipMemcpyHostToDevice, c->stream));
@@ -1556,27 +1101,24 @@ int de_debug_history(de_ctx* c, const float* mean, const int32_t* n, const float
         HIP_TRY(hipGetLastError());
     }
     HistoryArgs a;
-    a.hdr = (const float*)b.p[0]; a.tile_spp = nullptr; a.samples = 1;
+    a.s.hdr = (const float*)b.p[0]; a.s.tile_spp = nullptr; a.s.samples = 1; a.s.W = W; a.s.H = H;
     a.n_tile = nullptr; a.n_pixel = (const int32_t*)b.p[1]; a.n_frame = 0;
     a.dist = (const float*)b.p[2]; a.fc = (const FrameConsts*)b.p[5];
     a.hist_c = hist_c ? (const float4*)b.p[3] : nullptr; a.hist_d = (const float*)b.p[4]; a.hist_cam = cams;
     a.out = (float*)b.p[7]; a.cand_c = (float4*)b.p[8]; a.cand_d = (float*)b.p[9]; a.cand_cam = cams + 1;
-    a.W = W; a.H = H; a.max_history = max_history; a.depth_tolerance = depth_tolerance;
+    a.max_history = max_history; a.depth_tolerance = depth_tolerance;
     hipLaunchKernelGGL(history_blend_kernel, dn_grid(c), dim3(256), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(hcol.data(), b.p[8], bytes[8], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(m.data(), b.p[7], bytes[7], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < W; ++i)
-        for (int j = 0; j < H; ++j) {
-            const size_t p = (size_t)j * W + i;
-            const float4 v = hcol[p];
-            // the mean the display would read and the candidate's colour are the same three stores
-            if (memcmp(&m[p * 3], &v.x, sizeof(float)) != 0 || memcmp(&m[p * 3 + 1], &v.y, sizeof(float)) != 0 || memcmp(&m[p * 3 + 2], &v.z, sizeof(float)) != 0)
-                return fail(DE_ERR_HIP, "history_blend_kernel: the display's mean and the candidate differ");
-            float* o = out + ((size_t)i * H + j) * 4;
-            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-        }
+    for (size_t p = 0; p < npx; ++p) {
+        const float4 v = hcol[p];
+        // the mean the display would read and the candidate's colour are the same three stores
+        if (memcmp(&m[p * 3], &v.x, sizeof(float)) != 0 || memcmp(&m[p * 3 + 1], &v.y, sizeof(float)) != 0 || memcmp(&m[p * 3 + 2], &v.z, sizeof(float)) != 0)
+            return fail(DE_ERR_HIP, "history_blend_kernel: the display's mean and the candidate differ");
+    }
+    to_host_layout(reinterpret_cast<const float*>(hcol.data()), out, W, H, 4);
     return DE_OK;
 }
 
@@ -1594,37 +1136,14 @@ int de_set_local_exposure(de_ctx* c, const de_local_exposure* s) {
     c->lx_on = true;
     return DE_OK;
 }
-int de_get_local_exposure(de_ctx* c, de_local_exposure* out) {
-    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (c->lx_on) *out = c->lx; else memset(out, 0, sizeof(*out));
-    out->struct_bytes = (uint32_t)sizeof(de_local_exposure);
-    return DE_OK;
-}
+int de_get_local_exposure(de_ctx* c, de_local_exposure* out) { return get_settings(c, &de_ctx::lx_on, &de_ctx::lx, out); }
 int de_fetch_local_exposure_hdr(de_ctx* c, float* out) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
-    if (!c->lx_on) return fail(DE_ERR_STATE, "local exposure is off (de_set_local_exposure)");
-    if (!c->luts_set) return fail(DE_ERR_STATE, "LUTs must be uploaded before fetch_local_exposure_hdr");
-    if (c->dn_on) { int rc = denoise_refusal(c); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = run_setup(c);      // the anchor is read from the frame constants
-    if (rc) return rc;
-    rc = join_slots(c);
-    if (rc) return rc;
-    touched_hdr(c);
-    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }
     DisplayArgs d;
     bool per_tile;
-    display_source(c, d, per_tile);
-    d.fc = c->d_fc;
-    // as the display does
-    if (c->hs_on) { rc = run_history(c, d, per_tile); if (rc) return rc; }
-    if (c->ae_on) { rc = run_meter(c, d, per_tile); if (rc) return rc; d.fc = c->d_fc_ae; }
-    if (c->bl_on) { rc = run_bloom(c, d, per_tile); if (rc) return rc; }
-    rc = run_local_exposure(c, d, per_tile);
+    int rc = display_chain(c, STOP_LOCAL_EXPOSURE, &d, &per_tile);
     if (rc) return rc;
-    hipLaunchKernelGGL(hdr_transpose_kernel, dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)), dim3(256), 0, c->stream, (const float*)c->d_lx_out, c->d_scratch, c->W, c->H);
-    HIP_TRY(hipGetLastError());
-    return copy_out(c, out, c->d_scratch);
+    return fetch_transposed(c, d.hdr, out);
 }
 /* The stage once on a host-given mean.  A source and a FrameConsts of its own; the pyramid and the output are the context's (nothing between displays
  * lives in them). */
@@ -1635,16 +1154,11 @@ int de_debug_local_exposure(de_ctx* c, const float* mean, float exposure_scale, 
     { int rc = lx_alloc(c); if (rc) return rc; }
     const int W = c->W, H = c->H;
     const size_t npx = (size_t)W * H;
-    struct Bufs {   // freed on every exit path
-        void* p[2] = {};
-        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
-    } b;
+    DeviceBufs<2> b;
     HIP_TRY(hipMalloc(&b.p[0], npx * 3 * sizeof(float)));
     HIP_TRY(hipMalloc(&b.p[1], sizeof(FrameConsts)));
-    std::vector<float> m(npx * 3);      // host layout (W, H, 3) -> device layout [H][W][3]
-    for (int i = 0; i < W; ++i)
-        for (int j = 0; j < H; ++j)
-            for (int ch = 0; ch < 3; ++ch) m[((size_t)j * W + i) * 3 + ch] = mean[((size_t)i * H + j) * 3 + ch];
+    std::vector<float> m(npx * 3);
+    to_device_layout(mean, m.data(), W, H, 3);
     FrameConsts fc;
     memset(&fc, 0, sizeof(fc));
     fc.exposure_scale = exposure_scale;      // the only field the stage reads
@@ -1658,37 +1172,11 @@ int de_debug_local_exposure(de_ctx* c, const float* mean, float exposure_scale, 
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(m.data(), c->d_lx_out, npx * 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < W; ++i)
-        for (int j = 0; j < H; ++j)
-            for (int ch = 0; ch < 3; ++ch) out[((size_t)i * H + j) * 3 + ch] = m[((size_t)j * W + i) * 3 + ch];
+    to_host_layout(m.data(), out, W, H, 3);
     return DE_OK;
 }
 
 /* ---- 8-bit pixel output: include/digital_earth_pixels.h (pixels_kernels.hip) */
-namespace {
-size_t px_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (size_t)c->px.channels; }      // of the output size (include/digital_earth_output_scale.h): W x H while that stage is off
-size_t px_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 4; }      // every buffer holds either format: de_set_pixels frees nothing
-int px_settings_check(const de_pixels* s) {
-    if (s->struct_bytes != (uint32_t)sizeof(de_pixels)) return fail(DE_ERR_INVALID, "de_pixels.struct_bytes does not match this library's struct");
-    if (s->channels != 3 && s->channels != 4) return fail(DE_ERR_INVALID, "de_pixels.channels must be 3 or 4");
-    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_pixels.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
-    return DE_OK;
-}
-int px_host_alloc(uint8_t** p, size_t* have, size_t bytes) {      // one that is too small for a new output size is replaced: no copy into it is in flight
-    if (*p && *have < bytes) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
-    if (!*p) {
-        if (hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the pixel staging buffers"); }
-        *have = bytes;
-    }
-    return DE_OK;
-}
-void px_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_pixels& s, uint32_t phase) {
-    PixelsArgs a;
-    a.image = image; a.out = out; a.W = W; a.H = H; a.channels = s.channels; a.mode = s.mode; a.seed = s.seed; a.phase = phase;
-    hipLaunchKernelGGL(pixels_pack_kernel, dim3((unsigned)((W + PX_TILE - 1) / PX_TILE), (unsigned)((H + PX_TILE - 1) / PX_TILE)), dim3(256), 0, stream, a);
-}
-}  // namespace
-
 int de_set_pixels(de_ctx* c, const de_pixels* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     { int rc = px_settings_check(s); if (rc) return rc; }
@@ -1769,10 +1257,7 @@ int de_debug_pixels(de_ctx* c, const float* image, int W, int H, const de_pixels
         return fail(DE_ERR_INVALID, "bad arguments (W a multiple of 16, H a multiple of 8, as de_create asks)");
     { int rc = px_settings_check(s); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
-    struct Bufs {   // freed on every exit path
-        void* p[2] = {};
-        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
-    } b;
+    DeviceBufs<2> b;
     const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), out_bytes = (size_t)W * H * (size_t)s->channels;
     HIP_TRY(hipMalloc(&b.p[0], in_bytes));
     HIP_TRY(hipMalloc(&b.p[1], out_bytes));
@@ -1784,7 +1269,7 @@ int de_debug_pixels(de_ctx* c, const float* image, int W, int H, const de_pixels
     return DE_OK;
 }
 
-/* ---- output scaling: include/digital_earth_output_scale.h (the helpers stand ahead of de_render_to_image) */
+/* ---- output scaling: include/digital_earth_output_scale.h (output_scale_kernels.hip) */
 int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     int ow = 0, oh = 0;
@@ -1813,10 +1298,9 @@ int de_debug_output_scale(de_ctx* c, const float* image, int W, int H, const de_
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, W, H, &ow, &oh); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
-    struct Bufs {   // freed on every exit path
-        void* p[3] = {};
+    struct Bufs : DeviceBufs<3> {   // and the two axes' tables
         de_ctx::ScaleDev t[2];
-        ~Bufs() { for (void* q : p) if (q) hipFree(q); for (auto& d : t) { if (d.first) hipFree(d.first); if (d.w) hipFree(d.w); } }
+        ~Bufs() { for (auto& d : t) { if (d.first) hipFree(d.first); if (d.w) hipFree(d.w); } }
     } b;
     const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), mid_bytes = (size_t)W * oh * 3 * sizeof(float), out_bytes = (size_t)ow * oh * 3 * sizeof(float);
     HIP_TRY(hipMalloc(&b.p[0], in_bytes));
@@ -1849,19 +1333,6 @@ int de_debug_output_scale_weights(de_ctx* c, int n_src, int n_dst, int filter, i
 }
 
 /* ---- HDR display output: include/digital_earth_hdr_output.h (hdr_output_kernels.hip) */
-namespace {
-size_t hpx_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (c->ho.pixel_format == DE_HDR_PIXELS_RGB16 ? 6u : 4u); }
-size_t hpx_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 6; }      // every buffer holds either format
-int ho_settings_check(const de_hdr_output* s) {
-    if (s->struct_bytes != (uint32_t)sizeof(de_hdr_output)) return fail(DE_ERR_INVALID, "de_hdr_output.struct_bytes does not match this library's struct");
-    if (!(s->peak_nits >= 100.0f && s->peak_nits <= 10000.0f)) return fail(DE_ERR_INVALID, "de_hdr_output.peak_nits must lie in [100, 10000]");      // NaN fails both
-    if (s->gamut < DE_HDR_GAMUT_REC709 || s->gamut > DE_HDR_GAMUT_REC2020) return fail(DE_ERR_INVALID, "de_hdr_output.gamut must be DE_HDR_GAMUT_REC709, _P3D65 or _REC2020");
-    if (s->transfer < DE_HDR_TRANSFER_LINEAR || s->transfer > DE_HDR_TRANSFER_HLG) return fail(DE_ERR_INVALID, "de_hdr_output.transfer must be DE_HDR_TRANSFER_LINEAR, _PQ or _HLG");
-    if (s->pixel_format < DE_HDR_PIXELS_RGB10A2 || s->pixel_format > DE_HDR_PIXELS_RGB16) return fail(DE_ERR_INVALID, "de_hdr_output.pixel_format must be DE_HDR_PIXELS_RGB10A2 or _RGB16");
-    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_hdr_output.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
-    return DE_OK;
-}
-}  // namespace
 
 int de_set_hdr_output(de_ctx* c, const de_hdr_output* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
@@ -1918,10 +1389,7 @@ int de_debug_hdr_transform(de_ctx* c, const float* rgb, uint64_t n, const de_hdr
     HdrConsts h;
     hdr_output_consts((double)s->peak_nits, s->gamut, s->transfer, &h);
     HIP_TRY(hipSetDevice(c->device));
-    struct Bufs {   // freed on every exit path
-        void* p[2] = {};
-        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
-    } b;
+    DeviceBufs<2> b;
     const size_t bytes = (size_t)n * 3 * sizeof(float);
     HIP_TRY(hipMalloc(&b.p[0], bytes));
     HIP_TRY(hipMalloc(&b.p[1], bytes));

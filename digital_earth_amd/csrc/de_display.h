@@ -1,0 +1,493 @@
+// de_display.h — the host side of the display path: what runs on the context stream between the frame's sums and the image a caller is handed.
+//   * the small helpers every entry point of that path shares: host <-> device layouts, a transposed fetch, a settings getter, device scratch buffers;
+//   * each opt-in stage's allocation and launch sequence (denoiser, auto-exposure, bloom, history reprojection, local exposure), the stages behind the
+//     display (output scaling, 8-bit and HDR pixels) and the two refusals;
+//   * display_chain: the ONE statement of the order denoise -> history -> meter -> bloom -> local exposure -> display and of its preconditions, which
+//     de_render_to_image and the four intermediate fetches of de_api.hip run up to their own stage.
+// The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, the source every stage reads display_source.h.
+#pragma once
+#include "de_launch.h"
+#include "../../include/digital_earth_denoise.h"
+
+namespace {
+// ---- layouts.  The host's arrays are (W, H, k), u outermost (the reference's fields); the device's are [H][W][k].
+template <class T>
+void to_device_layout(const T* host, T* dev, int W, int H, int k) {
+    for (int i = 0; i < W; ++i)
+        for (int j = 0; j < H; ++j)
+            for (int ch = 0; ch < k; ++ch) dev[((size_t)j * W + i) * k + ch] = host[((size_t)i * H + j) * k + ch];
+}
+template <class T>
+void to_host_layout(const T* dev, T* host, int W, int H, int k) {
+    for (int i = 0; i < W; ++i)
+        for (int j = 0; j < H; ++j)
+            for (int ch = 0; ch < k; ++ch) host[((size_t)i * H + j) * k + ch] = dev[((size_t)j * W + i) * k + ch];
+}
+dim3 tiles16(int w, int h) { return dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)); }
+dim3 tiles32(const de_ctx* c) { return dim3((unsigned)((c->W + 31) / 32), (unsigned)((c->H + 31) / 32)); }
+// A device [H][W][3] buffer to the caller's (W, H, 3) array: transposed into d_scratch on the context stream, then copied out.  Ends in frame_status.
+int fetch_transposed(de_ctx* c, const float* d_src, float* out) {
+    hipLaunchKernelGGL(hdr_transpose_kernel, tiles32(c), dim3(256), 0, c->stream, d_src, c->d_scratch, c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    return copy_out(c, out, c->d_scratch);
+}
+// de_get_<stage>: the settings while the stage is on, zeros while it is off; struct_bytes always.
+template <class S>
+int get_settings(de_ctx* c, bool de_ctx::*on, S de_ctx::*settings, S* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (c->*on) *out = c->*settings; else memset(out, 0, sizeof(*out));
+    out->struct_bytes = (uint32_t)sizeof(S);
+    return DE_OK;
+}
+// N device buffers of a debug entry point, freed on every exit path.
+template <int N>
+struct DeviceBufs {
+    void* p[N] = {};
+    ~DeviceBufs() { for (void* q : p) if (q) hipFree(q); }
+};
+
+// ---- the source (display_source.h) of a display launch's arguments
+DisplaySrc display_src(const DisplayArgs& d, bool per_tile) {
+    DisplaySrc s;
+    s.hdr = d.hdr; s.tile_spp = per_tile ? d.tile_spp : nullptr; s.samples = d.samples; s.W = d.W; s.H = d.H;
+    return s;
+}
+// 16-byte aligned: the kernels' float4 loads (the context's own buffers always are; a bound buffer or a display source may not be)
+bool src_aligned(const DisplaySrc& s) { return (reinterpret_cast<uintptr_t>(s.hdr) & 15u) == 0u; }
+
+// ---- the denoiser (include/digital_earth_denoise.h, denoise_kernels.hip)
+int denoise_refusal(de_ctx* c) {
+    if (c->tiles_world > 1) return fail(DE_ERR_STATE, "the denoiser filters whole frames: not under a tile partition");
+    if (c->sample_world > 1) return fail(DE_ERR_STATE, "the denoiser filters whole frames: not under a sample partition");
+    if (c->display_src) return fail(DE_ERR_STATE, "the denoiser filters this context's own frame: not with a display source or after de_reduce_progressive");
+    return DE_OK;
+}
+// ---- the HDR display output (include/digital_earth_hdr_output.h, hdr_output_kernels.hip)
+int hdr_output_refusal(de_ctx* c) {
+    if (c->p.flags & DE_FLAG_AGX) return fail(DE_ERR_STATE, "the HDR display output runs OpenDRT: not with DE_FLAG_AGX, an SDR transform");
+    return DE_OK;
+}
+// the guides alone: what guide_kernel writes (the history reprojection reads their distance without the denoiser's other buffers)
+int dn_alloc_guides(de_ctx* c) {
+    const size_t npx = (size_t)c->W * c->H;
+    if (!c->d_dn_nc) HIP_TRY(hipMalloc(&c->d_dn_nc, npx * sizeof(float4)));
+    if (!c->d_dn_at) HIP_TRY(hipMalloc(&c->d_dn_at, npx * sizeof(float4)));
+    if (!c->d_dn_dist) HIP_TRY(hipMalloc(&c->d_dn_dist, npx * sizeof(float)));
+    return DE_OK;
+}
+int dn_alloc(de_ctx* c) {
+    const size_t npx = (size_t)c->W * c->H;
+    { int rc = dn_alloc_guides(c); if (rc) return rc; }
+    for (int k = 0; k < 2; ++k) if (!c->d_dn_buf[k]) HIP_TRY(hipMalloc(&c->d_dn_buf[k], npx * sizeof(float4)));
+    if (!c->d_dn_out) HIP_TRY(hipMalloc(&c->d_dn_out, npx * 3 * sizeof(float)));
+    return DE_OK;
+}
+DenoiseGuides dn_guides(de_ctx* c) { DenoiseGuides g; g.nc = c->d_dn_nc; g.at = c->d_dn_at; g.dist = c->d_dn_dist; return g; }
+dim3 dn_grid(de_ctx* c) { return tiles16(c->W, c->H); }
+// The guides of the current camera, maps and address mode: once per frame (de_reset, a map or a camera change clears them).
+int dn_ensure_guides(de_ctx* c) {
+    int rc = dn_alloc_guides(c);
+    if (rc) return rc;
+    if (c->dn_guides_valid) return DE_OK;
+    RenderArgs a;
+    rc = fill_render_args(c, &a);          // packs the maps and rebuilds the frame constants if needed
+    if (rc) return rc;
+    if (c->p.flags & DE_FLAG_CLAMP_SAMPLER) hipLaunchKernelGGL(guide_kernel<true>, dn_grid(c), dim3(256), 0, c->stream, a, dn_guides(c));
+    else hipLaunchKernelGGL(guide_kernel<false>, dn_grid(c), dim3(256), 0, c->stream, a, dn_guides(c));
+    HIP_TRY(hipGetLastError());
+    c->dn_guides_valid = true;
+    return DE_OK;
+}
+// The a-trous levels over d_dn_buf[1] (colour, variance); the last one also writes the filtered mean to d_dn_out.  Returns the buffer that holds the result.
+int dn_levels(de_ctx* c, int levels, float sigma_l, float4** result) {
+    AtrousArgs t;
+    t.g = dn_guides(c); t.W = c->W; t.H = c->H; t.sigma_l = sigma_l;
+    int cur = 1;
+    for (int l = 0; l < levels; ++l) {
+        t.in = c->d_dn_buf[cur]; t.out = c->d_dn_buf[cur ^ 1]; t.step = 1 << l;
+        t.out3 = l == levels - 1 ? c->d_dn_out : nullptr;
+        hipLaunchKernelGGL(atrous_kernel, dn_grid(c), dim3(256), 0, c->stream, t);
+        HIP_TRY(hipGetLastError());
+        cur ^= 1;
+    }
+    *result = c->d_dn_buf[cur];
+    return DE_OK;
+}
+// The frame's filtered mean into d_dn_out, on the context stream (the caller has joined the launch slots and marked the HDR buffer as read).
+// Variance source: the per-pixel estimate from S2 when S2 is complete and the pixel has n >= 4 samples, else the 7x7 spatial estimate.
+int run_denoise(de_ctx* c) {
+    int rc = dn_alloc(c);
+    if (rc) return rc;
+    rc = dn_ensure_guides(c);
+    if (rc) return rc;
+    DenoisePrepArgs pa;
+    const bool adaptive = c->frame_kind == DE_FRAME_ADAPTIVE;
+    pa.s1 = c->display_src ? c->display_src : c->d_hdr;
+    pa.s2 = (c->dn_s2_complete || adaptive) ? c->d_s2 : nullptr;
+    pa.tile_spp = adaptive ? c->d_tile_spp : nullptr;
+    pa.spp = c->current_spp; pa.W = c->W; pa.H = c->H; pa.out = c->d_dn_buf[0];
+    hipLaunchKernelGGL(prep_mean_kernel, dn_grid(c), dim3(256), 0, c->stream, pa);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prep_spatial_kernel, dn_grid(c), dim3(256), 0, c->stream, (const float4*)c->d_dn_buf[0], c->d_dn_buf[1], c->W, c->H);
+    HIP_TRY(hipGetLastError());
+    float4* res = nullptr;
+    rc = dn_levels(c, c->dn_levels, c->dn_sigma_l, &res);
+    if (rc) return rc;
+    c->dn_out_valid = true;
+    return DE_OK;
+}
+// ---- auto-exposure (include/digital_earth_exposure.h, exposure_kernels.hip)
+int ae_alloc(de_ctx* c) {
+    if (!c->d_ae_partial) HIP_TRY(hipMalloc(&c->d_ae_partial, (size_t)AE_MAX_WG * AE_ROW * sizeof(uint32_t)));
+    if (!c->d_ae_state) HIP_TRY(hipMalloc(&c->d_ae_state, sizeof(MeterState)));
+    if (!c->d_fc_ae) HIP_TRY(hipMalloc(&c->d_fc_ae, sizeof(FrameConsts)));
+    if (!c->d_ae_result) HIP_TRY(hipMalloc(&c->d_ae_result, sizeof(MeterResult)));
+    if (!c->d_ae_centre) {
+        // log2 of the bins' centres: bin k = octave (k >> 3) - 24, sub-bin k & 7 of 8 linear ones; uploaded once, so that the device computes no logarithm
+        double centre[AE_BINS];
+        for (int k = 0; k < AE_BINS; ++k) centre[k] = (double)((k >> 3) - 24) + log2(1.0 + ((double)(k & 7) + 0.5) / 8.0);
+        HIP_TRY(hipMalloc(&c->d_ae_centre, sizeof(centre)));
+        HIP_TRY(hipMemcpyAsync(c->d_ae_centre, centre, sizeof(centre), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));      // the table is a local: once per context, when the feature is first turned on, never in a display
+    }
+    return DE_OK;
+}
+// The two metering kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).
+int run_meter(de_ctx* c, const DisplayArgs& d, bool per_tile) {
+    const de_auto_exposure& s = c->ae;
+    const bool whole = !(s.region[0] | s.region[1] | s.region[2] | s.region[3]);
+    MeterArgs m;
+    m.s = display_src(d, per_tile);
+    m.x0 = whole ? 0 : s.region[0]; m.y0 = whole ? 0 : s.region[1]; m.x1 = whole ? c->W : s.region[2]; m.y1 = whole ? c->H : s.region[3];
+    m.gx0 = m.x0 >> 2; m.gw = ((m.x1 + 3) >> 2) - m.gx0;
+    const unsigned long long items = (unsigned long long)m.gw * (unsigned long long)(m.y1 - m.y0);      // at most the region's pixels
+    if ((unsigned long long)(m.x1 - m.x0) * (unsigned long long)(m.y1 - m.y0) >= (1ull << 31))
+        return fail(DE_ERR_INVALID, "the metering region must hold fewer than 2^31 pixels (the counts and the item index are 32-bit)");
+    m.n_items = (uint32_t)items;
+    m.partial = c->d_ae_partial;
+    const unsigned n_wg = (unsigned)std::min<unsigned long long>((items + 255ull) / 256ull, (unsigned long long)AE_MAX_WG);
+    if (src_aligned(m.s)) hipLaunchKernelGGL(meter_hist_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, m);
+    else hipLaunchKernelGGL(meter_hist_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, m);
+    HIP_TRY(hipGetLastError());
+    MeterSolveArgs v;
+    v.partial = c->d_ae_partial; v.n_rows = (int)n_wg;
+    v.low = s.low_fraction; v.high = s.high_fraction; v.adapt = s.adapt; v.compensation = s.compensation; v.ev_min = s.ev_min; v.ev_max = s.ev_max;
+    v.manual = c->p.exposure;
+    v.log2_key = log2((double)s.key);
+    v.centre = c->d_ae_centre; v.state = c->d_ae_state; v.fc = c->d_fc; v.fc_ae = c->d_fc_ae; v.res = c->d_ae_result;
+    hipLaunchKernelGGL(meter_solve_kernel, dim3(1), dim3(1024), 0, c->stream, v);
+    HIP_TRY(hipGetLastError());
+    c->ae_displayed = true;
+    return DE_OK;
+}
+// ---- bloom (include/digital_earth_bloom.h, bloom_kernels.hip).  d_bl_pyr holds D_l at the plan's off[l] and U_l `total` further, in float4.
+int bl_alloc(de_ctx* c) {
+    const PyramidPlan p = pyr_plan(c->W, c->H, BL_MAX_LEVELS);      // room for every setting of `levels`: the offsets of a level do not depend on it
+    if (!c->d_bl_pyr) HIP_TRY(hipMalloc(&c->d_bl_pyr, 2 * p.total * sizeof(float4)));
+    if (!c->d_bl_out) HIP_TRY(hipMalloc(&c->d_bl_out, (size_t)c->W * c->H * 3 * sizeof(float)));
+    return DE_OK;
+}
+// The bloom kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).  Afterwards `d`
+// describes the composited mean: the unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).
+int run_bloom(de_ctx* c, DisplayArgs& d, bool& per_tile) {
+    const de_bloom& b = c->bl;
+    const PyramidPlan p = pyr_plan(c->W, c->H, b.levels);
+    float4* D = c->d_bl_pyr;
+    float4* U = c->d_bl_pyr + pyr_plan(c->W, c->H, BL_MAX_LEVELS).total;
+    BloomSrc s;
+    static_cast<DisplaySrc&>(s) = display_src(d, per_tile);
+    s.threshold = b.threshold; s.knee = b.knee; s.clamp = b.clamp;
+    const bool vec = src_aligned(s);
+    if (vec) hipLaunchKernelGGL(bloom_down0_kernel<true>, tiles16(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    else hipLaunchKernelGGL(bloom_down0_kernel<false>, tiles16(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    HIP_TRY(hipGetLastError());
+    for (int l = 1; l < p.L; ++l) {
+        hipLaunchKernelGGL(bloom_down_kernel, tiles16(p.w[l + 1], p.h[l + 1]), dim3(256), 0, c->stream, (const float4*)(D + p.off[l]), p.w[l], p.h[l], D + p.off[l + 1], p.w[l + 1], p.h[l + 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    const float4* top = D + p.off[p.L];      // U_L = D_L
+    for (int l = p.L - 1; l >= 1; --l) {
+        BloomUpArgs u;
+        u.coarse = top; u.fine = D + p.off[l]; u.out = U + p.off[l];
+        u.Wc = p.w[l + 1]; u.Hc = p.h[l + 1]; u.Wf = p.w[l]; u.Hf = p.h[l];
+        u.keep = 1.0f - b.spread; u.spread = b.spread;
+        hipLaunchKernelGGL(bloom_up_kernel, tiles16(p.w[l], p.h[l]), dim3(256), 0, c->stream, u);
+        HIP_TRY(hipGetLastError());
+        top = u.out;
+    }
+    // level 0 is not blended in: the glow never holds the unblurred image
+    const unsigned n_wg = (unsigned)(((size_t)(c->W >> 2) * (size_t)c->H + 255u) / 256u);
+    if (vec) hipLaunchKernelGGL(bloom_composite_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, s, top, p.w[1], p.h[1], b.intensity, c->d_bl_out);
+    else hipLaunchKernelGGL(bloom_composite_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, s, top, p.w[1], p.h[1], b.intensity, c->d_bl_out);
+    HIP_TRY(hipGetLastError());
+    d.hdr = c->d_bl_out; d.samples = 1; per_tile = false;
+    return DE_OK;
+}
+// ---- history reprojection (include/digital_earth_history.h, history_kernels.hip)
+int hs_alloc(de_ctx* c) {
+    const size_t npx = (size_t)c->W * c->H;
+    for (int k = 0; k < 2; ++k) {
+        if (!c->d_hs_c[k]) HIP_TRY(hipMalloc(&c->d_hs_c[k], npx * sizeof(float4)));
+        if (!c->d_hs_d[k]) HIP_TRY(hipMalloc(&c->d_hs_d[k], npx * sizeof(float)));
+        if (!c->d_hs_cam[k]) HIP_TRY(hipMalloc(&c->d_hs_cam[k], sizeof(HistoryCam)));
+    }
+    if (!c->d_hs_out) HIP_TRY(hipMalloc(&c->d_hs_out, npx * 3 * sizeof(float)));
+    return DE_OK;
+}
+// All weights 0: neither the history nor a candidate written before this point is read again (host flags: the buffers need no clearing).
+void hs_drop(de_ctx* c) { c->hs_valid = false; c->hs_cand_valid = false; }
+// Does the step from de_params a to b change radiance?  Camera fields reproject; exposure, gamma, CRF, vignette and DE_FLAG_AGX are display-only.
+bool hs_radiance_changed(const de_params& a, const de_params& b) {
+    return memcmp(&a.sun_angle, &b.sun_angle, sizeof(float)) != 0 || memcmp(&a.sun_path_rot, &b.sun_path_rot, sizeof(float)) != 0 ||
+           memcmp(&a.land_height_scale, &b.land_height_scale, sizeof(float)) != 0 || memcmp(&a.fixed_wavelength, &b.fixed_wavelength, sizeof(float)) != 0 ||
+           a.topo_res_override != b.topo_res_override || ((a.flags ^ b.flags) & ~(uint32_t)DE_FLAG_AGX) != 0u;
+}
+// The blend on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).  Afterwards `d` describes
+// the blended mean: the unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).  The same launch writes the next history candidate.
+int run_history(de_ctx* c, DisplayArgs& d, bool& per_tile) {
+    int rc = hs_alloc(c);
+    if (rc) return rc;
+    rc = dn_ensure_guides(c);      // the distance of the current camera: once per frame, shared with the denoiser
+    if (rc) return rc;
+    const int cur = c->hs_cur, cand = cur ^ 1;
+    HistoryArgs a;
+    a.s = display_src(d, per_tile);
+    a.n_tile = c->frame_kind == DE_FRAME_ADAPTIVE ? c->d_tile_spp : nullptr; a.n_pixel = nullptr; a.n_frame = c->current_spp;
+    a.dist = c->d_dn_dist; a.fc = c->d_fc;
+    a.hist_c = c->hs_valid ? c->d_hs_c[cur] : nullptr; a.hist_d = c->d_hs_d[cur]; a.hist_cam = c->d_hs_cam[cur];
+    a.out = c->d_hs_out; a.cand_c = c->d_hs_c[cand]; a.cand_d = c->d_hs_d[cand]; a.cand_cam = c->d_hs_cam[cand];
+    a.max_history = c->hs.max_history; a.depth_tolerance = c->hs.depth_tolerance;
+    hipLaunchKernelGGL(history_blend_kernel, dn_grid(c), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    c->hs_cand_valid = true;
+    d.hdr = c->d_hs_out; d.samples = 1; per_tile = false;
+    return DE_OK;
+}
+// ---- local exposure (include/digital_earth_local_exposure.h, local_exposure_kernels.hip)
+int lx_alloc(de_ctx* c) {
+    const PyramidPlan p = pyr_plan(c->W, c->H, LX_MAX_LEVELS);      // room for every setting of `levels`: the offsets of a level do not depend on it
+    if (!c->d_lx_pyr) HIP_TRY(hipMalloc(&c->d_lx_pyr, p.total * sizeof(float2)));
+    if (!c->d_lx_base) HIP_TRY(hipMalloc(&c->d_lx_base, p.total * sizeof(float)));
+    if (!c->d_lx_out) HIP_TRY(hipMalloc(&c->d_lx_out, (size_t)c->W * c->H * 3 * sizeof(float)));
+    return DE_OK;
+}
+int lx_settings_check(const de_local_exposure* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_local_exposure)) return fail(DE_ERR_INVALID, "de_local_exposure.struct_bytes does not match this library's struct");
+    if (!(s->highlights >= 0.0f) || !(s->highlights <= 1.0f) || !(s->shadows >= 0.0f) || !(s->shadows <= 1.0f))
+        return fail(DE_ERR_INVALID, "local exposure settings: highlights and shadows in [0, 1]");
+    if (!(s->sigma > 0.0f) || !(s->sigma < 1e30f) || !(s->max_ev >= 0.0f) || !(s->max_ev < 1e30f) || !(s->key > 0.0f) || !(s->key < 1e30f))
+        return fail(DE_ERR_INVALID, "local exposure settings: finite sigma > 0, finite max_ev >= 0, finite key > 0");
+    if (s->levels < 1 || s->levels > LX_MAX_LEVELS) return fail(DE_ERR_INVALID, "local exposure settings: levels in 1 .. 10");
+    return DE_OK;
+}
+// The kernels on the context stream with the settings `x`, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>)
+// and with the anchor from d.fc (the metered FrameConsts while auto-exposure is on: no host round trip).  Afterwards `d` describes the dodged mean: the
+// unchanged display_kernel<false> with samples = 1 (x / 1.0f == x).
+int lx_run(de_ctx* c, const de_local_exposure& x, DisplayArgs& d, bool& per_tile) {
+    const PyramidPlan p = pyr_plan(c->W, c->H, x.levels);
+    float2* D = c->d_lx_pyr;
+    float* B = c->d_lx_base;
+    const DisplaySrc s = display_src(d, per_tile);
+    const bool vec = src_aligned(s);
+    const float inv_sigma = 1.0f / x.sigma;
+    if (vec) hipLaunchKernelGGL(lx_down0_kernel<true>, tiles16(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    else hipLaunchKernelGGL(lx_down0_kernel<false>, tiles16(p.w[1], p.h[1]), dim3(256), 0, c->stream, s, D + p.off[1], p.w[1], p.h[1]);
+    HIP_TRY(hipGetLastError());
+    for (int l = 1; l < p.L; ++l) {
+        hipLaunchKernelGGL(lx_down_kernel, tiles16(p.w[l + 1], p.h[l + 1]), dim3(256), 0, c->stream, (const float2*)(D + p.off[l]), p.w[l], p.h[l], D + p.off[l + 1], p.w[l + 1], p.h[l + 1]);
+        HIP_TRY(hipGetLastError());
+    }
+    const float* top = nullptr;      // B_L is the top level's guide: not stored
+    for (int l = p.L - 1; l >= 1; --l) {
+        LxUpArgs u;
+        u.fine = D + p.off[l]; u.coarse = D + p.off[l + 1]; u.coarse_b = top; u.out = B + p.off[l];
+        u.Wc = p.w[l + 1]; u.Hc = p.h[l + 1]; u.Wf = p.w[l]; u.Hf = p.h[l]; u.inv_sigma = inv_sigma;
+        hipLaunchKernelGGL(lx_up_kernel, dim3((unsigned)(((size_t)u.Wf * (size_t)u.Hf + 255u) / 256u)), dim3(256), 0, c->stream, u);
+        HIP_TRY(hipGetLastError());
+        top = u.out;
+    }
+    LxApplyArgs a;
+    a.s = s; a.d1 = D + p.off[1]; a.b1 = top; a.W1 = p.w[1]; a.H1 = p.h[1]; a.fc = d.fc;
+    a.highlights = x.highlights; a.shadows = x.shadows; a.inv_sigma = inv_sigma; a.max_ev = x.max_ev; a.key = x.key; a.out = c->d_lx_out;
+    const unsigned n_wg = (unsigned)(((size_t)(c->W >> 2) * (size_t)c->H + 255u) / 256u);
+    if (vec) hipLaunchKernelGGL(lx_apply_kernel<true>, dim3(n_wg), dim3(256), 0, c->stream, a);
+    else hipLaunchKernelGGL(lx_apply_kernel<false>, dim3(n_wg), dim3(256), 0, c->stream, a);
+    HIP_TRY(hipGetLastError());
+    d.hdr = c->d_lx_out; d.samples = 1; per_tile = false;
+    return DE_OK;
+}
+int run_local_exposure(de_ctx* c, DisplayArgs& d, bool& per_tile) { return lx_run(c, c->lx, d, per_tile); }
+// ---- output scaling (include/digital_earth_output_scale.h, output_scale_kernels.hip): every call that hands out the displayed image sizes itself from these
+bool os_active(const de_ctx* c) { return c->os.enabled && c->os.width > 0 && (c->os.width != c->W || c->os.height != c->H); }      // on at W x H is the identity: nothing runs
+int out_w(const de_ctx* c) { return os_active(c) ? c->os.width : c->W; }
+int out_h(const de_ctx* c) { return os_active(c) ? c->os.height : c->H; }
+size_t out_image_bytes(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3 * sizeof(float); }
+const float* shown_image(const de_ctx* c) { return os_active(c) ? c->d_os_out : c->d_image; }
+// The settings against a source size; *ow, *oh = the output size they ask for (0, 0: the source's).
+int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_output_scale)) return fail(DE_ERR_INVALID, "de_output_scale.struct_bytes does not match this library's struct");
+    if (s->filter < DE_SCALE_BOX || s->filter > DE_SCALE_LANCZOS3) return fail(DE_ERR_INVALID, "de_output_scale.filter must be DE_SCALE_BOX, _TRIANGLE, _MITCHELL or _LANCZOS3");
+    const int w = (s->width == 0 && s->height == 0) ? W : s->width, h = (s->width == 0 && s->height == 0) ? H : s->height;
+    if (w <= 0 || h <= 0 || (w % 16) != 0 || (h % 8) != 0) return fail(DE_ERR_INVALID, "de_output_scale: width must be a positive multiple of 16 and height of 8");
+    if ((long long)w * 8 < W || (long long)W * 8 < w || (long long)h * 8 < H || (long long)H * 8 < h) return fail(DE_ERR_INVALID, "de_output_scale: each axis' ratio out / source must lie in [1/8, 8]");
+    if ((long long)w * h > (1ll << 28)) return fail(DE_ERR_INVALID, "de_output_scale: width * height must not exceed 2^28");
+    *ow = w; *oh = h;
+    return DE_OK;
+}
+// A device buffer of at least `bytes`: one that is too small is replaced (hipFree waits for the work that reads it).
+int os_device_ensure(void** p, size_t* have, size_t bytes) {
+    if (*p && *have >= bytes) return DE_OK;
+    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
+    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no device memory for the output scaling's buffers"); }
+    *have = bytes;
+    return DE_OK;
+}
+// One axis' table on the device, rebuilt only when the axis or the filter changed.  The upload reads pageable host memory that dies with this call: waited for.
+int os_table_ensure(hipStream_t stream, de_ctx::ScaleDev& d, int n_src, int n_dst, int filter) {
+    if (d.first && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
+    ScaleTable T;
+    if (!os_build_table(n_src, n_dst, filter, &T)) return fail(DE_ERR_INVALID, "output scaling: no table for this pair of sizes");
+    size_t fb = d.first_cap * sizeof(int32_t), wb = d.w_cap * sizeof(float);
+    int rc = os_device_ensure((void**)&d.first, &fb, T.first.size() * sizeof(int32_t));
+    d.first_cap = fb / sizeof(int32_t);
+    if (rc) return rc;
+    rc = os_device_ensure((void**)&d.w, &wb, T.w.size() * sizeof(float));
+    d.w_cap = wb / sizeof(float);
+    if (rc) return rc;
+    d.filter = -1;
+    HIP_TRY(hipMemcpyAsync(d.first, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d.w, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    d.n_src = n_src; d.n_dst = n_dst; d.filter = filter; d.taps = T.taps;
+    return DE_OK;
+}
+// The passes of (W, H, 3) -> (ow, oh, 3), not both sizes equal: along v into `mid` (or straight into `out` when the other axis is a copy), then along u.
+int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh, const de_ctx::ScaleDev& tv, const de_ctx::ScaleDev& tu, float* mid, float* out) {
+    const float* in = src;
+    if (oh != H) {
+        ScaleArgs a;
+        a.src = in; a.dst = ow != W ? mid : out; a.first = tv.first; a.w = tv.w; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
+        const unsigned long long blocks = (unsigned long long)W * (unsigned long long)os_v_tiles(oh);
+        if (blocks * OS_V_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the image has too many columns for one launch");
+        hipLaunchKernelGGL(output_scale_v_kernel, dim3((unsigned)blocks), dim3(OS_V_THREADS), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+        in = a.dst;
+    }
+    if (ow != W) {
+        ScaleArgs a;
+        a.src = in; a.dst = out; a.first = tu.first; a.w = tu.w; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
+        const unsigned long long blocks = (unsigned long long)ow * (unsigned long long)os_u_chunks(oh * 3);
+        if (blocks * OS_U_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the output has too many columns for one launch");
+        hipLaunchKernelGGL(output_scale_u_kernel, dim3((unsigned)blocks), dim3(OS_U_THREADS), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return DE_OK;
+}
+// Behind the display on the context stream: d_image -> d_os_out.
+int run_output_scale(de_ctx* c) {
+    const int W = c->W, H = c->H, ow = c->os.width, oh = c->os.height;
+    int rc = DE_OK;
+    if (oh != H) { rc = os_table_ensure(c->stream, c->os_tab[0], H, oh, c->os.filter); if (rc) return rc; }
+    if (ow != W) { rc = os_table_ensure(c->stream, c->os_tab[1], W, ow, c->os.filter); if (rc) return rc; }
+    if (oh != H && ow != W) { rc = os_device_ensure((void**)&c->d_os_mid, &c->os_mid_bytes, (size_t)W * (size_t)oh * 3 * sizeof(float)); if (rc) return rc; }
+    rc = os_device_ensure((void**)&c->d_os_out, &c->os_out_bytes, (size_t)ow * (size_t)oh * 3 * sizeof(float));
+    if (rc) return rc;
+    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], c->d_os_mid, c->d_os_out);
+}
+// ---- 8-bit pixel output (include/digital_earth_pixels.h, pixels_kernels.hip)
+size_t px_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (size_t)c->px.channels; }      // of the output size (include/digital_earth_output_scale.h): W x H while that stage is off
+size_t px_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 4; }      // every buffer holds either format: de_set_pixels frees nothing
+int px_settings_check(const de_pixels* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_pixels)) return fail(DE_ERR_INVALID, "de_pixels.struct_bytes does not match this library's struct");
+    if (s->channels != 3 && s->channels != 4) return fail(DE_ERR_INVALID, "de_pixels.channels must be 3 or 4");
+    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_pixels.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
+    return DE_OK;
+}
+int px_host_alloc(uint8_t** p, size_t* have, size_t bytes) {      // one that is too small for a new output size is replaced: no copy into it is in flight
+    if (*p && *have < bytes) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
+    if (!*p) {
+        if (hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the pixel staging buffers"); }
+        *have = bytes;
+    }
+    return DE_OK;
+}
+void px_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_pixels& s, uint32_t phase) {
+    PixelsArgs a;
+    a.image = image; a.out = out; a.W = W; a.H = H; a.channels = s.channels; a.mode = s.mode; a.seed = s.seed; a.phase = phase;
+    hipLaunchKernelGGL(pixels_pack_kernel, dim3((unsigned)((W + PX_TILE - 1) / PX_TILE), (unsigned)((H + PX_TILE - 1) / PX_TILE)), dim3(256), 0, stream, a);
+}
+// ---- HDR display output: the packed pixels (include/digital_earth_hdr_output.h, hdr_output_kernels.hip)
+size_t hpx_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (c->ho.pixel_format == DE_HDR_PIXELS_RGB16 ? 6u : 4u); }
+size_t hpx_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 6; }      // every buffer holds either format
+int ho_settings_check(const de_hdr_output* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_hdr_output)) return fail(DE_ERR_INVALID, "de_hdr_output.struct_bytes does not match this library's struct");
+    if (!(s->peak_nits >= 100.0f && s->peak_nits <= 10000.0f)) return fail(DE_ERR_INVALID, "de_hdr_output.peak_nits must lie in [100, 10000]");      // NaN fails both
+    if (s->gamut < DE_HDR_GAMUT_REC709 || s->gamut > DE_HDR_GAMUT_REC2020) return fail(DE_ERR_INVALID, "de_hdr_output.gamut must be DE_HDR_GAMUT_REC709, _P3D65 or _REC2020");
+    if (s->transfer < DE_HDR_TRANSFER_LINEAR || s->transfer > DE_HDR_TRANSFER_HLG) return fail(DE_ERR_INVALID, "de_hdr_output.transfer must be DE_HDR_TRANSFER_LINEAR, _PQ or _HLG");
+    if (s->pixel_format < DE_HDR_PIXELS_RGB10A2 || s->pixel_format > DE_HDR_PIXELS_RGB16) return fail(DE_ERR_INVALID, "de_hdr_output.pixel_format must be DE_HDR_PIXELS_RGB10A2 or _RGB16");
+    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_hdr_output.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
+    return DE_OK;
+}
+
+// ---- the chain.  Where a caller leaves it: behind the stage it hands out (an intermediate fetch), or in front of the display launch.
+enum DisplayStop { STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE, STOP_IMAGE };
+
+// What must hold before anything is enqueued, in the order in which a caller learns of it: the stage it asks for is on; the maps (the history's own
+// fetch only: it answers before the guides' launch would); the LUTs, wherever the frame constants are read — the history's camera, the anchor of local
+// exposure, the display transform — so not for the bloom or the denoiser alone; the denoiser's refusal whenever it is on; the HDR output's for the display.
+int display_chain_refusal(de_ctx* c, DisplayStop stop) {
+    static const char* const fetch_name[] = {"fetch_denoised_hdr", "fetch_history_hdr", "fetch_bloom_hdr", "fetch_local_exposure_hdr", "fetch_image"};
+    if (stop == STOP_DENOISE && !c->dn_on) return fail(DE_ERR_STATE, "the denoiser is off (de_set_denoise)");
+    if (stop == STOP_HISTORY && !c->hs_on) return fail(DE_ERR_STATE, "history reprojection is off (de_set_history)");
+    if (stop == STOP_BLOOM && !c->bl_on) return fail(DE_ERR_STATE, "bloom is off (de_set_bloom)");
+    if (stop == STOP_LOCAL_EXPOSURE && !c->lx_on) return fail(DE_ERR_STATE, "local exposure is off (de_set_local_exposure)");
+    if (stop == STOP_HISTORY)
+        for (int i = 0; i < DE_TEX_COUNT; ++i)
+            if (!c->tex[i].set) return fail(DE_ERR_STATE, "history reprojection takes its distances from the maps: all 7 must be uploaded or generated first");
+    if ((stop == STOP_HISTORY || stop == STOP_LOCAL_EXPOSURE || stop == STOP_IMAGE) && !c->luts_set)
+        return fail(DE_ERR_STATE, std::string("LUTs must be uploaded before ") + fetch_name[stop]);
+    if (c->dn_on) { int rc = denoise_refusal(c); if (rc) return rc; }
+    if (stop == STOP_IMAGE && c->ho.on) { int rc = hdr_output_refusal(c); if (rc) return rc; }
+    return DE_OK;
+}
+
+// The stages that are on, in their one order, up to and including `stop`'s, on the context stream.  Afterwards *d and *per_tile describe what the next
+// consumer reads: a transposed copy-out of d->hdr, or the display launch (per_tile: display_kernel<true>, every tile divided by its own count).  Every
+// stage replaces d->hdr by a mean of its own, to be read with samples = 1 through the unchanged transform: x / 1.0f == x.
+int display_chain(de_ctx* c, DisplayStop stop, DisplayArgs* d, bool* per_tile) {
+    int rc = display_chain_refusal(c, stop);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // The frame constants of the current parameters.  A no-op unless a parameter changed; every caller runs it, also the bloom's fetch of a context
+    // whose later stages are off and that reads none: what setup_kernel writes is a function of the parameters and the LUTs alone, whoever reads the
+    // constants next runs it anyway, and every change of either marks them dirty again.
+    rc = run_setup(c);
+    if (rc) return rc;
+    // The launches in flight first, and the next accumulate_kernel must not overwrite what this reads; then the filter, which reads S1 and S2: all
+    // ahead of everything below, which reads the sums or the filtered mean.
+    rc = join_slots(c);
+    if (rc) return rc;
+    touched_hdr(c);
+    if (c->dn_on) { rc = run_denoise(c); if (rc) return rc; }
+    // what the display reads: the sums with the frame's or the tiles' counts, a display source, or the filtered mean
+    d->fc = c->d_fc; d->hdr = c->display_src ? c->display_src : c->d_hdr; d->image = c->d_image;
+    d->crf.data = c->d_crf; d->crf.w = 1024; d->crf.h = c->n_crf;
+    d->W = c->W; d->H = c->H; d->samples = c->current_spp; d->clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) ? 1 : 0;
+    d->tile_spp = c->d_tile_spp;
+    if (c->dn_on) { d->hdr = c->d_dn_out; d->samples = 1; }
+    *per_tile = c->frame_kind == DE_FRAME_ADAPTIVE && !c->dn_on;
+    if (stop == STOP_DENOISE) return DE_OK;
+    // ahead of the meter and the bloom: they see the stabilised image
+    if (c->hs_on) { rc = run_history(c, *d, *per_tile); if (rc) return rc; }
+    if (stop == STOP_HISTORY) return DE_OK;
+    // The meter, only when the chain goes past the bloom: local exposure and the display alone read d->fc, and the meter has state (the adaptation in
+    // d_ae_state, ae_displayed) that a fetch of the history's or the bloom's mean must not advance.  Ahead of the bloom: the scene is metered, not the
+    // lens.  The same transform over the metered exposure: a second FrameConsts, written on the device.
+    if (c->ae_on && stop > STOP_BLOOM) { rc = run_meter(c, *d, *per_tile); if (rc) return rc; d->fc = c->d_fc_ae; }
+    if (c->bl_on) { rc = run_bloom(c, *d, *per_tile); if (rc) return rc; }
+    if (stop == STOP_BLOOM) return DE_OK;
+    // last: the scene is metered, the lens glares, the print is dodged; the anchor is d->fc's exposure
+    if (c->lx_on) { rc = run_local_exposure(c, *d, *per_tile); if (rc) return rc; }
+    return DE_OK;
+}
+}  // namespace

@@ -6,16 +6,14 @@
 //                       (a copy of the frame's with exposure_scale = 2^ev) that the display reads instead, and the result block of de_get_metering
 // Integer counts: the histogram does not depend on the order of anything.  Included into de_api.hip's translation unit; display_kernel is untouched.
 #include "de_kernels.h"
+#include "display_source.h"
 
 #define AE_BINS 256
 #define AE_ROW 258          // a partial row: 256 bins, then the pixels below 2^-24 (not metered), then those at or above 2^8 (also in bin 255)
 #define AE_MAX_WG 512       // two workgroups per CU: the rows the solve kernel has to sum stay at 528 KB
 
 struct MeterArgs {
-    const float* hdr;           // [H][W][3]: DisplayArgs::hdr
-    const int32_t* tile_spp;    // [H/8][W/8] when the display divides every tile by its own count (display_kernel<true>), else null
-    int samples;                // DisplayArgs::samples
-    int W;
+    DisplaySrc s;               // what the display launch is about to read
     int x0, y0, x1, y1;         // the metering region, half-open
     int gx0, gw;                // the region's columns in groups of 4 pixels: first group, groups per row
     uint32_t n_items;           // gw * (y1 - y0)
@@ -60,22 +58,14 @@ __global__ void __launch_bounds__(256) meter_hist_kernel(MeterArgs a) {
         if (item < a.n_items) {
             const uint32_t row = item / (uint32_t)a.gw;
             const int j = a.y0 + (int)row, i0 = (a.gx0 + (int)(item - row * (uint32_t)a.gw)) * 4;      // i0 + 3 < W: W is a multiple of 16
-            const float* p = a.hdr + ((size_t)j * a.W + i0) * 3;
             float px[12];
-            if (VEC) {
-                const float4 v0 = reinterpret_cast<const float4*>(p)[0], v1 = reinterpret_cast<const float4*>(p)[1], v2 = reinterpret_cast<const float4*>(p)[2];
-                px[0] = v0.x; px[1] = v0.y; px[2] = v0.z; px[3] = v0.w; px[4] = v1.x; px[5] = v1.y; px[6] = v1.z; px[7] = v1.w;
-                px[8] = v2.x; px[9] = v2.y; px[10] = v2.z; px[11] = v2.w;
-            } else {
-                for (int k = 0; k < 12; ++k) px[k] = p[k];
-            }
-            // display_pixel's own sample count and division (a group of 4 pixels lies in one 8x8 tile)
-            const float samples = a.tile_spp ? (float)a.tile_spp[(j >> 3) * (a.W >> 3) + (i0 >> 3)] : (float)a.samples;
+            src_load4<VEC>(a.s.hdr + ((size_t)j * a.s.W + i0) * 3, px);
+            const float samples = src_samples(a.s, i0, j);      // display_pixel's own sample count and division
             for (int k = 0; k < 4; ++k) {
                 const int i = i0 + k;
                 if (i < a.x0 || i >= a.x1) continue;
                 const float r = px[3 * k] / samples, g = px[3 * k + 1] / samples, b = px[3 * k + 2] / samples;
-                const float Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b;      // no vignette: the scene is metered, not the lens
+                const float Y = src_luminance(r, g, b);
                 code[k] = ae_bin(Y);
                 clipped[k] = Y >= 0x1p8f;
             }

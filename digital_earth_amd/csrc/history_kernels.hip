@@ -13,6 +13,8 @@
 #include "de_kernels.h"
 #endif
 
+#include "display_source.h"
+
 #include <float.h>
 
 // The camera of a displayed picture: what FrameConsts holds of it.
@@ -22,9 +24,7 @@ struct HistoryCam {
 };
 
 struct HistoryArgs {
-    const float* hdr;             // [H][W][3]: DisplayArgs::hdr ...
-    const int32_t* tile_spp;      // ... its per-tile divisor [H/8][W/8] when the display divides every tile by its own count, else null ...
-    int samples;                  // ... and DisplayArgs::samples
+    DisplaySrc s;                 // what the display launch is about to read; (s.W, s.H) is the size of every array here
     const int32_t* n_tile;        // the pixel's sample count n: its tile's [H/8][W/8] (an adaptive frame), ...
     const int32_t* n_pixel;       // ... its own [H][W] (de_debug_history), ...
     int n_frame;                  // ... or the frame's
@@ -37,7 +37,6 @@ struct HistoryArgs {
     float4* cand_c;               // [H][W] (out, Wout): the next history
     float* cand_d;                // [H][W] a copy of dist (the guides are recomputed after the move)
     HistoryCam* cand_cam;
-    int W, H;
     float max_history, depth_tolerance;
 };
 
@@ -47,8 +46,8 @@ DE_DEV bool history_finite3(float x, float y, float z) { return __builtin_fabsf(
 struct HistoryTap { float b, w, c0, c1, c2; };
 DE_DEV HistoryTap history_tap(const HistoryArgs& a, int xi, int yi, float b, bool land, float r, float tol) {
     HistoryTap t = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (xi < 0 || xi >= a.W || yi < 0 || yi >= a.H) return t;
-    const size_t tp = (size_t)yi * a.W + xi;
+    if (xi < 0 || xi >= a.s.W || yi < 0 || yi >= a.s.H) return t;
+    const size_t tp = (size_t)yi * a.s.W + xi;
     const float4 c = a.hist_c[tp];
     const float hd = a.hist_d[tp];
     const bool surface = land ? (hd > 0.0f && __builtin_fabsf(hd - r) <= tol) : hd == 0.0f;
@@ -62,7 +61,7 @@ DE_DEV HistoryTap history_tap(const HistoryArgs& a, int xi, int yi, float b, boo
 DE_DEV bool history_reproject(const HistoryArgs& a, int u, int v, float t, float* h, float* w) {
     const FrameConsts& fc = *a.fc;
     const HistoryCam& hc = *a.hist_cam;
-    const float Hf = (float)a.H;
+    const float Hf = (float)a.s.H;
     // guide_kernel's expression at the pixel centre
     const float fu = (2.0f * fc.fov * ((float)u + 0.5f) / Hf - fc.fov * fc.aspect_ratio - 1e-5f) * fc.aspect_scale;
     const float fv = 2.0f * fc.fov * ((float)v + 0.5f) / Hf - fc.fov - 1e-5f;
@@ -85,7 +84,7 @@ DE_DEV bool history_reproject(const HistoryArgs& a, int u, int v, float t, float
     const float xo = ((gu / hc.aspect_scale + 1e-5f) + hc.fov * hc.aspect_ratio) * Hf / (2.0f * hc.fov) - 0.5f;
     const float yo = ((gv + 1e-5f) + hc.fov) * Hf / (2.0f * hc.fov) - 0.5f;
     // no tap of (floor, floor + 1) inside the image (or a NaN): nothing to read, and nothing to convert to an integer
-    if (!(xo >= -1.0f && xo < (float)a.W && yo >= -1.0f && yo < Hf)) return false;
+    if (!(xo >= -1.0f && xo < (float)a.s.W && yo >= -1.0f && yo < Hf)) return false;
     const float fx = __builtin_floorf(xo), fy = __builtin_floorf(yo);
     const float bx = xo - fx, by = yo - fy;
     const int x0 = (int)fx, y0 = (int)fy;
@@ -106,10 +105,10 @@ DE_DEV bool history_reproject(const HistoryArgs& a, int u, int v, float t, float
 
 // Steps 1 and 7, the display's mean and the next history candidate.
 DE_DEV void history_pixel(const HistoryArgs& a, int u, int v) {
-    const size_t p = (size_t)v * a.W + u;
-    const int tile = (v >> 3) * (a.W >> 3) + (u >> 3);
-    const float samples = a.tile_spp ? (float)a.tile_spp[tile] : (float)a.samples;      // display_pixel's own sample count and division
-    const float* px = a.hdr + p * 3;
+    const size_t p = (size_t)v * a.s.W + u;
+    const int tile = (v >> 3) * (a.s.W >> 3) + (u >> 3);
+    const float samples = src_samples(a.s, u, v);      // display_pixel's own sample count and division
+    const float* px = a.s.hdr + p * 3;
     const float m0 = px[0] / samples, m1 = px[1] / samples, m2 = px[2] / samples;
     const int n = a.n_pixel ? a.n_pixel[p] : (a.n_tile ? a.n_tile[tile] : a.n_frame);
     const float nf = (float)n;
@@ -140,7 +139,7 @@ __global__ void __launch_bounds__(256) history_blend_kernel(HistoryArgs a) {
         k->cam_pos = fc.cam_pos; k->d = fc.d; k->du = fc.du; k->dv = fc.dv;
         k->fov = fc.fov; k->aspect_ratio = fc.aspect_ratio; k->aspect_scale = fc.aspect_scale;
     }
-    if (u >= a.W || v >= a.H) return;
+    if (u >= a.s.W || v >= a.s.H) return;
     history_pixel(a, u, v);
 }
 

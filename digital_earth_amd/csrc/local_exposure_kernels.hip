@@ -15,89 +15,35 @@
 #include "de_kernels.h"
 #endif
 
+#include "display_source.h"
+#include "pyramid.h"
+
 #include <float.h>
 
-#define LX_MAX_LEVELS 10
-#define LX_SRC_COLS 40      // down0: the 34 source columns 32 bx - 1 .. 32 bx + 32 lie in the ten groups of 4 pixels from 32 bx - 4 on
-#define LX_SRC_STRIDE 41    // odd row strides: the 16 lanes of the next row start on an odd bank, so the stride-2 reads of the row pass do not collide
-#define LX_LVL_STRIDE 35
-#define LX_H_STRIDE 24      // two rows down is 48 = 16 mod 32 banks on: the column pass of lanes (x, y) and (x, y + 1) covers all 32 banks once
-
-// What the display launch is about to read.
-struct LxSrc {
-    const float* hdr;           // [H][W][3]: DisplayArgs::hdr
-    const int32_t* tile_spp;    // [H/8][W/8] when the display divides every tile by its own count (display_kernel<true>), else null
-    int samples;                // DisplayArgs::samples
-    int W, H;
-};
-
-// Twelve floats = 4 pixels of a row.  VEC: the buffer is 16-byte aligned (the context's own always are; a bound buffer or a display source may not be).
-template <bool VEC>
-DE_DEV void lx_load4(const float* p, float* px) {
-    if (VEC) {
-        const float4 v0 = reinterpret_cast<const float4*>(p)[0], v1 = reinterpret_cast<const float4*>(p)[1], v2 = reinterpret_cast<const float4*>(p)[2];
-        px[0] = v0.x; px[1] = v0.y; px[2] = v0.z; px[3] = v0.w; px[4] = v1.x; px[5] = v1.y; px[6] = v1.z; px[7] = v1.w;
-        px[8] = v2.x; px[9] = v2.y; px[10] = v2.z; px[11] = v2.w;
-    } else {
-        for (int k = 0; k < 12; ++k) px[k] = p[k];
-    }
-}
-
-// display_pixel's own sample count (a group of 4 pixels lies in one 8x8 tile)
-DE_DEV float lx_samples(const LxSrc& s, int i, int j) {
-    return s.tile_spp ? (float)s.tile_spp[(j >> 3) * (s.W >> 3) + (i >> 3)] : (float)s.samples;
-}
+#define LX_MAX_LEVELS PYR_MAX_LEVELS
 
 // Step 1: the mean m (display_pixel's own division), its luminance and l = log2 Y.  Valid: 2^-24 <= Y <= FLT_MAX (the meter's lower bound); black
 // space, negatives, NaN and Inf are not, weigh nothing anywhere and leave the stage as m.
 DE_DEV bool lx_pixel(const float* px, float samples, float* m, float* l) {
     m[0] = px[0] / samples; m[1] = px[1] / samples; m[2] = px[2] / samples;
-    const float Y = (0.2126f * m[0] + 0.7152f * m[1]) + 0.0722f * m[2];      // the meter's expression
+    const float Y = src_luminance(m[0], m[1], m[2]);
     if (!(Y >= 0x1p-24f && Y <= FLT_MAX)) { *l = 0.0f; return false; }
     *l = de_log(Y) * DE_LOG2E;
     return true;
 }
 
-DE_DEV int lx_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-DE_DEV float lx_tent4(float p0, float p1, float p2, float p3) { return (0.125f * p0 + 0.375f * p1) + (0.375f * p2 + 0.125f * p3); }
-
-// ---- one level down (§12's "Down" on both components).  src: two planes (l w, w) of 34 rows; plane row r is source row r0 + r, plane column k is
-// source column c0 + k; only rows and columns inside the level were staged, and the clamped indices read only those.
-// Row pass: 34 x 16 values per plane.
-template <int STRIDE>
-DE_DEV void lx_row_pass(const float (*src)[34][STRIDE], float (*hb)[34][LX_H_STRIDE], int t, int bx, int by, int c0, int Ws, int Hs, int Wd) {
-    const int X0 = bx * 16, r0 = by * 32 - 1;
-    for (int it = t; it < 34 * 16; it += 256) {
-        const int row = it >> 4, x = it & 15, X = X0 + x, j = r0 + row;
-        if (j < 0 || j >= Hs || X >= Wd) continue;
-        const int k0 = lx_clampi(2 * X - 1, 0, Ws - 1) - c0, k1 = 2 * X - c0, k2 = lx_clampi(2 * X + 1, 0, Ws - 1) - c0, k3 = lx_clampi(2 * X + 2, 0, Ws - 1) - c0;
-        for (int c = 0; c < 2; ++c) hb[c][row][x] = lx_tent4(src[c][row][k0], src[c][row][k1], src[c][row][k2], src[c][row][k3]);
-    }
-}
-// Column pass: 16 x 16 outputs of (Wd, Hd) = ((Ws + 1) >> 1, (Hs + 1) >> 1).
-DE_DEV void lx_col_pass(const float (*hb)[34][LX_H_STRIDE], int t, int bx, int by, int Hs, int Wd, int Hd, float2* out) {
-    const int r0 = by * 32 - 1;
-    const int x = t & 15, y = t >> 4, X = bx * 16 + x, Y = by * 16 + y;
-    if (X >= Wd || Y >= Hd) return;
-    const int q0 = lx_clampi(2 * Y - 1, 0, Hs - 1) - r0, q1 = 2 * Y - r0, q2 = lx_clampi(2 * Y + 1, 0, Hs - 1) - r0, q3 = lx_clampi(2 * Y + 2, 0, Hs - 1) - r0;
-    float2 o;
-    o.x = lx_tent4(hb[0][q0][x], hb[0][q1][x], hb[0][q2][x], hb[0][q3][x]);
-    o.y = lx_tent4(hb[1][q0][x], hb[1][q1][x], hb[1][q2][x], hb[1][q3][x]);
-    out[(size_t)Y * Wd + X] = o;
-}
-
 // Source -> the staged tile of level 0: (l, 1) for a valid pixel, (0, 0) otherwise.  W is a multiple of 16, so a group of 4 source pixels is inside
 // the image or outside it.
 template <bool VEC>
-DE_DEV void lx_stage0(const LxSrc& s, float (*src)[34][LX_SRC_STRIDE], int t, int bx, int by) {
+DE_DEV void lx_stage0(const DisplaySrc& s, float (*src)[34][PYR_SRC_STRIDE], int t, int bx, int by) {
     const int c0 = bx * 32 - 4, r0 = by * 32 - 1;
-    for (int it = t; it < 34 * (LX_SRC_COLS / 4); it += 256) {
-        const int row = it / (LX_SRC_COLS / 4), g = it - row * (LX_SRC_COLS / 4);
+    for (int it = t; it < 34 * (PYR_SRC_COLS / 4); it += 256) {
+        const int row = it / (PYR_SRC_COLS / 4), g = it - row * (PYR_SRC_COLS / 4);
         const int j = r0 + row, i0 = c0 + 4 * g;
         if (j < 0 || j >= s.H || i0 < 0 || i0 >= s.W) continue;
         float px[12];
-        lx_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
-        const float samples = lx_samples(s, i0, j);
+        src_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
+        const float samples = src_samples(s, i0, j);
         for (int k = 0; k < 4; ++k) {
             float m[3], l;
             const bool valid = lx_pixel(px + 3 * k, samples, m, &l);
@@ -105,22 +51,8 @@ DE_DEV void lx_stage0(const LxSrc& s, float (*src)[34][LX_SRC_STRIDE], int t, in
         }
     }
 }
-// A float2 level -> its staged tile.
-DE_DEV void lx_stage(const float2* in, int Ws, int Hs, float (*src)[34][LX_LVL_STRIDE], int t, int bx, int by) {
-    const int c0 = bx * 32 - 1, r0 = by * 32 - 1;
-    for (int it = t; it < 34 * 34; it += 256) {
-        const int row = it / 34, col = it - row * 34;
-        const int j = r0 + row, i = c0 + col;
-        if (j < 0 || j >= Hs || i < 0 || i >= Ws) continue;
-        const float2 v = in[(size_t)j * Ws + i];
-        src[0][row][col] = v.x; src[1][row][col] = v.y;
-    }
-}
 
-// ---- the base, coarse to fine
-// far neighbour of fine index x on the coarse level of n entries: near - 1 for even x, near + 1 for odd x, clamped
-DE_DEV int lx_far(int x, int n) { return lx_clampi((x & 1) ? (x >> 1) + 1 : (x >> 1) - 1, 0, n - 1); }
-
+// ---- the base, coarse to fine (one level down is the shared pyramid's, pyramid.h: §12's "Down" on both components)
 // One entry of the coarser level as a tap: does it count (its weight is positive), its guide D.x / D.y and its base (the guide itself on the top level,
 // whose bases are not stored: b == null).  An entry that does not count is not divided and its base is not read.
 struct LxTap { float g, b; bool on; };
@@ -165,14 +97,14 @@ DE_DEV void lx_up_item(const LxUpArgs& a, uint32_t item) {
     const float2 d = a.fine[item];
     if (!(d.y > 0.0f)) { a.out[item] = 0.0f; return; }      // never read: every reader tests the weight first
     const float guide = d.x / d.y;
-    const int xn = X >> 1, xf = lx_far(X, a.Wc), yn = Y >> 1, yf = lx_far(Y, a.Hc);
+    const int xn = X >> 1, xf = pyr_far(X, a.Wc), yn = Y >> 1, yf = pyr_far(Y, a.Hc);
     const LxTap nn = lx_read_tap(a.coarse, a.coarse_b, (size_t)yn * a.Wc + xn), fn = lx_read_tap(a.coarse, a.coarse_b, (size_t)yn * a.Wc + xf);
     const LxTap nf = lx_read_tap(a.coarse, a.coarse_b, (size_t)yf * a.Wc + xn), ff = lx_read_tap(a.coarse, a.coarse_b, (size_t)yf * a.Wc + xf);
     a.out[item] = lx_blend(nn, fn, nf, ff, guide, a.inv_sigma);
 }
 
 struct LxApplyArgs {
-    LxSrc s;
+    DisplaySrc s;
     const float2* d1;         // D_1
     const float* b1;          // B_1, or null when the pyramid has one level
     int W1, H1;
@@ -184,18 +116,18 @@ struct LxApplyArgs {
 // three float4 stores.
 template <bool VEC>
 DE_DEV void lx_apply_item(const LxApplyArgs& a, uint32_t item) {
-    const LxSrc& s = a.s;
+    const DisplaySrc& s = a.s;
     const uint32_t gw = (uint32_t)s.W >> 2;
     if (item >= gw * (uint32_t)s.H) return;
     const int j = (int)(item / gw), i0 = (int)(item - (uint32_t)j * gw) * 4;
     float px[12];
-    lx_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
-    const float samples = lx_samples(s, i0, j);
-    const int cx = i0 >> 1, rn = j >> 1, rf = lx_far(j, a.H1);
+    src_load4<VEC>(s.hdr + ((size_t)j * s.W + i0) * 3, px);
+    const float samples = src_samples(s, i0, j);
+    const int cx = i0 >> 1, rn = j >> 1, rf = pyr_far(j, a.H1);
     LxTap tn[4], tf[4];      // columns cx - 1 .. cx + 2, clamped, of the near and the far row
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const int col = lx_clampi(cx - 1 + k, 0, a.W1 - 1);
+        const int col = pyr_clampi(cx - 1 + k, 0, a.W1 - 1);
         tn[k] = lx_read_tap(a.d1, a.b1, (size_t)rn * a.W1 + col);
         tf[k] = lx_read_tap(a.d1, a.b1, (size_t)rf * a.W1 + col);
     }
@@ -224,27 +156,27 @@ DE_DEV void lx_apply_item(const LxApplyArgs& a, uint32_t item) {
 #ifndef DE_LX_STANDALONE
 // Source -> level 1.  Grid: 16 x 16 output tiles of level 1.
 template <bool VEC>
-__global__ void __launch_bounds__(256) lx_down0_kernel(LxSrc s, float2* out, int Wd, int Hd) {
-    __shared__ float src[2][34][LX_SRC_STRIDE];
-    __shared__ float hb[2][34][LX_H_STRIDE];
+__global__ void __launch_bounds__(256) lx_down0_kernel(DisplaySrc s, float2* out, int Wd, int Hd) {
+    __shared__ float src[2][34][PYR_SRC_STRIDE];
+    __shared__ float hb[2][34][PYR_H_STRIDE];
     const int t = (int)threadIdx.x, bx = (int)blockIdx.x, by = (int)blockIdx.y;
     lx_stage0<VEC>(s, src, t, bx, by);
     __syncthreads();
-    lx_row_pass<LX_SRC_STRIDE>(src, hb, t, bx, by, bx * 32 - 4, s.W, s.H, Wd);
+    pyr_row_pass<2, PYR_SRC_STRIDE>(src, hb, t, bx, by, bx * 32 - 4, s.W, s.H, Wd);
     __syncthreads();
-    lx_col_pass(hb, t, bx, by, s.H, Wd, Hd, out);
+    pyr_col_pass<2>(hb, t, bx, by, s.H, Wd, Hd, out);
 }
 
 // Level l -> level l + 1.  Grid: 16 x 16 output tiles.
 __global__ void __launch_bounds__(256) lx_down_kernel(const float2* in, int Ws, int Hs, float2* out, int Wd, int Hd) {
-    __shared__ float src[2][34][LX_LVL_STRIDE];
-    __shared__ float hb[2][34][LX_H_STRIDE];
+    __shared__ float src[2][34][PYR_LVL_STRIDE];
+    __shared__ float hb[2][34][PYR_H_STRIDE];
     const int t = (int)threadIdx.x, bx = (int)blockIdx.x, by = (int)blockIdx.y;
-    lx_stage(in, Ws, Hs, src, t, bx, by);
+    pyr_stage_level<2>(in, Ws, Hs, src, t, bx, by);
     __syncthreads();
-    lx_row_pass<LX_LVL_STRIDE>(src, hb, t, bx, by, bx * 32 - 1, Ws, Hs, Wd);
+    pyr_row_pass<2, PYR_LVL_STRIDE>(src, hb, t, bx, by, bx * 32 - 1, Ws, Hs, Wd);
     __syncthreads();
-    lx_col_pass(hb, t, bx, by, Hs, Wd, Hd, out);
+    pyr_col_pass<2>(hb, t, bx, by, Hs, Wd, Hd, out);
 }
 
 // B_l.  Grid: one thread per entry of level l.

@@ -257,6 +257,40 @@ def test_bloom_reads_a_display_source(R, offset_floats):
     r.close(); other.close()
 
 
+@pytest.fixture(scope="module")
+def wide(R):
+    """144x72 reading a second context's buffer: the levels are 72x36, 36x18, 18x9, 9x5, 5x3 and 3x2 — level 1 spans several 16-output tiles in both
+    axes and is wider than the 34-column staged tile, the widths and heights turn odd, and the plan stops at six levels whatever is asked for."""
+    W, H = 144, 72
+    r = R.Renderer((W, H), (0, 1, 0), texture_source="constant")
+    other = R.Renderer((W, H + 8), (0, 1, 0), texture_source="constant")      # larger: the shifted window stays inside it
+    r.copy_textures()
+    rng = np.random.default_rng(144)
+    big = (np.exp2(rng.uniform(-12.0, 4.0, (W, H + 8, 1))) * rng.uniform(0.2, 1.5, (W, H + 8, 3))).astype(np.float32)
+    other.upload_hdr(big, 1)
+    r.upload_hdr(np.full((W, H, 3), 0.4, np.float32), 3)
+    yield r, other, np.ascontiguousarray(big.transpose(1, 0, 2)).ravel()      # the device layout [H][W][3]
+    r.close(); other.close()
+
+
+@pytest.mark.parametrize("offset_floats", [0, 1])
+@pytest.mark.parametrize("levels", [1, 2, 10])
+def test_pyramid_at_144x72(wide, levels, offset_floats):
+    """The source aligned, and offset by one float (no longer 16-byte aligned: the scalar-load kernels)."""
+    W, H = 144, 72
+    r, other, flat = wide
+    ptr, _ = other.hdr_device_pointer()
+    kw = dict(intensity=0.4, threshold=0.1, levels=levels)
+    assert bl.levels_used(W, H, levels) == min(levels, 6)
+    r.set_display_source(ptr + 4 * offset_floats)
+    r.set_bloom(True, **kw)
+    got = r.fetch_bloom_hdr()
+    seen = flat[offset_floats:offset_floats + W * H * 3].reshape(H, W, 3).transpose(1, 0, 2)
+    r.set_bloom(False)
+    r.set_display_source(None)
+    _same(got, bl.bloom(seen, 3, **kw)[0])
+
+
 # ---------------------------------------------------------------- 5. the scene is metered, not the lens
 def test_auto_exposure_meters_the_image_before_the_bloom(contexts):
     W, H = 80, 56

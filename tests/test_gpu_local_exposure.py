@@ -157,6 +157,39 @@ def test_unaligned_display_source_takes_the_scalar_loads(R):
     r.close(); other.close()
 
 
+@pytest.fixture(scope="module")
+def wide(R):
+    """144x72 reading a second context's buffer: the levels are 72x36, 36x18, 18x9, 9x5, 5x3 and 3x2 — level 1 spans several 16-output tiles in both
+    axes and is wider than the 34-column staged tile, the widths and heights turn odd, and the plan stops at six levels whatever is asked for."""
+    W, H = 144, 72
+    r = R.Renderer((W, H), (0, 1, 0), texture_source="constant")
+    other = R.Renderer((W, H + 8), (0, 1, 0), texture_source="constant")      # larger: the shifted window stays inside it
+    r.copy_textures()
+    rng = np.random.default_rng(144)
+    big = (np.exp2(rng.uniform(-10.0, 2.0, (W, H + 8, 1))) * rng.uniform(0.6, 1.4, (W, H + 8, 3))).astype(np.float32)
+    other.upload_hdr(big, 1)
+    r.upload_hdr(np.full((W, H, 3), 0.4, np.float32), 3)
+    yield r, other, np.ascontiguousarray(big.transpose(1, 0, 2)).ravel()      # the device layout [H][W][3]
+    r.close(); other.close()
+
+
+@pytest.mark.parametrize("offset_floats", [0, 1])
+@pytest.mark.parametrize("levels", [1, 2, 10])
+def test_pyramid_at_144x72(wide, levels, offset_floats):
+    """The source aligned, and offset by one float (no longer 16-byte aligned: the scalar loads)."""
+    W, H = 144, 72
+    r, other, flat = wide
+    ptr, _ = other.hdr_device_pointer()
+    assert lx.levels_used(W, H, levels) == min(levels, 6)
+    r.set_display_source(ptr + 4 * offset_floats)
+    r.set_local_exposure(True, levels=levels)
+    got = r.fetch_local_exposure_hdr()
+    seen = flat[offset_floats:offset_floats + W * H * 3].reshape(H, W, 3).transpose(1, 0, 2)
+    r.set_local_exposure(False)
+    r.set_display_source(None)
+    _same(got, lx.local_exposure(seen, 3, scale_of(r, float(r.exposure[None])), levels=levels, **device_math(r))[0])
+
+
 # ---------------------------------------------------------------- 2. a rendered frame
 def _rendered(R, seed=11, spp=2):
     r = R.Renderer((64, 32), (0, 1, 0), texture_source="synthetic", texture_size=(1024, 512), seed=seed)

@@ -119,7 +119,7 @@ def test_range_refusals_come_before_any_device_call():
     lib.de_debug_local_exposure.restype = ctypes.c_int
     lib.de_debug_local_exposure.argtypes = _native.LOCAL_EXPOSURE_SYMBOLS["de_debug_local_exposure"][1]
     assert lib.de_debug_local_exposure(None, None, 1.0, ctypes.byref(s), None) == _native.DE_ERR_INVALID
-    src = open(os.path.join(build.CSRC, "de_api.hip")).read()
+    src = open(os.path.join(build.CSRC, "de_display.h")).read()      # the stages' host code
     check = src[src.index("int lx_settings_check("):src.index("int lx_run(")]
     for text in ("s->highlights >= 0.0f", "s->highlights <= 1.0f", "s->shadows >= 0.0f", "s->shadows <= 1.0f", "s->sigma > 0.0f", "s->max_ev >= 0.0f", "s->key > 0.0f",
                  "s->levels < 1 || s->levels > LX_MAX_LEVELS", "sizeof(de_local_exposure)"):
@@ -133,6 +133,13 @@ def test_build_tracks_the_new_sources():
     assert any(d.endswith("digital_earth_local_exposure.h") for d in build.DEPS)
     ctx = open(os.path.join(build.CSRC, "de_context.h")).read()
     assert ctx.index('#include "local_exposure_kernels.hip"') > ctx.index('#include "bloom_kernels.hip"')      # in the product library's one translation unit
+    assert "de_display.h" in build.DEPS
+    # last ahead of the display launch: last in the chain (de_display.h), which de_render_to_image runs to its end before it launches the display
+    chain = open(os.path.join(build.CSRC, "de_display.h")).read()
+    chain = chain[chain.index("int display_chain("):]
+    assert chain.index("run_bloom(") < chain.index("run_local_exposure(") < chain.rindex("return DE_OK;")
+    assert chain.count("run_") == chain[:chain.index("run_local_exposure(")].count("run_") + 1      # no stage runs after it
     api = open(os.path.join(build.CSRC, "de_api.hip")).read()
     body = api[api.index("int de_render_to_image("):api.index("int de_fetch_image(")]
-    assert body.index("run_bloom(") < body.index("run_local_exposure(") < body.index("display_kernel<true>")      # last ahead of the display launch
+    assert "run_bloom(" not in body and "run_local_exposure(" not in body
+    assert body.index("display_chain(c, STOP_IMAGE") < body.index("display_kernel<true>")

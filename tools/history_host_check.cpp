@@ -65,12 +65,12 @@ int main(int argc, char** argv) {
     history_camera_kernel(par[0], W, H, &fc, nullptr);
     history_camera_kernel(par[1], W, H, nullptr, &cams[0]);
     HistoryArgs a;
-    a.hdr = m.data(); a.tile_spp = nullptr; a.samples = 1;
+    a.s.hdr = m.data(); a.s.tile_spp = nullptr; a.s.samples = 1;
     a.n_tile = nullptr; a.n_pixel = n.data(); a.n_frame = 0;
     a.dist = dist.data(); a.fc = &fc;
     a.hist_c = has ? hist_c.data() : nullptr; a.hist_d = hist_d.data(); a.hist_cam = &cams[0];
     a.out = out.data(); a.cand_c = cand_c.data(); a.cand_d = cand_d.data(); a.cand_cam = &cams[1];
-    a.W = W; a.H = H; a.max_history = set[0]; a.depth_tolerance = set[1];
+    a.s.W = W; a.s.H = H; a.max_history = set[0]; a.depth_tolerance = set[1];
     for (unsigned by = 0; by < (unsigned)((H + 15) / 16); ++by)
         for (unsigned bx = 0; bx < (unsigned)((W + 15) / 16); ++bx)
             for (unsigned t = 0; t < 256u; ++t) {

@@ -3,7 +3,8 @@
 // (tools/local_exposure_host_check.py builds and drives this, with tools/host_shim on the include path in place of the HIP runtime header;
 // DESIGN.md §15).  Every kernel is its phases around its barriers: this program runs each phase for the 256 threads of a workgroup, then the next,
 // one workgroup at a time.  The LDS tiles are heap blocks of exactly the kernels' LDS sizes filled with NaN (a read of a word that was never staged
-// would show in the output), and every level is a heap block of exactly its size.
+// would show in the output), and every level is a heap block of exactly its size.  The plan of the levels, the staging of a level and the row and
+// column passes are the shared pyramid's (csrc/pyramid.h): this program exercises the passes that the bloom runs too.
 //   local_exposure_host_check run IN OUT     IN: int32 W, H, levels, vec; f32 exposure_scale, highlights, shadows, sigma, max_ev, key; then the mean
 //                                            [H][W][3] f32.  OUT: the dodged mean [H][W][3] f32.
 //   local_exposure_host_check log IN OUT     IN: f32 values.  OUT: de_log of each — what the Python side injects into the restatement ...
@@ -12,7 +13,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
 #include <limits>
 #include <vector>
 
@@ -37,9 +37,9 @@ static std::vector<float> take_all(FILE* f) {
 template <int STRIDE>
 struct Tiles {      // one workgroup's LDS
     std::vector<float> src, hb;
-    Tiles() : src((size_t)2 * 34 * STRIDE, std::numeric_limits<float>::quiet_NaN()), hb((size_t)2 * 34 * LX_H_STRIDE, std::numeric_limits<float>::quiet_NaN()) {}
+    Tiles() : src((size_t)2 * 34 * STRIDE, std::numeric_limits<float>::quiet_NaN()), hb((size_t)2 * 34 * PYR_H_STRIDE, std::numeric_limits<float>::quiet_NaN()) {}
     float (*s())[34][STRIDE] { return reinterpret_cast<float (*)[34][STRIDE]>(src.data()); }
-    float (*h())[34][LX_H_STRIDE] { return reinterpret_cast<float (*)[34][LX_H_STRIDE]>(hb.data()); }
+    float (*h())[34][PYR_H_STRIDE] { return reinterpret_cast<float (*)[34][PYR_H_STRIDE]>(hb.data()); }
 };
 
 int main(int argc, char** argv) {
@@ -57,34 +57,30 @@ int main(int argc, char** argv) {
         const int W = head[0], H = head[1], levels = head[2];
         const bool vec = head[3] != 0;
         const std::vector<float> mean = take<float>(f, (size_t)W * H * 3);
-        // the host side's plan (de_api.hip: bl_plan)
-        std::vector<int> w(1, W), h(1, H);
-        while ((int)w.size() - 1 < levels) {
-            const int nw = (w.back() + 1) >> 1, nh = (h.back() + 1) >> 1;
-            if (w.size() > 1 && std::min(nw, nh) < 2) break;
-            w.push_back(nw); h.push_back(nh);
-        }
-        const int L = (int)w.size() - 1;
+        const PyramidPlan plan = pyr_plan(W, H, levels);      // the host side's own (csrc/pyramid.h)
+        const int* w = plan.w;
+        const int* h = plan.h;
+        const int L = plan.L;
         std::vector<std::vector<float2>> D(L + 1);
         std::vector<std::vector<float>> B(L + 1);
         for (int l = 1; l <= L; ++l) { D[l].resize((size_t)w[l] * h[l]); if (l < L) B[l].resize((size_t)w[l] * h[l]); }
         const FrameConsts fc = {set[0]};
-        LxSrc s;
+        DisplaySrc s;
         s.hdr = mean.data(); s.tile_spp = nullptr; s.samples = 1; s.W = W; s.H = H;
         for (int by = 0; by < (h[1] + 15) / 16; ++by)
             for (int bx = 0; bx < (w[1] + 15) / 16; ++bx) {
-                Tiles<LX_SRC_STRIDE> lds;
+                Tiles<PYR_SRC_STRIDE> lds;
                 for (int t = 0; t < 256; ++t) { if (vec) lx_stage0<true>(s, lds.s(), t, bx, by); else lx_stage0<false>(s, lds.s(), t, bx, by); }
-                for (int t = 0; t < 256; ++t) lx_row_pass<LX_SRC_STRIDE>(lds.s(), lds.h(), t, bx, by, bx * 32 - 4, W, H, w[1]);
-                for (int t = 0; t < 256; ++t) lx_col_pass(lds.h(), t, bx, by, H, w[1], h[1], D[1].data());
+                for (int t = 0; t < 256; ++t) pyr_row_pass<2, PYR_SRC_STRIDE>(lds.s(), lds.h(), t, bx, by, bx * 32 - 4, W, H, w[1]);
+                for (int t = 0; t < 256; ++t) pyr_col_pass<2>(lds.h(), t, bx, by, H, w[1], h[1], D[1].data());
             }
         for (int l = 1; l < L; ++l)
             for (int by = 0; by < (h[l + 1] + 15) / 16; ++by)
                 for (int bx = 0; bx < (w[l + 1] + 15) / 16; ++bx) {
-                    Tiles<LX_LVL_STRIDE> lds;
-                    for (int t = 0; t < 256; ++t) lx_stage(D[l].data(), w[l], h[l], lds.s(), t, bx, by);
-                    for (int t = 0; t < 256; ++t) lx_row_pass<LX_LVL_STRIDE>(lds.s(), lds.h(), t, bx, by, bx * 32 - 1, w[l], h[l], w[l + 1]);
-                    for (int t = 0; t < 256; ++t) lx_col_pass(lds.h(), t, bx, by, h[l], w[l + 1], h[l + 1], D[l + 1].data());
+                    Tiles<PYR_LVL_STRIDE> lds;
+                    for (int t = 0; t < 256; ++t) pyr_stage_level<2>(D[l].data(), w[l], h[l], lds.s(), t, bx, by);
+                    for (int t = 0; t < 256; ++t) pyr_row_pass<2, PYR_LVL_STRIDE>(lds.s(), lds.h(), t, bx, by, bx * 32 - 1, w[l], h[l], w[l + 1]);
+                    for (int t = 0; t < 256; ++t) pyr_col_pass<2>(lds.h(), t, bx, by, h[l], w[l + 1], h[l + 1], D[l + 1].data());
                 }
         const float inv_sigma = 1.0f / set[3];
         const float* top = nullptr;
