@@ -856,7 +856,7 @@ int de_debug_samples(de_ctx* c, uint64_t seed, int sample_index, float* out) {
     return DE_OK;
 }
 
-int de_debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n) {
+static int debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n, bool fast) {
     if (!c || !a || !out || fn < 0 || fn > 31) return fail(DE_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(c->device));
     DeviceBufs<3> m;      // a, b (null without one), out
@@ -865,12 +865,15 @@ int de_debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out,
     if (b) HIP_TRY(hipMalloc(&m.p[1], n * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(m.p[0], a, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (b) HIP_TRY(hipMemcpyAsync(m.p[1], b, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m.p[0], (const float*)m.p[1], (float*)m.p[2], (size_t)n);
+    if (fast) HIP_TRY(de_fast_launch_math(fn, (const float*)m.p[0], (const float*)m.p[1], (float*)m.p[2], (size_t)n, c->stream));
+    else hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m.p[0], (const float*)m.p[1], (float*)m.p[2], (size_t)n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, m.p[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DE_OK;
 }
+int de_debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n) { return debug_math(c, fn, a, b, out, n, false); }
+int de_debug_math_fast(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n) { return debug_math(c, fn, a, b, out, n, true); }
 
 
 /* ---- the denoiser: include/digital_earth_denoise.h */

@@ -229,6 +229,7 @@ int v6_reserve(de_ctx* c, int idx, hipStream_t stream, unsigned long long n_item
 }
 }  // namespace
 hipError_t de_fast_launch_v6(const bs::Args& A, const FrameConsts* fc, dim3 grid, dim3 block, hipStream_t stream, bool clamp, bool tail);      // de_fast.hip
+hipError_t de_fast_launch_math(int fn, const float* a, const float* b, float* out, size_t n, hipStream_t stream);      // de_fast.hip: de_debug_math_fast
 namespace {
 hipError_t launch_v6(de_ctx* c, const RenderArgs& a, hipStream_t stream, int idx) {
     de_ctx::V6State& S = c->v6s[idx];

@@ -29,7 +29,7 @@ DE_DEV float de_saturate(float x) { return de_clamp(x, 0.0f, 1.0f); }
 #ifdef DE_FAST_MATH
 // ---------------------------------------------------------------------------------------------------- DE_FLAG_FAST_MATH (round 5, opt-in)
 // The same functions on the hardware's transcendental units — v_exp_f32 / v_log_f32 / v_sin_f32 / v_cos_f32 / v_sqrt_f32 / v_rcp_f32 / v_rsq_f32
-// (about 1 ulp each, unspecified roundings) — and shorter polynomials for atan2 / asin: what the arithmetic contract costs, priced
+// (1 ulp each, unspecified roundings; v_sin_f32 / v_cos_f32: the smaller of 2^-22 absolute and 2^-20 relative) — and shorter polynomials for atan2 / asin: what the arithmetic contract costs, priced
 // (profiles/r5_fast_math.md).  NOT bit-reproducible against the CPU oracle: a sample whose `rand < p` test lands on the other side follows a
 // different path from there on.  Compiled into a second instantiation of render_kernel_v6 only (de_fast.hip); the default kernels never see this.
 DE_DEV float de_div_rc_ng(float x, float c, float rc) { (void)c; return x * rc; }
@@ -54,14 +54,15 @@ DE_DEV void de_sincos(float x, float* s_out, float* c_out) {
 }
 DE_DEV float de_sin(float x) { return __builtin_amdgcn_sinf(x * DE_INV_2PI); }
 DE_DEV float de_cos(float x) { return __builtin_amdgcn_cosf(x * DE_INV_2PI); }
-// atan2: four coefficients (1.7e-5 rad: 0.06 texel of a 21 600-wide map); asin: the contract's four with the hardware sqrt
+// atan2: four coefficients (1.73e-5 rad: 0.06 texel of a 21 600-wide map); asin: the contract's four with the hardware sqrt.
+// Each function's error budget is composed from these claims in tests/fast_math_budget.py and held on the device by tests/test_gpu_fast_math_leaves.py.
 DE_DEV float de_atan2(float y, float x) {
     float ax = de_abs(x), ay = de_abs(y);
     bool swap = ay > ax;
     float mx = swap ? ay : ax, mn = swap ? ax : ay;
     float a = mn * __builtin_amdgcn_rcpf(mx);
     float s = a * a;
-    float p = 0x1.79d11ep-6f;                             // four coefficients fitted on [0, 1] (odd polynomial a + a s p(s)): 1.7e-5 rad
+    float p = 0x1.79d11ep-6f;                             // four coefficients fitted on [0, 1] (odd polynomial a + a s p(s)): 1.73e-5 rad
     p = de_fma(p, s, -0x1.727c04p-4f);
     p = de_fma(p, s, 0x1.79d652p-3f);
     p = de_fma(p, s, -0x1.53a54cp-2f);

@@ -1150,14 +1150,16 @@ class Renderer:
         check(self._lib.de_debug_samples(self._h, self.seed, int(sample_index), out.ctypes.data))
         return out
 
-    def debug_math(self, fn, a, b=None):
+    def debug_math(self, fn, a, b=None, fast=False):
+        """Function `fn` of include/digital_earth_debug.h on the device; fast=True: the DE_FLAG_FAST_MATH kernel's definitions."""
         a = np.ascontiguousarray(a, dtype=np.float32)
         out = np.empty_like(a)
         bp = None
         if b is not None:
             b = np.ascontiguousarray(b, dtype=np.float32)
             bp = b.ctypes.data
-        check(self._lib.de_debug_math(self._h, int(fn), a.ctypes.data, bp, out.ctypes.data, a.size))
+        call = self._lib.de_debug_math_fast if fast else self._lib.de_debug_math
+        check(call(self._h, int(fn), a.ctypes.data, bp, out.ctypes.data, a.size))
         return out
 
     @staticmethod

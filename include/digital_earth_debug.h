@@ -63,9 +63,12 @@ int de_debug_cloud_bound(de_ctx* ctx, uint8_t* out, uint64_t out_bytes, int* cel
  * de_debug_math: evaluate a deterministic f32 elementary function on the GPU (fn: 0 exp, 1 log, 2 sin, 3 cos,
  * 4 atan2(a,b), 5 asin, 6 pow(a,b), 7 a/b, 8 sqrt, 9 the short sqrt de_sqrt_nr, 10 the 3-operation a/b for literal divisors, 11 a * RN(1/b) (contract-2 quotient),
  * 12 log of a random draw de_log_unit, 13 the 3-operation reciprocal de_rcp_nr,
- * 14 exp of a non-positive argument de_exp_nonpos), for bit-exact comparison against the oracle. */
+ * 14 exp of a non-positive argument de_exp_nonpos), for bit-exact comparison against the oracle.
+ * de_debug_math_fast: the same function numbers evaluated by the DE_FLAG_FAST_MATH kernel's translation unit — the hardware's transcendental units and
+ * the shorter polynomials — plus 15 / 16, the sine / cosine output of its de_sincos; for comparison against float64 (tests/test_gpu_fast_math_leaves.py). */
 int de_debug_samples(de_ctx* ctx, uint64_t seed, int sample_index, float* out);
 int de_debug_math(de_ctx* ctx, int fn, const float* a, const float* b, float* out, uint64_t n);
+int de_debug_math_fast(de_ctx* ctx, int fn, const float* a, const float* b, float* out, uint64_t n);
 /* Read a map back as uploaded (row-major, `channels` bytes per texel) — lets tests hand the same texels to the oracle. */
 int de_download_texture(de_ctx* ctx, int slot, uint8_t* out, uint64_t out_bytes);
 /* The per-pixel sums of squares S2 of the last adaptive frame (de_accumulate_adaptive), (W, H, 3) f32 in de_fetch_hdr's layout.  DE_ERR_STATE before the

@@ -164,6 +164,8 @@ def test_fast_math_flag_is_statistically_the_same_image(Renderer):
     profiles/r5_fast_math.md) — so the tolerance is statistical: at 1 spp fewer than 25 % of the samples take another path, the others agree
     to 1e-3 relative (roundings); the mean radiance of a 64-spp frame agrees to 1 %, and the frame differs from the contract's by less than
     two renders of the contract's kernel with different seeds differ (the flag moves samples, not the estimate).
+    Sharper checks of the same kernel: its leaf functions against float64 (test_gpu_fast_math_leaves.py), its bias per region by paired samples and the special
+    cameras (test_gpu_fast_math_frames.py), its launch invariants (test_gpu_fast_math_invariants.py).
     The default (flag off) stays the arithmetic contract: bit-identical to the oracle (every other test)."""
     kw = dict(texture_source="synthetic", texture_size=(2048, 1024))
     frames = {}
