@@ -93,6 +93,12 @@ class DeHdrOutput(ctypes.Structure):
                 ("pixel_format", ctypes.c_int32), ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("animate", ctypes.c_int32)]
 
 
+class DeVideo(ctypes.Structure):
+    """`de_video` (include/digital_earth_video.h): the format of the video frame output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("format", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32), ("siting", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("animate", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -243,6 +249,19 @@ HDR_OUTPUT_SYMBOLS = {
     "de_debug_hdr_transform": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.POINTER(DeHdrOutput), _P]),
 }
 
+# video frame output: include/digital_earth_video.h (same library, additions only; not part of the binder's header)
+VIDEO_SYMBOLS = {
+    "de_set_video": (ctypes.c_int, [_P, ctypes.POINTER(DeVideo)]),
+    "de_get_video": (ctypes.c_int, [_P, ctypes.POINTER(DeVideo), ctypes.POINTER(ctypes.c_uint32)]),
+    "de_videoframe_bytes": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+    "de_render_to_video": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_video": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
+    "de_fetch_videoframe_view": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
+    "de_fetch_videoframe_begin": (ctypes.c_int, [_P]),
+    "de_fetch_videoframe_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))]),
+    "de_debug_video": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeVideo), ctypes.c_uint32, _P]),
+}
+
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
 LEGACY_SYMBOLS = {
     "de_debug_v5_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -322,7 +341,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

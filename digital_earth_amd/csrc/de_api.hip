@@ -108,13 +108,15 @@ int de_destroy(de_ctx* c) {
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
                      c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
                      c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px, c->d_lx_pyr, c->d_lx_base, c->d_lx_out,
-                     c->os_tab[0].first, c->os_tab[0].w, c->os_tab[1].first, c->os_tab[1].w, c->d_os_mid, c->d_os_out, c->d_hpx};
+                     c->os_tab[0].first, c->os_tab[0].w, c->os_tab[1].first, c->os_tab[1].w, c->d_os_mid, c->d_os_out, c->d_hpx, c->d_vd};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_stage) hipHostFree(c->h_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
     if (c->h_px_stage) hipHostFree(c->h_px_stage);
     if (c->h_hpx_stage) hipHostFree(c->h_hpx_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_px_ring[k]) hipHostFree(c->h_px_ring[k]); if (c->ev_px_ring[k]) hipEventDestroy(c->ev_px_ring[k]); }
+    if (c->h_vd_stage) hipHostFree(c->h_vd_stage);
+    for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_vd_ring[k]) hipHostFree(c->h_vd_ring[k]); if (c->ev_vd_ring[k]) hipEventDestroy(c->ev_vd_ring[k]); }
     if (c->h_issued) hipHostFree(c->h_issued);
     if (c->h_ad_count) hipHostFree(c->h_ad_count);
 #ifdef DE_LEGACY_VARIANTS
@@ -1279,6 +1281,7 @@ int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
     if (c->fetch_begun != c->fetch_ended) return fail(DE_ERR_STATE, "image fetches are in flight: de_fetch_image_end first");
     if (c->px_begun != c->px_ended) return fail(DE_ERR_STATE, "pixel fetches are in flight: de_fetch_pixels_end first");
+    if (c->vd_begun != c->vd_ended) return fail(DE_ERR_STATE, "video fetches are in flight: de_fetch_videoframe_end first");
     c->os = *s;
     c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
     return DE_OK;
@@ -1385,6 +1388,115 @@ int de_fetch_hdr_pixels(de_ctx* c, void* out, uint64_t out_bytes) {
     memcpy(out, c->h_hpx_stage, hpx_size(c));
     return DE_OK;
 }
+/* ---- video frame output: include/digital_earth_video.h (videoframe_kernels.hip) */
+int de_set_video(de_ctx* c, const de_video* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = vd_settings_check(s); if (rc) return rc; }
+    if (c->vd_begun != c->vd_ended) return fail(DE_ERR_STATE, "video fetches are in flight: de_fetch_videoframe_end first");
+    c->vd = *s;
+    c->vd.animate = s->animate ? 1 : 0;
+    c->vd_consts = vd_make_consts(s->format, s->matrix, s->range);
+    c->vd_count = 0; c->vd_last_phase = 0;
+    return DE_OK;
+}
+int de_get_video(de_ctx* c, de_video* out, uint32_t* last_phase) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->vd;
+    if (last_phase) *last_phase = c->vd_last_phase;
+    return DE_OK;
+}
+int de_videoframe_bytes(de_ctx* c, uint64_t* bytes, uint64_t* plane_offsets, uint64_t* plane_strides) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    const uint64_t W = (uint64_t)out_w(c), H = (uint64_t)out_h(c), B = (uint64_t)vd_sample_bytes(c->vd);
+    const bool interleaved = c->vd.format == DE_VIDEO_NV12 || c->vd.format == DE_VIDEO_P010;
+    if (bytes) *bytes = (uint64_t)vd_size(c);
+    if (plane_offsets) { plane_offsets[0] = 0; plane_offsets[1] = W * H * B; plane_offsets[2] = interleaved ? W * H * B + B : (W * H + (W / 2) * (H / 2)) * B; }
+    if (plane_strides) { plane_strides[0] = W * B; plane_strides[1] = plane_strides[2] = (interleaved ? W : W / 2) * B; }
+    return DE_OK;
+}
+int de_render_to_video(de_ctx* c, const void** device_frame) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->d_vd && c->d_vd_bytes < vd_capacity(c)) { (void)hipFree(c->d_vd); c->d_vd = nullptr; c->d_vd_bytes = 0; }      // the output size grew (hipFree waits for the work that reads it)
+    if (!c->d_vd) { HIP_TRY(hipMalloc(&c->d_vd, vd_capacity(c))); c->d_vd_bytes = vd_capacity(c); }
+    int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
+    if (rc) return rc;
+    const uint32_t phase = c->vd.animate ? c->vd_count : 0u;
+    vd_launch(c->stream, shown_image(c), c->d_vd, out_w(c), out_h(c), c->vd, c->vd_consts, phase);
+    HIP_TRY(hipGetLastError());
+    c->vd_count++; c->vd_last_phase = phase;
+    if (device_frame) *device_frame = c->d_vd;
+    return DE_OK;
+}
+int de_fetch_videoframe_view(de_ctx* c, const void** host) {
+    if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = px_host_alloc(&c->h_vd_stage, &c->h_vd_stage_bytes, vd_capacity(c));
+    if (rc) return rc;
+    rc = de_render_to_video(c, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_vd_stage, c->d_vd, vd_size(c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *host = c->h_vd_stage;
+    return frame_status(c);
+}
+int de_fetch_video(de_ctx* c, void* out, uint64_t out_bytes) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    if (out_bytes < (uint64_t)vd_size(c)) return fail(DE_ERR_INVALID, "out_bytes is smaller than the frame (de_videoframe_bytes)");
+    const void* host = nullptr;
+    int rc = de_fetch_videoframe_view(c, &host);
+    if (rc) return rc;
+    memcpy(out, host, vd_size(c));
+    return DE_OK;
+}
+int de_fetch_videoframe_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    if (c->vd_begun - c->vd_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four video fetches are in flight already: de_fetch_videoframe_end first");
+    const int k = (int)(c->vd_begun % (unsigned)DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = px_host_alloc(&c->h_vd_ring[k], &c->h_vd_ring_bytes[k], vd_capacity(c));
+    if (rc) return rc;
+    if (!c->ev_vd_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_vd_ring[k], hipEventDisableTiming));
+    rc = de_render_to_video(c, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->h_vd_ring[k], c->d_vd, vd_size(c), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_vd_ring[k], c->stream));
+    c->vd_begun++;
+    return DE_OK;
+}
+int de_fetch_videoframe_end(de_ctx* c, const void** host) {
+    if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
+    if (c->vd_begun == c->vd_ended) return fail(DE_ERR_STATE, "no video fetch in flight: de_fetch_videoframe_begin first");
+    const int k = (int)(c->vd_ended % (unsigned)DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(c->ev_vd_ring[k]));
+    c->vd_ended++;
+    *host = c->h_vd_ring[k];
+    return frame_status(c);
+}
+/* the conversion once on a host-given image of any even size.  Buffers of its own; the context's frame and phase counter are not touched. */
+int de_debug_video(de_ctx* c, const float* image, int W, int H, const de_video* s, uint32_t phase, void* out) {
+    if (!c || !image || !s || !out || W <= 0 || H <= 0 || (W & 1) || (H & 1) || (long long)W * H > (1ll << 28))
+        return fail(DE_ERR_INVALID, "bad arguments (W and H positive and even, W * H at most 2^28)");
+    { int rc = vd_settings_check(s); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    DeviceBufs<2> b;
+    const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), out_bytes = vd_frame_bytes(W, H, *s);
+    HIP_TRY(hipMalloc(&b.p[0], in_bytes));
+    HIP_TRY(hipMalloc(&b.p[1], out_bytes));
+    HIP_TRY(hipMemcpyAsync(b.p[0], image, in_bytes, hipMemcpyHostToDevice, c->stream));
+    vd_launch(c->stream, (const float*)b.p[0], (uint8_t*)b.p[1], W, H, *s, vd_make_consts(s->format, s->matrix, s->range), phase);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b.p[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+
 /* the transform alone on n colours.  Buffers of its own; the context's setting is not touched. */
 int de_debug_hdr_transform(de_ctx* c, const float* rgb, uint64_t n, const de_hdr_output* s, float* out) {
     if (!c || !rgb || !s || !out || n == 0 || n > (1ull << 28)) return fail(DE_ERR_INVALID, "bad arguments (1 <= n <= 2^28)");

@@ -8,6 +8,7 @@
 #include "../../include/digital_earth_local_exposure.h"
 #include "../../include/digital_earth_output_scale.h"
 #include "../../include/digital_earth_hdr_output.h"
+#include "../../include/digital_earth_video.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -37,6 +38,7 @@
 #include "output_scale_kernels.hip"
 #include "local_exposure_kernels.hip"
 #include "hdr_output_kernels.hip"
+#include "videoframe_kernels.hip"
 
 namespace {
 
@@ -280,6 +282,19 @@ struct de_ctx {
     void* d_hpx = nullptr;
     uint8_t* h_hpx_stage = nullptr;
     size_t d_hpx_bytes = 0, h_hpx_stage_bytes = 0;
+    // Video frame output (include/digital_earth_video.h).  The constants of the settings are computed by de_set_video and travel in the
+    // kernel's arguments.  Allocated on first use, each for the 10-bit formats (out_w * out_h * 3 bytes) so that de_set_video never frees a buffer a caller
+    // may still read: the frame on the device, one pinned staging buffer and four pinned ring cells; a ring, counters and events of its own.
+    de_video vd = {(uint32_t)sizeof(de_video), DE_VIDEO_NV12, DE_VIDEO_MATRIX_BT709, DE_VIDEO_RANGE_LIMITED, DE_VIDEO_SITING_LEFT, DE_PIXELS_ROUND, 0u, 0};
+    VideoConsts vd_consts = vd_make_consts(DE_VIDEO_NV12, DE_VIDEO_MATRIX_BT709, DE_VIDEO_RANGE_LIMITED);      // of `vd`: once per de_set_video
+    uint32_t vd_count = 0;          // conversions since de_set_video
+    uint32_t vd_last_phase = 0;
+    uint8_t* d_vd = nullptr;
+    uint8_t* h_vd_stage = nullptr;
+    uint8_t* h_vd_ring[DE_FETCH_RING] = {};
+    hipEvent_t ev_vd_ring[DE_FETCH_RING] = {};
+    unsigned vd_begun = 0, vd_ended = 0;
+    size_t d_vd_bytes = 0, h_vd_stage_bytes = 0, h_vd_ring_bytes[DE_FETCH_RING] = {};
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

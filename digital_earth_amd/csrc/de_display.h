@@ -1,7 +1,7 @@
 // de_display.h — the host side of the display path: what runs on the context stream between the frame's sums and the image a caller is handed.
 //   * the small helpers every entry point of that path shares: host <-> device layouts, a transposed fetch, a settings getter, device scratch buffers;
 //   * each opt-in stage's allocation and launch sequence (denoiser, auto-exposure, bloom, history reprojection, local exposure), the stages behind the
-//     display (output scaling, 8-bit and HDR pixels) and the two refusals;
+//     display (output scaling, 8-bit and HDR pixels, video frames) and the two refusals;
 //   * display_chain: the ONE statement of the order denoise -> history -> meter -> bloom -> local exposure -> display and of its preconditions, which
 //     de_render_to_image and the four intermediate fetches of de_api.hip run up to their own stage.
 // The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, the source every stage reads display_source.h.
@@ -427,6 +427,29 @@ int ho_settings_check(const de_hdr_output* s) {
     if (s->pixel_format < DE_HDR_PIXELS_RGB10A2 || s->pixel_format > DE_HDR_PIXELS_RGB16) return fail(DE_ERR_INVALID, "de_hdr_output.pixel_format must be DE_HDR_PIXELS_RGB10A2 or _RGB16");
     if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_hdr_output.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
     return DE_OK;
+}
+// ---- video frame output (include/digital_earth_video.h, videoframe_kernels.hip)
+size_t vd_sample_bytes(const de_video& s) { return s.format >= DE_VIDEO_P010 ? 2u : 1u; }
+size_t vd_frame_bytes(int W, int H, const de_video& s) { return (size_t)W * (size_t)H / 2 * 3 * vd_sample_bytes(s); }
+size_t vd_size(const de_ctx* c) { return vd_frame_bytes(out_w(c), out_h(c), c->vd); }      // of the output size, as px_size
+size_t vd_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3; }      // every buffer holds any format: de_set_video frees nothing
+int vd_settings_check(const de_video* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_video)) return fail(DE_ERR_INVALID, "de_video.struct_bytes does not match this library's struct");
+    if (s->format < DE_VIDEO_NV12 || s->format > DE_VIDEO_I010) return fail(DE_ERR_INVALID, "de_video.format must be DE_VIDEO_NV12, _I420, _P010 or _I010");
+    if (s->matrix < DE_VIDEO_MATRIX_BT709 || s->matrix > DE_VIDEO_MATRIX_BT2020) return fail(DE_ERR_INVALID, "de_video.matrix must be DE_VIDEO_MATRIX_BT709, _BT601 or _BT2020");
+    if (s->range < DE_VIDEO_RANGE_LIMITED || s->range > DE_VIDEO_RANGE_FULL) return fail(DE_ERR_INVALID, "de_video.range must be DE_VIDEO_RANGE_LIMITED or _FULL");
+    if (s->siting < DE_VIDEO_SITING_LEFT || s->siting > DE_VIDEO_SITING_TOPLEFT) return fail(DE_ERR_INVALID, "de_video.siting must be DE_VIDEO_SITING_LEFT, _CENTER or _TOPLEFT");
+    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_video.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
+    return DE_OK;
+}
+int vd_even_check(const de_ctx* c) {
+    if ((out_w(c) | out_h(c)) & 1) return fail(DE_ERR_STATE, "a 4:2:0 frame needs an even width and height: the output size is odd");
+    return DE_OK;
+}
+void vd_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_video& s, const VideoConsts& k, uint32_t phase) {
+    VideoArgs a;
+    a.image = image; a.out = out; a.W = W; a.H = H; a.format = s.format; a.siting = s.siting; a.mode = s.mode; a.seed = s.seed; a.phase = phase; a.k = k;
+    hipLaunchKernelGGL(videoframe_pack_kernel, dim3((unsigned)((W + VD_TILE - 1) / VD_TILE), (unsigned)((H + VD_TILE - 1) / VD_TILE)), dim3(256), 0, stream, a);
 }
 
 // ---- the chain.  Where a caller leaves it: behind the stage it hands out (an intermediate fetch), or in front of the display launch.

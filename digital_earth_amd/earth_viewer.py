@@ -265,11 +265,17 @@ class EarthViewer:
         pixels=True: the iteration returns the packed 8-bit picture instead of the float field — (H, W, channels) uint8, rows top-down, converted on the
         GPU in the format of Renderer.set_pixels() (Renderer.fetch_pixels) — with the same copy / pipelined rules; finish(pixels=True) ends that loop.
         hdr_pixels=True (a keyword beside the sliders, none of them): the iteration returns the packed HDR pixels of Renderer.fetch_hdr_pixels() — uint32
-        (H, W) or uint16 (H, W, 3) — always a copy, never pipelined: these pixels have no ring.  The HDR display output must be on."""
+        (H, W) or uint16 (H, W, 3) — always a copy, never pipelined: these pixels have no ring.  The HDR display output must be on.
+        video=True (a keyword beside the sliders too): the iteration returns one video frame in the format of Renderer.set_video() — a flat
+        uint8 array, Renderer.fetch_video — under the same copy / pipelined rules as pixels=True, through the video ring; finish(video=True)
+        ends that loop.  It goes with neither pixels=True nor hdr_pixels=True, and the picture save() holds is left as it was."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
+        video = bool(sliders.pop("video", False))
         if hdr_pixels and (pixels or pipelined):
             raise ValueError("hdr_pixels=True goes with neither pixels=True nor pipelined")
+        if video and (pixels or hdr_pixels):
+            raise ValueError("video=True goes with neither pixels=True nor hdr_pixels=True")
         should_reset = False
         if self.camera.update_camera(0.0):
             r.set_camera_pos(*self.camera.position)
@@ -277,7 +283,10 @@ class EarthViewer:
             r.set_up(*self.camera._up)
             should_reset = True
         r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
-        if hdr_pixels:
+        frame = None
+        if video:
+            frame = r.fetch_video(copy=copy, lag=int(pipelined))
+        elif hdr_pixels:
             self._pixels, self._image = r.fetch_hdr_pixels(), None
         elif pixels:
             self._pixels, self._image = r.fetch_pixels(copy=copy, lag=int(pipelined)), None
@@ -287,7 +296,9 @@ class EarthViewer:
         # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
         # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
         shown = self._pixels if (pixels or hdr_pixels) else self._image
-        if pipelined:
+        if video:
+            pass                                # no picture of save()'s changed hands
+        elif pipelined:
             self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
             if shown is not None:
                 self._held_hdr = self._hdr_in_flight[bool(pixels)].pop(0)
@@ -310,10 +321,42 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
+        if video:
+            return frame
         return self._pixels if (pixels or hdr_pixels) else self._image
 
-    def finish(self, copy=True, pixels=False):
-        """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop."""
+    def record(self, path, frames, spp=1, fps=(TARGET_FPS, 1), **sliders_per_frame):
+        """Write `frames` iterations of frame(video=True) to `path` as a Y4M file (digital_earth_amd/y4m.py) that every player opens, through the
+        pipelined video ring: the GPU renders frame k + 1 while frame k is packed, copied and written.  The video output must be planar — "i420" or
+        "i010" (Renderer.set_video; ValueError otherwise, before anything is rendered or written).  Every slider keyword is either a value, held
+        for the whole recording, or a sequence of one value per frame (a sun angle per frame is a time-lapse); move the camera between calls, or
+        record in several calls.  Returns the number of frames written."""
+        from . import y4m
+        r = self.renderer
+        fmt = r.video()
+        n = int(frames)
+        for k, v in sliders_per_frame.items():
+            if hasattr(v, "__len__") and len(v) != n:
+                raise ValueError("slider %r has %d values for %d frames" % (k, len(v), n))
+        w = y4m.Y4MWriter(path, fmt["size"][0], fmt["size"][1], fps=fps, format=fmt["format"], range=fmt["range"], siting=fmt["siting"])
+        try:
+            for i in range(n):
+                now = {k: (v[i] if hasattr(v, "__len__") else v) for k, v in sliders_per_frame.items()}
+                got = self.frame(spp=spp, copy=False, pipelined=1, video=True, **now)
+                if got is not None:
+                    w.write(got)
+                del got
+            for got in r.fetch_pending(all_images=True, video=True):
+                w.write(got)
+        finally:
+            w.close()
+        return w.frames
+
+    def finish(self, copy=True, pixels=False, video=False):
+        """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop;
+        video=True: the frame of a frame(video=True) loop."""
+        if video:
+            return self.renderer.fetch_pending(copy=copy, video=True)
         img = self.renderer.fetch_pending(copy=copy, pixels=pixels)
         queue = self._hdr_in_flight[bool(pixels)]
         if img is not None and queue:

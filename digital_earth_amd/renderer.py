@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -143,6 +143,9 @@ class Renderer:
             ref = getattr(self, "_pixel_view_ref", None)
             if ref is not None and ref() is not None:
                 raise RuntimeError("a fetch_pixels(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
+            ref = getattr(self, "_vd_view_ref", None)
+            if ref is not None and ref() is not None:
+                raise RuntimeError("a fetch_video(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
             check(self._lib.de_destroy(self._h))
             self._h = ctypes.c_void_p()
             self._lender = None
@@ -767,12 +770,18 @@ class Renderer:
         view = self._staging_view(ptr)
         return np.array(view) if copy else view
 
-    def fetch_pending(self, copy=True, all_images=False, pixels=False):
+    def fetch_pending(self, copy=True, all_images=False, pixels=False, video=False):
         """End the pipelined window loop: wait for the fetches still in flight and return the newest image (None when there is none);
         all_images=True: the list of all of them, oldest first (copies).  pixels=True: the same for the lagged fetch_pixels() calls, which have a
-        ring of their own; the float fetches are left alone, as the pixel fetches are without it."""
+        ring of their own; the float fetches are left alone, as the pixel fetches are without it.  video=True: the same for the lagged
+        fetch_video() calls and their ring."""
         imgs = []
-        if pixels:
+        if video:
+            if pixels:
+                raise ValueError("pixels=True and video=True name two rings: one call each")
+            while getattr(self, "_vd_fetches", 0) > 0:
+                imgs.append(self._fetch_vd_end(copy or all_images))
+        elif pixels:
             while getattr(self, "_pixel_fetches", 0) > 0:
                 imgs.append(self._fetch_pixels_end(copy or all_images))
         else:
@@ -862,8 +871,132 @@ class Renderer:
         check(self._lib.de_debug_pixels(self._h, image.ctypes.data, W, H, ctypes.byref(s), ctypes.c_uint32(int(phase) & 0xffffffff), out.ctypes.data))
         return out
 
+    # ------------------------------------------------------------------ video frame output (include/digital_earth_video.h)
+    VIDEO_FORMATS = ("nv12", "i420", "p010", "i010")
+    VIDEO_MATRICES = ("bt709", "bt601", "bt2020")
+    VIDEO_RANGES = ("limited", "full")
+    VIDEO_SITINGS = ("left", "center", "topleft")
+
+    def _vd_settings(self, format, matrix, range, siting, mode, seed, animate):
+        for value, names, what in ((format, self.VIDEO_FORMATS, "format"), (matrix, self.VIDEO_MATRICES, "matrix"), (range, self.VIDEO_RANGES, "range"),
+                                   (siting, self.VIDEO_SITINGS, "siting"), (mode, self.PIXEL_MODES, "mode")):
+            if value not in names:
+                raise ValueError("%s must be one of %s" % (what, names))
+        s = DeVideo()
+        s.struct_bytes = ctypes.sizeof(DeVideo)
+        s.format, s.matrix, s.range, s.siting = self.VIDEO_FORMATS.index(format), self.VIDEO_MATRICES.index(matrix), self.VIDEO_RANGES.index(range), self.VIDEO_SITINGS.index(siting)
+        s.mode, s.seed, s.animate = self.PIXEL_MODES.index(mode), int(seed) & 0xffffffff, 1 if animate else 0
+        return s
+
+    def set_video(self, format="nv12", matrix="bt709", range="limited", siting="left", mode="round", seed=0, animate=False):
+        """The format of fetch_video(): Y'CbCr 4:2:0 planes packed on the GPU behind the display transform (and behind output scaling).
+        format "nv12" / "i420" (8 bits) or "p010" / "i010" (10 bits in uint16 words: high bits / low bits, i010 = yuv420p10le); matrix "bt709",
+        "bt601" or "bt2020" (non-constant luminance); range "limited" (16-235 / 16-240, scaled by 4 at 10 bits) or "full"; chroma siting "left"
+        (MPEG-2 / H.264), "center" (JPEG) or "topleft" (BT.2020 / HDR); mode, seed and animate as set_pixels, rounding by default.  Every call resets
+        the phase counter; refused (DE_ERR_STATE) while lagged video fetches are in flight.  No other fetch is affected.  With set_hdr_output(True,
+        transfer="pq", gamut="rec2020") ahead of it, format="i010", matrix="bt2020", siting="topleft" is the HDR10 frame (set_hdr_output's known
+        limit on that gamut carries over)."""
+        check(self._lib.de_set_video(self._h, ctypes.byref(self._vd_settings(format, matrix, range, siting, mode, seed, animate))))
+
+    def video(self):
+        """The video format as a dict (set_video's keywords) plus last_phase, size = (width, height), frame_bytes, and the byte offsets and row
+        strides of the Y, Cb and Cr samples (plane_offsets, plane_strides)."""
+        s, phase = DeVideo(), ctypes.c_uint32()
+        check(self._lib.de_get_video(self._h, ctypes.byref(s), ctypes.byref(phase)))
+        n, off, stride = ctypes.c_uint64(), (ctypes.c_uint64 * 3)(), (ctypes.c_uint64 * 3)()
+        check(self._lib.de_videoframe_bytes(self._h, ctypes.byref(n), off, stride))
+        return dict(format=self.VIDEO_FORMATS[s.format], matrix=self.VIDEO_MATRICES[s.matrix], range=self.VIDEO_RANGES[s.range], siting=self.VIDEO_SITINGS[s.siting],
+                    mode=self.PIXEL_MODES[s.mode], seed=int(s.seed), animate=bool(s.animate), last_phase=int(phase.value), size=self.output_size(),
+                    frame_bytes=int(n.value), plane_offsets=tuple(int(x) for x in off), plane_strides=tuple(int(x) for x in stride))
+
+    def _vd_view(self, ptr, nbytes):
+        view = np.ctypeslib.as_array(ptr, shape=(nbytes,)).view(_StagingView)
+        view.flags.writeable = False
+        view._owner = self
+        self._vd_view_ref = weakref.ref(view)
+        return view
+
+    def fetch_video(self, copy=True, lag=0):
+        """The displayed image as one video frame in the format of set_video(): a flat uint8 array of video()["frame_bytes"] bytes, the
+        planes one after the other, rows top-down — what an encoder or a raw-video pipe takes as it is; split_video() views it as planes.  1.5 (8-bit)
+        or 3 (10-bit) bytes per pixel cross the link.  copy=False: a read-only view of the library's pinned video staging buffer, valid until the next
+        fetch_video call.  lag=1, 2 or 3: pipelined like fetch_pixels(lag=...), through a ring of its own — the call returns the frame of the
+        lag-th previous call (None until there is one); fetch_pending(video=True) hands out the rest."""
+        if not self._textures_copied:
+            self.copy_textures()
+        if lag not in (0, 1, 2, 3):
+            raise ValueError("lag must be 0 ... 3")
+        n = ctypes.c_uint64()
+        check(self._lib.de_videoframe_bytes(self._h, ctypes.byref(n), None, None))
+        if lag:
+            check(self._lib.de_fetch_videoframe_begin(self._h))
+            self._vd_fetches = getattr(self, "_vd_fetches", 0) + 1
+            self._vd_bytes = int(n.value)
+            if self._vd_fetches <= lag:
+                return None
+            return self._fetch_vd_end(copy)
+        if getattr(self, "_vd_fetches", 0):
+            raise RuntimeError("lagged video fetches are in flight: fetch_pending(video=True) first")
+        if not copy:
+            ptr = ctypes.POINTER(ctypes.c_uint8)()
+            check(self._lib.de_fetch_videoframe_view(self._h, ctypes.byref(ptr)))
+            return self._vd_view(ptr, int(n.value))
+        out = np.empty(int(n.value), dtype=np.uint8)
+        check(self._lib.de_fetch_video(self._h, out.ctypes.data, ctypes.c_uint64(out.nbytes)))
+        return out
+
+    def _fetch_vd_end(self, copy):
+        ptr = ctypes.POINTER(ctypes.c_uint8)()
+        self._vd_fetches -= 1
+        check(self._lib.de_fetch_videoframe_end(self._h, ctypes.byref(ptr)))
+        view = self._vd_view(ptr, self._vd_bytes)      # set_video and set_output_scale are refused while fetches are in flight: the size is the begin's
+        return np.array(view) if copy else view
+
+    def split_video(self, frame, size=None, format=None):
+        """A frame as numpy views, no copy: (Y, Cb, Cr) for "i420" / "i010", (Y, CbCr) with CbCr of shape (H / 2, W / 2, 2) for "nv12" / "p010"; uint8
+        or, for the 10-bit formats, uint16.  size = (width, height) and format default to this renderer's current output size and video format."""
+        if size is None:
+            size = self.output_size()
+        if format is None:
+            format = self.video()["format"]
+        W, H = int(size[0]), int(size[1])
+        if format not in self.VIDEO_FORMATS:
+            raise ValueError("format must be one of %s" % (self.VIDEO_FORMATS,))
+        if W <= 0 or H <= 0 or W % 2 or H % 2:
+            raise ValueError("a 4:2:0 frame has an even width and height")
+        flat = np.asarray(frame).reshape(-1).view(np.uint8)
+        if format in ("p010", "i010"):
+            flat = flat.view(np.uint16)
+        if flat.size != W * H * 3 // 2:
+            raise ValueError("the frame does not hold %d x %d samples of %s" % (W, H, format))
+        y = flat[:W * H].reshape(H, W)
+        if format in ("nv12", "p010"):
+            return y, flat[W * H:].reshape(H // 2, W // 2, 2)
+        n = (W // 2) * (H // 2)
+        return y, flat[W * H:W * H + n].reshape(H // 2, W // 2), flat[W * H + n:].reshape(H // 2, W // 2)
+
+    def render_to_video(self):
+        """Run the display and the video pack and leave the frame on the device (de_render_to_video); returns its address."""
+        if not self._textures_copied:
+            self.copy_textures()
+        p = ctypes.c_void_p()
+        check(self._lib.de_render_to_video(self._h, ctypes.byref(p)))
+        return p.value
+
+    def debug_video(self, image, format="nv12", matrix="bt709", range="limited", siting="left", mode="round", seed=0, phase=0):
+        """The conversion once on a given (W, H, 3) float32 image (de_debug_video), W and H even but free of this renderer's size; returns the frame as
+        a flat uint8 array (split_video(frame, (W, H), format) views it).  The renderer's own settings, frame and phase counter are not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (W, H, 3)")
+        W, H = image.shape[:2]
+        s = self._vd_settings(format, matrix, range, siting, mode, seed, False)
+        out = np.empty(max(W * H // 2, 1) * 3 * (2 if format in ("p010", "i010") else 1), dtype=np.uint8)
+        check(self._lib.de_debug_video(self._h, image.ctypes.data, W, H, ctypes.byref(s), ctypes.c_uint32(int(phase) & 0xffffffff), out.ctypes.data))
+        return out
+
     # ------------------------------------------------------------------ HDR display output (include/digital_earth_hdr_output.h, DESIGN.md §17)
-    HDR_GAMUTS = ("rec709", "p3d65", "rec2020")
+    HDR_GAMUTS =("rec709", "p3d65", "rec2020")
     HDR_TRANSFERS = ("linear", "pq", "hlg")
     HDR_PIXEL_FORMATS = ("rgb10a2", "rgb16")
 
