@@ -99,6 +99,13 @@ class DeVideo(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("seed", ctypes.c_uint32), ("animate", ctypes.c_int32)]
 
 
+class DeLook(ctypes.Structure):
+    """`de_look` (include/digital_earth_look.h): the look LUTs behind the display."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("enabled", ctypes.c_int32), ("interpolation", ctypes.c_int32), ("strength", ctypes.c_float),
+                ("size_1d", ctypes.c_int32), ("min_1d", ctypes.c_float * 3), ("max_1d", ctypes.c_float * 3),
+                ("size_3d", ctypes.c_int32), ("min_3d", ctypes.c_float * 3), ("max_3d", ctypes.c_float * 3)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 
@@ -262,6 +269,13 @@ VIDEO_SYMBOLS = {
     "de_debug_video": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeVideo), ctypes.c_uint32, _P]),
 }
 
+# look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
+LOOK_SYMBOLS = {
+    "de_set_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook), _P, _P]),
+    "de_get_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook)]),
+    "de_debug_look": (ctypes.c_int, [_P, _P, ctypes.c_uint64, ctypes.POINTER(DeLook), _P, _P, _P]),
+}
+
 # entry points of the legacy library only (include/digital_earth_legacy.h): bound when present
 LEGACY_SYMBOLS = {
     "de_debug_v5_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
@@ -341,7 +355,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

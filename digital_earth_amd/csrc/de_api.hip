@@ -115,6 +115,7 @@ int de_destroy(de_ctx* c) {
     if (c->h_px_stage) hipHostFree(c->h_px_stage);
     if (c->h_hpx_stage) hipHostFree(c->h_hpx_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_px_ring[k]) hipHostFree(c->h_px_ring[k]); if (c->ev_px_ring[k]) hipEventDestroy(c->ev_px_ring[k]); }
+    lk_free(c->lk_dev);
     if (c->h_vd_stage) hipHostFree(c->h_vd_stage);
     for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_vd_ring[k]) hipHostFree(c->h_vd_ring[k]); if (c->ev_vd_ring[k]) hipEventDestroy(c->ev_vd_ring[k]); }
     if (c->h_issued) hipHostFree(c->h_issued);
@@ -447,6 +448,10 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     // a device-to-host copy of the image enqueued behind the display (de_fetch_image_begin) does not hold the next frame's sums back
     HIP_TRY(hipEventRecord(c->ev_main, c->stream));
     c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
+    if (c->lk_on) {              // the look LUTs, in place on d_image; behind ev_main too: the stage reads nothing the next frame's sums write
+        lk_launch(c->stream, c->d_image, (uint64_t)c->W * (uint64_t)c->H, c->lk, c->lk_dev);
+        HIP_TRY(hipGetLastError());
+    }
     if (os_active(c)) { rc = run_output_scale(c); if (rc) return rc; }      // behind ev_main: the next frame's sums do not wait for the resampling
     if (device_image) *device_image = shown_image(c);
     return DE_OK;
@@ -1493,6 +1498,40 @@ int de_debug_video(de_ctx* c, const float* image, int W, int H, const de_video* 
     vd_launch(c->stream, (const float*)b.p[0], (uint8_t*)b.p[1], W, H, *s, vd_make_consts(s->format, s->matrix, s->range), phase);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, b.p[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+
+/* ---- look LUTs: include/digital_earth_look.h (look_kernels.hip) */
+int de_set_look(de_ctx* c, const de_look* s, const float* table_1d, const float* table_3d) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = lk_settings_check(s, table_1d, table_3d); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    de_ctx::LookDev fresh;
+    { int rc = lk_upload(c->stream, *s, table_1d, table_3d, fresh); if (rc) return rc; }
+    lk_free(c->lk_dev);           // waits for a display in flight that still reads the previous tables (a lagged fetch)
+    c->lk_dev = fresh;
+    c->lk = *s;
+    c->lk.enabled = s->enabled ? 1 : 0;
+    c->lk_on = s->enabled != 0;
+    return DE_OK;
+}
+int de_get_look(de_ctx* c, de_look* out) { return get_settings(c, &de_ctx::lk_on, &de_ctx::lk, out); }
+/* the kernel once on n host-given pixels.  Buffers of its own; the context's look is not touched. */
+int de_debug_look(de_ctx* c, const float* rgb, uint64_t n, const de_look* s, const float* table_1d, const float* table_3d, float* out) {
+    if (!c || !rgb || !s || !out || n == 0 || n > (1ull << 28)) return fail(DE_ERR_INVALID, "bad arguments (1 <= n_pixels <= 2^28)");
+    { int rc = lk_settings_check(s, table_1d, table_3d); if (rc) return rc; }
+    if (!s->size_1d && !s->size_3d) return fail(DE_ERR_INVALID, "de_look: no table");
+    HIP_TRY(hipSetDevice(c->device));
+    struct Tables { de_ctx::LookDev d; ~Tables() { lk_free(d); } } t;
+    { int rc = lk_upload(c->stream, *s, table_1d, table_3d, t.d); if (rc) return rc; }
+    DeviceBufs<1> b;
+    const size_t bytes = (size_t)n * 3 * sizeof(float);
+    HIP_TRY(hipMalloc(&b.p[0], bytes));
+    HIP_TRY(hipMemcpyAsync(b.p[0], rgb, bytes, hipMemcpyHostToDevice, c->stream));
+    lk_launch(c->stream, (float*)b.p[0], n, *s, t.d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b.p[0], bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DE_OK;
 }

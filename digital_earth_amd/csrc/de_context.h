@@ -9,6 +9,7 @@
 #include "../../include/digital_earth_output_scale.h"
 #include "../../include/digital_earth_hdr_output.h"
 #include "../../include/digital_earth_video.h"
+#include "../../include/digital_earth_look.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -39,6 +40,7 @@
 #include "local_exposure_kernels.hip"
 #include "hdr_output_kernels.hip"
 #include "videoframe_kernels.hip"
+#include "look_kernels.hip"
 
 namespace {
 
@@ -295,6 +297,16 @@ struct de_ctx {
     hipEvent_t ev_vd_ring[DE_FETCH_RING] = {};
     unsigned vd_begun = 0, vd_ended = 0;
     size_t d_vd_bytes = 0, h_vd_stage_bytes = 0, h_vd_ring_bytes[DE_FETCH_RING] = {};
+    // Look LUTs (include/digital_earth_look.h): the settings as de_set_look took them (lk_on = lk.enabled) and their tables on the
+    // device.  de_set_look uploads into fresh buffers and swaps: a refused or failed call leaves these as they were.
+    struct LookDev {              // the tables of one look and the constants of their axes
+        float* t1 = nullptr;      // [size_1d][3]
+        float4* t3 = nullptr;     // [size_3d]^3, one float4 per lattice point
+        LookAxis a1[3] = {}, a3[3] = {};
+    };
+    bool lk_on = false;
+    de_look lk = {};
+    LookDev lk_dev;
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

@@ -1,7 +1,7 @@
 // de_display.h — the host side of the display path: what runs on the context stream between the frame's sums and the image a caller is handed.
 //   * the small helpers every entry point of that path shares: host <-> device layouts, a transposed fetch, a settings getter, device scratch buffers;
 //   * each opt-in stage's allocation and launch sequence (denoiser, auto-exposure, bloom, history reprojection, local exposure), the stages behind the
-//     display (output scaling, 8-bit and HDR pixels, video frames) and the two refusals;
+//     display (look LUTs, output scaling, 8-bit and HDR pixels, video frames) and the two refusals;
 //   * display_chain: the ONE statement of the order denoise -> history -> meter -> bloom -> local exposure -> display and of its preconditions, which
 //     de_render_to_image and the four intermediate fetches of de_api.hip run up to their own stage.
 // The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, the source every stage reads display_source.h.
@@ -450,6 +450,68 @@ void vd_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int 
     VideoArgs a;
     a.image = image; a.out = out; a.W = W; a.H = H; a.format = s.format; a.siting = s.siting; a.mode = s.mode; a.seed = s.seed; a.phase = phase; a.k = k;
     hipLaunchKernelGGL(videoframe_pack_kernel, dim3((unsigned)((W + VD_TILE - 1) / VD_TILE), (unsigned)((H + VD_TILE - 1) / VD_TILE)), dim3(256), 0, stream, a);
+}
+// ---- look LUTs (include/digital_earth_look.h, look_kernels.hip): in place on the displayed image, directly behind the display launch
+// Everything de_set_look and de_debug_look refuse, in the header's order.
+int lk_settings_check(const de_look* s, const float* t1, const float* t3) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_look)) return fail(DE_ERR_INVALID, "de_look.struct_bytes does not match this library's struct");
+    if (s->interpolation < DE_LOOK_TRILINEAR || s->interpolation > DE_LOOK_TETRAHEDRAL) return fail(DE_ERR_INVALID, "de_look.interpolation must be DE_LOOK_TRILINEAR or _TETRAHEDRAL");
+    if (!(s->strength >= 0.0f && s->strength <= 1.0f)) return fail(DE_ERR_INVALID, "de_look.strength must lie in [0, 1]");      // NaN fails both
+    if (s->size_1d != 0 && (s->size_1d < 2 || s->size_1d > DE_LOOK_MAX_1D)) return fail(DE_ERR_INVALID, "de_look.size_1d must be 0 or 2 ... DE_LOOK_MAX_1D");
+    if (s->size_3d != 0 && (s->size_3d < 2 || s->size_3d > DE_LOOK_MAX_3D)) return fail(DE_ERR_INVALID, "de_look.size_3d must be 0 or 2 ... DE_LOOK_MAX_3D");
+    if (s->enabled && !s->size_1d && !s->size_3d) return fail(DE_ERR_INVALID, "de_look: the stage cannot be on without a table");
+    if ((s->size_1d && !t1) || (s->size_3d && !t3)) return fail(DE_ERR_INVALID, "de_look: a table of non-zero size is null");
+    for (int tab = 0; tab < 2; ++tab) {
+        const int N = tab ? s->size_3d : s->size_1d;
+        if (!N) continue;
+        const float* lo = tab ? s->min_3d : s->min_1d;
+        const float* hi = tab ? s->max_3d : s->max_1d;
+        for (int c = 0; c < 3; ++c)
+            if (!isfinite(lo[c]) || !isfinite(hi[c]) || !(hi[c] > lo[c]) || !isfinite(lk_scale(N, lo[c], hi[c])))
+                return fail(DE_ERR_INVALID, "de_look: a table's domain must be finite with max > min");
+        const float* t = tab ? t3 : t1;
+        const size_t n = tab ? (size_t)N * N * N * 3 : (size_t)N * 3;
+        for (size_t i = 0; i < n; ++i)
+            if (!isfinite(t[i])) return fail(DE_ERR_INVALID, "de_look: a table value is not finite");
+    }
+    return DE_OK;
+}
+void lk_free(de_ctx::LookDev& d) {      // hipFree waits for the work that reads the tables
+    if (d.t1) (void)hipFree(d.t1);
+    if (d.t3) (void)hipFree(d.t3);
+    d.t1 = nullptr; d.t3 = nullptr;
+}
+// Checked settings and tables onto the device, into `d` (empty on entry; empty again when the call fails).  The upload reads host memory that dies
+// with the caller: waited for.
+int lk_upload(hipStream_t stream, const de_look& s, const float* t1, const float* t3, de_ctx::LookDev& d) {
+    std::vector<float> wide;      // the 3D table, one float4 per lattice point; alive until the copy has been waited for
+    for (int c = 0; c < 3; ++c) {
+        if (s.size_1d) { d.a1[c].lo = s.min_1d[c]; d.a1[c].k = lk_scale(s.size_1d, s.min_1d[c], s.max_1d[c]); }
+        if (s.size_3d) { d.a3[c].lo = s.min_3d[c]; d.a3[c].k = lk_scale(s.size_3d, s.min_3d[c], s.max_3d[c]); }
+    }
+    hipError_t e = hipSuccess;
+    if (s.size_1d) {
+        const size_t bytes = (size_t)s.size_1d * 3 * sizeof(float);
+        e = hipMalloc((void**)&d.t1, bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(d.t1, t1, bytes, hipMemcpyHostToDevice, stream);
+    }
+    if (e == hipSuccess && s.size_3d) {
+        const size_t n = (size_t)s.size_3d * s.size_3d * s.size_3d;
+        wide.resize(n * 4);
+        for (size_t i = 0; i < n; ++i) { wide[4 * i] = t3[3 * i]; wide[4 * i + 1] = t3[3 * i + 1]; wide[4 * i + 2] = t3[3 * i + 2]; wide[4 * i + 3] = 0.0f; }
+        e = hipMalloc((void**)&d.t3, n * sizeof(float4));
+        if (e == hipSuccess) e = hipMemcpyAsync(d.t3, wide.data(), n * sizeof(float4), hipMemcpyHostToDevice, stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); lk_free(d); return fail(DE_ERR_HIP, std::string("look tables: ") + hipGetErrorString(e)); }
+    return DE_OK;
+}
+void lk_launch(hipStream_t stream, float* image, uint64_t n_pixels, const de_look& s, const de_ctx::LookDev& d) {
+    LookArgs a;
+    a.image = image; a.n = n_pixels; a.t1 = s.size_1d ? d.t1 : nullptr; a.t3 = s.size_3d ? d.t3 : nullptr; a.n1 = s.size_1d; a.n3 = s.size_3d;
+    a.tetrahedral = s.interpolation == DE_LOOK_TETRAHEDRAL ? 1 : 0; a.strength = s.strength;
+    for (int c = 0; c < 3; ++c) { a.a1[c] = d.a1[c]; a.a3[c] = d.a3[c]; }
+    hipLaunchKernelGGL(look_apply_kernel, dim3((unsigned)((lk_threads(n_pixels) + 255u) / 256u)), dim3(256), 0, stream, a);
 }
 
 // ---- the chain.  Where a caller leaves it: behind the stage it hands out (an intermediate fetch), or in front of the display launch.

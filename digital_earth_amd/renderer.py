@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -993,6 +993,78 @@ class Renderer:
         s = self._vd_settings(format, matrix, range, siting, mode, seed, False)
         out = np.empty(max(W * H // 2, 1) * 3 * (2 if format in ("p010", "i010") else 1), dtype=np.uint8)
         check(self._lib.de_debug_video(self._h, image.ctypes.data, W, H, ctypes.byref(s), ctypes.c_uint32(int(phase) & 0xffffffff), out.ctypes.data))
+        return out
+
+    # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h)
+    LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
+
+    @staticmethod
+    def _look_table(item, kind, what):
+        """A path or a Cube -> the Cube, of the kind the slot takes."""
+        from . import cube as cube_mod
+        if item is None:
+            return None
+        c = item if isinstance(item, cube_mod.Cube) else cube_mod.read_cube(os.fspath(item))
+        if c.kind != kind:
+            raise ValueError("%s takes a %s table, not a %s one" % (what, kind.upper(), c.kind.upper()))
+        return c
+
+    def _look_settings(self, cube, shaper, strength, interpolation, enabled):
+        """(DeLook, 1D table or None, 3D table or None); the arrays must outlive the call they are passed to."""
+        if interpolation not in self.LOOK_INTERPOLATIONS:
+            raise ValueError("interpolation must be one of %s" % (self.LOOK_INTERPOLATIONS,))
+        s = DeLook()
+        s.struct_bytes = ctypes.sizeof(DeLook)
+        s.enabled, s.interpolation, s.strength = 1 if enabled else 0, self.LOOK_INTERPOLATIONS.index(interpolation), float(strength)
+        t1 = t3 = None
+        if shaper is not None:
+            s.size_1d, s.min_1d, s.max_1d = shaper.size, (ctypes.c_float * 3)(*shaper.domain_min), (ctypes.c_float * 3)(*shaper.domain_max)
+            t1 = np.ascontiguousarray(np.frombuffer(shaper.table, dtype=np.float32))
+        if cube is not None:
+            s.size_3d, s.min_3d, s.max_3d = cube.size, (ctypes.c_float * 3)(*cube.domain_min), (ctypes.c_float * 3)(*cube.domain_max)
+            t3 = np.ascontiguousarray(np.frombuffer(cube.table, dtype=np.float32))
+        return s, t1, t3
+
+    def set_look(self, cube=None, shaper=None, strength=1.0, interpolation="tetrahedral", enabled=True):
+        """Grade the displayed image through lookup tables on the GPU, directly behind the display transform: `cube` is a 3D table, `shaper` a 1D
+        table applied ahead of it; each is the path of a .cube file, a digital_earth_amd.cube.Cube or None (no such table).  The graded pixel is
+        mixed with the ungraded one by `strength` in [0, 1] and clamped to [0, 1]; interpolation "tetrahedral" or "trilinear" is the 3D table's.
+        Every fetch of the displayed image — fetch_image, fetch_pixels, fetch_hdr_pixels, fetch_video, their views and rings,
+        render_to_image_device, behind output scaling too — delivers the graded image; fetch_hdr() and the intermediate fetches do not change.
+        The tables act on whatever signal the display wrote: load one made for that signal (an SDR look for the SDR picture, a PQ one under
+        set_hdr_output(transfer="pq")).  With neither `cube` nor `shaper` the tables of the previous call are kept: set_look(enabled=False)
+        turns the stage off, set_look() turns it on again, set_look(strength=0.5) changes the mix.  May be called while lagged fetches are in flight."""
+        if cube is None and shaper is None:
+            cube, shaper = getattr(self, "_look_held", (None, None))
+            if cube is None and shaper is None and enabled:
+                raise ValueError("set_look needs a cube or a shaper")
+        else:
+            cube, shaper = self._look_table(cube, "3d", "cube"), self._look_table(shaper, "1d", "shaper")
+        s, t1, t3 = self._look_settings(cube, shaper, strength, interpolation, enabled)
+        check(self._lib.de_set_look(self._h, ctypes.byref(s), t1.ctypes.data if t1 is not None else None, t3.ctypes.data if t3 is not None else None))
+        self._look_held = (cube, shaper)
+
+    def look(self):
+        """The look as a dict — enabled, strength, interpolation, and per table its size and domain (cube_size, cube_domain, shaper_size,
+        shaper_domain; size 0 and domain None without that table) — or None while the stage is off."""
+        s = DeLook()
+        check(self._lib.de_get_look(self._h, ctypes.byref(s)))
+        if not s.enabled:
+            return None
+        return dict(enabled=True, strength=float(s.strength), interpolation=self.LOOK_INTERPOLATIONS[s.interpolation],
+                    cube_size=int(s.size_3d), cube_domain=(tuple(s.min_3d), tuple(s.max_3d)) if s.size_3d else None,
+                    shaper_size=int(s.size_1d), shaper_domain=(tuple(s.min_1d), tuple(s.max_1d)) if s.size_1d else None)
+
+    def debug_look(self, rgb, cube=None, shaper=None, strength=1.0, interpolation="tetrahedral"):
+        """The look kernel once on (..., 3) float32 pixels (de_debug_look), with tables given as to set_look; returns the graded pixels in the same
+        shape.  The renderer's own look is not touched."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim < 1 or rgb.shape[-1] != 3:
+            raise ValueError("rgb must have shape (..., 3)")
+        s, t1, t3 = self._look_settings(self._look_table(cube, "3d", "cube"), self._look_table(shaper, "1d", "shaper"), strength, interpolation, True)
+        out = np.empty_like(rgb)
+        check(self._lib.de_debug_look(self._h, rgb.ctypes.data, ctypes.c_uint64(rgb.size // 3), ctypes.byref(s),
+                                      t1.ctypes.data if t1 is not None else None, t3.ctypes.data if t3 is not None else None, out.ctypes.data))
         return out
 
     # ------------------------------------------------------------------ HDR display output (include/digital_earth_hdr_output.h, DESIGN.md §17)
