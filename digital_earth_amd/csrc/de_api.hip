@@ -1,7 +1,7 @@
 // de_api.hip — the C ABI of libdigitalearth_hip.so (include/digital_earth.h): context life cycle, uploads, parameters, the frame loop, fetches.
 // No CPU fallback exists: every entry point needs a HIP device.  The launches are in de_launch.h, the collectives in de_rccl.h, the display path's stages
-// and their one chain in de_display.h, the context in de_context.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS
-// (legacy/).  This file holds entry points only.
+// and their one chain in de_display.h, how an output leaves the GPU (staging, rings, the packed outputs' frame) in de_fetch.h, the context in
+// de_context.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS (legacy/).  This file holds entry points only.
 #include "de_rccl.h"
 #include "de_display.h"
 
@@ -107,17 +107,13 @@ int de_destroy(de_ctx* c) {
                      c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
                      c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
                      c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
-                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_px, c->d_lx_pyr, c->d_lx_base, c->d_lx_out,
-                     c->os_tab[0].first, c->os_tab[0].w, c->os_tab[1].first, c->os_tab[1].w, c->d_os_mid, c->d_os_out, c->d_hpx, c->d_vd};
+                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_lx_pyr, c->d_lx_base, c->d_lx_out,
+                     c->os_tab[0].first.p, c->os_tab[0].w.p, c->os_tab[1].first.p, c->os_tab[1].w.p, c->os_mid.p, c->os_out.p};
     for (void* p : ptrs) if (p) hipFree(p);
-    if (c->h_stage) hipHostFree(c->h_stage);
-    for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_ring[k]) hipHostFree(c->h_ring[k]); if (c->ev_ring[k]) hipEventDestroy(c->ev_ring[k]); }
-    if (c->h_px_stage) hipHostFree(c->h_px_stage);
-    if (c->h_hpx_stage) hipHostFree(c->h_hpx_stage);
-    for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_px_ring[k]) hipHostFree(c->h_px_ring[k]); if (c->ev_px_ring[k]) hipEventDestroy(c->ev_px_ring[k]); }
+    pinned_release(c->h_stage);
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) ring_release(*r);
+    for (PackedOut* o : {&c->px_out, &c->hpx_out, &c->vd_out}) packed_release(*o);
     lk_free(c->lk_dev);
-    if (c->h_vd_stage) hipHostFree(c->h_vd_stage);
-    for (int k = 0; k < DE_FETCH_RING; ++k) { if (c->h_vd_ring[k]) hipHostFree(c->h_vd_ring[k]); if (c->ev_vd_ring[k]) hipEventDestroy(c->ev_vd_ring[k]); }
     if (c->h_issued) hipHostFree(c->h_issued);
     if (c->h_ad_count) hipHostFree(c->h_ad_count);
 #ifdef DE_LEGACY_VARIANTS
@@ -466,47 +462,18 @@ int de_fetch_image(de_ctx* c, float* out) {
 
 int de_fetch_image_view(de_ctx* c, const float** host_image) {
     if (!host_image) return fail(DE_ERR_INVALID, "host_image is null");
-    int rc = de_render_to_image(c, nullptr);
-    if (rc) return rc;
-    const size_t bytes = out_image_bytes(c);
-    if (stage_ensure(c, bytes) != hipSuccess) return fail(DE_ERR_NOMEM, "no pinned host memory for the staging buffer");
-    HIP_TRY(hipMemcpyAsync(c->h_stage, shown_image(c), bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *host_image = c->h_stage;
-    return frame_status(c);
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    return fetch_staged(c, c->h_stage, c->img.noun, de_render_to_image, out_image_bytes(c), out_image_bytes(c), host_image);
 }
 
-/* The window loop pipelined (include/digital_earth.h).  begin: the display transform of the frame as it stands and its copy into one of four pinned
- * buffers are ENQUEUED on the context stream (which waits, on the device, for the launches issued so far); the host returns at once and may issue the
- * next frame's de_accumulate — its render launch runs beside the display and the copy.  end: wait for the oldest fetch begun and hand out its image. */
+/* The window loop pipelined (include/digital_earth.h; de_fetch.h: the lagged path), through the float image's ring. */
 int de_fetch_image_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
-    if (c->fetch_begun - c->fetch_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four fetches are in flight already: de_fetch_image_end first");
-    const int k = (int)(c->fetch_begun % (unsigned)DE_FETCH_RING);
-    const size_t bytes = out_image_bytes(c);
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->h_ring[k] && c->h_ring_bytes[k] < bytes) { (void)hipHostFree(c->h_ring[k]); c->h_ring[k] = nullptr; c->h_ring_bytes[k] = 0; }      // the output size grew; cell k is not in flight
-    if (!c->h_ring[k]) {
-        if (hipHostMalloc((void**)&c->h_ring[k], bytes, hipHostMallocDefault) != hipSuccess) { c->h_ring[k] = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the staging buffers"); }
-        c->h_ring_bytes[k] = bytes;
-    }
-    if (!c->ev_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_ring[k], hipEventDisableTiming));
-    int rc = de_render_to_image(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_ring[k], shown_image(c), bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_ring[k], c->stream));
-    c->fetch_begun++;
-    return DE_OK;
+    return ring_begin(c, c->img, de_render_to_image, out_image_bytes(c), out_image_bytes(c));
 }
 int de_fetch_image_end(de_ctx* c, const float** host_image) {
     if (!c || !host_image) return fail(DE_ERR_INVALID, "null argument");
-    if (c->fetch_begun == c->fetch_ended) return fail(DE_ERR_STATE, "no fetch in flight: de_fetch_image_begin first");
-    const int k = (int)(c->fetch_ended % (unsigned)DE_FETCH_RING);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev_ring[k]));
-    c->fetch_ended++;
-    *host_image = c->h_ring[k];
-    return frame_status(c);
+    return ring_end(c, c->img, host_image);
 }
 
 int de_fetch_hdr(de_ctx* c, float* out) {
@@ -1190,42 +1157,29 @@ int de_debug_local_exposure(de_ctx* c, const float* mean, float exposure_scale, 
 int de_set_pixels(de_ctx* c, const de_pixels* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     { int rc = px_settings_check(s); if (rc) return rc; }
-    if (c->px_begun != c->px_ended) return fail(DE_ERR_STATE, "pixel fetches are in flight: de_fetch_pixels_end first");
+    { int rc = refuse_in_flight(c->px_ring); if (rc) return rc; }
     c->px = *s;
-    c->px_count = 0; c->px_last_phase = 0;
+    packed_reset(c->px_out);
     return DE_OK;
 }
 int de_get_pixels(de_ctx* c, de_pixels* out, uint32_t* last_phase) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
     *out = c->px;
-    if (last_phase) *last_phase = c->px_last_phase;
+    if (last_phase) *last_phase = c->px_out.last_phase;
     return DE_OK;
 }
 int de_render_to_pixels(de_ctx* c, const uint8_t** device_pixels) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->d_px && c->d_px_bytes < px_capacity(c)) { (void)hipFree(c->d_px); c->d_px = nullptr; c->d_px_bytes = 0; }      // the output size grew (hipFree waits for the work that reads it)
-    if (!c->d_px) { HIP_TRY(hipMalloc(&c->d_px, px_capacity(c))); c->d_px_bytes = px_capacity(c); }
-    int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
+    int rc = render_packed(c, c->px_out, px_capacity(c), c->px.animate != 0, [c](uint32_t phase) {
+        px_launch(c->stream, shown_image(c), (uint8_t*)c->px_out.dev.p, out_w(c), out_h(c), c->px, phase);
+    });
     if (rc) return rc;
-    const uint32_t phase = c->px.animate ? c->px_count : 0u;
-    px_launch(c->stream, shown_image(c), c->d_px, out_w(c), out_h(c), c->px, phase);
-    HIP_TRY(hipGetLastError());
-    c->px_count++; c->px_last_phase = phase;
-    if (device_pixels) *device_pixels = c->d_px;
+    if (device_pixels) *device_pixels = (const uint8_t*)c->px_out.dev.p;
     return DE_OK;
 }
 int de_fetch_pixels_view(de_ctx* c, const uint8_t** host) {
     if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_px_stage, &c->h_px_stage_bytes, px_capacity(c));
-    if (rc) return rc;
-    rc = de_render_to_pixels(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_px_stage, c->d_px, px_size(c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *host = c->h_px_stage;
-    return frame_status(c);
+    return fetch_staged(c, c->px_out.stage, c->px_out.noun, de_render_to_pixels, px_capacity(c), px_size(c), host);
 }
 int de_fetch_pixels(de_ctx* c, uint8_t* out, uint64_t out_bytes) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
@@ -1238,28 +1192,11 @@ int de_fetch_pixels(de_ctx* c, uint8_t* out, uint64_t out_bytes) {
 }
 int de_fetch_pixels_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
-    if (c->px_begun - c->px_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four pixel fetches are in flight already: de_fetch_pixels_end first");
-    const int k = (int)(c->px_begun % (unsigned)DE_FETCH_RING);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_px_ring[k], &c->h_px_ring_bytes[k], px_capacity(c));
-    if (rc) return rc;
-    if (!c->ev_px_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_px_ring[k], hipEventDisableTiming));
-    rc = de_render_to_pixels(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_px_ring[k], c->d_px, px_size(c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_px_ring[k], c->stream));
-    c->px_begun++;
-    return DE_OK;
+    return ring_begin(c, c->px_ring, de_render_to_pixels, px_capacity(c), px_size(c));
 }
 int de_fetch_pixels_end(de_ctx* c, const uint8_t** host) {
     if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
-    if (c->px_begun == c->px_ended) return fail(DE_ERR_STATE, "no pixel fetch in flight: de_fetch_pixels_begin first");
-    const int k = (int)(c->px_ended % (unsigned)DE_FETCH_RING);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev_px_ring[k]));
-    c->px_ended++;
-    *host = c->h_px_ring[k];
-    return frame_status(c);
+    return ring_end(c, c->px_ring, host);
 }
 /* include/digital_earth_debug.h: the conversion once on a host-given image.  Buffers of its own; the context's pixels and phase counter are not touched. */
 int de_debug_pixels(de_ctx* c, const float* image, int W, int H, const de_pixels* s, uint32_t phase, uint8_t* out) {
@@ -1284,9 +1221,7 @@ int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
-    if (c->fetch_begun != c->fetch_ended) return fail(DE_ERR_STATE, "image fetches are in flight: de_fetch_image_end first");
-    if (c->px_begun != c->px_ended) return fail(DE_ERR_STATE, "pixel fetches are in flight: de_fetch_pixels_end first");
-    if (c->vd_begun != c->vd_ended) return fail(DE_ERR_STATE, "video fetches are in flight: de_fetch_videoframe_end first");
+    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
     c->os = *s;
     c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
     return DE_OK;
@@ -1311,7 +1246,7 @@ int de_debug_output_scale(de_ctx* c, const float* image, int W, int H, const de_
     HIP_TRY(hipSetDevice(c->device));
     struct Bufs : DeviceBufs<3> {   // and the two axes' tables
         de_ctx::ScaleDev t[2];
-        ~Bufs() { for (auto& d : t) { if (d.first) hipFree(d.first); if (d.w) hipFree(d.w); } }
+        ~Bufs() { for (auto& d : t) { device_release(d.first); device_release(d.w); } }
     } b;
     const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), mid_bytes = (size_t)W * oh * 3 * sizeof(float), out_bytes = (size_t)ow * oh * 3 * sizeof(float);
     HIP_TRY(hipMalloc(&b.p[0], in_bytes));
@@ -1351,63 +1286,52 @@ int de_set_hdr_output(de_ctx* c, const de_hdr_output* s) {
     c->ho = *s;
     c->ho.on = s->on ? 1 : 0;
     hdr_output_consts((double)s->peak_nits, s->gamut, s->transfer, &c->ho_consts);
-    c->ho_count = 0; c->ho_last_phase = 0;
+    packed_reset(c->hpx_out);
     return DE_OK;
 }
 int de_get_hdr_output(de_ctx* c, de_hdr_output* out, uint32_t* last_phase) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
     *out = c->ho;
-    if (last_phase) *last_phase = c->ho_last_phase;
+    if (last_phase) *last_phase = c->hpx_out.last_phase;
     return DE_OK;
 }
 int de_render_to_hdr_pixels(de_ctx* c, const void** device_pixels) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (!c->ho.on) return fail(DE_ERR_STATE, "the HDR display output is off: de_set_hdr_output first");
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->d_hpx && c->d_hpx_bytes < hpx_capacity(c)) { (void)hipFree(c->d_hpx); c->d_hpx = nullptr; c->d_hpx_bytes = 0; }      // the output size grew (hipFree waits for the work that reads it)
-    if (!c->d_hpx) { HIP_TRY(hipMalloc(&c->d_hpx, hpx_capacity(c))); c->d_hpx_bytes = hpx_capacity(c); }
-    int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
+    int rc = render_packed(c, c->hpx_out, hpx_capacity(c), c->ho.animate != 0, [c](uint32_t phase) {
+        HdrPackArgs a;
+        a.image = shown_image(c); a.out = c->hpx_out.dev.p; a.W = out_w(c); a.H = out_h(c); a.format = c->ho.pixel_format; a.mode = c->ho.mode; a.seed = c->ho.seed; a.phase = phase;
+        hipLaunchKernelGGL(hdr_pack_kernel, dim3((unsigned)((a.W + HPX_TILE - 1) / HPX_TILE), (unsigned)((a.H + HPX_TILE - 1) / HPX_TILE)), dim3(256), 0, c->stream, a);
+    });
     if (rc) return rc;
-    const uint32_t phase = c->ho.animate ? c->ho_count : 0u;
-    HdrPackArgs a;
-    a.image = shown_image(c); a.out = c->d_hpx; a.W = out_w(c); a.H = out_h(c); a.format = c->ho.pixel_format; a.mode = c->ho.mode; a.seed = c->ho.seed; a.phase = phase;
-    hipLaunchKernelGGL(hdr_pack_kernel, dim3((unsigned)((a.W + HPX_TILE - 1) / HPX_TILE), (unsigned)((a.H + HPX_TILE - 1) / HPX_TILE)), dim3(256), 0, c->stream, a);
-    HIP_TRY(hipGetLastError());
-    c->ho_count++; c->ho_last_phase = phase;
-    if (device_pixels) *device_pixels = c->d_hpx;
+    if (device_pixels) *device_pixels = c->hpx_out.dev.p;
     return DE_OK;
 }
 int de_fetch_hdr_pixels(de_ctx* c, void* out, uint64_t out_bytes) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
     if (!c->ho.on) return fail(DE_ERR_STATE, "the HDR display output is off: de_set_hdr_output first");
     if (out_bytes < (uint64_t)hpx_size(c)) return fail(DE_ERR_INVALID, "out_bytes is smaller than width * height * 4 (RGB10A2) or * 6 (RGB16)");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_hpx_stage, &c->h_hpx_stage_bytes, hpx_capacity(c));
+    const void* host = nullptr;
+    int rc = fetch_staged(c, c->hpx_out.stage, c->hpx_out.noun, de_render_to_hdr_pixels, hpx_capacity(c), hpx_size(c), &host);
     if (rc) return rc;
-    rc = de_render_to_hdr_pixels(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_hpx_stage, c->d_hpx, hpx_size(c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    rc = frame_status(c);
-    if (rc) return rc;
-    memcpy(out, c->h_hpx_stage, hpx_size(c));
+    memcpy(out, host, hpx_size(c));
     return DE_OK;
 }
 /* ---- video frame output: include/digital_earth_video.h (videoframe_kernels.hip) */
 int de_set_video(de_ctx* c, const de_video* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     { int rc = vd_settings_check(s); if (rc) return rc; }
-    if (c->vd_begun != c->vd_ended) return fail(DE_ERR_STATE, "video fetches are in flight: de_fetch_videoframe_end first");
+    { int rc = refuse_in_flight(c->vd_ring); if (rc) return rc; }
     c->vd = *s;
     c->vd.animate = s->animate ? 1 : 0;
     c->vd_consts = vd_make_consts(s->format, s->matrix, s->range);
-    c->vd_count = 0; c->vd_last_phase = 0;
+    packed_reset(c->vd_out);
     return DE_OK;
 }
 int de_get_video(de_ctx* c, de_video* out, uint32_t* last_phase) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
     *out = c->vd;
-    if (last_phase) *last_phase = c->vd_last_phase;
+    if (last_phase) *last_phase = c->vd_out.last_phase;
     return DE_OK;
 }
 int de_videoframe_bytes(de_ctx* c, uint64_t* bytes, uint64_t* plane_offsets, uint64_t* plane_strides) {
@@ -1423,30 +1347,17 @@ int de_videoframe_bytes(de_ctx* c, uint64_t* bytes, uint64_t* plane_offsets, uin
 int de_render_to_video(de_ctx* c, const void** device_frame) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     { int rc = vd_even_check(c); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->d_vd && c->d_vd_bytes < vd_capacity(c)) { (void)hipFree(c->d_vd); c->d_vd = nullptr; c->d_vd_bytes = 0; }      // the output size grew (hipFree waits for the work that reads it)
-    if (!c->d_vd) { HIP_TRY(hipMalloc(&c->d_vd, vd_capacity(c))); c->d_vd_bytes = vd_capacity(c); }
-    int rc = de_render_to_image(c, nullptr);      // records ev_main behind the display: the next frame's sums wait for neither the conversion nor a copy
+    int rc = render_packed(c, c->vd_out, vd_capacity(c), c->vd.animate != 0, [c](uint32_t phase) {
+        vd_launch(c->stream, shown_image(c), (uint8_t*)c->vd_out.dev.p, out_w(c), out_h(c), c->vd, c->vd_consts, phase);
+    });
     if (rc) return rc;
-    const uint32_t phase = c->vd.animate ? c->vd_count : 0u;
-    vd_launch(c->stream, shown_image(c), c->d_vd, out_w(c), out_h(c), c->vd, c->vd_consts, phase);
-    HIP_TRY(hipGetLastError());
-    c->vd_count++; c->vd_last_phase = phase;
-    if (device_frame) *device_frame = c->d_vd;
+    if (device_frame) *device_frame = c->vd_out.dev.p;
     return DE_OK;
 }
 int de_fetch_videoframe_view(de_ctx* c, const void** host) {
     if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
     { int rc = vd_even_check(c); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_vd_stage, &c->h_vd_stage_bytes, vd_capacity(c));
-    if (rc) return rc;
-    rc = de_render_to_video(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_vd_stage, c->d_vd, vd_size(c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *host = c->h_vd_stage;
-    return frame_status(c);
+    return fetch_staged(c, c->vd_out.stage, c->vd_out.noun, de_render_to_video, vd_capacity(c), vd_size(c), host);
 }
 int de_fetch_video(de_ctx* c, void* out, uint64_t out_bytes) {
     if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
@@ -1461,28 +1372,11 @@ int de_fetch_video(de_ctx* c, void* out, uint64_t out_bytes) {
 int de_fetch_videoframe_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     { int rc = vd_even_check(c); if (rc) return rc; }
-    if (c->vd_begun - c->vd_ended >= (unsigned)DE_FETCH_RING) return fail(DE_ERR_STATE, "four video fetches are in flight already: de_fetch_videoframe_end first");
-    const int k = (int)(c->vd_begun % (unsigned)DE_FETCH_RING);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = px_host_alloc(&c->h_vd_ring[k], &c->h_vd_ring_bytes[k], vd_capacity(c));
-    if (rc) return rc;
-    if (!c->ev_vd_ring[k]) HIP_TRY(hipEventCreateWithFlags(&c->ev_vd_ring[k], hipEventDisableTiming));
-    rc = de_render_to_video(c, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->h_vd_ring[k], c->d_vd, vd_size(c), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_vd_ring[k], c->stream));
-    c->vd_begun++;
-    return DE_OK;
+    return ring_begin(c, c->vd_ring, de_render_to_video, vd_capacity(c), vd_size(c));
 }
 int de_fetch_videoframe_end(de_ctx* c, const void** host) {
     if (!c || !host) return fail(DE_ERR_INVALID, "null argument");
-    if (c->vd_begun == c->vd_ended) return fail(DE_ERR_STATE, "no video fetch in flight: de_fetch_videoframe_begin first");
-    const int k = (int)(c->vd_ended % (unsigned)DE_FETCH_RING);
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev_vd_ring[k]));
-    c->vd_ended++;
-    *host = c->h_vd_ring[k];
-    return frame_status(c);
+    return ring_end(c, c->vd_ring, host);
 }
 /* the conversion once on a host-given image of any even size.  Buffers of its own; the context's frame and phase counter are not touched. */
 int de_debug_video(de_ctx* c, const float* image, int W, int H, const de_video* s, uint32_t phase, void* out) {

@@ -69,6 +69,23 @@ struct LaunchSlot {
     uint64_t seen_render = 0, seen_hdr = 0;
 };
 
+// What a fetch leaves the GPU through.  Plain state: de_fetch.h holds every operation on it (ensure, release, begin, end, the synchronous path), once.
+struct PinnedBuf { void* p = nullptr; size_t bytes = 0; };      // pinned host memory and its size
+struct DeviceBuf { void* p = nullptr; size_t bytes = 0; };      // device memory and its size
+struct FetchRing {                       // the lagged fetches of one output: begun - ended = fetches in flight, at most DE_FETCH_RING
+    const char* noun;                    // for messages: "pixel", and the entry points' stem, "de_fetch_pixels" (+ "_begin" / "_end")
+    const char* entry;
+    PinnedBuf cell[DE_FETCH_RING];       // fetch n is copied into cell n % DE_FETCH_RING ...
+    hipEvent_t ev[DE_FETCH_RING] = {};   // ... and its event recorded behind the copy
+    unsigned begun = 0, ended = 0;       // calls of _begin and of _end
+};
+struct PackedOut {                       // an output converted from the displayed image: 8-bit pixels, HDR pixels, video frames
+    const char* noun;
+    DeviceBuf dev;                       // the packed output; sized for the largest format at the output size, so that a change of format frees nothing
+    PinnedBuf stage;                     // where a synchronous fetch lands
+    uint32_t count = 0, last_phase = 0;  // conversions since the settings were set; the dither phase of the newest
+};
+
 struct DevTexture {
     int w = 0, h = 0, ch = 0;
     uint8_t* linear = nullptr;    // as uploaded: [h][w][ch]
@@ -126,14 +143,9 @@ struct de_ctx {
     float* d_hdr_own = nullptr;
     float* d_image = nullptr;    // (W, H, 3)
     float* d_scratch = nullptr;  // (W, H, 3) / debug [H][W][4]
-    float* h_stage = nullptr;     // pinned host staging for fetch_image / fetch_hdr (a pageable destination copies at a fraction of the link rate)
-    size_t h_stage_bytes = 0;     // its size: W * H * 3 floats, or the output size's when that is larger (include/digital_earth_output_scale.h)
-    // de_fetch_image_begin / _end: the window loop pipelined — display + device-to-host copy of frame k run on the context stream while launch k + 1 renders.
-    // DE_FETCH_RING pinned buffers and events; fetch_begun / fetch_ended count the calls (begun - ended = fetches in flight, at most DE_FETCH_RING).
-    float* h_ring[DE_FETCH_RING] = {};
-    size_t h_ring_bytes[DE_FETCH_RING] = {};
-    hipEvent_t ev_ring[DE_FETCH_RING] = {};
-    unsigned fetch_begun = 0, fetch_ended = 0;
+    PinnedBuf h_stage;            // copy_out's and de_fetch_image_view's staging (a pageable destination copies at a fraction of the link rate): W * H * 3 floats, or the output size's when that is larger
+    // de_fetch_image_begin / _end: the window loop pipelined — display + device-to-host copy of frame k run on the context stream while launch k + 1 renders (de_fetch.h).
+    FetchRing img = {"image", "de_fetch_image"};
     uint32_t* d_tiles = nullptr;
     int n_tiles = 0, tiles_rank = -1, tiles_world = -1;
     unsigned long long* d_counters = nullptr;
@@ -243,17 +255,11 @@ struct de_ctx {
     int hs_cur = 0;
     float* d_hs_out = nullptr;      // [H][W][3]
     // 8-bit pixel output (include/digital_earth_pixels.h).  Allocated on first use, each for 4 channels so that de_set_pixels never frees a
-    // buffer a caller may still read: W * H * 4 bytes on the device, and as much pinned per staging buffer and ring cell (five in all, W * H * channels of
-    // each in use); a ring, counters and events of its own, independent of the float image's.
+    // buffer a caller may still read: W * H * 4 bytes on the device, and as much pinned for the staging buffer and per ring cell (W * H * channels of each
+    // in use).  The ring is independent of the float image's.
     de_pixels px = {(uint32_t)sizeof(de_pixels), 4, DE_PIXELS_TRUNCATE, 0u, 0};      // the settings
-    uint32_t px_count = 0;          // conversions since de_set_pixels
-    uint32_t px_last_phase = 0;     // the phase of the newest conversion
-    uint8_t* d_px = nullptr;        // [H][W][channels]
-    uint8_t* h_px_stage = nullptr;
-    uint8_t* h_px_ring[DE_FETCH_RING] = {};
-    hipEvent_t ev_px_ring[DE_FETCH_RING] = {};
-    unsigned px_begun = 0, px_ended = 0;
-    size_t d_px_bytes = 0, h_px_stage_bytes = 0, h_px_ring_bytes[DE_FETCH_RING] = {};      // sized from the output size: a buffer too small for a new one is re-allocated
+    PackedOut px_out = {"pixel"};   // [H][W][channels]
+    FetchRing px_ring = {"pixel", "de_fetch_pixels"};
     // Local exposure (include/digital_earth_local_exposure.h).  Allocated on first use: the float2 pyramid D_1 .. D_L (l w, w) and the f32
     // bases B_1 .. B_{L-1} of the largest L the image admits (5.5 + 2.8 MB at 1080p) and the dodged mean that the display reads with samples = 1 (25 MB
     // at 1080p).  Per context.
@@ -266,37 +272,23 @@ struct de_ctx {
     // w[taps][n_dst] each), the intermediate (W, oh, 3) and the output (ow, oh, 3); re-allocated when a new size needs more.  Per context.
     de_output_scale os = {(uint32_t)sizeof(de_output_scale), 0, 0, 0, DE_SCALE_LANCZOS3};      // the settings; width = height = 0 until the first set: W, H
     struct ScaleDev {               // one axis' table on the device, and what it was built for
-        int32_t* first = nullptr;
-        float* w = nullptr;
-        size_t first_cap = 0, w_cap = 0;      // elements
+        DeviceBuf first, w;             // int32_t first[n_dst], float w[taps][n_dst]
         int n_src = 0, n_dst = 0, filter = -1, taps = 0;
     } os_tab[2];                    // [0] along v, [1] along u
-    float* d_os_mid = nullptr;
-    float* d_os_out = nullptr;
-    size_t os_mid_bytes = 0, os_out_bytes = 0;
+    DeviceBuf os_mid, os_out;
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.
     de_hdr_output ho = {(uint32_t)sizeof(de_hdr_output), 0, 1000.0f, DE_HDR_GAMUT_REC2020, DE_HDR_TRANSFER_PQ, DE_HDR_PIXELS_RGB10A2, DE_PIXELS_TRUNCATE, 0u, 0};
     HdrConsts ho_consts = {};       // of `ho`; valid while ho.on
-    uint32_t ho_count = 0;          // conversions since de_set_hdr_output
-    uint32_t ho_last_phase = 0;
-    void* d_hpx = nullptr;
-    uint8_t* h_hpx_stage = nullptr;
-    size_t d_hpx_bytes = 0, h_hpx_stage_bytes = 0;
+    PackedOut hpx_out = {"HDR pixel"};
     // Video frame output (include/digital_earth_video.h).  The constants of the settings are computed by de_set_video and travel in the
     // kernel's arguments.  Allocated on first use, each for the 10-bit formats (out_w * out_h * 3 bytes) so that de_set_video never frees a buffer a caller
-    // may still read: the frame on the device, one pinned staging buffer and four pinned ring cells; a ring, counters and events of its own.
+    // may still read: the frame on the device, one pinned staging buffer and four pinned ring cells.  The ring is independent of the other two.
     de_video vd = {(uint32_t)sizeof(de_video), DE_VIDEO_NV12, DE_VIDEO_MATRIX_BT709, DE_VIDEO_RANGE_LIMITED, DE_VIDEO_SITING_LEFT, DE_PIXELS_ROUND, 0u, 0};
     VideoConsts vd_consts = vd_make_consts(DE_VIDEO_NV12, DE_VIDEO_MATRIX_BT709, DE_VIDEO_RANGE_LIMITED);      // of `vd`: once per de_set_video
-    uint32_t vd_count = 0;          // conversions since de_set_video
-    uint32_t vd_last_phase = 0;
-    uint8_t* d_vd = nullptr;
-    uint8_t* h_vd_stage = nullptr;
-    uint8_t* h_vd_ring[DE_FETCH_RING] = {};
-    hipEvent_t ev_vd_ring[DE_FETCH_RING] = {};
-    unsigned vd_begun = 0, vd_ended = 0;
-    size_t d_vd_bytes = 0, h_vd_stage_bytes = 0, h_vd_ring_bytes[DE_FETCH_RING] = {};
+    PackedOut vd_out = {"video"};
+    FetchRing vd_ring = {"video", "de_fetch_videoframe"};
     // Look LUTs (include/digital_earth_look.h): the settings as de_set_look took them (lk_on = lk.enabled) and their tables on the
     // device.  de_set_look uploads into fresh buffers and swaps: a refused or failed call leaves these as they were.
     struct LookDev {              // the tables of one look and the constants of their axes

@@ -1,12 +1,13 @@
 // de_display.h — the host side of the display path: what runs on the context stream between the frame's sums and the image a caller is handed.
-//   * the small helpers every entry point of that path shares: host <-> device layouts, a transposed fetch, a settings getter, device scratch buffers;
+//   * the small helpers every entry point of that path shares: host <-> device layouts, a transposed fetch, a settings getter, device scratch buffers
+//     (how an output leaves the GPU — staging, the rings, the packed outputs' conversion frame — is de_fetch.h);
 //   * each opt-in stage's allocation and launch sequence (denoiser, auto-exposure, bloom, history reprojection, local exposure), the stages behind the
 //     display (look LUTs, output scaling, 8-bit and HDR pixels, video frames) and the two refusals;
 //   * display_chain: the ONE statement of the order denoise -> history -> meter -> bloom -> local exposure -> display and of its preconditions, which
 //     de_render_to_image and the four intermediate fetches of de_api.hip run up to their own stage.
 // The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, the source every stage reads display_source.h.
 #pragma once
-#include "de_launch.h"
+#include "de_fetch.h"
 #include "../../include/digital_earth_denoise.h"
 
 namespace {
@@ -322,7 +323,7 @@ bool os_active(const de_ctx* c) { return c->os.enabled && c->os.width > 0 && (c-
 int out_w(const de_ctx* c) { return os_active(c) ? c->os.width : c->W; }
 int out_h(const de_ctx* c) { return os_active(c) ? c->os.height : c->H; }
 size_t out_image_bytes(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3 * sizeof(float); }
-const float* shown_image(const de_ctx* c) { return os_active(c) ? c->d_os_out : c->d_image; }
+const float* shown_image(const de_ctx* c) { return os_active(c) ? (const float*)c->os_out.p : c->d_image; }
 // The settings against a source size; *ow, *oh = the output size they ask for (0, 0: the source's).
 int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) {
     if (s->struct_bytes != (uint32_t)sizeof(de_output_scale)) return fail(DE_ERR_INVALID, "de_output_scale.struct_bytes does not match this library's struct");
@@ -334,29 +335,18 @@ int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) 
     *ow = w; *oh = h;
     return DE_OK;
 }
-// A device buffer of at least `bytes`: one that is too small is replaced (hipFree waits for the work that reads it).
-int os_device_ensure(void** p, size_t* have, size_t bytes) {
-    if (*p && *have >= bytes) return DE_OK;
-    if (*p) { (void)hipFree(*p); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no device memory for the output scaling's buffers"); }
-    *have = bytes;
-    return DE_OK;
-}
 // One axis' table on the device, rebuilt only when the axis or the filter changed.  The upload reads pageable host memory that dies with this call: waited for.
 int os_table_ensure(hipStream_t stream, de_ctx::ScaleDev& d, int n_src, int n_dst, int filter) {
-    if (d.first && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
+    if (d.first.p && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
     ScaleTable T;
     if (!os_build_table(n_src, n_dst, filter, &T)) return fail(DE_ERR_INVALID, "output scaling: no table for this pair of sizes");
-    size_t fb = d.first_cap * sizeof(int32_t), wb = d.w_cap * sizeof(float);
-    int rc = os_device_ensure((void**)&d.first, &fb, T.first.size() * sizeof(int32_t));
-    d.first_cap = fb / sizeof(int32_t);
+    int rc = device_ensure(d.first, T.first.size() * sizeof(int32_t), "output scaling's");
     if (rc) return rc;
-    rc = os_device_ensure((void**)&d.w, &wb, T.w.size() * sizeof(float));
-    d.w_cap = wb / sizeof(float);
+    rc = device_ensure(d.w, T.w.size() * sizeof(float), "output scaling's");
     if (rc) return rc;
     d.filter = -1;
-    HIP_TRY(hipMemcpyAsync(d.first, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d.w, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d.first.p, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d.w.p, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     d.n_src = n_src; d.n_dst = n_dst; d.filter = filter; d.taps = T.taps;
     return DE_OK;
@@ -366,7 +356,7 @@ int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh
     const float* in = src;
     if (oh != H) {
         ScaleArgs a;
-        a.src = in; a.dst = ow != W ? mid : out; a.first = tv.first; a.w = tv.w; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
+        a.src = in; a.dst = ow != W ? mid : out; a.first = (const int32_t*)tv.first.p; a.w = (const float*)tv.w.p; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
         const unsigned long long blocks = (unsigned long long)W * (unsigned long long)os_v_tiles(oh);
         if (blocks * OS_V_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the image has too many columns for one launch");
         hipLaunchKernelGGL(output_scale_v_kernel, dim3((unsigned)blocks), dim3(OS_V_THREADS), 0, stream, a);
@@ -375,7 +365,7 @@ int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh
     }
     if (ow != W) {
         ScaleArgs a;
-        a.src = in; a.dst = out; a.first = tu.first; a.w = tu.w; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
+        a.src = in; a.dst = out; a.first = (const int32_t*)tu.first.p; a.w = (const float*)tu.w.p; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
         const unsigned long long blocks = (unsigned long long)ow * (unsigned long long)os_u_chunks(oh * 3);
         if (blocks * OS_U_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the output has too many columns for one launch");
         hipLaunchKernelGGL(output_scale_u_kernel, dim3((unsigned)blocks), dim3(OS_U_THREADS), 0, stream, a);
@@ -383,16 +373,16 @@ int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh
     }
     return DE_OK;
 }
-// Behind the display on the context stream: d_image -> d_os_out.
+// Behind the display on the context stream: d_image -> os_out.
 int run_output_scale(de_ctx* c) {
     const int W = c->W, H = c->H, ow = c->os.width, oh = c->os.height;
     int rc = DE_OK;
     if (oh != H) { rc = os_table_ensure(c->stream, c->os_tab[0], H, oh, c->os.filter); if (rc) return rc; }
     if (ow != W) { rc = os_table_ensure(c->stream, c->os_tab[1], W, ow, c->os.filter); if (rc) return rc; }
-    if (oh != H && ow != W) { rc = os_device_ensure((void**)&c->d_os_mid, &c->os_mid_bytes, (size_t)W * (size_t)oh * 3 * sizeof(float)); if (rc) return rc; }
-    rc = os_device_ensure((void**)&c->d_os_out, &c->os_out_bytes, (size_t)ow * (size_t)oh * 3 * sizeof(float));
+    if (oh != H && ow != W) { rc = device_ensure(c->os_mid, (size_t)W * (size_t)oh * 3 * sizeof(float), "output scaling's"); if (rc) return rc; }
+    rc = device_ensure(c->os_out, (size_t)ow * (size_t)oh * 3 * sizeof(float), "output scaling's");
     if (rc) return rc;
-    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], c->d_os_mid, c->d_os_out);
+    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], (float*)c->os_mid.p, (float*)c->os_out.p);
 }
 // ---- 8-bit pixel output (include/digital_earth_pixels.h, pixels_kernels.hip)
 size_t px_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (size_t)c->px.channels; }      // of the output size (include/digital_earth_output_scale.h): W x H while that stage is off
@@ -401,14 +391,6 @@ int px_settings_check(const de_pixels* s) {
     if (s->struct_bytes != (uint32_t)sizeof(de_pixels)) return fail(DE_ERR_INVALID, "de_pixels.struct_bytes does not match this library's struct");
     if (s->channels != 3 && s->channels != 4) return fail(DE_ERR_INVALID, "de_pixels.channels must be 3 or 4");
     if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_pixels.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
-    return DE_OK;
-}
-int px_host_alloc(uint8_t** p, size_t* have, size_t bytes) {      // one that is too small for a new output size is replaced: no copy into it is in flight
-    if (*p && *have < bytes) { (void)hipHostFree(*p); *p = nullptr; *have = 0; }
-    if (!*p) {
-        if (hipHostMalloc((void**)p, bytes, hipHostMallocDefault) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no pinned host memory for the pixel staging buffers"); }
-        *have = bytes;
-    }
     return DE_OK;
 }
 void px_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_pixels& s, uint32_t phase) {

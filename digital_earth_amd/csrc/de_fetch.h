@@ -1,0 +1,143 @@
+// de_fetch.h — how an output leaves the GPU, each mechanism stated once (the state they work on is in de_context.h: PinnedBuf, DeviceBuf, FetchRing, PackedOut):
+//   * the ring arithmetic of the lagged fetches, plain integers;
+//   * a pinned host buffer and a device buffer "of at least n bytes";
+//   * copy_out: device -> caller's buffer through the context's staging buffer;
+//   * the conversion frame of the packed outputs (8-bit pixels, HDR pixels, video frames): allocate, display, phase, launch, count;
+//   * the synchronous path (render, copy, wait) and the lagged one (begin: render, copy, record; end: wait, hand out).
+// The entry points of de_api.hip check their own arguments and call one of these.
+#pragma once
+
+// ---- ring arithmetic.  No HIP: tools/fetch_ring_host_check.cpp compiles this part alone (DE_FETCH_STANDALONE) under the address and undefined-behaviour
+// sanitizers.  `begun` and `ended` count the calls of _begin and _end and wrap at 2^32, a multiple of the depth (a power of two): across the wrap their
+// difference is still the number of fetches in flight, and each of them modulo the depth still visits the cells in the one order 0, 1, .., depth - 1, 0, ..
+inline unsigned ring_in_flight(unsigned begun, unsigned ended) { return begun - ended; }
+inline bool ring_full(unsigned begun, unsigned ended, unsigned depth) { return begun - ended >= depth; }      // _begin refuses
+inline bool ring_empty(unsigned begun, unsigned ended) { return begun == ended; }                            // _end refuses
+inline int ring_cell(unsigned calls, unsigned depth) { return (int)(calls % depth); }                        // of `begun`: the cell _begin fills; of `ended`: the cell _end hands out
+
+#ifndef DE_FETCH_STANDALONE
+#include "de_launch.h"
+
+namespace {
+static_assert((DE_FETCH_RING & (DE_FETCH_RING - 1)) == 0, "the ring's depth must divide 2^32 (ring arithmetic above)");
+
+// ---- a pinned host buffer of at least `bytes`: one that is too small (the output size grew, include/digital_earth_output_scale.h) is replaced.  The
+// callers see to it that no copy into it is in flight: a staging buffer's copy is waited for before its call returns, a ring cell being filled is not in flight.
+void pinned_release(PinnedBuf& b) {
+    if (b.p) (void)hipHostFree(b.p);
+    b = PinnedBuf();
+}
+hipError_t pinned_ensure(PinnedBuf& b, size_t bytes) {
+    if (b.p && b.bytes >= bytes) return hipSuccess;
+    pinned_release(b);
+    hipError_t e = hipHostMalloc(&b.p, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return e; }
+    b.bytes = bytes;
+    return hipSuccess;
+}
+int pinned_ensure(PinnedBuf& b, size_t bytes, const char* noun, const char* what) {
+    if (pinned_ensure(b, bytes) != hipSuccess) return fail(DE_ERR_NOMEM, std::string("no pinned host memory for the ") + noun + " " + what);
+    return DE_OK;
+}
+// ---- a device buffer of at least `bytes`: one that is too small is replaced (hipFree waits for the work that reads it).
+void device_release(DeviceBuf& b) {
+    if (b.p) (void)hipFree(b.p);
+    b = DeviceBuf();
+}
+int device_ensure(DeviceBuf& b, size_t bytes, const char* noun) {
+    if (b.p && b.bytes >= bytes) return DE_OK;
+    device_release(b);
+    if (hipMalloc(&b.p, bytes) != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, std::string("no device memory for the ") + noun + " buffers"); }
+    b.bytes = bytes;
+    return DE_OK;
+}
+
+// device (W*H*3 floats, or `bytes`) -> caller's buffer through the pinned staging buffer; straight into the caller's pageable memory when none can be had
+int copy_out(de_ctx* c, float* out, const float* d_src, size_t bytes = 0) {
+    if (!bytes) bytes = (size_t)c->W * c->H * 3 * sizeof(float);
+    const bool staged = pinned_ensure(c->h_stage, bytes) == hipSuccess;
+    HIP_TRY(hipMemcpyAsync(staged ? c->h_stage.p : out, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (staged) memcpy(out, c->h_stage.p, bytes);
+    return frame_status(c);
+}
+
+// ---- the packed outputs.  One conversion: the displayed image, then `launch(phase)` packs it into o.dev.  de_render_to_image records ev_main behind the
+// display and ahead of everything enqueued here and by the fetches below — the pack, the copy — so the next frame's sums wait for neither.  The dither
+// phase is the number of conversions since the settings were set while they animate, 0 otherwise.
+template <class Launch>
+int render_packed(de_ctx* c, PackedOut& o, size_t capacity, bool animate, Launch launch) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = device_ensure(o.dev, capacity, o.noun);
+    if (rc) return rc;
+    rc = de_render_to_image(c, nullptr);
+    if (rc) return rc;
+    const uint32_t phase = animate ? o.count : 0u;
+    launch(phase);
+    HIP_TRY(hipGetLastError());
+    o.count++; o.last_phase = phase;
+    return DE_OK;
+}
+void packed_reset(PackedOut& o) { o.count = 0; o.last_phase = 0; }      // new settings
+void packed_release(PackedOut& o) { device_release(o.dev); pinned_release(o.stage); }
+
+// ---- the synchronous path.  `render` is an output's de_render_to_* entry point: it enqueues the frame as it stands and answers where on the device it
+// lies.  `size` bytes of it are copied into `stage`, which holds `capacity` (the largest format: a change of format re-allocates nothing), and waited for.
+template <class T, class H>
+int fetch_staged(de_ctx* c, PinnedBuf& stage, const char* noun, int (*render)(de_ctx*, const T**), size_t capacity, size_t size, const H** host) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = pinned_ensure(stage, capacity, noun, "staging buffer");
+    if (rc) return rc;
+    const T* src = nullptr;
+    rc = render(c, &src);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(stage.p, src, size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *host = (const H*)stage.p;
+    return frame_status(c);
+}
+
+// ---- the lagged path (include/digital_earth.h: the window loop pipelined).  begin: the frame as it stands and its copy into the ring's next cell are
+// ENQUEUED on the context stream (which waits, on the device, for the launches issued so far); the host returns at once and may issue the next frame's
+// de_accumulate — its render launch runs beside the display, the pack and the copy.  end: wait for the oldest fetch begun and hand out its cell.
+unsigned in_flight(const FetchRing& r) { return ring_in_flight(r.begun, r.ended); }
+int refuse_in_flight(const FetchRing& r) {      // what changes the size or the format of a ring's cells waits for them
+    if (in_flight(r)) return fail(DE_ERR_STATE, std::string(r.noun) + " fetches are in flight: " + r.entry + "_end first");
+    return DE_OK;
+}
+template <class T>
+int ring_begin(de_ctx* c, FetchRing& r, int (*render)(de_ctx*, const T**), size_t capacity, size_t size) {
+    if (ring_full(r.begun, r.ended, DE_FETCH_RING)) return fail(DE_ERR_STATE, std::string("four ") + r.noun + " fetches are in flight already: " + r.entry + "_end first");
+    const int k = ring_cell(r.begun, DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = pinned_ensure(r.cell[k], capacity, r.noun, "ring");      // cell k is not in flight
+    if (rc) return rc;
+    if (!r.ev[k]) HIP_TRY(hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
+    const T* src = nullptr;
+    rc = render(c, &src);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(r.cell[k].p, src, size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(r.ev[k], c->stream));
+    r.begun++;
+    return DE_OK;
+}
+template <class H>
+int ring_end(de_ctx* c, FetchRing& r, const H** host) {
+    if (ring_empty(r.begun, r.ended)) return fail(DE_ERR_STATE, std::string("no ") + r.noun + " fetch in flight: " + r.entry + "_begin first");
+    const int k = ring_cell(r.ended, DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(r.ev[k]));
+    r.ended++;
+    *host = (const H*)r.cell[k].p;
+    return frame_status(c);
+}
+void ring_release(FetchRing& r) {
+    for (int k = 0; k < DE_FETCH_RING; ++k) {
+        pinned_release(r.cell[k]);
+        if (r.ev[k]) hipEventDestroy(r.ev[k]);
+        r.ev[k] = nullptr;
+    }
+}
+
+}  // namespace
+#endif  // DE_FETCH_STANDALONE

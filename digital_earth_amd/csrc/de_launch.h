@@ -378,32 +378,6 @@ hipError_t launch_render(de_ctx* c, const RenderArgs& a, hipStream_t stream, Pre
     return hipGetLastError();
 }
 
-// The pinned staging buffer holds at least `bytes`: one that is too small (the output size grew, include/digital_earth_output_scale.h) is replaced.  Every
-// copy into it is waited for before its call returns, so none is in flight here.
-hipError_t stage_ensure(de_ctx* c, size_t bytes) {
-    if (c->h_stage && c->h_stage_bytes < bytes) { (void)hipHostFree(c->h_stage); c->h_stage = nullptr; c->h_stage_bytes = 0; }
-    if (c->h_stage) return hipSuccess;
-    hipError_t e = hipHostMalloc((void**)&c->h_stage, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { c->h_stage = nullptr; (void)hipGetLastError(); return e; }
-    c->h_stage_bytes = bytes;
-    return hipSuccess;
-}
-
-// device (W*H*3 floats, or `bytes`) -> caller's buffer through the pinned staging buffer
-int copy_out(de_ctx* c, float* out, const float* d_src, size_t bytes = 0) {
-    if (!bytes) bytes = (size_t)c->W * c->H * 3 * sizeof(float);
-    (void)stage_ensure(c, bytes);
-    if (c->h_stage) {
-        HIP_TRY(hipMemcpyAsync(c->h_stage, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memcpy(out, c->h_stage, bytes);
-    } else {
-        HIP_TRY(hipMemcpyAsync(out, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return frame_status(c);
-}
-
 // The launches of one de_accumulate call on the product's kernels.  `spp` = the samples per pixel THIS context renders of the call (all of
 // them, or its share of a sample partition), `first_index` = the frame's sample index of the first one (the others follow at a.spp_stride).
 //   * render_kernel_v6 (one persistent launch per call, stage queues in LDS) for calls of at least auto_v6_min_items paths, or when forced;

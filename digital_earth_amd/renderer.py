@@ -68,6 +68,59 @@ class _StagingView(np.ndarray):
         self._owner = getattr(obj, "_owner", None)
 
 
+class _FetchRing:
+    """One output's fetches (csrc/de_fetch.h is the native side): synchronous, into a fresh array or as a view of the library's staging buffer, and
+    lagged through the output's ring of four.  Holds what the lag protocol needs: the fetches in flight, what `capture` answered at the newest begin
+    (the setters that would change it are refused while fetches are in flight: it holds for every one of them) and a weak reference to the last view
+    handed out, so that close() can refuse while it is referenced.  `array(ptr, captured)` is the output's shape rule, a method of the Renderer
+    (_staging_view, _pixel_view, _vd_view): the array over the library's buffer at `ptr`, or a fresh one of that shape (ptr None).  The Renderer
+    and its method are passed in, not kept: no reference cycle."""
+
+    def __init__(self, lib, stem, fetch, ctype, capture, name, busy):
+        self._begin, self._end, self._view, self._fetch = (getattr(lib, n) for n in (stem + "_begin", stem + "_end", stem + "_view", fetch))
+        self._sized = len(self._fetch.argtypes) == 3      # de_fetch_pixels / de_fetch_video take the size of `out`
+        self._ctype, self._capture, self.name, self._busy = ctype, capture, name, busy
+        self.in_flight, self.captured, self.view_ref = 0, None, None
+
+    def view(self, r, array, ptr, captured):
+        view = array(ptr, captured).view(_StagingView)
+        view.flags.writeable = False
+        view._owner = r                            # the memory belongs to the context: the view keeps its Renderer alive ...
+        self.view_ref = weakref.ref(view)          # ... and close() refuses while the view is
+        return view
+
+    def fetch(self, r, array, copy, lag):
+        if not r._textures_copied:
+            r.copy_textures()
+        if lag not in (0, 1, 2, 3):
+            raise ValueError("lag must be 0 ... 3")
+        captured = self._capture(r)
+        if lag:
+            check(self._begin(r._h))
+            self.in_flight += 1
+            self.captured = captured
+            return None if self.in_flight <= lag else self.end(r, array, copy)
+        if self.in_flight:
+            raise RuntimeError(self._busy)
+        if not copy:
+            ptr = ctypes.POINTER(self._ctype)()
+            check(self._view(r._h, ctypes.byref(ptr)))
+            return self.view(r, array, ptr, captured)
+        out = array(None, captured)
+        check(self._fetch(r._h, out.ctypes.data, *((ctypes.c_uint64(out.nbytes),) if self._sized else ())))
+        return out
+
+    def end(self, r, array, copy):
+        ptr = ctypes.POINTER(self._ctype)()
+        self.in_flight -= 1
+        check(self._end(r._h, ctypes.byref(ptr)))
+        view = self.view(r, array, ptr, self.captured)
+        return np.array(view) if copy else view
+
+    def referenced(self):
+        return self.view_ref is not None and self.view_ref() is not None
+
+
 class Renderer:
     """GPU implementation of the reference `Renderer` (renderer.py:15-401).
 
@@ -93,6 +146,12 @@ class Renderer:
         self.seed = int(seed)
         self.tile_rank, self.tile_world = 0, 1
         self._h = ctypes.c_void_p()
+        self._image_ring = _FetchRing(self._lib, "de_fetch_image", "de_fetch_image", ctypes.c_float, lambda r: None, "fetch_image",
+                                      "lagged fetches are in flight: fetch_pending() first")
+        self._pixel_ring = _FetchRing(self._lib, "de_fetch_pixels", "de_fetch_pixels", ctypes.c_uint8, lambda r: r.pixels()["channels"], "fetch_pixels",
+                                      "lagged pixel fetches are in flight: fetch_pending(pixels=True) first")
+        self._vd_ring = _FetchRing(self._lib, "de_fetch_videoframe", "de_fetch_video", ctypes.c_uint8, Renderer._vd_bytes, "fetch_video",
+                                   "lagged video fetches are in flight: fetch_pending(video=True) first")
         check(self._lib.de_create(int(device), self.image_res[0], self.image_res[1], ctypes.byref(self._h)))
         _native.apply_env_tuning(self._h)      # experiment overrides (DE_KERNEL, DE_V6_* ...): read HERE, not in the library
         self._params = DeParams()
@@ -137,15 +196,9 @@ class Renderer:
         """de_destroy.  Fails (DigitalEarthError, DE_ERR_STATE) while another Renderer still borrows this one's maps, and (RuntimeError)
         while a zero-copy image of fetch_image(copy=False) is still referenced: that array IS the context's pinned staging buffer."""
         if getattr(self, "_h", None):
-            ref = getattr(self, "_view_ref", None)
-            if ref is not None and ref() is not None:
-                raise RuntimeError("a fetch_image(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
-            ref = getattr(self, "_pixel_view_ref", None)
-            if ref is not None and ref() is not None:
-                raise RuntimeError("a fetch_pixels(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
-            ref = getattr(self, "_vd_view_ref", None)
-            if ref is not None and ref() is not None:
-                raise RuntimeError("a fetch_video(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
+            for ring in (self._image_ring, self._pixel_ring, self._vd_ring):
+                if ring.referenced():
+                    raise RuntimeError("a %s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % ring.name)
             check(self._lib.de_destroy(self._h))
             self._h = ctypes.c_void_p()
             self._lender = None
@@ -724,13 +777,9 @@ class Renderer:
         check(self._lib.de_debug_output_scale_weights(self._h, int(n_src), int(n_dst), f, first.ctypes.data, w.ctypes.data, ctypes.byref(taps)))
         return first, w
 
-    def _staging_view(self, ptr):
+    def _staging_view(self, ptr, _=None):
         ow, oh = self.output_size()
-        view = np.ctypeslib.as_array(ptr, shape=(ow, oh, 3)).view(_StagingView)
-        view.flags.writeable = False
-        view._owner = self                      # the memory belongs to the context: the view keeps its Renderer alive ...
-        self._view_ref = weakref.ref(view)      # ... and close() refuses while the view is
-        return view
+        return np.empty((ow, oh, 3), dtype=np.float32) if ptr is None else np.ctypeslib.as_array(ptr, shape=(ow, oh, 3))
 
     def fetch_image(self, copy=True, lag=0):
         """renderer.py:382-384 — display transform of the accumulation; (W, H, 3) float32 in [0, 1].  copy=False returns a read-only
@@ -742,51 +791,19 @@ class Renderer:
         accumulate() renders while this frame is displayed and copied.  A lone one-sample launch takes ~10 ms (its longest path), so lag=1 runs
         at ~5.1 ms per 1080p frame, lag=2 at ~4.1 ms, lag=3 at ~3.5 ms (the floor, launches back to back without any fetch, is 2.9 ms).  Every image equals what the synchronous loop returns for the same frame, bit for bit,
         `lag` calls later; fetch_pending() hands out the rest.  A view (copy=False) stays valid until the next fetch_image call."""
-        if not self._textures_copied:
-            self.copy_textures()
-        if lag not in (0, 1, 2, 3):
-            raise ValueError("lag must be 0 ... 3")
-        if lag:
-            check(self._lib.de_fetch_image_begin(self._h))
-            self._fetches = getattr(self, "_fetches", 0) + 1
-            if self._fetches <= lag:
-                return None
-            return self._fetch_end(copy)
-        if getattr(self, "_fetches", 0):
-            raise RuntimeError("lagged fetches are in flight: fetch_pending() first")
-        if not copy:
-            ptr = ctypes.POINTER(ctypes.c_float)()
-            check(self._lib.de_fetch_image_view(self._h, ctypes.byref(ptr)))
-            return self._staging_view(ptr)
-        ow, oh = self.output_size()
-        out = np.empty((ow, oh, 3), dtype=np.float32)
-        check(self._lib.de_fetch_image(self._h, out.ctypes.data))
-        return out
-
-    def _fetch_end(self, copy):
-        ptr = ctypes.POINTER(ctypes.c_float)()
-        self._fetches -= 1
-        check(self._lib.de_fetch_image_end(self._h, ctypes.byref(ptr)))
-        view = self._staging_view(ptr)
-        return np.array(view) if copy else view
+        return self._image_ring.fetch(self, self._staging_view, copy, lag)
 
     def fetch_pending(self, copy=True, all_images=False, pixels=False, video=False):
         """End the pipelined window loop: wait for the fetches still in flight and return the newest image (None when there is none);
         all_images=True: the list of all of them, oldest first (copies).  pixels=True: the same for the lagged fetch_pixels() calls, which have a
         ring of their own; the float fetches are left alone, as the pixel fetches are without it.  video=True: the same for the lagged
         fetch_video() calls and their ring."""
+        if video and pixels:
+            raise ValueError("pixels=True and video=True name two rings: one call each")
+        ring, array = (self._vd_ring, self._vd_view) if video else (self._pixel_ring, self._pixel_view) if pixels else (self._image_ring, self._staging_view)
         imgs = []
-        if video:
-            if pixels:
-                raise ValueError("pixels=True and video=True name two rings: one call each")
-            while getattr(self, "_vd_fetches", 0) > 0:
-                imgs.append(self._fetch_vd_end(copy or all_images))
-        elif pixels:
-            while getattr(self, "_pixel_fetches", 0) > 0:
-                imgs.append(self._fetch_pixels_end(copy or all_images))
-        else:
-            while getattr(self, "_fetches", 0) > 0:
-                imgs.append(self._fetch_end(copy or all_images))
+        while ring.in_flight > 0:
+            imgs.append(ring.end(self, array, copy or all_images))
         if all_images:
             return imgs
         return imgs[-1] if imgs else None
@@ -814,11 +831,7 @@ class Renderer:
 
     def _pixel_view(self, ptr, channels):
         ow, oh = self.output_size()
-        view = np.ctypeslib.as_array(ptr, shape=(oh, ow, channels)).view(_StagingView)
-        view.flags.writeable = False
-        view._owner = self
-        self._pixel_view_ref = weakref.ref(view)
-        return view
+        return np.empty((oh, ow, channels), dtype=np.uint8) if ptr is None else np.ctypeslib.as_array(ptr, shape=(oh, ow, channels))
 
     def fetch_pixels(self, copy=True, lag=0):
         """The displayed image as packed 8-bit pixels, converted on the GPU behind the display transform: (H, W, channels) uint8, rows top-down — what
@@ -826,36 +839,7 @@ class Renderer:
         link and the host converts nothing.  copy=False: a read-only view of the library's pinned pixel staging buffer, valid until the next
         fetch_pixels call.  lag=1, 2 or 3: pipelined like fetch_image(lag=...), through a ring of its own — the call returns the pixels of the
         lag-th previous call (None until there is one); fetch_pending(pixels=True) hands out the rest."""
-        if not self._textures_copied:
-            self.copy_textures()
-        if lag not in (0, 1, 2, 3):
-            raise ValueError("lag must be 0 ... 3")
-        if lag:
-            channels = self.pixels()["channels"]
-            check(self._lib.de_fetch_pixels_begin(self._h))
-            self._pixel_fetches = getattr(self, "_pixel_fetches", 0) + 1
-            self._pixel_channels = channels
-            if self._pixel_fetches <= lag:
-                return None
-            return self._fetch_pixels_end(copy)
-        if getattr(self, "_pixel_fetches", 0):
-            raise RuntimeError("lagged pixel fetches are in flight: fetch_pending(pixels=True) first")
-        channels = self.pixels()["channels"]
-        if not copy:
-            ptr = ctypes.POINTER(ctypes.c_uint8)()
-            check(self._lib.de_fetch_pixels_view(self._h, ctypes.byref(ptr)))
-            return self._pixel_view(ptr, channels)
-        ow, oh = self.output_size()
-        out = np.empty((oh, ow, channels), dtype=np.uint8)
-        check(self._lib.de_fetch_pixels(self._h, out.ctypes.data, ctypes.c_uint64(out.nbytes)))
-        return out
-
-    def _fetch_pixels_end(self, copy):
-        ptr = ctypes.POINTER(ctypes.c_uint8)()
-        self._pixel_fetches -= 1
-        check(self._lib.de_fetch_pixels_end(self._h, ctypes.byref(ptr)))
-        view = self._pixel_view(ptr, self._pixel_channels)      # set_pixels is refused while fetches are in flight: the format is the begin's
-        return np.array(view) if copy else view
+        return self._pixel_ring.fetch(self, self._pixel_view, copy, lag)
 
     def debug_pixels(self, image, channels=4, mode="truncate", seed=0, phase=0):
         """The conversion once on a given (W, H, 3) float32 image (include/digital_earth_debug.h: de_debug_pixels), W a multiple of 16 and H of 8 but
@@ -909,12 +893,13 @@ class Renderer:
                     mode=self.PIXEL_MODES[s.mode], seed=int(s.seed), animate=bool(s.animate), last_phase=int(phase.value), size=self.output_size(),
                     frame_bytes=int(n.value), plane_offsets=tuple(int(x) for x in off), plane_strides=tuple(int(x) for x in stride))
 
+    def _vd_bytes(self):
+        n = ctypes.c_uint64()
+        check(self._lib.de_videoframe_bytes(self._h, ctypes.byref(n), None, None))
+        return int(n.value)
+
     def _vd_view(self, ptr, nbytes):
-        view = np.ctypeslib.as_array(ptr, shape=(nbytes,)).view(_StagingView)
-        view.flags.writeable = False
-        view._owner = self
-        self._vd_view_ref = weakref.ref(view)
-        return view
+        return np.empty(nbytes, dtype=np.uint8) if ptr is None else np.ctypeslib.as_array(ptr, shape=(nbytes,))
 
     def fetch_video(self, copy=True, lag=0):
         """The displayed image as one video frame in the format of set_video(): a flat uint8 array of video()["frame_bytes"] bytes, the
@@ -922,35 +907,7 @@ class Renderer:
         or 3 (10-bit) bytes per pixel cross the link.  copy=False: a read-only view of the library's pinned video staging buffer, valid until the next
         fetch_video call.  lag=1, 2 or 3: pipelined like fetch_pixels(lag=...), through a ring of its own — the call returns the frame of the
         lag-th previous call (None until there is one); fetch_pending(video=True) hands out the rest."""
-        if not self._textures_copied:
-            self.copy_textures()
-        if lag not in (0, 1, 2, 3):
-            raise ValueError("lag must be 0 ... 3")
-        n = ctypes.c_uint64()
-        check(self._lib.de_videoframe_bytes(self._h, ctypes.byref(n), None, None))
-        if lag:
-            check(self._lib.de_fetch_videoframe_begin(self._h))
-            self._vd_fetches = getattr(self, "_vd_fetches", 0) + 1
-            self._vd_bytes = int(n.value)
-            if self._vd_fetches <= lag:
-                return None
-            return self._fetch_vd_end(copy)
-        if getattr(self, "_vd_fetches", 0):
-            raise RuntimeError("lagged video fetches are in flight: fetch_pending(video=True) first")
-        if not copy:
-            ptr = ctypes.POINTER(ctypes.c_uint8)()
-            check(self._lib.de_fetch_videoframe_view(self._h, ctypes.byref(ptr)))
-            return self._vd_view(ptr, int(n.value))
-        out = np.empty(int(n.value), dtype=np.uint8)
-        check(self._lib.de_fetch_video(self._h, out.ctypes.data, ctypes.c_uint64(out.nbytes)))
-        return out
-
-    def _fetch_vd_end(self, copy):
-        ptr = ctypes.POINTER(ctypes.c_uint8)()
-        self._vd_fetches -= 1
-        check(self._lib.de_fetch_videoframe_end(self._h, ctypes.byref(ptr)))
-        view = self._vd_view(ptr, self._vd_bytes)      # set_video and set_output_scale are refused while fetches are in flight: the size is the begin's
-        return np.array(view) if copy else view
+        return self._vd_ring.fetch(self, self._vd_view, copy, lag)
 
     def split_video(self, frame, size=None, format=None):
         """A frame as numpy views, no copy: (Y, Cb, Cr) for "i420" / "i010", (Y, CbCr) with CbCr of shape (H / 2, W / 2, 2) for "nv12" / "p010"; uint8

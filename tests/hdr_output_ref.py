@@ -181,9 +181,8 @@ def transform(rgb, peak_nits=1000.0, gamut="rec2020", transfer="pq", pow=pow_np,
     return np.stack(out, axis=-1).astype(F).reshape(shape)
 
 
-def display(sums, samples, exposure_scale, vignette=(0.9, 0.0, 0.5, 0.5), sqrt=sqrt_np, **kw):
-    """The stage on a frame: sums (W, H, 3) in fetch_hdr's layout, samples a count or (W, H) per-pixel counts, exposure_scale the display's 2^exposure,
-    vignette = (strength, radius, centre x, centre y) (renderer.py:349-355).  kw: transform's."""
+def display_linear(sums, samples, exposure_scale, vignette=(0.9, 0.0, 0.5, 0.5), sqrt=sqrt_np):
+    """What the stage reads: the frame's mean, vignetted and exposed (renderer.py:349-355), display-linear.  Arguments as display()."""
     sums = np.asarray(sums, F)
     W, H = sums.shape[:2]
     n = np.asarray(samples).astype(F)
@@ -197,7 +196,13 @@ def display(sums, samples, exposure_scale, vignette=(0.9, 0.0, 0.5, 0.5), sqrt=s
         dist = np.asarray(sqrt((du * du + dv * dv).astype(F)), F)
         darken = F(1) - strength * _max(dist - radius, F(0))
         linear = ((sums / n) * darken[..., None]) * F(exposure_scale)
-    return transform(linear.astype(F), sqrt=sqrt, **kw)
+    return linear.astype(F)
+
+
+def display(sums, samples, exposure_scale, vignette=(0.9, 0.0, 0.5, 0.5), sqrt=sqrt_np, **kw):
+    """The stage on a frame: sums (W, H, 3) in fetch_hdr's layout, samples a count or (W, H) per-pixel counts, exposure_scale the display's 2^exposure,
+    vignette = (strength, radius, centre x, centre y) (renderer.py:349-355).  kw: transform's."""
+    return transform(display_linear(sums, samples, exposure_scale, vignette, sqrt), sqrt=sqrt, **kw)
 
 
 # ---------------------------------------------------------------------------------------------- the pack

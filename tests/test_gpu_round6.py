@@ -123,7 +123,7 @@ def test_five_fetches_in_flight_are_refused(Renderer):
     for _ in range(4):
         _native.check(r._lib.de_fetch_image_begin(r._h))
     assert r._lib.de_fetch_image_begin(r._h) == -4            # DE_ERR_STATE: four fetches in flight is the ring's size
-    r._fetches = 4
+    r._image_ring.in_flight = 4
     assert r.fetch_pending() is not None
     import ctypes
     ptr = ctypes.POINTER(ctypes.c_float)()
