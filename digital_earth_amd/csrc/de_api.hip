@@ -833,18 +833,13 @@ int de_debug_samples(de_ctx* c, uint64_t seed, int sample_index, float* out) {
 static int debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n, bool fast) {
     if (!c || !a || !out || fn < 0 || fn > 31) return fail(DE_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(c->device));
-    DeviceBufs<3> m;      // a, b (null without one), out
-    HIP_TRY(hipMalloc(&m.p[0], n * sizeof(float)));
-    HIP_TRY(hipMalloc(&m.p[2], n * sizeof(float)));
-    if (b) HIP_TRY(hipMalloc(&m.p[1], n * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(m.p[0], a, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (b) HIP_TRY(hipMemcpyAsync(m.p[1], b, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (fast) HIP_TRY(de_fast_launch_math(fn, (const float*)m.p[0], (const float*)m.p[1], (float*)m.p[2], (size_t)n, c->stream));
-    else hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m.p[0], (const float*)m.p[1], (float*)m.p[2], (size_t)n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, m.p[2], n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    const size_t bytes[3] = {n * sizeof(float), b ? n * sizeof(float) : 0, n * sizeof(float)};      // a, b (null without one), out
+    const void* const in[3] = {a, b, nullptr};
+    return debug_round_trip(c->stream, bytes, in, 2, out, [&](void* const* m) -> hipError_t {
+        if (fast) return de_fast_launch_math(fn, (const float*)m[0], (const float*)m[1], (float*)m[2], (size_t)n, c->stream);
+        hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m[0], (const float*)m[1], (float*)m[2], (size_t)n);
+        return hipSuccess;
+    });
 }
 int de_debug_math(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n) { return debug_math(c, fn, a, b, out, n, false); }
 int de_debug_math_fast(de_ctx* c, int fn, const float* a, const float* b, float* out, uint64_t n) { return debug_math(c, fn, a, b, out, n, true); }
@@ -1204,16 +1199,9 @@ int de_debug_pixels(de_ctx* c, const float* image, int W, int H, const de_pixels
         return fail(DE_ERR_INVALID, "bad arguments (W a multiple of 16, H a multiple of 8, as de_create asks)");
     { int rc = px_settings_check(s); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
-    DeviceBufs<2> b;
-    const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), out_bytes = (size_t)W * H * (size_t)s->channels;
-    HIP_TRY(hipMalloc(&b.p[0], in_bytes));
-    HIP_TRY(hipMalloc(&b.p[1], out_bytes));
-    HIP_TRY(hipMemcpyAsync(b.p[0], image, in_bytes, hipMemcpyHostToDevice, c->stream));
-    px_launch(c->stream, (const float*)b.p[0], (uint8_t*)b.p[1], W, H, *s, phase);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, b.p[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    const size_t bytes[2] = {(size_t)W * H * 3 * sizeof(float), (size_t)W * H * (size_t)s->channels};
+    const void* const in[2] = {image, nullptr};
+    return debug_round_trip(c->stream, bytes, in, 1, out, [&](void* const* b) { px_launch(c->stream, (const float*)b[0], (uint8_t*)b[1], W, H, *s, phase); return hipSuccess; });
 }
 
 /* ---- output scaling: include/digital_earth_output_scale.h (output_scale_kernels.hip) */
@@ -1299,9 +1287,7 @@ int de_render_to_hdr_pixels(de_ctx* c, const void** device_pixels) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (!c->ho.on) return fail(DE_ERR_STATE, "the HDR display output is off: de_set_hdr_output first");
     int rc = render_packed(c, c->hpx_out, hpx_capacity(c), c->ho.animate != 0, [c](uint32_t phase) {
-        HdrPackArgs a;
-        a.image = shown_image(c); a.out = c->hpx_out.dev.p; a.W = out_w(c); a.H = out_h(c); a.format = c->ho.pixel_format; a.mode = c->ho.mode; a.seed = c->ho.seed; a.phase = phase;
-        hipLaunchKernelGGL(hdr_pack_kernel, dim3((unsigned)((a.W + HPX_TILE - 1) / HPX_TILE), (unsigned)((a.H + HPX_TILE - 1) / HPX_TILE)), dim3(256), 0, c->stream, a);
+        hpx_launch(c->stream, shown_image(c), c->hpx_out.dev.p, out_w(c), out_h(c), c->ho, phase);
     });
     if (rc) return rc;
     if (device_pixels) *device_pixels = c->hpx_out.dev.p;
@@ -1384,16 +1370,9 @@ int de_debug_video(de_ctx* c, const float* image, int W, int H, const de_video* 
         return fail(DE_ERR_INVALID, "bad arguments (W and H positive and even, W * H at most 2^28)");
     { int rc = vd_settings_check(s); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
-    DeviceBufs<2> b;
-    const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), out_bytes = vd_frame_bytes(W, H, *s);
-    HIP_TRY(hipMalloc(&b.p[0], in_bytes));
-    HIP_TRY(hipMalloc(&b.p[1], out_bytes));
-    HIP_TRY(hipMemcpyAsync(b.p[0], image, in_bytes, hipMemcpyHostToDevice, c->stream));
-    vd_launch(c->stream, (const float*)b.p[0], (uint8_t*)b.p[1], W, H, *s, vd_make_consts(s->format, s->matrix, s->range), phase);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, b.p[1], out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    const size_t bytes[2] = {(size_t)W * H * 3 * sizeof(float), vd_frame_bytes(W, H, *s)};
+    const void* const in[2] = {image, nullptr};
+    return debug_round_trip(c->stream, bytes, in, 1, out, [&](void* const* b) { vd_launch(c->stream, (const float*)b[0], (uint8_t*)b[1], W, H, *s, vd_make_consts(s->format, s->matrix, s->range), phase); return hipSuccess; });
 }
 
 /* ---- look LUTs: include/digital_earth_look.h (look_kernels.hip) */
@@ -1419,15 +1398,9 @@ int de_debug_look(de_ctx* c, const float* rgb, uint64_t n, const de_look* s, con
     HIP_TRY(hipSetDevice(c->device));
     struct Tables { de_ctx::LookDev d; ~Tables() { lk_free(d); } } t;
     { int rc = lk_upload(c->stream, *s, table_1d, table_3d, t.d); if (rc) return rc; }
-    DeviceBufs<1> b;
-    const size_t bytes = (size_t)n * 3 * sizeof(float);
-    HIP_TRY(hipMalloc(&b.p[0], bytes));
-    HIP_TRY(hipMemcpyAsync(b.p[0], rgb, bytes, hipMemcpyHostToDevice, c->stream));
-    lk_launch(c->stream, (float*)b.p[0], n, *s, t.d);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, b.p[0], bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    const size_t bytes[1] = {(size_t)n * 3 * sizeof(float)};      // in place
+    const void* const in[1] = {rgb};
+    return debug_round_trip(c->stream, bytes, in, 0, out, [&](void* const* b) { lk_launch(c->stream, (float*)b[0], n, *s, t.d); return hipSuccess; });
 }
 
 /* the transform alone on n colours.  Buffers of its own; the context's setting is not touched. */
@@ -1437,16 +1410,9 @@ int de_debug_hdr_transform(de_ctx* c, const float* rgb, uint64_t n, const de_hdr
     HdrConsts h;
     hdr_output_consts((double)s->peak_nits, s->gamut, s->transfer, &h);
     HIP_TRY(hipSetDevice(c->device));
-    DeviceBufs<2> b;
-    const size_t bytes = (size_t)n * 3 * sizeof(float);
-    HIP_TRY(hipMalloc(&b.p[0], bytes));
-    HIP_TRY(hipMalloc(&b.p[1], bytes));
-    HIP_TRY(hipMemcpyAsync(b.p[0], rgb, bytes, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(hdr_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b.p[0], (float*)b.p[1], (size_t)n, h);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, b.p[1], bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    const size_t bytes[2] = {(size_t)n * 3 * sizeof(float), (size_t)n * 3 * sizeof(float)};
+    const void* const in[2] = {rgb, nullptr};
+    return debug_round_trip(c->stream, bytes, in, 1, out, [&](void* const* b) { hipLaunchKernelGGL(hdr_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float*)b[0], (float*)b[1], (size_t)n, h); return hipSuccess; });
 }
 /* include/digital_earth_debug.h: the constants alone, on the host.  settings = NULL: the six constants setup_kernel is handed for the SDR display
  * (opendrt_consts), the other thirteen 0 — so that a test can put the two host functions side by side. */

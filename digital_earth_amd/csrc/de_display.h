@@ -5,7 +5,8 @@
 //     display (look LUTs, output scaling, 8-bit and HDR pixels, video frames) and the two refusals;
 //   * display_chain: the ONE statement of the order denoise -> history -> meter -> bloom -> local exposure -> display and of its preconditions, which
 //     de_render_to_image and the four intermediate fetches of de_api.hip run up to their own stage.
-// The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, the source every stage reads display_source.h.
+// The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, what the packed outputs share pack.h, the source
+// every stage reads display_source.h.
 #pragma once
 #include "de_fetch.h"
 #include "../../include/digital_earth_denoise.h"
@@ -46,6 +47,19 @@ struct DeviceBufs {
     void* p[N] = {};
     ~DeviceBufs() { for (void* q : p) if (q) hipFree(q); }
 };
+// A debug entry point's round trip on `stream`: N device buffers of its own (bytes[k] each; 0: none, the launch sees a null pointer), in[k] uploaded
+// into buffer k where given, `launch(buffers)` and its launch error, buffer `result` downloaded into `out`, and a wait.  Freed on every exit path.
+template <int N, class Launch>
+int debug_round_trip(hipStream_t stream, const size_t (&bytes)[N], const void* const (&in)[N], int result, void* out, Launch launch) {
+    DeviceBufs<N> b;
+    for (int k = 0; k < N; ++k) if (bytes[k]) HIP_TRY(hipMalloc(&b.p[k], bytes[k]));
+    for (int k = 0; k < N; ++k) if (in[k]) HIP_TRY(hipMemcpyAsync(b.p[k], in[k], bytes[k], hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch(b.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b.p[result], bytes[result], hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DE_OK;
+}
 
 // ---- the source (display_source.h) of a display launch's arguments
 DisplaySrc display_src(const DisplayArgs& d, bool per_tile) {
@@ -384,21 +398,25 @@ int run_output_scale(de_ctx* c) {
     if (rc) return rc;
     return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], (float*)c->os_mid.p, (float*)c->os_out.p);
 }
+// ---- the packed outputs (pack.h): their settings share the quantiser's mode, their launches the grid (pack_grid).  `who`: the settings struct's name.
+int pack_mode_check(int mode, const char* who) {
+    if (mode < DE_PIXELS_TRUNCATE || mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, std::string(who) + ".mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
+    return DE_OK;
+}
 // ---- 8-bit pixel output (include/digital_earth_pixels.h, pixels_kernels.hip)
 size_t px_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (size_t)c->px.channels; }      // of the output size (include/digital_earth_output_scale.h): W x H while that stage is off
 size_t px_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 4; }      // every buffer holds either format: de_set_pixels frees nothing
 int px_settings_check(const de_pixels* s) {
     if (s->struct_bytes != (uint32_t)sizeof(de_pixels)) return fail(DE_ERR_INVALID, "de_pixels.struct_bytes does not match this library's struct");
     if (s->channels != 3 && s->channels != 4) return fail(DE_ERR_INVALID, "de_pixels.channels must be 3 or 4");
-    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_pixels.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
-    return DE_OK;
+    return pack_mode_check(s->mode, "de_pixels");
 }
 void px_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_pixels& s, uint32_t phase) {
     PixelsArgs a;
     a.image = image; a.out = out; a.W = W; a.H = H; a.channels = s.channels; a.mode = s.mode; a.seed = s.seed; a.phase = phase;
-    hipLaunchKernelGGL(pixels_pack_kernel, dim3((unsigned)((W + PX_TILE - 1) / PX_TILE), (unsigned)((H + PX_TILE - 1) / PX_TILE)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(pixels_pack_kernel, pack_grid(W, H), dim3(256), 0, stream, a);
 }
-// ---- HDR display output: the packed pixels (include/digital_earth_hdr_output.h, hdr_output_kernels.hip)
+// ---- HDR display output: the packed pixels (include/digital_earth_hdr_output.h, hdr_output_kernels.hip, hdr_pack.h)
 size_t hpx_size(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * (c->ho.pixel_format == DE_HDR_PIXELS_RGB16 ? 6u : 4u); }
 size_t hpx_capacity(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 6; }      // every buffer holds either format
 int ho_settings_check(const de_hdr_output* s) {
@@ -407,8 +425,12 @@ int ho_settings_check(const de_hdr_output* s) {
     if (s->gamut < DE_HDR_GAMUT_REC709 || s->gamut > DE_HDR_GAMUT_REC2020) return fail(DE_ERR_INVALID, "de_hdr_output.gamut must be DE_HDR_GAMUT_REC709, _P3D65 or _REC2020");
     if (s->transfer < DE_HDR_TRANSFER_LINEAR || s->transfer > DE_HDR_TRANSFER_HLG) return fail(DE_ERR_INVALID, "de_hdr_output.transfer must be DE_HDR_TRANSFER_LINEAR, _PQ or _HLG");
     if (s->pixel_format < DE_HDR_PIXELS_RGB10A2 || s->pixel_format > DE_HDR_PIXELS_RGB16) return fail(DE_ERR_INVALID, "de_hdr_output.pixel_format must be DE_HDR_PIXELS_RGB10A2 or _RGB16");
-    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_hdr_output.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
-    return DE_OK;
+    return pack_mode_check(s->mode, "de_hdr_output");
+}
+void hpx_launch(hipStream_t stream, const float* image, void* out, int W, int H, const de_hdr_output& s, uint32_t phase) {
+    HdrPackArgs a;
+    a.image = image; a.out = out; a.W = W; a.H = H; a.format = s.pixel_format; a.mode = s.mode; a.seed = s.seed; a.phase = phase;
+    hipLaunchKernelGGL(hdr_pack_kernel, pack_grid(W, H), dim3(256), 0, stream, a);
 }
 // ---- video frame output (include/digital_earth_video.h, videoframe_kernels.hip)
 size_t vd_sample_bytes(const de_video& s) { return s.format >= DE_VIDEO_P010 ? 2u : 1u; }
@@ -421,8 +443,7 @@ int vd_settings_check(const de_video* s) {
     if (s->matrix < DE_VIDEO_MATRIX_BT709 || s->matrix > DE_VIDEO_MATRIX_BT2020) return fail(DE_ERR_INVALID, "de_video.matrix must be DE_VIDEO_MATRIX_BT709, _BT601 or _BT2020");
     if (s->range < DE_VIDEO_RANGE_LIMITED || s->range > DE_VIDEO_RANGE_FULL) return fail(DE_ERR_INVALID, "de_video.range must be DE_VIDEO_RANGE_LIMITED or _FULL");
     if (s->siting < DE_VIDEO_SITING_LEFT || s->siting > DE_VIDEO_SITING_TOPLEFT) return fail(DE_ERR_INVALID, "de_video.siting must be DE_VIDEO_SITING_LEFT, _CENTER or _TOPLEFT");
-    if (s->mode < DE_PIXELS_TRUNCATE || s->mode > DE_PIXELS_DITHER) return fail(DE_ERR_INVALID, "de_video.mode must be DE_PIXELS_TRUNCATE, _ROUND or _DITHER");
-    return DE_OK;
+    return pack_mode_check(s->mode, "de_video");
 }
 int vd_even_check(const de_ctx* c) {
     if ((out_w(c) | out_h(c)) & 1) return fail(DE_ERR_STATE, "a 4:2:0 frame needs an even width and height: the output size is odd");
@@ -431,7 +452,7 @@ int vd_even_check(const de_ctx* c) {
 void vd_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int H, const de_video& s, const VideoConsts& k, uint32_t phase) {
     VideoArgs a;
     a.image = image; a.out = out; a.W = W; a.H = H; a.format = s.format; a.siting = s.siting; a.mode = s.mode; a.seed = s.seed; a.phase = phase; a.k = k;
-    hipLaunchKernelGGL(videoframe_pack_kernel, dim3((unsigned)((W + VD_TILE - 1) / VD_TILE), (unsigned)((H + VD_TILE - 1) / VD_TILE)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(videoframe_pack_kernel, pack_grid(W, H), dim3(256), 0, stream, a);
 }
 // ---- look LUTs (include/digital_earth_look.h, look_kernels.hip): in place on the displayed image, directly behind the display launch
 // Everything de_set_look and de_debug_look refuse, in the header's order.

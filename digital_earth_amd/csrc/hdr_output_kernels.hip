@@ -7,13 +7,12 @@
 //                                  arguments — FrameConsts, which the render kernels read, is untouched.  No camera response, gamma or sRGB OETF.
 //   hdr_transform_kernel           the transform alone on n colours (de_debug_hdr_transform)
 //   hdr_pack_kernel                pixels_pack_kernel's shape: one block = one 32 x 32 tile of the displayed image read along its contiguous columns,
-//                                  quantised to 10 or 16 bits (truncate / round / dither: pixels_quantise's formulas with 255 replaced by maxcode, the
-//                                  same hash and keying), staged in LDS as dwords (one per pixel, or one plane per channel; rows padded to 33) and
+//                                  quantised to 10 or 16 bits (truncate / round / dither: the shared quantiser and noise of pack.h with maxcode in
+//                                  255's place), staged in LDS as dwords (one per pixel, or one plane per channel; rows padded to 33) and
 //                                  written as whole row segments of 32-bit words, rows top-down: RGB10A2 one dword per pixel (128 contiguous bytes
-//                                  per row of a tile), RGB16 three halfwords per pixel = 48 dwords (192 bytes) per row.
-// Alignment of the dword stores (derived, as in pixels_kernels.hip): W is a multiple of 16 (de_create, de_set_output_scale), a tile starts at
-// x0 = 32 bx: a row starts at byte r W 4 or r W 6 and a tile's segment 128 bx or 192 bx further, all multiples of 4; the buffer comes from hipMalloc.
-// W = 16 mod 32 leaves half a tile: 16 pixels = 16 or 24 whole dwords.
+//                                  per row of a tile), RGB16 three halfwords per pixel = 48 dwords (192 bytes) per row.  The kernel is here; its
+//                                  two halves around the barrier and HdrPackArgs are hdr_pack.h's, which a host build can include without the transform
+//                                  (the derived alignment of its dword stores is stated there).
 // The functions from hdr_eotf_pq to hdr_openDR_transform restate the algorithm of OpenDRT v0.2.2 ("Open Display Transform", written by Jed Smith,
 // https://github.com/jedypod/open-display-transform), which the reference carries as a Taichi port in lib/OpenDRT.py under the notice
 // "License: GPL v3" (lib/OpenDRT.py:5-10) — the same notice as on aux_kernels.hip's restatement of the live configuration.
@@ -22,6 +21,7 @@
 // No atomics, no scratch; every index is range-checked before its load or store.  Included into de_api.hip's translation unit behind aux_kernels.hip,
 // whose helpers (sdivf, sdivf3f, vdot_rows, narrow_hue_angles) it shares; display_kernel is untouched.
 #include "de_kernels.h"
+#include "hdr_pack.h"
 
 struct HdrConsts {
     float m, s, fl, ds, clamp_max, dch_s;      // lib/OpenDRT.py:270-271, 306-319, 404 for the settings' Lp and EOTF
@@ -135,81 +135,10 @@ __global__ void __launch_bounds__(256) hdr_transform_kernel(const float* rgb, fl
     out[k * 3] = t.x; out[k * 3 + 1] = t.y; out[k * 3 + 2] = t.z;
 }
 
-// ------------------------------------------------------------------------------------------------ the pack
-#define HPX_TILE 32
-#define HPX_LDS_STRIDE 33     // dwords per staged row: one dword of padding
-
-struct HdrPackArgs {
-    const float* image;     // (W, H, 3): index (u H + v) 3 + c, v = 0 at the bottom
-    void* out;              // RGB10A2: uint32 [H][W]; RGB16: uint16 [H][W][3]; row 0 at the top
-    int W, H;
-    int format;             // DE_HDR_PIXELS_*
-    int mode;               // DE_PIXELS_*
-    uint32_t seed, phase;   // of the dither's hash
-};
-
-// pixels_quantise with 255 replaced by maxcode (1023 or 65535; s + 0.5 and maxcode - s are exact-or-rounded f32 like there).
-// `key` = pixels_mix(seed + 0x9E3779B9 phase), `idx` = (r W + x) 4 + c.
-DE_DEV uint32_t hdr_quantise(float t, float maxcode, int mode, uint32_t key, uint32_t idx) {
-    const float cl = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;      // NaN and -0.0 fail the first test
-    const float s = cl * maxcode;
-    if (mode == 0) return (uint32_t)(int)s;
-    if (mode == 1) return (uint32_t)(int)(s + 0.5f);
-    const uint32_t h = pixels_mix(key ^ idx);
-    const float tri = (float)(h >> 16) * 0x1p-16f - (float)(h & 0xffffu) * 0x1p-16f;
-    const float e = maxcode - s;
-    const float m = s < e ? s : e;
-    const float amp = m < 1.0f ? m : 1.0f;
-    return (uint32_t)(int)((s + 0.5f) + amp * tri);                  // amp <= s, amp <= maxcode - s, |tri| < 1: within 0 ... maxcode
-}
-
+// ------------------------------------------------------------------------------------------------ the pack: its two halves are hdr_pack.h's
 __global__ void __launch_bounds__(256) hdr_pack_kernel(HdrPackArgs a) {
-    __shared__ uint32_t tile[3][HPX_TILE][HPX_LDS_STRIDE];      // RGB10A2: [0] holds the packed dword; RGB16: one plane per channel
-    const int t = (int)threadIdx.x, bx = (int)blockIdx.x, by = (int)blockIdx.y;
-    const int u0 = bx * HPX_TILE;
-    const uint32_t key = pixels_mix(a.seed + 0x9E3779B9u * a.phase);
-    const bool wide = a.format == 1;
-    const float maxcode = wide ? 65535.0f : 1023.0f;
-    // thread t quantises pixels (column ul = p >> 5, row vl = p & 31), p = t + 256 k, read along the image's contiguous columns
-    for (int k = 0; k < 4; ++k) {
-        const int p = t + 256 * k;
-        const int ul = p >> 5, vl = p & 31;
-        const int u = u0 + ul, v = by * HPX_TILE + vl;
-        if (u < a.W && v < a.H) {
-            const float* px = a.image + ((size_t)u * (size_t)a.H + (size_t)v) * 3;
-            const uint32_t idx = ((uint32_t)(a.H - 1 - v) * (uint32_t)a.W + (uint32_t)u) * 4u;
-            const uint32_t r = hdr_quantise(px[0], maxcode, a.mode, key, idx), g = hdr_quantise(px[1], maxcode, a.mode, key, idx + 1u),
-                           b = hdr_quantise(px[2], maxcode, a.mode, key, idx + 2u);
-            if (wide) {
-                tile[0][vl][ul] = r; tile[1][vl][ul] = g; tile[2][vl][ul] = b;
-            } else {
-                tile[0][vl][ul] = r | (g << 10) | (b << 20) | 0xc0000000u;
-            }
-        }
-    }
+    __shared__ uint32_t tile[HPX_PLANES][PACK_TILE][PACK_LDS_STRIDE];
+    hdr_stage_tile(a, tile, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y);
     __syncthreads();
-    if (!wide) {
-        for (int k = 0; k < 4; ++k) {
-            const int p = t + 256 * k;
-            const int vl = p >> 5, d = p & 31;
-            const int v = by * HPX_TILE + vl, x = u0 + d;
-            if (v < a.H && x < a.W) {
-                uint32_t* row = static_cast<uint32_t*>(a.out) + (size_t)(a.H - 1 - v) * (size_t)a.W;
-                row[x] = tile[0][vl][d];
-            }
-        }
-    } else {
-        // dword d of a tile's row segment holds halfwords 2 d and 2 d + 1: channel (2 d) % 3 of pixel (2 d) / 3 and the halfword after it, which belongs
-        // to pixel (2 d + 1) / 3 — so a word whose second pixel is inside the row is inside the row.  A row of the output holds W 3 / 2 dwords.
-        for (int k = 0; k < 6; ++k) {
-            const int p = t + 256 * k;                                   // 0 ... 1535 = 32 rows x 48 words
-            const int vl = p / 48, d = p % 48;
-            const int v = by * HPX_TILE + vl, x1 = u0 + (2 * d + 1) / 3;
-            if (v < a.H && x1 < a.W) {
-                uint32_t* row = static_cast<uint32_t*>(a.out) + (size_t)(a.H - 1 - v) * ((size_t)a.W * 3 / 2);
-                const int h0 = 2 * d, h1 = 2 * d + 1;
-                row[(u0 * 3) / 2 + d] = tile[h0 % 3][vl][h0 / 3] | (tile[h1 % 3][vl][h1 / 3] << 16);
-            }
-        }
-    }
+    hdr_store_tile(a, tile, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y);
 }

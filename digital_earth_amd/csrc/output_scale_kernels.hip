@@ -19,7 +19,7 @@
 //                        one fully coalesced load of the same 256 floats of a source column (a wave reads 256 contiguous bytes), `first` and the
 //                        weights depend on the workgroup alone (wave-uniform: scalar loads), no LDS.
 // Both kernels: acc = 0.0f; acc = acc + w[t] * src[t] in ascending tap order, the zero padding included (a multiply then an add: -ffp-contract=off);
-// source indices are clamped to the axis when gathered; the last pass clamps its result to [0, 1] as pixels_quantise does.  An axis of equal size
+// source indices are clamped to the axis when gathered; the last pass clamps its result to [0, 1] with the packs' clamp (pack.h).  An axis of equal size
 // runs no pass.  One-dimensional grids (a dimension of 65 535 blocks would not hold a 4K column count times its tiles).  No atomics, no scratch; every
 // index is range-checked, or clamped into a range derived above, before its load or store.
 // Included into de_api.hip's translation unit after pixels_kernels.hip; display_kernel and pixels_pack_kernel are untouched.
@@ -29,6 +29,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <vector>
+#include "pack.h"      // pack_clamp01 alone
 
 #define OS_MAX_TAPS 49            // 2 ceil(3 * 8) + 1: Lanczos-3 shrinking by 8
 #define OS_V_TILE 64              // output samples of a column per workgroup of the pass along v
@@ -119,7 +120,6 @@ inline bool os_build_table(int n_src, int n_dst, int filter, ScaleTable* T) {
 
 DE_DEV int os_skew(int i) { return i + (i >> 5); }
 DE_DEV int os_clampi(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }
-DE_DEV float os_clamp01(float t) { return t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f; }      // NaN and -0.0 fail the first test
 
 // The source segment of tile `tile` of a column: pixels lo ... lo + n - 1, every (clamped) tap of the tile's outputs among them because `first` ascends.
 DE_DEV void os_v_segment(const ScaleArgs& a, int tile, int* lo, int* n) {
@@ -151,7 +151,7 @@ DE_DEV void os_v_filter(const ScaleArgs& a, const float* lds, int t, int column,
         const int li = os_clampi(os_clampi(f + k, a.n_src) - lo, n);      // within the segment by construction; clamped into it all the same
         acc = acc + a.w[(size_t)k * (size_t)a.n_dst + (size_t)j] * lds[os_skew(li * 3 + ch)];
     }
-    a.dst[((size_t)column * (size_t)a.n_dst + (size_t)j) * 3 + (size_t)ch] = a.clamp ? os_clamp01(acc) : acc;
+    a.dst[((size_t)column * (size_t)a.n_dst + (size_t)j) * 3 + (size_t)ch] = a.clamp ? pack_clamp01(acc) : acc;
 }
 
 // Pass along u: thread t of the workgroup of (output column j, chunk) filters float e = 256 chunk + t of the column.
@@ -164,7 +164,7 @@ DE_DEV void os_u_filter(const ScaleArgs& a, int t, int j, int chunk) {
         const int i = os_clampi(f + k, a.n_src);
         acc = acc + a.w[(size_t)k * (size_t)a.n_dst + (size_t)j] * a.src[(size_t)i * (size_t)a.lines + (size_t)e];
     }
-    a.dst[(size_t)j * (size_t)a.lines + (size_t)e] = a.clamp ? os_clamp01(acc) : acc;
+    a.dst[(size_t)j * (size_t)a.lines + (size_t)e] = a.clamp ? pack_clamp01(acc) : acc;
 }
 
 #ifndef DE_OUTPUT_SCALE_STANDALONE

@@ -17,9 +17,7 @@
 #ifndef DE_PIXELS_STANDALONE      // a host build of this file alone brings its own DE_DEV (tools/pixels_host_check.cpp)
 #include "de_kernels.h"
 #endif
-
-#define PX_TILE 32
-#define PX_LDS_STRIDE 33      // dwords per staged row: one dword of padding
+#include "pack.h"             // the hash, the quantiser, the tile and its walk: what this pack shares with the HDR and video packs
 
 struct PixelsArgs {
     const float* image;     // (W, H, 3): index (u H + v) 3 + c, v = 0 at the bottom
@@ -30,62 +28,33 @@ struct PixelsArgs {
     uint32_t seed, phase;   // of the dither's hash
 };
 
-DE_DEV uint32_t pixels_mix(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-// One value of the displayed image to its byte.  `key` = pixels_mix(seed + 0x9E3779B9 phase), `idx` = (r W + x) 4 + c.
-DE_DEV uint32_t pixels_quantise(float t, int mode, uint32_t key, uint32_t idx) {
-    const float cl = t > 0.0f ? (t < 1.0f ? t : 1.0f) : 0.0f;      // NaN and -0.0 fail the first test
-    const float s = cl * 255.0f;
-    if (mode == 0) return (uint32_t)(int)s;
-    if (mode == 1) return (uint32_t)(int)(s + 0.5f);
-    const uint32_t h = pixels_mix(key ^ idx);
-    const float tri = (float)(h >> 16) * 0x1p-16f - (float)(h & 0xffffu) * 0x1p-16f;      // both terms and the difference are exact
-    const float e = 255.0f - s;
-    const float m = s < e ? s : e;
-    const float amp = m < 1.0f ? m : 1.0f;
-    return (uint32_t)(int)((s + 0.5f) + amp * tri);                  // amp <= s, amp <= 255 - s, |tri| < 1: within 0 ... 255
-}
-
-// First half: thread t quantises pixels (column ul = p >> 5, row vl = p & 31), p = t + 256 k, of tile (bx, by) into tile[vl][ul].
-DE_DEV void pixels_stage_tile(const PixelsArgs& a, uint32_t (*tile)[PX_LDS_STRIDE], int t, int bx, int by) {
-    const uint32_t key = pixels_mix(a.seed + 0x9E3779B9u * a.phase);
+// First half: thread t quantises its four cells (pack.h: column ul, row vl) of tile (bx, by) into tile[vl][ul].  `idx` = (r W + x) 4 + c.
+DE_DEV void pixels_stage_tile(const PixelsArgs& a, uint32_t (*tile)[PACK_LDS_STRIDE], int t, int bx, int by) {
+    const uint32_t key = pack_key(a.seed, a.phase);
     for (int k = 0; k < 4; ++k) {
-        const int p = t + 256 * k;
-        const int ul = p >> 5, vl = p & 31;
-        const int u = bx * PX_TILE + ul, v = by * PX_TILE + vl;
-        if (u < a.W && v < a.H) {
-            const float* px = a.image + ((size_t)u * (size_t)a.H + (size_t)v) * 3;
-            const uint32_t idx = ((uint32_t)(a.H - 1 - v) * (uint32_t)a.W + (uint32_t)u) * 4u;
-            const uint32_t r = pixels_quantise(px[0], a.mode, key, idx), g = pixels_quantise(px[1], a.mode, key, idx + 1u), b = pixels_quantise(px[2], a.mode, key, idx + 2u);
-            tile[vl][ul] = r | (g << 8) | (b << 16);
+        const PackCell c = pack_cell(t + 256 * k, bx, by);
+        if (c.u < a.W && c.v < a.H) {
+            const float* px = pack_pixel(a.image, a.H, c.u, c.v);
+            const uint32_t idx = pack_idx(a.W, a.H, c.u, c.v);
+            const uint32_t r = pack_quantise01(px[0], 255.0f, a.mode, key, idx), g = pack_quantise01(px[1], 255.0f, a.mode, key, idx + 1u), b = pack_quantise01(px[2], 255.0f, a.mode, key, idx + 2u);
+            tile[c.vl][c.ul] = r | (g << 8) | (b << 16);
         }
     }
 }
 
-// Second half: the tile's rows as 32-bit words.  RGBA8: word d of staged row vl is pixel d.  RGB8: word d = 3 g + j holds bytes 4 d ... 4 d + 3 of
-// the row segment, the upper 3 - j bytes of pixel 4 g + j and the lower j + 1 bytes of pixel 4 g + j + 1; its last byte, 3 u0 + 4 d + 3, is at or
-// below the last byte of that second pixel, 3 (u0 + 4 g + j + 1) + 2, so a word whose second pixel is inside the row is inside the row.
-DE_DEV void pixels_store_tile(const PixelsArgs& a, const uint32_t (*tile)[PX_LDS_STRIDE], int t, int bx, int by) {
-    const int u0 = bx * PX_TILE;
+// Second half: the tile's rows as 32-bit words.  RGBA8: word d of staged row vl is pixel d (pack.h's store, alpha or-ed in).  RGB8: word d = 3 g + j
+// holds bytes 4 d ... 4 d + 3 of the row segment, the upper 3 - j bytes of pixel 4 g + j and the lower j + 1 bytes of pixel 4 g + j + 1; its last byte,
+// 3 u0 + 4 d + 3, is at or below the last byte of that second pixel, 3 (u0 + 4 g + j + 1) + 2, so a word whose second pixel is inside the row is inside the row.
+DE_DEV void pixels_store_tile(const PixelsArgs& a, const uint32_t (*tile)[PACK_LDS_STRIDE], int t, int bx, int by) {
     if (a.channels == 4) {
-        for (int k = 0; k < 4; ++k) {
-            const int p = t + 256 * k;
-            const int vl = p >> 5, d = p & 31;
-            const int v = by * PX_TILE + vl, x = u0 + d;
-            if (v < a.H && x < a.W) {
-                uint32_t* row = reinterpret_cast<uint32_t*>(a.out + (size_t)(a.H - 1 - v) * (size_t)a.W * 4);
-                row[x] = tile[vl][d] | 0xff000000u;
-            }
-        }
+        pack_store_dwords(reinterpret_cast<uint32_t*>(a.out), a.W, a.H, tile, 0xff000000u, t, bx, by);
     } else {
+        const int u0 = bx * PACK_TILE;
         for (int k = 0; k < 3; ++k) {
             const int p = t + 256 * k;                                   // 0 ... 767 = 32 rows x 24 words
             const int vl = p / 24, d = p % 24;
             const int g = d / 3, j = d % 3;
-            const int v = by * PX_TILE + vl, x1 = u0 + 4 * g + j + 1;     // the word's second pixel; 4 g + j + 1 <= 31
+            const int v = by * PACK_TILE + vl, x1 = u0 + 4 * g + j + 1;   // the word's second pixel; 4 g + j + 1 <= 31
             if (v < a.H && x1 < a.W) {
                 uint32_t* row = reinterpret_cast<uint32_t*>(a.out + (size_t)(a.H - 1 - v) * (size_t)a.W * 3);
                 const uint32_t lo = tile[vl][4 * g + j], hi = tile[vl][4 * g + j + 1];
@@ -97,7 +66,7 @@ DE_DEV void pixels_store_tile(const PixelsArgs& a, const uint32_t (*tile)[PX_LDS
 
 #ifndef DE_PIXELS_STANDALONE
 __global__ void __launch_bounds__(256) pixels_pack_kernel(PixelsArgs a) {
-    __shared__ uint32_t tile[PX_TILE][PX_LDS_STRIDE];
+    __shared__ uint32_t tile[PACK_TILE][PACK_LDS_STRIDE];
     pixels_stage_tile(a, tile, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y);
     __syncthreads();
     pixels_store_tile(a, tile, (int)threadIdx.x, (int)blockIdx.x, (int)blockIdx.y);

@@ -28,16 +28,10 @@
 // Included into de_api.hip's translation unit; display_kernel and pixels_pack_kernel are untouched.
 #ifndef DE_VIDEO_STANDALONE      // a host build of this file alone brings its own DE_DEV (the host check under tools/)
 #include "de_kernels.h"
-#else
-DE_DEV uint32_t pixels_mix(uint32_t x) {      // pixels_kernels.hip's hash
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
 #endif
+#include "pack.h"             // the hash, the quantiser, the clamp and the tile (PACK_TILE, PACK_LDS_STRIDE): what this pack shares with the pixel packs
 
-#define VD_TILE 32
 #define VD_CELLS 33           // staged cells per axis: the tile, one column to its left (cell column 0 is u0 - 1), one row above it (cell row 32 is v0 + 32)
-#define VD_LDS_STRIDE 33      // words per staged row
 #define VD_CTILE 16
 #define VD_C_STRIDE 17
 
@@ -79,29 +73,19 @@ static inline VideoConsts vd_make_consts(int format, int matrix, int range) {
 }
 
 struct VideoTile {       // the workgroup's LDS: 2 x 4356 + 4224 + 2176 = 15112 bytes
-    float cb[VD_CELLS][VD_LDS_STRIDE];
-    float cr[VD_CELLS][VD_LDS_STRIDE];
-    uint32_t y[VD_TILE][VD_LDS_STRIDE];
+    float cb[VD_CELLS][PACK_LDS_STRIDE];
+    float cr[VD_CELLS][PACK_LDS_STRIDE];
+    uint32_t y[PACK_TILE][PACK_LDS_STRIDE];
     uint32_t c[2][VD_CTILE][VD_C_STRIDE];
 };
 
-// One clipped value s in [lo, hi] to its code.  `key` = pixels_mix(seed + 0x9E3779B9 phase), `idx` = 4 (sample index in its plane) + plane.
-DE_DEV uint32_t vd_quantise(float s, float lo, float hi, int mode, uint32_t key, uint32_t idx) {
-    if (mode == 0) return (uint32_t)(int)s;
-    if (mode == 1) return (uint32_t)(int)(s + 0.5f);
-    const uint32_t h = pixels_mix(key ^ idx);
-    const float tri = (float)(h >> 16) * 0x1p-16f - (float)(h & 0xffffu) * 0x1p-16f;      // both terms and the difference are exact
-    const float d = s - lo, e = hi - s;
-    const float m = d < e ? d : e;
-    const float amp = m < 1.0f ? m : 1.0f;
-    return (uint32_t)(int)((s + 0.5f) + amp * tri);                  // amp <= s - lo, amp <= hi - s, |tri| < 1: within lo ... hi
-}
+// The codes come from pack_quantise(s, lo, hi, ...) on a clipped s; `idx` = 4 (sample index in its plane) + plane: 0 for Y, 1 for Cb, 2 for Cr.
 DE_DEV float vd_clip(float v, float lo, float hi) { return v > lo ? (v < hi ? v : hi) : lo; }
 
 // Step 1: thread t computes cells p = t + 256 k (cell column cl = p / 33 is image column u0 - 1 + cl, cell row rl = p % 33 is image row v0 + rl).
 DE_DEV void vd_stage_tile(const VideoArgs& a, VideoTile& tile, int t, int bx, int by) {
-    const uint32_t key = pixels_mix(a.seed + 0x9E3779B9u * a.phase);
-    const int u0 = bx * VD_TILE, v0 = by * VD_TILE;
+    const uint32_t key = pack_key(a.seed, a.phase);
+    const int u0 = bx * PACK_TILE, v0 = by * PACK_TILE;
     for (int k = 0; k < 5; ++k) {
         const int p = t + 256 * k;
         if (p >= VD_CELLS * VD_CELLS) break;
@@ -109,17 +93,13 @@ DE_DEV void vd_stage_tile(const VideoArgs& a, VideoTile& tile, int t, int bx, in
         const int u = u0 - 1 + cl, v = v0 + rl;
         if (u < a.W && v <= a.H) {                                   // u >= -1; the cells the filter of a sample inside the image can reach
             const int us = u < 0 ? 0 : u, vs = v < a.H ? v : a.H - 1;      // the edge pixel repeated
-            const float* px = a.image + ((size_t)us * (size_t)a.H + (size_t)vs) * 3;
-            const float tr = px[0], tg = px[1], tb = px[2];
-            const float R = tr > 0.0f ? (tr < 1.0f ? tr : 1.0f) : 0.0f;      // NaN and -0.0 fail the first test
-            const float G = tg > 0.0f ? (tg < 1.0f ? tg : 1.0f) : 0.0f;
-            const float B = tb > 0.0f ? (tb < 1.0f ? tb : 1.0f) : 0.0f;
+            const float* px = pack_pixel(a.image, a.H, us, vs);
+            const float R = pack_clamp01(px[0]), G = pack_clamp01(px[1]), B = pack_clamp01(px[2]);
             const float Y = ((a.k.kr * R) + (a.k.kb * B)) + (a.k.kg * G);
             tile.cb[rl][cl] = (B - Y) * a.k.sb;
             tile.cr[rl][cl] = (R - Y) * a.k.sr;
-            if (cl >= 1 && rl < VD_TILE && v < a.H) {                // inside the tile and the image: its Y code
-                const uint32_t idx = ((uint32_t)(a.H - 1 - v) * (uint32_t)a.W + (uint32_t)u) * 4u;
-                tile.y[rl][cl - 1] = vd_quantise(vd_clip(Y * a.k.ys + a.k.yo, a.k.ylo, a.k.yhi), a.k.ylo, a.k.yhi, a.mode, key, idx);
+            if (cl >= 1 && rl < PACK_TILE && v < a.H) {                // inside the tile and the image: its Y code
+                tile.y[rl][cl - 1] = pack_quantise(vd_clip(Y * a.k.ys + a.k.yo, a.k.ylo, a.k.yhi), a.k.ylo, a.k.yhi, a.mode, key, pack_idx(a.W, a.H, u, v));
             }
         }
     }
@@ -127,7 +107,7 @@ DE_DEV void vd_stage_tile(const VideoArgs& a, VideoTile& tile, int t, int bx, in
 
 // The siting's filter of one staged difference around cell column c0 = 2 i (image column x - 1) and cell row r0 = 2 ml (the pair's bottom row; the
 // top row of the pair, output row 2 j, is r0 + 1 and the row above it, output row 2 j - 1, is r0 + 2).
-DE_DEV float vd_filter(const float (*c)[VD_LDS_STRIDE], int siting, int c0, int r0) {
+DE_DEV float vd_filter(const float (*c)[PACK_LDS_STRIDE], int siting, int c0, int r0) {
     if (siting == 1) {                                               // CENTER
         const float ht = c[r0 + 1][c0 + 1] + c[r0 + 1][c0 + 2], hb = c[r0][c0 + 1] + c[r0][c0 + 2];
         return (ht + hb) * 0.25f;
@@ -141,22 +121,21 @@ DE_DEV float vd_filter(const float (*c)[VD_LDS_STRIDE], int siting, int c0, int 
 
 // Step 2: thread t filters and quantises chroma sample (i = t & 15, ml = t >> 4) of the block into tile.c[plane][ml][i].
 DE_DEV void vd_chroma_tile(const VideoArgs& a, VideoTile& tile, int t, int bx, int by) {
-    const uint32_t key = pixels_mix(a.seed + 0x9E3779B9u * a.phase);
+    const uint32_t key = pack_key(a.seed, a.phase);
     const int i = t & 15, ml = t >> 4;
-    const int x = bx * VD_TILE + 2 * i, vb = by * VD_TILE + 2 * ml;
+    const int x = bx * PACK_TILE + 2 * i, vb = by * PACK_TILE + 2 * ml;
     if (x < a.W && vb < a.H) {                                       // then x + 1 < W and vb + 2 <= H: every cell read below was staged
-        const int j = (a.H >> 1) - 1 - (vb >> 1);
-        const uint32_t idx = ((uint32_t)j * (uint32_t)(a.W >> 1) + (uint32_t)(x >> 1)) * 4u;
+        const uint32_t idx = pack_idx(a.W >> 1, a.H >> 1, x >> 1, vb >> 1);      // the chroma plane is (W / 2, H / 2), rows top-down like Y
         const float fb = vd_filter(tile.cb, a.siting, 2 * i, 2 * ml), fr = vd_filter(tile.cr, a.siting, 2 * i, 2 * ml);
-        tile.c[0][ml][i] = vd_quantise(vd_clip(fb * a.k.cs + a.k.co, a.k.clo, a.k.chi), a.k.clo, a.k.chi, a.mode, key, idx + 1u);
-        tile.c[1][ml][i] = vd_quantise(vd_clip(fr * a.k.cs + a.k.co, a.k.clo, a.k.chi), a.k.clo, a.k.chi, a.mode, key, idx + 2u);
+        tile.c[0][ml][i] = pack_quantise(vd_clip(fb * a.k.cs + a.k.co, a.k.clo, a.k.chi), a.k.clo, a.k.chi, a.mode, key, idx + 1u);
+        tile.c[1][ml][i] = pack_quantise(vd_clip(fr * a.k.cs + a.k.co, a.k.clo, a.k.chi), a.k.clo, a.k.chi, a.mode, key, idx + 2u);
     }
 }
 
 // Step 3: the tile's rows into the planes (the alignment of every 32-bit store: the head of this file).
 DE_DEV void vd_store_tile(const VideoArgs& a, const VideoTile& tile, int t, int bx, int by) {
     const int W = a.W, H = a.H, CW = W >> 1, CH = H >> 1;
-    const int u0 = bx * VD_TILE, v0 = by * VD_TILE;
+    const int u0 = bx * PACK_TILE, v0 = by * PACK_TILE;
     const bool wide16 = a.format >= 2;                               // P010, I010: two bytes per sample
     const int shift = a.format == 2 ? 6 : 0;                         // P010: the code in the high bits
     const size_t npx = (size_t)W * (size_t)H;

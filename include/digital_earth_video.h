@@ -34,7 +34,7 @@
  *     DE_PIXELS_TRUNCATE  q = (int)s
  *     DE_PIXELS_ROUND     q = (int)(s + 0.5)
  *     DE_PIXELS_DITHER    q = (int)((s + 0.5) + a * tri),  d = s - lo, e = hi - s, a = min(min(d, e), 1),  tri = pixels' triangular noise of
- *                         pixels_mix(key ^ idx), key = pixels_mix(seed + 0x9E3779B9 phase), idx = 4 * (the sample's index in its plane, row-major,
+ *                         mix(key ^ idx), key = mix(seed + 0x9E3779B9 phase) (DESIGN.md §14 has mix), idx = 4 * (the sample's index in its plane, row-major,
  *                         r W + x for Y and j CW + i for Cb and Cr) + plane (0 = Y, 1 = Cb, 2 = Cr)
  * so the lowest and the highest legal code of a plane stay exact in every mode: black is (16, 128, 128) k and white (235, 128, 128) k in limited
  * range.  With animate = 0 the phase is 0 always; otherwise it counts this context's conversions since de_set_video.  tests/video_ref.py restates all

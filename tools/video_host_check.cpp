@@ -29,8 +29,8 @@ static std::vector<uint32_t> run(const std::vector<float>& image, int W, int H, 
     a.k = vd_make_consts(format, matrix, range);
     // the 32-bit stores need a 4-byte aligned base, as hipMalloc gives: operator new's is 16-byte aligned
     a.out = exact.data();
-    for (int by = 0; by < (H + VD_TILE - 1) / VD_TILE; ++by)
-        for (int bx = 0; bx < (W + VD_TILE - 1) / VD_TILE; ++bx) {
+    for (int by = 0; by < (H + PACK_TILE - 1) / PACK_TILE; ++by)
+        for (int bx = 0; bx < (W + PACK_TILE - 1) / PACK_TILE; ++bx) {
             std::vector<VideoTile> lds(1);
             memset(&lds[0], 0xA5, sizeof(VideoTile));      // a staged word never read before it is written would show in the bytes
             for (int t = 0; t < 256; ++t) vd_stage_tile(a, lds[0], t, bx, by);
