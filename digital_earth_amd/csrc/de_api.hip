@@ -1,7 +1,7 @@
 // de_api.hip — the C ABI of libdigitalearth_hip.so (include/digital_earth.h): context life cycle, uploads, parameters, the frame loop, fetches.
 // No CPU fallback exists: every entry point needs a HIP device.  The launches are in de_launch.h, the collectives in de_rccl.h, the display path's stages
 // and their one chain in de_display.h, how an output leaves the GPU (staging, rings, the packed outputs' frame) in de_fetch.h, the context in
-// de_context.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS (legacy/).  This file holds entry points only.
+// de_context.h, the owner of all its memory (Dev<T>, Pinned<T>: nothing here allocates or frees by hand) in de_memory.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS (legacy/).  This file holds entry points only.
 #include "de_rccl.h"
 #include "de_display.h"
 
@@ -17,6 +17,46 @@ hipError_t create_slot_stream(de_ctx* c, hipStream_t* out) {
     memset(mask, 0, sizeof(mask));
     for (int i = 0; i < keep && i < 512; ++i) mask[i >> 5] |= 1u << (i & 31);
     return hipExtStreamCreateWithCUMask(out, (uint32_t)((n + 31) / 32), mask);
+}
+// A launch slot: its stream and its three events.  de_create makes the first n_slots, de_set_launch_slots the ones that did not exist yet.
+hipError_t create_slot(de_ctx* c, LaunchSlot& s) {
+    if (s.stream) return hipSuccess;
+    HIP_RET(create_slot_stream(c, &s.stream));
+    HIP_RET(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    HIP_RET(hipEventCreate(&s.t0));
+    return hipEventCreate(&s.t1);
+}
+// The context's own stream carries the small operations between frames and the collective: highest priority, so that wave slots freed by the draining
+// render kernels of the launch slots go to them first.
+hipError_t create_context_stream(hipStream_t* out) {
+    int prio_lo = 0, prio_hi = 0;
+    hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    return hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio_hi);
+}
+// What every context holds from de_create on: its stream, the launch slots, the frame's buffers and tables.  Everything else is allocated on first use.
+hipError_t create_resources(de_ctx* c) {
+    const size_t npx = (size_t)c->W * c->H;
+    HIP_RET(create_context_stream(&c->stream));
+    c->own_stream = true;
+    for (int i = 0; i < c->n_slots; ++i) HIP_RET(create_slot(c, c->slot[i]));      // launches in flight per context (de_set_launch_slots; 1 = every launch waits for the previous one)
+    HIP_RET(hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
+    HIP_RET(c->d_hdr_own.ensure(npx * 3 * sizeof(float)));
+    c->d_hdr = c->d_hdr_own;
+    HIP_RET(c->d_image.ensure(npx * 3 * sizeof(float)));
+    HIP_RET(c->d_scratch.ensure(npx * 4 * sizeof(float)));
+    HIP_RET(c->d_fc.ensure(sizeof(FrameConsts)));
+    HIP_RET(c->d_nodes.ensure(DE_N_NODES * sizeof(LambdaNode)));
+    HIP_RET(c->d_node_val.ensure(256 * sizeof(float)));
+    HIP_RET(c->d_counters.ensure(DE_N_COUNTERS * sizeof(unsigned long long)));
+    HIP_RET(c->d_work_counter.ensure(16 * (DE_MAX_SLOTS + 1) * sizeof(uint32_t)));
+    HIP_RET(c->d_dens_table.ensure((size_t)DE_DENS_TABLE_N * DE_DENS_STRIDE * sizeof(float)));
+    HIP_RET(c->d_cie.ensure(441 * 2 * 3 * sizeof(float)));
+    HIP_RET(c->d_srgb2spec.ensure(900 * sizeof(float)));
+    HIP_RET(c->d_o3.ensure(441 * sizeof(float)));
+    HIP_RET(hipMemsetAsync(c->d_hdr, 0, npx * 3 * sizeof(float), c->stream));
+    HIP_RET(hipMemsetAsync(c->d_counters, 0, DE_N_COUNTERS * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(dens_table_kernel, dim3((DE_DENS_TABLE_N + 255) / 256), dim3(256), 0, c->stream, c->d_dens_table);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -48,42 +88,7 @@ int de_create(int device, int width, int height, de_ctx** out) {
 #endif
     memset(&c->counters, 0, sizeof(c->counters));
     c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    size_t npx = (size_t)width * height;
-    // the context stream carries the small operations between frames and the collective: highest priority, so that wave slots
-    // freed by the draining render kernels of the launch slots go to them first
-    int prio_lo = 0, prio_hi = 0;
-    hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    hipError_t e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi);
-    c->own_stream = (e == hipSuccess);
-    {   // launch slots: launches in flight per context (de_set_launch_slots; 1 = every launch waits for the previous one)
-        for (int i = 0; i < c->n_slots && e == hipSuccess; ++i) {
-            LaunchSlot& s = c->slot[i];
-            e = create_slot_stream(c, &s.stream);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreate(&s.t0);
-            if (e == hipSuccess) e = hipEventCreate(&s.t1);
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming);
-    }
-    if (e == hipSuccess) e = hipMalloc(&c->d_hdr_own, npx * 3 * sizeof(float));
-    c->d_hdr = c->d_hdr_own;
-    if (e == hipSuccess) e = hipMalloc(&c->d_image, npx * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_scratch, npx * 4 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_fc, sizeof(FrameConsts));
-    if (e == hipSuccess) e = hipMalloc(&c->d_nodes, DE_N_NODES * sizeof(LambdaNode));
-    if (e == hipSuccess) e = hipMalloc(&c->d_node_val, 256 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_counters, DE_N_COUNTERS * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&c->d_work_counter, 16 * (DE_MAX_SLOTS + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&c->d_dens_table, (size_t)DE_DENS_TABLE_N * DE_DENS_STRIDE * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_cie, 441 * 2 * 3 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_srgb2spec, 900 * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&c->d_o3, 441 * sizeof(float));
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_hdr, 0, npx * 3 * sizeof(float), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_counters, 0, DE_N_COUNTERS * sizeof(unsigned long long), c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(dens_table_kernel, dim3((DE_DENS_TABLE_N + 255) / 256), dim3(256), 0, c->stream, c->d_dens_table);
-        e = hipGetLastError();
-    }
+    const hipError_t e = create_resources(c);
     if (e != hipSuccess) {
         std::string msg = std::string("de_create: ") + hipGetErrorString(e);
         de_destroy(c);
@@ -101,31 +106,13 @@ int de_destroy(de_ctx* c) {
     hipStreamSynchronize(c->stream);
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
-    for (auto& t : c->tex) { if (t.borrowed) continue; if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); if (t.bound) hipFree(t.bound); }
-    if (c->luts_borrowed) { c->d_cie = nullptr; c->d_srgb2spec = nullptr; c->d_o3 = nullptr; c->d_crf = nullptr; }
-    void* ptrs[] = {c->d_cie, c->d_srgb2spec, c->d_o3, c->d_crf, c->d_fc, c->d_nodes, c->d_node_val, c->d_hdr_own, c->d_image, c->d_scratch, c->d_tiles, c->d_counters, c->d_work_counter, c->d_dens_table, c->d_assembled, c->d_gather, c->d_standin,
-                     c->d_s2, c->d_alist[0], c->d_alist[1], c->d_tile_spp, c->d_keep, c->d_ad_count,
-                     c->d_dn_nc, c->d_dn_at, c->d_dn_dist, c->d_dn_buf[0], c->d_dn_buf[1], c->d_dn_out,
-                     c->d_ae_partial, c->d_ae_centre, c->d_ae_state, c->d_fc_ae, c->d_ae_result, c->d_bl_pyr, c->d_bl_out,
-                     c->d_hs_c[0], c->d_hs_c[1], c->d_hs_d[0], c->d_hs_d[1], c->d_hs_cam[0], c->d_hs_cam[1], c->d_hs_out, c->d_lx_pyr, c->d_lx_base, c->d_lx_out,
-                     c->os_tab[0].first.p, c->os_tab[0].w.p, c->os_tab[1].first.p, c->os_tab[1].w.p, c->os_mid.p, c->os_out.p};
-    for (void* p : ptrs) if (p) hipFree(p);
-    pinned_release(c->h_stage);
-    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) ring_release(*r);
-    for (PackedOut* o : {&c->px_out, &c->hpx_out, &c->vd_out}) packed_release(*o);
-    lk_free(c->lk_dev);
-    if (c->h_issued) hipHostFree(c->h_issued);
-    if (c->h_ad_count) hipHostFree(c->h_ad_count);
+    // events and streams; the memory is the members' (de_memory.h): `delete c` frees what this context owns and leaves what it borrows
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) ring_destroy_events(*r);
 #ifdef DE_LEGACY_VARIANTS
-    legacy_destroy(c);
+    destroy_legacy_events(c);
 #endif
-    for (auto& S : c->v6s) {
-        if (S.cold) hipFree(S.cold); if (S.ctl) hipFree(S.ctl); if (S.d_args) hipFree(S.d_args); if (S.pool[0]) hipFree(S.pool[0]); if (S.pool[1]) hipFree(S.pool[1]);
-        if (S.h_status) hipHostFree(S.h_status);
-    }
     for (int i = 0; i < DE_MAX_SLOTS; ++i) {
         LaunchSlot& s = c->slot[i];
-        if (s.contrib) hipFree(s.contrib);
         if (s.done) hipEventDestroy(s.done);
         if (s.t0) hipEventDestroy(s.t0);
         if (s.t1) hipEventDestroy(s.t1);
@@ -189,17 +176,13 @@ int de_share_textures(de_ctx* dst, de_ctx* src) {
     release_loan(dst);
     for (int i = 0; i < DE_TEX_COUNT; ++i) {
         DevTexture& t = dst->tex[i];
-        if (!t.borrowed) { if (t.linear) hipFree(t.linear); if (t.packed) hipFree(t.packed); if (t.bound) hipFree(t.bound); }
-        t = src->tex[i];          // (the cloud map's occupancy bound with it)
-        t.linear = nullptr;       // the as-uploaded copy stays the lender's alone: de_download_texture on the borrower fails cleanly
-        t.borrowed = true;
+        const DevTexture& s = src->tex[i];
+        t.linear.release();       // the as-uploaded copy stays the lender's alone: de_download_texture on the borrower fails cleanly
+        t.packed.borrow(s.packed); t.bound.borrow(s.bound);      // (the cloud map's occupancy bound with it)
+        t.w = s.w; t.h = s.h; t.ch = s.ch; t.tiles_x = s.tiles_x; t.tiles_y = s.tiles_y; t.packed_clamp = s.packed_clamp; t.set = s.set;
     }
-    if (!dst->luts_borrowed) {
-        void* own[] = {dst->d_cie, dst->d_srgb2spec, dst->d_o3, dst->d_crf};
-        for (void* q : own) if (q) hipFree(q);
-    }
-    dst->d_cie = src->d_cie; dst->d_srgb2spec = src->d_srgb2spec; dst->d_o3 = src->d_o3; dst->d_crf = src->d_crf;
-    dst->n_crf = src->n_crf; dst->luts_set = true; dst->luts_borrowed = true;
+    dst->d_cie.borrow(src->d_cie); dst->d_srgb2spec.borrow(src->d_srgb2spec); dst->d_o3.borrow(src->d_o3); dst->d_crf.borrow(src->d_crf);
+    dst->n_crf = src->n_crf; dst->luts_set = true;
     dst->params_dirty = true; dst->nodes_dirty = true;
     // the loan is on record: while it lasts the lender refuses to free, replace or repack its maps and LUTs, and to be destroyed
     dst->lender = src; src->loans++;
@@ -215,16 +198,15 @@ int de_trim_textures(de_ctx* c) {
     const bool clamp = (c->p.flags & DE_FLAG_CLAMP_SAMPLER) != 0;
     for (int i = 0; i < DE_TEX_COUNT; ++i) {
         DevTexture& t = c->tex[i];
-        if (!t.set || t.borrowed || !t.linear) continue;
+        if (!t.set || t.borrowed() || !t.linear) continue;
         int rc = ensure_packed(c, i, clamp);          // the packed copy must exist before its source goes (fails if that means repacking lent maps)
         if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int i = 0; i < DE_TEX_COUNT; ++i) {
         DevTexture& t = c->tex[i];
-        if (!t.set || t.borrowed || !t.linear) continue;
-        hipFree(t.linear);            // borrowers never hold this pointer (de_share_textures)
-        t.linear = nullptr;
+        if (!t.set || t.borrowed() || !t.linear) continue;
+        t.linear.release();
     }
     return DE_OK;
 }
@@ -232,7 +214,7 @@ int de_trim_textures(de_ctx* c) {
 int de_download_texture(de_ctx* c, int slot, uint8_t* out, uint64_t out_bytes) {
     if (!c || slot < 0 || slot >= DE_TEX_COUNT || !out || !c->tex[slot].set) return fail(DE_ERR_INVALID, "texture not set");
     const DevTexture& t = c->tex[slot];
-    if (t.borrowed) return fail(DE_ERR_STATE, "this map is borrowed (de_share_textures): download it from the context that owns it");
+    if (t.borrowed()) return fail(DE_ERR_STATE, "this map is borrowed (de_share_textures): download it from the context that owns it");
     if (!t.linear) return fail(DE_ERR_STATE, "the as-uploaded copy of this map was released (de_trim_textures)");
     size_t n = (size_t)t.w * t.h * t.ch;
     if (out_bytes < n) return fail(DE_ERR_INVALID, "output buffer too small");
@@ -262,17 +244,15 @@ int de_upload_luts(de_ctx* c, const float* cie, const uint16_t* srgb2spec_f16, c
     for (int x = 0; x < 1024; ++x)
         for (int y = 0; y < n_crf; ++y)
             for (int ch = 0; ch < 3; ++ch) r[((size_t)y * 1024 + x) * 3 + ch] = crf[((size_t)x * n_crf + y) * 3 + ch];
-    if (c->luts_borrowed) {                  // stop borrowing: own copies again
-        c->d_cie = nullptr; c->d_srgb2spec = nullptr; c->d_o3 = nullptr; c->d_crf = nullptr; c->luts_borrowed = false;
-        {   bool any = false;
-            for (int i = 0; i < DE_TEX_COUNT; ++i) any = any || c->tex[i].borrowed;
-            if (!any) release_loan(c); }
-        HIP_TRY(hipMalloc(&c->d_cie, 441 * 2 * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->d_srgb2spec, 900 * sizeof(float)));
-        HIP_TRY(hipMalloc(&c->d_o3, 441 * sizeof(float)));
+    if (c->luts_borrowed()) {                // stop borrowing: own copies again
+        c->d_cie.release(); c->d_srgb2spec.release(); c->d_o3.release();
+        if (!borrows_anything(c)) release_loan(c);
     }
-    if (c->d_crf) { hipFree(c->d_crf); c->d_crf = nullptr; }
-    HIP_TRY(hipMalloc(&c->d_crf, r.size() * sizeof(float)));
+    HIP_TRY(c->d_cie.ensure(441 * 2 * 3 * sizeof(float)));      // (held since de_create unless they were borrowed)
+    HIP_TRY(c->d_srgb2spec.ensure(900 * sizeof(float)));
+    HIP_TRY(c->d_o3.ensure(441 * sizeof(float)));
+    c->d_crf.release();                      // sized by n_crf
+    HIP_TRY(c->d_crf.ensure(r.size() * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(c->d_cie, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_srgb2spec, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_o3, o3, 441 * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -311,7 +291,7 @@ int de_reset(de_ctx* c) {
     c->dn_guides_valid = false; c->dn_out_valid = false;
     c->dn_s2_complete = false;
     if (c->dn_on) {                        // the denoiser tracks S2 from the frame's first sample on (zeroed before the first accumulate: same stream, touched_hdr above)
-        if (!c->d_s2) HIP_TRY(hipMalloc(&c->d_s2, (size_t)c->W * c->H * 3 * sizeof(float)));
+        HIP_TRY(c->d_s2.ensure((size_t)c->W * c->H * 3 * sizeof(float)));
         HIP_TRY(hipMemsetAsync(c->d_s2, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
         c->dn_s2_complete = true;
     }
@@ -524,12 +504,12 @@ int de_accumulate_adaptive(de_ctx* c, uint64_t seed, de_adaptive* io) {
     HIP_TRY(hipSetDevice(c->device));
     if (c->frame_kind != DE_FRAME_ADAPTIVE) {
         // frame start: S2 zeroed, every tile active with count 0
-        if (!c->d_s2) HIP_TRY(hipMalloc(&c->d_s2, (size_t)c->W * c->H * 3 * sizeof(float)));
-        for (int k = 0; k < 2; ++k) if (!c->d_alist[k]) HIP_TRY(hipMalloc(&c->d_alist[k], (size_t)n_tiles * sizeof(uint32_t)));
-        if (!c->d_tile_spp) HIP_TRY(hipMalloc(&c->d_tile_spp, (size_t)n_tiles * sizeof(int32_t)));
-        if (!c->d_keep) HIP_TRY(hipMalloc(&c->d_keep, (size_t)n_tiles * sizeof(uint32_t)));
-        if (!c->d_ad_count) HIP_TRY(hipMalloc(&c->d_ad_count, sizeof(int32_t)));
-        if (!c->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_ad_count), sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(c->d_s2.ensure((size_t)c->W * c->H * 3 * sizeof(float)));
+        for (int k = 0; k < 2; ++k) HIP_TRY(c->d_alist[k].ensure((size_t)n_tiles * sizeof(uint32_t)));
+        HIP_TRY(c->d_tile_spp.ensure((size_t)n_tiles * sizeof(int32_t)));
+        HIP_TRY(c->d_keep.ensure((size_t)n_tiles * sizeof(uint32_t)));
+        HIP_TRY(c->d_ad_count.ensure(sizeof(int32_t)));
+        HIP_TRY(c->h_ad_count.ensure(sizeof(int32_t)));
         { int rc = join_slots(c); if (rc) return rc; }
         touched_hdr(c); touched_render_inputs(c);      // the launches read the list and read-modify-write S2 after this
         HIP_TRY(hipMemsetAsync(c->d_s2, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
@@ -633,9 +613,7 @@ int de_use_own_stream(de_ctx* c) {
     { int rc = sync_all(c); if (rc) return rc; }
     if (c->own_stream) return DE_OK;
     hipStream_t s = nullptr;
-    int prio_lo = 0, prio_hi = 0;
-    hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, prio_hi));
+    HIP_TRY(create_context_stream(&s));
     c->stream = s; c->own_stream = true;
     touched_render_inputs(c); touched_hdr(c);
     return DE_OK;
@@ -748,14 +726,7 @@ int de_set_launch_slots(de_ctx* c, int n_slots, int n_big) {
     if (!c || n_slots < 1 || n_slots > DE_MAX_SLOTS || n_big < 1 || n_big > DE_MAX_SLOTS) return fail(DE_ERR_INVALID, "slot counts must be 1..8");
     HIP_TRY(hipSetDevice(c->device));
     { int rc = sync_all(c); if (rc) return rc; }
-    for (int i = c->n_slots; i < n_slots; ++i) {          // slots that did not exist yet
-        LaunchSlot& s = c->slot[i];
-        if (s.stream) continue;
-        HIP_TRY(create_slot_stream(c, &s.stream));
-        HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreate(&s.t0));
-        HIP_TRY(hipEventCreate(&s.t1));
-    }
+    for (int i = c->n_slots; i < n_slots; ++i) HIP_TRY(create_slot(c, c->slot[i]));          // slots that did not exist yet
     c->n_slots = n_slots; c->big_slots = n_big;
     c->next_slot = 0; c->last_slot = -1; c->last_v6_slot = -1;
     return DE_OK;
@@ -857,7 +828,7 @@ int de_set_denoise(de_ctx* c, const de_denoise* d) {
         { int rc = dn_alloc(c); if (rc) return rc; }
         if (c->frame_kind == DE_FRAME_NONE) {
             // no sample yet: S2 starts complete (zeroed on the context stream, ordered before the frame's first accumulate)
-            if (!c->d_s2) HIP_TRY(hipMalloc(&c->d_s2, (size_t)c->W * c->H * 3 * sizeof(float)));
+            HIP_TRY(c->d_s2.ensure((size_t)c->W * c->H * 3 * sizeof(float)));
             { int rc = join_slots(c); if (rc) return rc; }
             touched_hdr(c);
             HIP_TRY(hipMemsetAsync(c->d_s2, 0, (size_t)c->W * c->H * 3 * sizeof(float), c->stream));
@@ -1044,10 +1015,11 @@ int de_debug_history(de_ctx* c, const float* mean, const int32_t* n, const float
     HIP_TRY(hipSetDevice(c->device));
     const int W = c->W, H = c->H;
     const size_t npx = (size_t)W * H;
-    DeviceBufs<10> b;
+    Dev<void> own[10];
+    void* b[10] = {};
     const size_t bytes[10] = {npx * 3 * sizeof(float), npx * sizeof(int32_t), npx * sizeof(float), npx * sizeof(float4), npx * sizeof(float),
                               sizeof(FrameConsts), 2 * sizeof(HistoryCam), npx * 3 * sizeof(float), npx * sizeof(float4), npx * sizeof(float)};
-    for (int k = 0; k < 10; ++k) HIP_TRY(hipMalloc(&b.p[k], bytes[k]));
+    for (int k = 0; k < 10; ++k) { HIP_TRY(own[k].ensure(bytes[k])); b[k] = own[k]; }
     std::vector<float> m(npx * 3), t(npx), hd(npx);
     std::vector<int32_t> nn(npx);
     std::vector<float4> hcol(npx);
@@ -1058,31 +1030,31 @@ int de_debug_history(de_ctx* c, const float* mean, const int32_t* n, const float
         to_device_layout(hist_c, reinterpret_cast<float*>(hcol.data()), W, H, 4);
         to_device_layout(hist_d, hd.data(), W, H, 1);
     }
-    HIP_TRY(hipMemcpyAsync(b.p[0], m.data(), bytes[0], hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b.p[1], nn.data(), bytes[1], hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b.p[2], t.data(), bytes[2], hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b[0], m.data(), bytes[0], hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b[1], nn.data(), bytes[1], hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(b[2], t.data(), bytes[2], hipMemcpyHostToDevice, c->stream));
     if (hist_c) {
-        HIP_TRY(hipMemcpyAsync(b.p[3], hcol.data(), bytes[3], hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(b.p[4], hd.data(), bytes[4], hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b[3], hcol.data(), bytes[3], hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(b[4], hd.data(), bytes[4], hipMemcpyHostToDevice, c->stream));
     }
-    HistoryCam* cams = (HistoryCam*)b.p[6];
-    hipLaunchKernelGGL(history_camera_kernel, dim3(1), dim3(1), 0, c->stream, *cur, W, H, (FrameConsts*)b.p[5], (HistoryCam*)nullptr);
+    HistoryCam* cams = (HistoryCam*)b[6];
+    hipLaunchKernelGGL(history_camera_kernel, dim3(1), dim3(1), 0, c->stream, *cur, W, H, (FrameConsts*)b[5], (HistoryCam*)nullptr);
     HIP_TRY(hipGetLastError());
     if (hist_c) {
         hipLaunchKernelGGL(history_camera_kernel, dim3(1), dim3(1), 0, c->stream, *hist, W, H, (FrameConsts*)nullptr, cams);
         HIP_TRY(hipGetLastError());
     }
     HistoryArgs a;
-    a.s.hdr = (const float*)b.p[0]; a.s.tile_spp = nullptr; a.s.samples = 1; a.s.W = W; a.s.H = H;
-    a.n_tile = nullptr; a.n_pixel = (const int32_t*)b.p[1]; a.n_frame = 0;
-    a.dist = (const float*)b.p[2]; a.fc = (const FrameConsts*)b.p[5];
-    a.hist_c = hist_c ? (const float4*)b.p[3] : nullptr; a.hist_d = (const float*)b.p[4]; a.hist_cam = cams;
-    a.out = (float*)b.p[7]; a.cand_c = (float4*)b.p[8]; a.cand_d = (float*)b.p[9]; a.cand_cam = cams + 1;
+    a.s.hdr = (const float*)b[0]; a.s.tile_spp = nullptr; a.s.samples = 1; a.s.W = W; a.s.H = H;
+    a.n_tile = nullptr; a.n_pixel = (const int32_t*)b[1]; a.n_frame = 0;
+    a.dist = (const float*)b[2]; a.fc = (const FrameConsts*)b[5];
+    a.hist_c = hist_c ? (const float4*)b[3] : nullptr; a.hist_d = (const float*)b[4]; a.hist_cam = cams;
+    a.out = (float*)b[7]; a.cand_c = (float4*)b[8]; a.cand_d = (float*)b[9]; a.cand_cam = cams + 1;
     a.max_history = max_history; a.depth_tolerance = depth_tolerance;
     hipLaunchKernelGGL(history_blend_kernel, dn_grid(c), dim3(256), 0, c->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(hcol.data(), b.p[8], bytes[8], hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(m.data(), b.p[7], bytes[7], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(hcol.data(), b[8], bytes[8], hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(m.data(), b[7], bytes[7], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t p = 0; p < npx; ++p) {
         const float4 v = hcol[p];
@@ -1126,19 +1098,20 @@ int de_debug_local_exposure(de_ctx* c, const float* mean, float exposure_scale, 
     { int rc = lx_alloc(c); if (rc) return rc; }
     const int W = c->W, H = c->H;
     const size_t npx = (size_t)W * H;
-    DeviceBufs<2> b;
-    HIP_TRY(hipMalloc(&b.p[0], npx * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&b.p[1], sizeof(FrameConsts)));
+    Dev<float> d_mean;
+    Dev<FrameConsts> d_fc;
+    HIP_TRY(d_mean.ensure(npx * 3 * sizeof(float)));
+    HIP_TRY(d_fc.ensure(sizeof(FrameConsts)));
     std::vector<float> m(npx * 3);
     to_device_layout(mean, m.data(), W, H, 3);
     FrameConsts fc;
     memset(&fc, 0, sizeof(fc));
     fc.exposure_scale = exposure_scale;      // the only field the stage reads
-    HIP_TRY(hipMemcpyAsync(b.p[0], m.data(), npx * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(b.p[1], &fc, sizeof(fc), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_mean, m.data(), npx * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_fc, &fc, sizeof(fc), hipMemcpyHostToDevice, c->stream));
     DisplayArgs d;
     memset(&d, 0, sizeof(d));
-    d.fc = (const FrameConsts*)b.p[1]; d.hdr = (const float*)b.p[0]; d.W = W; d.H = H; d.samples = 1;
+    d.fc = d_fc; d.hdr = d_mean; d.W = W; d.H = H; d.samples = 1;
     bool per_tile = false;
     int rc = lx_run(c, *s, d, per_tile);
     if (rc) return rc;
@@ -1166,10 +1139,10 @@ int de_get_pixels(de_ctx* c, de_pixels* out, uint32_t* last_phase) {
 int de_render_to_pixels(de_ctx* c, const uint8_t** device_pixels) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     int rc = render_packed(c, c->px_out, px_capacity(c), c->px.animate != 0, [c](uint32_t phase) {
-        px_launch(c->stream, shown_image(c), (uint8_t*)c->px_out.dev.p, out_w(c), out_h(c), c->px, phase);
+        px_launch(c->stream, shown_image(c), c->px_out.dev, out_w(c), out_h(c), c->px, phase);
     });
     if (rc) return rc;
-    if (device_pixels) *device_pixels = (const uint8_t*)c->px_out.dev.p;
+    if (device_pixels) *device_pixels = c->px_out.dev;
     return DE_OK;
 }
 int de_fetch_pixels_view(de_ctx* c, const uint8_t** host) {
@@ -1232,23 +1205,21 @@ int de_debug_output_scale(de_ctx* c, const float* image, int W, int H, const de_
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, W, H, &ow, &oh); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
-    struct Bufs : DeviceBufs<3> {   // and the two axes' tables
-        de_ctx::ScaleDev t[2];
-        ~Bufs() { for (auto& d : t) { device_release(d.first); device_release(d.w); } }
-    } b;
+    Dev<float> d_in, d_mid, d_out;
+    de_ctx::ScaleDev t[2];          // and the two axes' tables
     const size_t in_bytes = (size_t)W * H * 3 * sizeof(float), mid_bytes = (size_t)W * oh * 3 * sizeof(float), out_bytes = (size_t)ow * oh * 3 * sizeof(float);
-    HIP_TRY(hipMalloc(&b.p[0], in_bytes));
-    HIP_TRY(hipMalloc(&b.p[1], mid_bytes));
-    HIP_TRY(hipMalloc(&b.p[2], out_bytes));
+    HIP_TRY(d_in.ensure(in_bytes));
+    HIP_TRY(d_mid.ensure(mid_bytes));
+    HIP_TRY(d_out.ensure(out_bytes));
     int rc = DE_OK;
-    if (oh != H) { rc = os_table_ensure(c->stream, b.t[0], H, oh, s->filter); if (rc) return rc; }
-    if (ow != W) { rc = os_table_ensure(c->stream, b.t[1], W, ow, s->filter); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(b.p[0], image, in_bytes, hipMemcpyHostToDevice, c->stream));
-    const void* result = b.p[0];      // both axes copies: the identity, nothing runs
+    if (oh != H) { rc = os_table_ensure(c->stream, t[0], H, oh, s->filter); if (rc) return rc; }
+    if (ow != W) { rc = os_table_ensure(c->stream, t[1], W, ow, s->filter); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(d_in, image, in_bytes, hipMemcpyHostToDevice, c->stream));
+    const float* result = d_in;      // both axes copies: the identity, nothing runs
     if (ow != W || oh != H) {
-        rc = os_launch(c->stream, (const float*)b.p[0], W, H, ow, oh, b.t[0], b.t[1], (float*)b.p[1], (float*)b.p[2]);
+        rc = os_launch(c->stream, d_in, W, H, ow, oh, t[0], t[1], d_mid, d_out);
         if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-        result = b.p[2];
+        result = d_out;
     }
     HIP_TRY(hipMemcpyAsync(out, result, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1287,10 +1258,10 @@ int de_render_to_hdr_pixels(de_ctx* c, const void** device_pixels) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     if (!c->ho.on) return fail(DE_ERR_STATE, "the HDR display output is off: de_set_hdr_output first");
     int rc = render_packed(c, c->hpx_out, hpx_capacity(c), c->ho.animate != 0, [c](uint32_t phase) {
-        hpx_launch(c->stream, shown_image(c), c->hpx_out.dev.p, out_w(c), out_h(c), c->ho, phase);
+        hpx_launch(c->stream, shown_image(c), c->hpx_out.dev, out_w(c), out_h(c), c->ho, phase);
     });
     if (rc) return rc;
-    if (device_pixels) *device_pixels = c->hpx_out.dev.p;
+    if (device_pixels) *device_pixels = c->hpx_out.dev;
     return DE_OK;
 }
 int de_fetch_hdr_pixels(de_ctx* c, void* out, uint64_t out_bytes) {
@@ -1334,10 +1305,10 @@ int de_render_to_video(de_ctx* c, const void** device_frame) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     { int rc = vd_even_check(c); if (rc) return rc; }
     int rc = render_packed(c, c->vd_out, vd_capacity(c), c->vd.animate != 0, [c](uint32_t phase) {
-        vd_launch(c->stream, shown_image(c), (uint8_t*)c->vd_out.dev.p, out_w(c), out_h(c), c->vd, c->vd_consts, phase);
+        vd_launch(c->stream, shown_image(c), c->vd_out.dev, out_w(c), out_h(c), c->vd, c->vd_consts, phase);
     });
     if (rc) return rc;
-    if (device_frame) *device_frame = c->vd_out.dev.p;
+    if (device_frame) *device_frame = c->vd_out.dev;
     return DE_OK;
 }
 int de_fetch_videoframe_view(de_ctx* c, const void** host) {
@@ -1382,8 +1353,7 @@ int de_set_look(de_ctx* c, const de_look* s, const float* table_1d, const float*
     HIP_TRY(hipSetDevice(c->device));
     de_ctx::LookDev fresh;
     { int rc = lk_upload(c->stream, *s, table_1d, table_3d, fresh); if (rc) return rc; }
-    lk_free(c->lk_dev);           // waits for a display in flight that still reads the previous tables (a lagged fetch)
-    c->lk_dev = fresh;
+    c->lk_dev = std::move(fresh);      // the previous tables go: hipFree waits for a display in flight that still reads them (a lagged fetch)
     c->lk = *s;
     c->lk.enabled = s->enabled ? 1 : 0;
     c->lk_on = s->enabled != 0;
@@ -1396,11 +1366,11 @@ int de_debug_look(de_ctx* c, const float* rgb, uint64_t n, const de_look* s, con
     { int rc = lk_settings_check(s, table_1d, table_3d); if (rc) return rc; }
     if (!s->size_1d && !s->size_3d) return fail(DE_ERR_INVALID, "de_look: no table");
     HIP_TRY(hipSetDevice(c->device));
-    struct Tables { de_ctx::LookDev d; ~Tables() { lk_free(d); } } t;
-    { int rc = lk_upload(c->stream, *s, table_1d, table_3d, t.d); if (rc) return rc; }
+    de_ctx::LookDev t;
+    { int rc = lk_upload(c->stream, *s, table_1d, table_3d, t); if (rc) return rc; }
     const size_t bytes[1] = {(size_t)n * 3 * sizeof(float)};      // in place
     const void* const in[1] = {rgb};
-    return debug_round_trip(c->stream, bytes, in, 0, out, [&](void* const* b) { lk_launch(c->stream, (float*)b[0], n, *s, t.d); return hipSuccess; });
+    return debug_round_trip(c->stream, bytes, in, 0, out, [&](void* const* b) { lk_launch(c->stream, (float*)b[0], n, *s, t); return hipSuccess; });
 }
 
 /* the transform alone on n colours.  Buffers of its own; the context's setting is not touched. */

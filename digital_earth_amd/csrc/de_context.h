@@ -53,6 +53,15 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(DE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+#define HIP_RET(expr)       /* in a function that answers a hipError_t: hand a failure on */ \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess) return e_;                                                    \
+    } while (0)
+
+}  // namespace
+#include "de_memory.h"      // Dev<T>, Pinned<T>: what owns every allocation below
+namespace {
 
 enum { DE_FRAME_NONE = 0, DE_FRAME_UNIFORM = 1, DE_FRAME_ADAPTIVE = 2 };   // de_ctx::frame_kind
 
@@ -62,39 +71,37 @@ struct LaunchSlot {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;           // recorded after the slot's latest accumulate_kernel
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    uint2* contrib = nullptr;            // per-sample (radiance, wavelength node) records of the launch in this slot
+    Dev<uint2> contrib;                  // per-sample (radiance, wavelength node) records of the launch in this slot
     size_t contrib_items = 0;
     bool pending = false;                // `done` has not been waited for by the context stream yet
     bool launched = false;               // `done` has been recorded at least once (an event never recorded reads as complete)
     uint64_t seen_render = 0, seen_hdr = 0;
 };
 
-// What a fetch leaves the GPU through.  Plain state: de_fetch.h holds every operation on it (ensure, release, begin, end, the synchronous path), once.
-struct PinnedBuf { void* p = nullptr; size_t bytes = 0; };      // pinned host memory and its size
-struct DeviceBuf { void* p = nullptr; size_t bytes = 0; };      // device memory and its size
+// What a fetch leaves the GPU through.  de_fetch.h holds every operation on it (begin, end, the synchronous path), once.
 struct FetchRing {                       // the lagged fetches of one output: begun - ended = fetches in flight, at most DE_FETCH_RING
     const char* noun;                    // for messages: "pixel", and the entry points' stem, "de_fetch_pixels" (+ "_begin" / "_end")
     const char* entry;
-    PinnedBuf cell[DE_FETCH_RING];       // fetch n is copied into cell n % DE_FETCH_RING ...
+    Pinned<void> cell[DE_FETCH_RING];     // fetch n is copied into cell n % DE_FETCH_RING ...
     hipEvent_t ev[DE_FETCH_RING] = {};   // ... and its event recorded behind the copy
     unsigned begun = 0, ended = 0;       // calls of _begin and of _end
 };
 struct PackedOut {                       // an output converted from the displayed image: 8-bit pixels, HDR pixels, video frames
     const char* noun;
-    DeviceBuf dev;                       // the packed output; sized for the largest format at the output size, so that a change of format frees nothing
-    PinnedBuf stage;                     // where a synchronous fetch lands
+    Dev<uint8_t> dev;                    // the packed output; sized for the largest format at the output size, so that a change of format frees nothing
+    Pinned<void> stage;                  // where a synchronous fetch lands
     uint32_t count = 0, last_phase = 0;  // conversions since the settings were set; the dither phase of the newest
 };
 
 struct DevTexture {
     int w = 0, h = 0, ch = 0;
-    uint8_t* linear = nullptr;    // as uploaded: [h][w][ch]
-    uint32_t* packed = nullptr;   // footprint tiles (ch == 1) or rgbx dwords (ch == 3)
+    Dev<uint8_t> linear;          // as uploaded: [h][w][ch]; a borrower holds none
+    Dev<uint32_t> packed;         // footprint tiles (ch == 1) or rgbx dwords (ch == 3)
     int tiles_x = 0, tiles_y = 0;
     int packed_clamp = -1;        // address mode the packed copy was built with
-    uint8_t* bound = nullptr;     // the cloud map only: its occupancy bound (DE_CLOUD_BOUND_BYTES), rebuilt with the packed copy
+    Dev<uint8_t> bound;           // the cloud map only: its occupancy bound (DE_CLOUD_BOUND_BYTES), rebuilt with the packed copy
     bool set = false;
-    bool borrowed = false;        // the allocations belong to another context (de_share_textures)
+    bool borrowed() const { return packed.borrowed(); }      // the packed copy and the bound are views of another context's (de_share_textures)
 };
 
 }  // namespace
@@ -119,7 +126,7 @@ struct de_ctx {
     int last_v6_slot = -1;          // the slot of the newest render_kernel_v6 launch (the tail's "has a successor on another slot" word is about v6 launches only)
     int cu_withhold = 0;            // de_tuning.v6_cu_withhold: CUs per XCD the launch slots' streams may NOT use (hipExtStreamCreateWithCUMask), so that small kernels of
                                     // the context stream (collective, accumulate, display) find a free CU while persistent workgroups own the others; 0 = plain streams
-    float* d_standin = nullptr;     // de_debug_standin_reduce: its second operand (zeros), its output and its copy target, [3][H][W][3]
+    Dev<float> d_standin;     // de_debug_standin_reduce: its second operand (zeros), its output and its copy target, [3][H][W][3]
     hipEvent_t ev_standin[16][2] = {};   // the last 16 stand-in collectives: de_last_reduce_ms answers their MEAN queue-to-finish time (frames in flight: no host wait per frame)
     unsigned standin_count = 0;
     bool last_reduce_standin = false;
@@ -129,37 +136,37 @@ struct de_ctx {
     bool timing_valid = false;
     bool timing_empty = false;      // the last de_accumulate launched nothing (an empty share): its duration is 0, not the previous call's
     DevTexture tex[DE_TEX_COUNT];
-    float* d_cie = nullptr;      // 441 x 2 x 3 (f16-quantised)
-    float* d_srgb2spec = nullptr;
-    float* d_o3 = nullptr;
-    float* d_crf = nullptr;      // [n][1024][3]
+    Dev<float> d_cie;      // 441 x 2 x 3 (f16-quantised)
+    Dev<float> d_srgb2spec;
+    Dev<float> d_o3;
+    Dev<float> d_crf;      // [n][1024][3]
     int n_crf = 0;
     bool luts_set = false;
-    bool luts_borrowed = false;
-    FrameConsts* d_fc = nullptr;
-    LambdaNode* d_nodes = nullptr;
-    float* d_node_val = nullptr;
-    float* d_hdr = nullptr;      // [H][W][3] (own allocation or bound by de_bind_hdr)
-    float* d_hdr_own = nullptr;
-    float* d_image = nullptr;    // (W, H, 3)
-    float* d_scratch = nullptr;  // (W, H, 3) / debug [H][W][4]
-    PinnedBuf h_stage;            // copy_out's and de_fetch_image_view's staging (a pageable destination copies at a fraction of the link rate): W * H * 3 floats, or the output size's when that is larger
+    bool luts_borrowed() const { return d_cie.borrowed(); }      // the four tables are views of another context's (de_share_textures)
+    Dev<FrameConsts> d_fc;
+    Dev<LambdaNode> d_nodes;
+    Dev<float> d_node_val;
+    float* d_hdr = nullptr;      // a view: [H][W][3], d_hdr_own or the buffer bound by de_bind_hdr
+    Dev<float> d_hdr_own;
+    Dev<float> d_image;    // (W, H, 3)
+    Dev<float> d_scratch;  // (W, H, 3) / debug [H][W][4]
+    Pinned<void> h_stage;          // copy_out's and de_fetch_image_view's staging (a pageable destination copies at a fraction of the link rate): W * H * 3 floats, or the output size's when that is larger
     // de_fetch_image_begin / _end: the window loop pipelined — display + device-to-host copy of frame k run on the context stream while launch k + 1 renders (de_fetch.h).
     FetchRing img = {"image", "de_fetch_image"};
-    uint32_t* d_tiles = nullptr;
+    Dev<uint32_t> d_tiles;
     int n_tiles = 0, tiles_rank = -1, tiles_world = -1;
-    unsigned long long* d_counters = nullptr;
-    uint32_t* d_work_counter = nullptr;   // 16 dwords per launch slot
-    float* d_dens_table = nullptr;   // get_density by altitude index (DE_DENS_TABLE_N x 3)
+    Dev<unsigned long long> d_counters;
+    Dev<uint32_t> d_work_counter;   // 16 dwords per launch slot
+    Dev<float> d_dens_table;   // get_density by altitude index (DE_DENS_TABLE_N x 3)
     int n_cus = 256;
     bool count = false;
     de_counters counters;
     int current_spp = 0;
     int sample_rank = 0, sample_world = 1;   // de_set_sample_partition: of the frame's sample indices this context renders those = rank (mod world)
-    float* d_assembled = nullptr;   // root's receive buffer of de_reduce_progressive ([H][W][3])
-    float* d_gather = nullptr;      // root of de_reduce_ordered: the other ranks' buffers, [world][H][W][3]
+    Dev<float> d_assembled;   // root's receive buffer of de_reduce_progressive ([H][W][3])
+    Dev<float> d_gather;      // root of de_reduce_ordered: the other ranks' buffers, [world][H][W][3]
     int gather_world = 0;
-    const float* display_src = nullptr;   // what the display transform / de_fetch_hdr read instead of d_hdr (de_set_display_source)
+    const float* display_src = nullptr;   // a view: what the display transform / de_fetch_hdr read instead of d_hdr (de_set_display_source)
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;   // around the last collective
     bool reduce_timing_valid = false;
     void* comm = nullptr;        // the context's own RCCL communicator (de_comm_init)
@@ -169,18 +176,18 @@ struct de_ctx {
     // render_kernel_v6 (kernel variant 6): one persistent launch per call, one workgroup per CU, stage queues in LDS.  Per launch slot:
     // the control words, one cold record per record slot of every workgroup, the launch's RenderArgs.
     struct V6State {
-        wf::Cold* cold = nullptr;
-        uint32_t* ctl = nullptr;
-        RenderArgs* d_args = nullptr;
-        uint32_t* h_status = nullptr;     // pinned, device-visible: the kernel's abort code
+        Dev<wf::Cold> cold;
+        Dev<uint32_t> ctl;
+        Dev<RenderArgs> d_args;
+        Pinned<uint32_t> h_status;     // pinned, device-visible: the kernel's abort code
         uint32_t n_wg = 0;
-        uint4* pool[2] = {nullptr, nullptr};      // the tail's pools (render_kernel_v6.hip: "The tail"): level k exports to pool[k & 1]
+        Dev<uint4> pool[2];      // the tail's pools (render_kernel_v6.hip: "The tail"): level k exports to pool[k & 1]
         uint32_t pool_cap[2] = {0, 0};            // entries
     } v6s[DE_MAX_SLOTS];
     int v6_tail_levels = 1, v6_tail_export[2] = {128, 96}, v6_tail_grid[2] = {64, 8};
     uint32_t v6_tail_min_paths = 4u << 20;
     int v6_tail_when_alone = 0;      // 1: export even when no launch is queued behind (tests; default: only then, see render_kernel_v6.hip schedule())
-    uint32_t* h_issued = nullptr;    // pinned, device-visible: the number of the newest render_kernel_v6 launch with a successor on another launch slot (read once per workgroup)
+    Pinned<uint32_t> h_issued;    // pinned, device-visible: the number of the newest render_kernel_v6 launch with a successor on another launch slot (read once per workgroup)
     uint32_t v6_launch_seq = 0;
     int v6_bands = 8;                // work counters of a launch: 8 = one band of the image per XCD, 1 = one for the whole launch (render_kernel_v6.hip: run_primary)
     int v6_stats = 0;                // 1: the instrumented kernel (env DE_V6_STATS; de_debug_v6_stats)
@@ -203,12 +210,12 @@ struct de_ctx {
     // What started the current frame (cleared by de_reset): de_accumulate / de_upload_hdr, or de_accumulate_adaptive — the two do not mix.
     int frame_kind = 0;          // DE_FRAME_*
     // Adaptive frame (de_accumulate_adaptive).  Allocated on first use: S2 12 B per pixel, two active lists, the tile counts and the keep flags 4 B per tile.
-    float* d_s2 = nullptr;           // [H][W][3] per-pixel sums of squares, accumulated by accumulate_moments_kernel
-    uint32_t* d_alist[2] = {nullptr, nullptr};   // active tile lists, ascending; a round's launches read alist[ad_cur], its compaction writes the other one
-    int32_t* d_tile_spp = nullptr;   // [H/8][W/8] samples per tile (the per-tile display reads it)
-    uint32_t* d_keep = nullptr;      // [active] flags of the convergence test
-    int32_t* d_ad_count = nullptr;   // tiles still active after the compaction ...
-    int32_t* h_ad_count = nullptr;   // ... and its pinned host copy: the host sizes the next round's launch with it
+    Dev<float> d_s2;           // [H][W][3] per-pixel sums of squares, accumulated by accumulate_moments_kernel
+    Dev<uint32_t> d_alist[2];   // active tile lists, ascending; a round's launches read alist[ad_cur], its compaction writes the other one
+    Dev<int32_t> d_tile_spp;   // [H/8][W/8] samples per tile (the per-tile display reads it)
+    Dev<uint32_t> d_keep;      // [active] flags of the convergence test
+    Dev<int32_t> d_ad_count;   // tiles still active after the compaction ...
+    Pinned<int32_t> h_ad_count;   // ... and its pinned host copy: the host sizes the next round's launch with it
     int ad_cur = 0, ad_active = 0, ad_n = 0, ad_rounds = 0;      // list in use, tiles active, samples of every active tile, rounds so far
     unsigned long long ad_pixel_samples = 0;
     uint64_t ad_seed = 0;
@@ -222,38 +229,38 @@ struct de_ctx {
     bool dn_s2_complete = false;    // every sample of the current frame went through accumulate_moments_kernel since the denoiser was on at its start
     bool dn_guides_valid = false;   // the guides belong to the current camera, maps and address mode (cleared by de_reset, map changes, camera changes)
     bool dn_out_valid = false;      // d_dn_out holds the filtered mean of the frame as last displayed
-    float4* d_dn_nc = nullptr;      // [H][W] (normal, coverage)
-    float4* d_dn_at = nullptr;      // [H][W] (albedo, cloud transmittance)
-    float* d_dn_dist = nullptr;     // [H][W]
-    float4* d_dn_buf[2] = {nullptr, nullptr};   // [H][W] (colour, variance): the levels alternate
-    float* d_dn_out = nullptr;      // [H][W][3] the filtered mean: what the display reads with samples = 1
+    Dev<float4> d_dn_nc;      // [H][W] (normal, coverage)
+    Dev<float4> d_dn_at;      // [H][W] (albedo, cloud transmittance)
+    Dev<float> d_dn_dist;     // [H][W]
+    Dev<float4> d_dn_buf[2];   // [H][W] (colour, variance): the levels alternate
+    Dev<float> d_dn_out;      // [H][W][3] the filtered mean: what the display reads with samples = 1
     // Auto-exposure (include/digital_earth_exposure.h).  Allocated on first use: the workgroups' partial histograms (528 KB), the bins' centres,
     // the adaptation state, the second FrameConsts and the result block.  Per context: a context that borrows its maps meters for itself.
     bool ae_on = false;
     bool ae_displayed = false;      // a display has been enqueued since the feature was turned on (de_get_metering answers)
     de_auto_exposure ae;            // the settings
-    uint32_t* d_ae_partial = nullptr;   // [AE_MAX_WG][AE_ROW]
-    double* d_ae_centre = nullptr;      // [AE_BINS]
-    MeterState* d_ae_state = nullptr;   // previous EV: survives de_reset, cleared by de_set_auto_exposure
-    FrameConsts* d_fc_ae = nullptr;     // *d_fc with the metered exposure_scale: what the display reads (d_fc itself is never written: render launches in flight read it)
-    MeterResult* d_ae_result = nullptr;
+    Dev<uint32_t> d_ae_partial;   // [AE_MAX_WG][AE_ROW]
+    Dev<double> d_ae_centre;      // [AE_BINS]
+    Dev<MeterState> d_ae_state;   // previous EV: survives de_reset, cleared by de_set_auto_exposure
+    Dev<FrameConsts> d_fc_ae;     // *d_fc with the metered exposure_scale: what the display reads (d_fc itself is never written: render launches in flight read it)
+    Dev<MeterResult> d_ae_result;
     // Bloom (include/digital_earth_bloom.h).  Allocated on first use: the pyramid (the levels D_1 .. D_L and U_1 .. U_{L-1} of the largest L the
     // image admits, float4: 22 MB at 1080p) and the composited mean that the display reads with samples = 1 (25 MB at 1080p).  Per context.
     bool bl_on = false;
     de_bloom bl;                    // the settings
-    float4* d_bl_pyr = nullptr;
-    float* d_bl_out = nullptr;      // [H][W][3]
+    Dev<float4> d_bl_pyr;
+    Dev<float> d_bl_out;      // [H][W][3]
     // History reprojection (include/digital_earth_history.h).  Allocated on first use: the history and the candidate (a float4 and an f32 per
     // pixel each, and a camera) and the blended mean that the display reads with samples = 1: 2 x (16 + 4) + 12 bytes per pixel (108 MB at 1080p).  Per context.
     bool hs_on = false;
     bool hs_valid = false;          // the history holds a displayed picture (cleared by everything that drops it)
     bool hs_cand_valid = false;     // the candidate was written by a display since the last swap: the next de_reset makes it the history
     de_history hs;                  // the settings
-    float4* d_hs_c[2] = {nullptr, nullptr};       // [H][W] (rgb, weight): [hs_cur] the history, [hs_cur ^ 1] the candidate
-    float* d_hs_d[2] = {nullptr, nullptr};        // [H][W] land distance
-    HistoryCam* d_hs_cam[2] = {nullptr, nullptr};
+    Dev<float4> d_hs_c[2];       // [H][W] (rgb, weight): [hs_cur] the history, [hs_cur ^ 1] the candidate
+    Dev<float> d_hs_d[2];        // [H][W] land distance
+    Dev<HistoryCam> d_hs_cam[2];
     int hs_cur = 0;
-    float* d_hs_out = nullptr;      // [H][W][3]
+    Dev<float> d_hs_out;      // [H][W][3]
     // 8-bit pixel output (include/digital_earth_pixels.h).  Allocated on first use, each for 4 channels so that de_set_pixels never frees a
     // buffer a caller may still read: W * H * 4 bytes on the device, and as much pinned for the staging buffer and per ring cell (W * H * channels of each
     // in use).  The ring is independent of the float image's.
@@ -265,17 +272,17 @@ struct de_ctx {
     // at 1080p).  Per context.
     bool lx_on = false;
     de_local_exposure lx;           // the settings
-    float2* d_lx_pyr = nullptr;
-    float* d_lx_base = nullptr;
-    float* d_lx_out = nullptr;      // [H][W][3]
+    Dev<float2> d_lx_pyr;
+    Dev<float> d_lx_base;
+    Dev<float> d_lx_out;      // [H][W][3]
     // Output scaling (include/digital_earth_output_scale.h).  Allocated on first use: the tables of the two axes (first[n_dst] and
     // w[taps][n_dst] each), the intermediate (W, oh, 3) and the output (ow, oh, 3); re-allocated when a new size needs more.  Per context.
     de_output_scale os = {(uint32_t)sizeof(de_output_scale), 0, 0, 0, DE_SCALE_LANCZOS3};      // the settings; width = height = 0 until the first set: W, H
     struct ScaleDev {               // one axis' table on the device, and what it was built for
-        DeviceBuf first, w;             // int32_t first[n_dst], float w[taps][n_dst]
+        Dev<int32_t> first; Dev<float> w;   // first[n_dst], w[taps][n_dst]
         int n_src = 0, n_dst = 0, filter = -1, taps = 0;
     } os_tab[2];                    // [0] along v, [1] along u
-    DeviceBuf os_mid, os_out;
+    Dev<float> os_mid, os_out;
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.
@@ -292,8 +299,8 @@ struct de_ctx {
     // Look LUTs (include/digital_earth_look.h): the settings as de_set_look took them (lk_on = lk.enabled) and their tables on the
     // device.  de_set_look uploads into fresh buffers and swaps: a refused or failed call leaves these as they were.
     struct LookDev {              // the tables of one look and the constants of their axes
-        float* t1 = nullptr;      // [size_1d][3]
-        float4* t3 = nullptr;     // [size_3d]^3, one float4 per lattice point
+        Dev<float> t1;      // [size_1d][3]
+        Dev<float4> t3;     // [size_3d]^3, one float4 per lattice point
         LookAxis a1[3] = {}, a3[3] = {};
     };
     bool lk_on = false;

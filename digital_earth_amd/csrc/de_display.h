@@ -41,22 +41,17 @@ int get_settings(de_ctx* c, bool de_ctx::*on, S de_ctx::*settings, S* out) {
     out->struct_bytes = (uint32_t)sizeof(S);
     return DE_OK;
 }
-// N device buffers of a debug entry point, freed on every exit path.
-template <int N>
-struct DeviceBufs {
-    void* p[N] = {};
-    ~DeviceBufs() { for (void* q : p) if (q) hipFree(q); }
-};
 // A debug entry point's round trip on `stream`: N device buffers of its own (bytes[k] each; 0: none, the launch sees a null pointer), in[k] uploaded
 // into buffer k where given, `launch(buffers)` and its launch error, buffer `result` downloaded into `out`, and a wait.  Freed on every exit path.
 template <int N, class Launch>
 int debug_round_trip(hipStream_t stream, const size_t (&bytes)[N], const void* const (&in)[N], int result, void* out, Launch launch) {
-    DeviceBufs<N> b;
-    for (int k = 0; k < N; ++k) if (bytes[k]) HIP_TRY(hipMalloc(&b.p[k], bytes[k]));
-    for (int k = 0; k < N; ++k) if (in[k]) HIP_TRY(hipMemcpyAsync(b.p[k], in[k], bytes[k], hipMemcpyHostToDevice, stream));
-    HIP_TRY(launch(b.p));
+    Dev<void> b[N];
+    void* p[N] = {};      // what the launch sees
+    for (int k = 0; k < N; ++k) if (bytes[k]) { HIP_TRY(b[k].ensure(bytes[k])); p[k] = b[k]; }
+    for (int k = 0; k < N; ++k) if (in[k]) HIP_TRY(hipMemcpyAsync(p[k], in[k], bytes[k], hipMemcpyHostToDevice, stream));
+    HIP_TRY(launch(p));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, b.p[result], bytes[result], hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(out, p[result], bytes[result], hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return DE_OK;
 }
@@ -85,16 +80,16 @@ int hdr_output_refusal(de_ctx* c) {
 // the guides alone: what guide_kernel writes (the history reprojection reads their distance without the denoiser's other buffers)
 int dn_alloc_guides(de_ctx* c) {
     const size_t npx = (size_t)c->W * c->H;
-    if (!c->d_dn_nc) HIP_TRY(hipMalloc(&c->d_dn_nc, npx * sizeof(float4)));
-    if (!c->d_dn_at) HIP_TRY(hipMalloc(&c->d_dn_at, npx * sizeof(float4)));
-    if (!c->d_dn_dist) HIP_TRY(hipMalloc(&c->d_dn_dist, npx * sizeof(float)));
+    HIP_TRY(c->d_dn_nc.ensure(npx * sizeof(float4)));
+    HIP_TRY(c->d_dn_at.ensure(npx * sizeof(float4)));
+    HIP_TRY(c->d_dn_dist.ensure(npx * sizeof(float)));
     return DE_OK;
 }
 int dn_alloc(de_ctx* c) {
     const size_t npx = (size_t)c->W * c->H;
     { int rc = dn_alloc_guides(c); if (rc) return rc; }
-    for (int k = 0; k < 2; ++k) if (!c->d_dn_buf[k]) HIP_TRY(hipMalloc(&c->d_dn_buf[k], npx * sizeof(float4)));
-    if (!c->d_dn_out) HIP_TRY(hipMalloc(&c->d_dn_out, npx * 3 * sizeof(float)));
+    for (int k = 0; k < 2; ++k) HIP_TRY(c->d_dn_buf[k].ensure(npx * sizeof(float4)));
+    HIP_TRY(c->d_dn_out.ensure(npx * 3 * sizeof(float)));
     return DE_OK;
 }
 DenoiseGuides dn_guides(de_ctx* c) { DenoiseGuides g; g.nc = c->d_dn_nc; g.at = c->d_dn_at; g.dist = c->d_dn_dist; return g; }
@@ -153,15 +148,15 @@ int run_denoise(de_ctx* c) {
 }
 // ---- auto-exposure (include/digital_earth_exposure.h, exposure_kernels.hip)
 int ae_alloc(de_ctx* c) {
-    if (!c->d_ae_partial) HIP_TRY(hipMalloc(&c->d_ae_partial, (size_t)AE_MAX_WG * AE_ROW * sizeof(uint32_t)));
-    if (!c->d_ae_state) HIP_TRY(hipMalloc(&c->d_ae_state, sizeof(MeterState)));
-    if (!c->d_fc_ae) HIP_TRY(hipMalloc(&c->d_fc_ae, sizeof(FrameConsts)));
-    if (!c->d_ae_result) HIP_TRY(hipMalloc(&c->d_ae_result, sizeof(MeterResult)));
+    HIP_TRY(c->d_ae_partial.ensure((size_t)AE_MAX_WG * AE_ROW * sizeof(uint32_t)));
+    HIP_TRY(c->d_ae_state.ensure(sizeof(MeterState)));
+    HIP_TRY(c->d_fc_ae.ensure(sizeof(FrameConsts)));
+    HIP_TRY(c->d_ae_result.ensure(sizeof(MeterResult)));
     if (!c->d_ae_centre) {
         // log2 of the bins' centres: bin k = octave (k >> 3) - 24, sub-bin k & 7 of 8 linear ones; uploaded once, so that the device computes no logarithm
         double centre[AE_BINS];
         for (int k = 0; k < AE_BINS; ++k) centre[k] = (double)((k >> 3) - 24) + log2(1.0 + ((double)(k & 7) + 0.5) / 8.0);
-        HIP_TRY(hipMalloc(&c->d_ae_centre, sizeof(centre)));
+        HIP_TRY(c->d_ae_centre.ensure(sizeof(centre)));
         HIP_TRY(hipMemcpyAsync(c->d_ae_centre, centre, sizeof(centre), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));      // the table is a local: once per context, when the feature is first turned on, never in a display
     }
@@ -198,8 +193,8 @@ int run_meter(de_ctx* c, const DisplayArgs& d, bool per_tile) {
 // ---- bloom (include/digital_earth_bloom.h, bloom_kernels.hip).  d_bl_pyr holds D_l at the plan's off[l] and U_l `total` further, in float4.
 int bl_alloc(de_ctx* c) {
     const PyramidPlan p = pyr_plan(c->W, c->H, BL_MAX_LEVELS);      // room for every setting of `levels`: the offsets of a level do not depend on it
-    if (!c->d_bl_pyr) HIP_TRY(hipMalloc(&c->d_bl_pyr, 2 * p.total * sizeof(float4)));
-    if (!c->d_bl_out) HIP_TRY(hipMalloc(&c->d_bl_out, (size_t)c->W * c->H * 3 * sizeof(float)));
+    HIP_TRY(c->d_bl_pyr.ensure(2 * p.total * sizeof(float4)));
+    HIP_TRY(c->d_bl_out.ensure((size_t)c->W * c->H * 3 * sizeof(float)));
     return DE_OK;
 }
 // The bloom kernels on the context stream, over exactly what the display launch `d` is about to read (per_tile: display_kernel<true>).  Afterwards `d`
@@ -242,11 +237,11 @@ int run_bloom(de_ctx* c, DisplayArgs& d, bool& per_tile) {
 int hs_alloc(de_ctx* c) {
     const size_t npx = (size_t)c->W * c->H;
     for (int k = 0; k < 2; ++k) {
-        if (!c->d_hs_c[k]) HIP_TRY(hipMalloc(&c->d_hs_c[k], npx * sizeof(float4)));
-        if (!c->d_hs_d[k]) HIP_TRY(hipMalloc(&c->d_hs_d[k], npx * sizeof(float)));
-        if (!c->d_hs_cam[k]) HIP_TRY(hipMalloc(&c->d_hs_cam[k], sizeof(HistoryCam)));
+        HIP_TRY(c->d_hs_c[k].ensure(npx * sizeof(float4)));
+        HIP_TRY(c->d_hs_d[k].ensure(npx * sizeof(float)));
+        HIP_TRY(c->d_hs_cam[k].ensure(sizeof(HistoryCam)));
     }
-    if (!c->d_hs_out) HIP_TRY(hipMalloc(&c->d_hs_out, npx * 3 * sizeof(float)));
+    HIP_TRY(c->d_hs_out.ensure(npx * 3 * sizeof(float)));
     return DE_OK;
 }
 // All weights 0: neither the history nor a candidate written before this point is read again (host flags: the buffers need no clearing).
@@ -281,9 +276,9 @@ int run_history(de_ctx* c, DisplayArgs& d, bool& per_tile) {
 // ---- local exposure (include/digital_earth_local_exposure.h, local_exposure_kernels.hip)
 int lx_alloc(de_ctx* c) {
     const PyramidPlan p = pyr_plan(c->W, c->H, LX_MAX_LEVELS);      // room for every setting of `levels`: the offsets of a level do not depend on it
-    if (!c->d_lx_pyr) HIP_TRY(hipMalloc(&c->d_lx_pyr, p.total * sizeof(float2)));
-    if (!c->d_lx_base) HIP_TRY(hipMalloc(&c->d_lx_base, p.total * sizeof(float)));
-    if (!c->d_lx_out) HIP_TRY(hipMalloc(&c->d_lx_out, (size_t)c->W * c->H * 3 * sizeof(float)));
+    HIP_TRY(c->d_lx_pyr.ensure(p.total * sizeof(float2)));
+    HIP_TRY(c->d_lx_base.ensure(p.total * sizeof(float)));
+    HIP_TRY(c->d_lx_out.ensure((size_t)c->W * c->H * 3 * sizeof(float)));
     return DE_OK;
 }
 int lx_settings_check(const de_local_exposure* s) {
@@ -337,7 +332,7 @@ bool os_active(const de_ctx* c) { return c->os.enabled && c->os.width > 0 && (c-
 int out_w(const de_ctx* c) { return os_active(c) ? c->os.width : c->W; }
 int out_h(const de_ctx* c) { return os_active(c) ? c->os.height : c->H; }
 size_t out_image_bytes(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3 * sizeof(float); }
-const float* shown_image(const de_ctx* c) { return os_active(c) ? (const float*)c->os_out.p : c->d_image; }
+const float* shown_image(const de_ctx* c) { return os_active(c) ? c->os_out : c->d_image; }
 // The settings against a source size; *ow, *oh = the output size they ask for (0, 0: the source's).
 int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) {
     if (s->struct_bytes != (uint32_t)sizeof(de_output_scale)) return fail(DE_ERR_INVALID, "de_output_scale.struct_bytes does not match this library's struct");
@@ -351,16 +346,16 @@ int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) 
 }
 // One axis' table on the device, rebuilt only when the axis or the filter changed.  The upload reads pageable host memory that dies with this call: waited for.
 int os_table_ensure(hipStream_t stream, de_ctx::ScaleDev& d, int n_src, int n_dst, int filter) {
-    if (d.first.p && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
+    if (d.first && d.n_src == n_src && d.n_dst == n_dst && d.filter == filter) return DE_OK;
     ScaleTable T;
     if (!os_build_table(n_src, n_dst, filter, &T)) return fail(DE_ERR_INVALID, "output scaling: no table for this pair of sizes");
-    int rc = device_ensure(d.first, T.first.size() * sizeof(int32_t), "output scaling's");
+    int rc = d.first.ensure(T.first.size() * sizeof(int32_t), "output scaling's buffers");
     if (rc) return rc;
-    rc = device_ensure(d.w, T.w.size() * sizeof(float), "output scaling's");
+    rc = d.w.ensure(T.w.size() * sizeof(float), "output scaling's buffers");
     if (rc) return rc;
     d.filter = -1;
-    HIP_TRY(hipMemcpyAsync(d.first.p, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d.w.p, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d.first, T.first.data(), T.first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(d.w, T.w.data(), T.w.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     d.n_src = n_src; d.n_dst = n_dst; d.filter = filter; d.taps = T.taps;
     return DE_OK;
@@ -370,7 +365,7 @@ int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh
     const float* in = src;
     if (oh != H) {
         ScaleArgs a;
-        a.src = in; a.dst = ow != W ? mid : out; a.first = (const int32_t*)tv.first.p; a.w = (const float*)tv.w.p; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
+        a.src = in; a.dst = ow != W ? mid : out; a.first = tv.first; a.w = tv.w; a.n_src = H; a.n_dst = oh; a.taps = tv.taps; a.lines = W; a.clamp = ow != W ? 0 : 1;
         const unsigned long long blocks = (unsigned long long)W * (unsigned long long)os_v_tiles(oh);
         if (blocks * OS_V_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the image has too many columns for one launch");
         hipLaunchKernelGGL(output_scale_v_kernel, dim3((unsigned)blocks), dim3(OS_V_THREADS), 0, stream, a);
@@ -379,7 +374,7 @@ int os_launch(hipStream_t stream, const float* src, int W, int H, int ow, int oh
     }
     if (ow != W) {
         ScaleArgs a;
-        a.src = in; a.dst = out; a.first = (const int32_t*)tu.first.p; a.w = (const float*)tu.w.p; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
+        a.src = in; a.dst = out; a.first = tu.first; a.w = tu.w; a.n_src = W; a.n_dst = ow; a.taps = tu.taps; a.lines = oh * 3; a.clamp = 1;
         const unsigned long long blocks = (unsigned long long)ow * (unsigned long long)os_u_chunks(oh * 3);
         if (blocks * OS_U_THREADS >= (1ull << 32)) return fail(DE_ERR_INVALID, "output scaling: the output has too many columns for one launch");
         hipLaunchKernelGGL(output_scale_u_kernel, dim3((unsigned)blocks), dim3(OS_U_THREADS), 0, stream, a);
@@ -393,10 +388,10 @@ int run_output_scale(de_ctx* c) {
     int rc = DE_OK;
     if (oh != H) { rc = os_table_ensure(c->stream, c->os_tab[0], H, oh, c->os.filter); if (rc) return rc; }
     if (ow != W) { rc = os_table_ensure(c->stream, c->os_tab[1], W, ow, c->os.filter); if (rc) return rc; }
-    if (oh != H && ow != W) { rc = device_ensure(c->os_mid, (size_t)W * (size_t)oh * 3 * sizeof(float), "output scaling's"); if (rc) return rc; }
-    rc = device_ensure(c->os_out, (size_t)ow * (size_t)oh * 3 * sizeof(float), "output scaling's");
+    if (oh != H && ow != W) { rc = c->os_mid.ensure((size_t)W * (size_t)oh * 3 * sizeof(float), "output scaling's buffers"); if (rc) return rc; }
+    rc = c->os_out.ensure((size_t)ow * (size_t)oh * 3 * sizeof(float), "output scaling's buffers");
     if (rc) return rc;
-    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], (float*)c->os_mid.p, (float*)c->os_out.p);
+    return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], c->os_mid, c->os_out);
 }
 // ---- the packed outputs (pack.h): their settings share the quantiser's mode, their launches the grid (pack_grid).  `who`: the settings struct's name.
 int pack_mode_check(int mode, const char* who) {
@@ -479,11 +474,6 @@ int lk_settings_check(const de_look* s, const float* t1, const float* t3) {
     }
     return DE_OK;
 }
-void lk_free(de_ctx::LookDev& d) {      // hipFree waits for the work that reads the tables
-    if (d.t1) (void)hipFree(d.t1);
-    if (d.t3) (void)hipFree(d.t3);
-    d.t1 = nullptr; d.t3 = nullptr;
-}
 // Checked settings and tables onto the device, into `d` (empty on entry; empty again when the call fails).  The upload reads host memory that dies
 // with the caller: waited for.
 int lk_upload(hipStream_t stream, const de_look& s, const float* t1, const float* t3, de_ctx::LookDev& d) {
@@ -495,18 +485,18 @@ int lk_upload(hipStream_t stream, const de_look& s, const float* t1, const float
     hipError_t e = hipSuccess;
     if (s.size_1d) {
         const size_t bytes = (size_t)s.size_1d * 3 * sizeof(float);
-        e = hipMalloc((void**)&d.t1, bytes);
+        e = d.t1.ensure(bytes);
         if (e == hipSuccess) e = hipMemcpyAsync(d.t1, t1, bytes, hipMemcpyHostToDevice, stream);
     }
     if (e == hipSuccess && s.size_3d) {
         const size_t n = (size_t)s.size_3d * s.size_3d * s.size_3d;
         wide.resize(n * 4);
         for (size_t i = 0; i < n; ++i) { wide[4 * i] = t3[3 * i]; wide[4 * i + 1] = t3[3 * i + 1]; wide[4 * i + 2] = t3[3 * i + 2]; wide[4 * i + 3] = 0.0f; }
-        e = hipMalloc((void**)&d.t3, n * sizeof(float4));
+        e = d.t3.ensure(n * sizeof(float4));
         if (e == hipSuccess) e = hipMemcpyAsync(d.t3, wide.data(), n * sizeof(float4), hipMemcpyHostToDevice, stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { (void)hipGetLastError(); lk_free(d); return fail(DE_ERR_HIP, std::string("look tables: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)hipGetLastError(); d.t1.release(); d.t3.release(); return fail(DE_ERR_HIP, std::string("look tables: ") + hipGetErrorString(e)); }
     return DE_OK;
 }
 void lk_launch(hipStream_t stream, float* image, uint64_t n_pixels, const de_look& s, const de_ctx::LookDev& d) {

@@ -1,6 +1,6 @@
-// de_fetch.h — how an output leaves the GPU, each mechanism stated once (the state they work on is in de_context.h: PinnedBuf, DeviceBuf, FetchRing, PackedOut):
+// de_fetch.h — how an output leaves the GPU, each mechanism stated once (the state they work on is in de_context.h: FetchRing, PackedOut; the buffers
+// "of at least n bytes" they are made of are de_memory.h's Pinned and Dev):
 //   * the ring arithmetic of the lagged fetches, plain integers;
-//   * a pinned host buffer and a device buffer "of at least n bytes";
 //   * copy_out: device -> caller's buffer through the context's staging buffer;
 //   * the conversion frame of the packed outputs (8-bit pixels, HDR pixels, video frames): allocate, display, phase, launch, count;
 //   * the synchronous path (render, copy, wait) and the lagged one (begin: render, copy, record; end: wait, hand out).
@@ -21,44 +21,13 @@ inline int ring_cell(unsigned calls, unsigned depth) { return (int)(calls % dept
 namespace {
 static_assert((DE_FETCH_RING & (DE_FETCH_RING - 1)) == 0, "the ring's depth must divide 2^32 (ring arithmetic above)");
 
-// ---- a pinned host buffer of at least `bytes`: one that is too small (the output size grew, include/digital_earth_output_scale.h) is replaced.  The
-// callers see to it that no copy into it is in flight: a staging buffer's copy is waited for before its call returns, a ring cell being filled is not in flight.
-void pinned_release(PinnedBuf& b) {
-    if (b.p) (void)hipHostFree(b.p);
-    b = PinnedBuf();
-}
-hipError_t pinned_ensure(PinnedBuf& b, size_t bytes) {
-    if (b.p && b.bytes >= bytes) return hipSuccess;
-    pinned_release(b);
-    hipError_t e = hipHostMalloc(&b.p, bytes, hipHostMallocDefault);
-    if (e != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return e; }
-    b.bytes = bytes;
-    return hipSuccess;
-}
-int pinned_ensure(PinnedBuf& b, size_t bytes, const char* noun, const char* what) {
-    if (pinned_ensure(b, bytes) != hipSuccess) return fail(DE_ERR_NOMEM, std::string("no pinned host memory for the ") + noun + " " + what);
-    return DE_OK;
-}
-// ---- a device buffer of at least `bytes`: one that is too small is replaced (hipFree waits for the work that reads it).
-void device_release(DeviceBuf& b) {
-    if (b.p) (void)hipFree(b.p);
-    b = DeviceBuf();
-}
-int device_ensure(DeviceBuf& b, size_t bytes, const char* noun) {
-    if (b.p && b.bytes >= bytes) return DE_OK;
-    device_release(b);
-    if (hipMalloc(&b.p, bytes) != hipSuccess) { b.p = nullptr; (void)hipGetLastError(); return fail(DE_ERR_NOMEM, std::string("no device memory for the ") + noun + " buffers"); }
-    b.bytes = bytes;
-    return DE_OK;
-}
-
 // device (W*H*3 floats, or `bytes`) -> caller's buffer through the pinned staging buffer; straight into the caller's pageable memory when none can be had
 int copy_out(de_ctx* c, float* out, const float* d_src, size_t bytes = 0) {
     if (!bytes) bytes = (size_t)c->W * c->H * 3 * sizeof(float);
-    const bool staged = pinned_ensure(c->h_stage, bytes) == hipSuccess;
-    HIP_TRY(hipMemcpyAsync(staged ? c->h_stage.p : out, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+    const bool staged = c->h_stage.ensure(bytes) == hipSuccess;      // (no copy into it is in flight: every staged copy is waited for before its call returns)
+    HIP_TRY(hipMemcpyAsync(staged ? c->h_stage.get() : out, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (staged) memcpy(out, c->h_stage.p, bytes);
+    if (staged) memcpy(out, c->h_stage, bytes);
     return frame_status(c);
 }
 
@@ -68,7 +37,7 @@ int copy_out(de_ctx* c, float* out, const float* d_src, size_t bytes = 0) {
 template <class Launch>
 int render_packed(de_ctx* c, PackedOut& o, size_t capacity, bool animate, Launch launch) {
     HIP_TRY(hipSetDevice(c->device));
-    int rc = device_ensure(o.dev, capacity, o.noun);
+    int rc = o.dev.ensure(capacity, std::string(o.noun) + " buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
     if (rc) return rc;
     rc = de_render_to_image(c, nullptr);
     if (rc) return rc;
@@ -79,21 +48,20 @@ int render_packed(de_ctx* c, PackedOut& o, size_t capacity, bool animate, Launch
     return DE_OK;
 }
 void packed_reset(PackedOut& o) { o.count = 0; o.last_phase = 0; }      // new settings
-void packed_release(PackedOut& o) { device_release(o.dev); pinned_release(o.stage); }
 
 // ---- the synchronous path.  `render` is an output's de_render_to_* entry point: it enqueues the frame as it stands and answers where on the device it
 // lies.  `size` bytes of it are copied into `stage`, which holds `capacity` (the largest format: a change of format re-allocates nothing), and waited for.
 template <class T, class H>
-int fetch_staged(de_ctx* c, PinnedBuf& stage, const char* noun, int (*render)(de_ctx*, const T**), size_t capacity, size_t size, const H** host) {
+int fetch_staged(de_ctx* c, Pinned<void>& stage, const char* noun, int (*render)(de_ctx*, const T**), size_t capacity, size_t size, const H** host) {
     HIP_TRY(hipSetDevice(c->device));
-    int rc = pinned_ensure(stage, capacity, noun, "staging buffer");
+    int rc = stage.ensure(capacity, std::string(noun) + " staging buffer");
     if (rc) return rc;
     const T* src = nullptr;
     rc = render(c, &src);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(stage.p, src, size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(stage, src, size, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    *host = (const H*)stage.p;
+    *host = (const H*)stage.get();
     return frame_status(c);
 }
 
@@ -110,13 +78,13 @@ int ring_begin(de_ctx* c, FetchRing& r, int (*render)(de_ctx*, const T**), size_
     if (ring_full(r.begun, r.ended, DE_FETCH_RING)) return fail(DE_ERR_STATE, std::string("four ") + r.noun + " fetches are in flight already: " + r.entry + "_end first");
     const int k = ring_cell(r.begun, DE_FETCH_RING);
     HIP_TRY(hipSetDevice(c->device));
-    int rc = pinned_ensure(r.cell[k], capacity, r.noun, "ring");      // cell k is not in flight
+    int rc = r.cell[k].ensure(capacity, std::string(r.noun) + " ring");      // cell k is not in flight
     if (rc) return rc;
     if (!r.ev[k]) HIP_TRY(hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
     const T* src = nullptr;
     rc = render(c, &src);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(r.cell[k].p, src, size, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(r.cell[k], src, size, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipEventRecord(r.ev[k], c->stream));
     r.begun++;
     return DE_OK;
@@ -128,15 +96,11 @@ int ring_end(de_ctx* c, FetchRing& r, const H** host) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipEventSynchronize(r.ev[k]));
     r.ended++;
-    *host = (const H*)r.cell[k].p;
+    *host = (const H*)r.cell[k].get();
     return frame_status(c);
 }
-void ring_release(FetchRing& r) {
-    for (int k = 0; k < DE_FETCH_RING; ++k) {
-        pinned_release(r.cell[k]);
-        if (r.ev[k]) hipEventDestroy(r.ev[k]);
-        r.ev[k] = nullptr;
-    }
+void ring_destroy_events(FetchRing& r) {      // de_destroy; the cells free themselves
+    for (hipEvent_t& ev : r.ev) { if (ev) hipEventDestroy(ev); ev = nullptr; }
 }
 
 }  // namespace

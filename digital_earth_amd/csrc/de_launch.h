@@ -47,12 +47,17 @@ int sync_all(de_ctx* c) {
 void release_loan(de_ctx* c) {
     if (c->lender) { c->lender->loans--; c->lender = nullptr; }
 }
+bool borrows_anything(const de_ctx* c) {      // false: a borrower owns every map and the LUTs again, and gives the loan back
+    bool any = c->luts_borrowed();
+    for (const DevTexture& t : c->tex) any = any || t.borrowed();
+    return any;
+}
 
 // the cloud map's occupancy bound from its packed copy (aux_kernels.hip: tile_max_kernel, cloud_bound_kernel), on the context stream after the packing
 int build_cloud_bound(de_ctx* c, DevTexture& t) {
-    if (!t.bound) HIP_TRY(hipMalloc(&t.bound, DE_CLOUD_BOUND_BYTES));
-    uint8_t* tiles = nullptr;
-    HIP_TRY(hipMalloc(&tiles, (size_t)t.tiles_x * t.tiles_y));
+    HIP_TRY(t.bound.ensure(DE_CLOUD_BOUND_BYTES));
+    Dev<uint8_t> tiles;                                             // scratch: freed on every path
+    HIP_TRY(tiles.ensure((size_t)t.tiles_x * t.tiles_y));
     hipLaunchKernelGGL(tile_max_kernel, dim3((unsigned)((t.tiles_x + 255) / 256), (unsigned)t.tiles_y), dim3(256), 0, c->stream, t.packed, tiles, t.w, t.h, t.tiles_x, t.tiles_y);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
@@ -61,7 +66,6 @@ int build_cloud_bound(de_ctx* c, DevTexture& t) {
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // upload time: the scratch tile maxima go now
     if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);    // (a launch failed: nothing of ours may still read the scratch when it is freed)
-    hipFree(tiles);                                                 // on every path
     if (e != hipSuccess) return fail(DE_ERR_HIP, std::string("building the cloud map's occupancy bound: ") + hipGetErrorString(e));
     return DE_OK;
 }
@@ -69,7 +73,7 @@ int build_cloud_bound(de_ctx* c, DevTexture& t) {
 int ensure_packed(de_ctx* c, int slot, bool clamp) {
     DevTexture& t = c->tex[slot];
     if (t.packed_clamp == (clamp ? 1 : 0)) return DE_OK;
-    if (t.borrowed) return fail(DE_ERR_STATE, "a shared texture keeps its owner's address mode: set DE_FLAG_CLAMP_SAMPLER on the owner and render there once, then share again");
+    if (t.borrowed()) return fail(DE_ERR_STATE, "a shared texture keeps its owner's address mode: set DE_FLAG_CLAMP_SAMPLER on the owner and render there once, then share again");
     if (!t.linear) return fail(DE_ERR_STATE, "the sampler address mode cannot change after de_trim_textures released the as-uploaded maps: upload or generate them again");
     if (c->loans > 0 && t.packed_clamp != -1) return fail(DE_ERR_STATE, "the maps are lent to another context (de_share_textures): they cannot be repacked for another address mode until every borrower is destroyed or holds maps of its own");
     { int rc = join_slots(c); if (rc) return rc; }
@@ -93,24 +97,17 @@ int alloc_texture(de_ctx* c, int slot, int w, int h, int ch) {
         return fail(DE_ERR_INVALID, "map too large: the packed copy (one dword per texel) must stay below 4 GB — the kernels address it with a 32-bit byte offset");
     if (c->loans > 0) return fail(DE_ERR_STATE, "the maps are lent to another context (de_share_textures): destroy the borrowers, or give them maps of their own, before replacing a map");
     { int rc = sync_all(c); if (rc) return rc; }      // no launch may still read the map that is being replaced
-    if (t.linear && !t.borrowed) hipFree(t.linear);
-    if (t.packed && !t.borrowed) hipFree(t.packed);
-    if (t.bound && !t.borrowed) hipFree(t.bound);
-    t.linear = nullptr; t.packed = nullptr; t.bound = nullptr; t.borrowed = false;
-    {   // a borrower that now owns every map again gives the loan back
-        bool any = false;
-        for (int i = 0; i < DE_TEX_COUNT; ++i) any = any || (i != slot && c->tex[i].borrowed);
-        if (!any && !c->luts_borrowed) release_loan(c);
-    }
+    t.linear.release(); t.packed.release(); t.bound.release();      // its own blocks, or its views of the lender's
+    if (!borrows_anything(c)) release_loan(c);
     touched_render_inputs(c);
     t.w = w; t.h = h; t.ch = ch; t.set = false; t.packed_clamp = -1;
-    HIP_TRY(hipMalloc(&t.linear, (size_t)w * h * ch));
+    HIP_TRY(t.linear.ensure((size_t)w * h * ch));
     if (ch == 1) {
         t.tiles_x = (w + 7) / 8; t.tiles_y = (h + 3) / 4;
-        HIP_TRY(hipMalloc(&t.packed, (size_t)t.tiles_x * t.tiles_y * 32 * sizeof(uint32_t)));
+        HIP_TRY(t.packed.ensure((size_t)t.tiles_x * t.tiles_y * 32 * sizeof(uint32_t)));
     } else {
         t.tiles_x = t.tiles_y = 0;
-        HIP_TRY(hipMalloc(&t.packed, (size_t)w * h * sizeof(uint32_t)));
+        HIP_TRY(t.packed.ensure((size_t)w * h * sizeof(uint32_t)));
     }
     return DE_OK;
 }
@@ -148,7 +145,7 @@ int build_tiles(de_ctx* c, int rank, int world) {
     for (int y = 0; y < ty; ++y)
         for (int x = 0; x < tx; ++x)
             if (world <= 1 || ((x + y) % world) == rank) tiles.push_back((uint32_t)(y * tx + x));
-    if (!c->d_tiles) HIP_TRY(hipMalloc(&c->d_tiles, (size_t)tx * ty * sizeof(uint32_t)));
+    HIP_TRY(c->d_tiles.ensure((size_t)tx * ty * sizeof(uint32_t)));
     if (!tiles.empty()) HIP_TRY(hipMemcpyAsync(c->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));   // `tiles` goes out of scope
     c->n_tiles = (int)tiles.size(); c->tiles_rank = rank; c->tiles_world = world;
@@ -208,21 +205,19 @@ int v6_reserve(de_ctx* c, int idx, hipStream_t stream, unsigned long long n_item
     for (int k = 0; k < 2; ++k) {
         if (S.pool_cap[k] >= want[k]) continue;
         HIP_TRY(hipStreamSynchronize(stream));
-        if (S.pool[k]) hipFree(S.pool[k]);
-        S.pool[k] = nullptr; S.pool_cap[k] = 0;
-        if (hipMalloc(&S.pool[k], (size_t)want[k] * DE_V6_POOL_ENTRY_BYTES + 64u) != hipSuccess) { (void)hipGetLastError(); S.pool[k] = nullptr; return fail(DE_ERR_NOMEM, "no room for the tail pool of a render_kernel_v6 launch slot"); }
+        S.pool[k].release(); S.pool_cap[k] = 0;
+        if (S.pool[k].ensure((size_t)want[k] * DE_V6_POOL_ENTRY_BYTES + 64u) != hipSuccess) return fail(DE_ERR_NOMEM, "no room for the tail pool of a render_kernel_v6 launch slot");
         S.pool_cap[k] = want[k];
     }
     if (S.cold && S.ctl && S.d_args && S.h_status && S.n_wg == n_wg) return DE_OK;      // all four or none: a slot whose allocation failed half way is completed (or fails again) here
     HIP_TRY(hipStreamSynchronize(stream));
-    if (S.cold) hipFree(S.cold);
-    S.cold = nullptr; S.n_wg = 0;
-    if (hipMalloc(&S.cold, (size_t)n_wg * DE_V6_P * sizeof(wf::Cold)) != hipSuccess) { (void)hipGetLastError(); S.cold = nullptr; return fail(DE_ERR_NOMEM, "no room for the cold records of a render_kernel_v6 launch slot (37 MB)"); }
+    S.cold.release(); S.n_wg = 0;      // made again for another number of workgroups (v6_cu_withhold), whatever the old block held
+    if (S.cold.ensure((size_t)n_wg * DE_V6_P * sizeof(wf::Cold)) != hipSuccess) return fail(DE_ERR_NOMEM, "no room for the cold records of a render_kernel_v6 launch slot (37 MB)");
     S.n_wg = n_wg;
-    if (!S.ctl) HIP_TRY(hipMalloc(&S.ctl, (size_t)bs::G_WORDS * DE_V6_CTL_STRIDE * sizeof(uint32_t)));
-    if (!S.d_args) HIP_TRY(hipMalloc(&S.d_args, sizeof(RenderArgs)));
+    HIP_TRY(S.ctl.ensure((size_t)bs::G_WORDS * DE_V6_CTL_STRIDE * sizeof(uint32_t)));
+    HIP_TRY(S.d_args.ensure(sizeof(RenderArgs)));
     if (!S.h_status) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_status), 64, hipHostMallocMapped));
+        HIP_TRY(S.h_status.ensure(64, hipHostMallocMapped));
         S.h_status[0] = 0u;
     }
     return DE_OK;
@@ -253,7 +248,7 @@ hipError_t launch_v6(de_ctx* c, const RenderArgs& a, hipStream_t stream, int idx
     // them, and up to two small launches of the same kernel — on this stream: the pool is complete when they start — finish them.
     const int levels = A.n_items >= c->v6_tail_min_paths ? c->v6_tail_levels : 0;
     if (!c->h_issued) {
-        e = hipHostMalloc(reinterpret_cast<void**>(&c->h_issued), 64, hipHostMallocMapped);
+        e = c->h_issued.ensure(64, hipHostMallocMapped);
         if (e != hipSuccess) return e;
         c->h_issued[0] = 0u;
     }
@@ -264,7 +259,7 @@ hipError_t launch_v6(de_ctx* c, const RenderArgs& a, hipStream_t stream, int idx
     // successor is issued (a successor on the same launch slot waits for the whole chain anyway: exporting would only add the tail launch's latency)
     // (the slot of the newest render_kernel_v6 launch, not of the newest launch of any kernel: a state-machine call in between is no successor — ADVICE r5)
     const uint32_t seq = ++c->v6_launch_seq;
-    if (c->last_v6_slot >= 0 && c->last_v6_slot != idx) __atomic_store_n(c->h_issued, seq - 1u, __ATOMIC_RELEASE);
+    if (c->last_v6_slot >= 0 && c->last_v6_slot != idx) __atomic_store_n(c->h_issued.get(), seq - 1u, __ATOMIC_RELEASE);
     c->last_v6_slot = idx;
     A.issued = d_issued; A.seq = c->v6_tail_when_alone ? 0xffffffffu : seq;      // (4 Mi paths by default: launches that fill the GPU several times over)
     const bool fast = (c->p.flags & DE_FLAG_FAST_MATH) != 0u;
@@ -434,9 +429,8 @@ int accumulate_default(de_ctx* c, RenderArgs& a, int spp, int first_index) {
                 LaunchSlot& sj = c->slot[j];
                 if (need <= sj.contrib_items) continue;
                 HIP_TRY(hipStreamSynchronize(sj.stream));      // the slot's previous launch still reads the old buffer
-                if (sj.contrib) hipFree(sj.contrib);
-                sj.contrib = nullptr; sj.contrib_items = 0;
-                if (hipMalloc(&sj.contrib, need * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no room for the per-sample records of a launch (8 bytes per path)"); }
+                sj.contrib_items = 0;
+                if (sj.contrib.ensure(need * sizeof(uint2)) != hipSuccess) return fail(DE_ERR_NOMEM, "no room for the per-sample records of a launch (8 bytes per path)");
                 sj.contrib_items = need;
             }
         }

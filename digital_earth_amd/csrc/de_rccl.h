@@ -121,7 +121,7 @@ int reduce_impl(de_ctx* c, void* comm, int root, bool progressive) {
     if (progressive) {
         // out of place: every rank keeps accumulating into its own buffer; the root receives the assembled frame elsewhere
         if (!c->d_assembled) {
-            HIP_TRY(hipMalloc(&c->d_assembled, count * sizeof(float)));
+            HIP_TRY(c->d_assembled.ensure(count * sizeof(float)));
             HIP_TRY(hipMemsetAsync(c->d_assembled, 0, count * sizeof(float), c->stream));      // non-root ranks: scratch, but never uninitialised
         }
         recv = c->d_assembled;
@@ -156,12 +156,11 @@ int ordered_root_buffers(de_ctx* c, int world, bool out_of_place) {
     const size_t count = (size_t)c->W * c->H * 3;
     if (c->gather_world < world) {
         { int rc2 = sync_all(c); if (rc2) return rc2; }
-        if (c->d_gather) hipFree(c->d_gather);
-        c->d_gather = nullptr; c->gather_world = 0;
-        if (hipMalloc(&c->d_gather, (size_t)world * count * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no room for the gather buffer of de_reduce_ordered"); }
+        c->gather_world = 0;
+        if (c->d_gather.ensure((size_t)world * count * sizeof(float)) != hipSuccess) return fail(DE_ERR_NOMEM, "no room for the gather buffer of de_reduce_ordered");
         c->gather_world = world;
     }
-    if (out_of_place && !c->d_assembled) HIP_TRY(hipMalloc(&c->d_assembled, count * sizeof(float)));
+    if (out_of_place) HIP_TRY(c->d_assembled.ensure(count * sizeof(float)));
     return DE_OK;
 }
 // the root's sum, on the context stream: part r = rank r's gathered buffer, the root's own accumulation buffer in place
@@ -249,7 +248,7 @@ int de_debug_standin_reduce(de_ctx* c, int extra_copies) {
     const size_t count = (size_t)c->W * c->H * 3;
     if (!c->d_standin) {
         // operand, output and copy target of its own ([3][H][W][3]): never the assembled buffer a progressive display may be reading
-        HIP_TRY(hipMalloc(&c->d_standin, 3 * count * sizeof(float)));
+        HIP_TRY(c->d_standin.ensure(3 * count * sizeof(float)));
         HIP_TRY(hipMemsetAsync(c->d_standin, 0, 3 * count * sizeof(float), c->stream));
     }
     const unsigned e = c->standin_count % 16u;

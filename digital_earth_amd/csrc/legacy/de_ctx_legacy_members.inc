@@ -3,14 +3,14 @@
     // render_kernel_v3: one "pipe" = a set of stage queues + cold records.  Two pipes let two batches of paths run side by side on
     // two launch slots, so that the tail-heavy small launches of one overlap the large launches of the other (env DE_V3_PIPES)
     struct V3Pipe {
-        wf::Rec* rec[wf::NQ] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // stage queues (64 B per path each)
-        uint32_t* ctl = nullptr;      // two sets of 2 control words per queue (the set being filled / the set to fill next)
+        Dev<wf::Rec> rec[wf::NQ];   // stage queues (64 B per path each)
+        Dev<uint32_t> ctl;           // two sets of 2 control words per queue (the set being filled / the set to fill next)
         int epoch[wf::NQ] = {0, 0, 0, 0, 0, 0, 0};   // completed drains per queue: parity selects the current set
-        wf::Cold* cold = nullptr;     // 64 B per path
+        Dev<wf::Cold> cold;          // 64 B per path
         size_t capacity = 0;          // paths the buffers hold
         // statistic for the automatic variant: records queued for vertex round 2 (holes included) of one launch, copied to pinned
         // host memory in stream order and read by a LATER de_accumulate call — never waited for
-        uint32_t* h_round2 = nullptr;
+        Pinned<uint32_t> h_round2;
         hipEvent_t stat_ev = nullptr, ev_t[3] = {nullptr, nullptr, nullptr};   // stat_ev: the copy has landed; ev_t: start / pipeline done / finisher done
         bool stat_pending = false, stat_timed = false;
         unsigned long long stat_items = 0;
@@ -42,13 +42,11 @@
     // render_kernel_v5 (kernel variant 5): one persistent stage-scheduler launch per call.  Each launch slot that runs it owns a chunk
     // pool, the queue rings, the control words and the cold records of its launch (launches of different slots overlap).
     struct V5State {
-        uint4* pool = nullptr;
-        uint32_t* ctl = nullptr;
-        uint32_t* rings = nullptr;
-        uint32_t* free_ring = nullptr;
-        unsigned long long* cold = nullptr;
-        RenderArgs* d_args = nullptr;     // the launch's RenderArgs (written by v5_init_kernel)
-        uint32_t* h_status = nullptr;     // pinned, device-visible: the kernel's abort code
+        Dev<uint4> pool;
+        Dev<uint32_t> ctl, rings, free_ring;
+        Dev<unsigned long long> cold;
+        Dev<RenderArgs> d_args;           // the launch's RenderArgs (written by v5_init_kernel)
+        Pinned<uint32_t> h_status;        // pinned, device-visible: the kernel's abort code
         size_t cold_items = 0;
         uint32_t pool_chunks = 0, ring_cells = 0, n_shards = 0;
     } v5s[DE_MAX_SLOTS + 4];         // one per launch slot (kernel variant 5), then one per pipe (the pipeline's finisher, v3_finisher = 5)

@@ -12,6 +12,10 @@ namespace {
 // empty leaves after one atomic.
 // Returns DE_OK, an error, or V3_NO_MEMORY: the device does not have room for queues of this size (the caller shrinks the batch).
 static const int V3_NO_MEMORY = 1000;
+void v3_release_queues(de_ctx::V3Pipe& P) {
+    for (auto& q : P.rec) q.release();
+    P.cold.release(); P.capacity = 0;
+}
 int v3_reserve(de_ctx* c, int pipe, size_t n_items) {
     de_ctx::V3Pipe& P = c->v3p[pipe];
     if (n_items <= P.capacity) return DE_OK;
@@ -31,32 +35,28 @@ int v3_reserve(de_ctx* c, int pipe, size_t n_items) {
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b + held_b < need_b + ((size_t)8 << 30)) return V3_NO_MEMORY;
     if (c->v3_test_budget && n_items > c->v3_test_budget) return V3_NO_MEMORY;      // tests: pretend larger queues do not fit
     { int rc = sync_all(c); if (rc) return rc; }
-    for (int i = 0; i < wf::NQ; ++i) { if (P.rec[i]) hipFree(P.rec[i]); P.rec[i] = nullptr; }
-    if (P.cold) hipFree(P.cold);
-    P.cold = nullptr; P.capacity = 0;
+    v3_release_queues(P);
     bool ok = true;
-    for (int i = 0; i < wf::NQ && ok; ++i) ok = hipMalloc(&P.rec[i], (n_items + slack) * sizeof(wf::Rec)) == hipSuccess;
-    if (ok) ok = hipMalloc(&P.cold, n_items * sizeof(wf::Cold)) == hipSuccess;
+    for (int i = 0; i < wf::NQ && ok; ++i) ok = P.rec[i].ensure((n_items + slack) * sizeof(wf::Rec)) == hipSuccess;
+    if (ok) ok = P.cold.ensure(n_items * sizeof(wf::Cold)) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        for (int i = 0; i < wf::NQ; ++i) { if (P.rec[i]) hipFree(P.rec[i]); P.rec[i] = nullptr; }
-        if (P.cold) hipFree(P.cold);
-        P.cold = nullptr;
+        v3_release_queues(P);
         return V3_NO_MEMORY;
     }
     if (!P.ctl) {
-        HIP_TRY(hipMalloc(&P.ctl, wf::NQ * 4 * sizeof(uint32_t)));
+        HIP_TRY(P.ctl.ensure(wf::NQ * 4 * sizeof(uint32_t)));
         // hipMemset runs on the null stream and may return before it has executed; the launch slots are non-blocking streams
         // that do not wait for the null stream: make sure the control words are zero before any kernel can read them
         HIP_TRY(hipMemset(P.ctl, 0, wf::NQ * 4 * sizeof(uint32_t)));
         HIP_TRY(hipDeviceSynchronize());
         for (int i = 0; i < wf::NQ; ++i) P.epoch[i] = 0;
-        if (hipHostMalloc(reinterpret_cast<void**>(&P.h_round2), sizeof(uint32_t), hipHostMallocDefault) == hipSuccess) {
+        if (P.h_round2.ensure(sizeof(uint32_t)) == hipSuccess) {
             *P.h_round2 = 0;
             bool ok = hipEventCreateWithFlags(&P.stat_ev, hipEventDisableTiming) == hipSuccess;
             for (int i = 0; i < 3 && ok; ++i) ok = hipEventCreate(&P.ev_t[i]) == hipSuccess;
-            if (!ok) { hipHostFree(P.h_round2); P.h_round2 = nullptr; }
-        } else P.h_round2 = nullptr;
+            if (!ok) P.h_round2.release();
+        }
         (void)hipGetLastError();
     }
     P.capacity = n_items;
@@ -133,9 +133,9 @@ hipError_t launch_v3(de_ctx* c, const RenderArgs& a, hipStream_t stream, int pip
     if (n_depths < 25) {
         bind();
         RenderArgs b = a;
-        b.resume_rec = reinterpret_cast<const uint4*>(P.rec[wf::Q_ST]);
+        b.resume_rec = reinterpret_cast<const uint4*>(P.rec[wf::Q_ST].get());
         b.resume_count = A.q[wf::Q_ST].ctl;
-        b.resume_cold = reinterpret_cast<const float*>(P.cold);
+        b.resume_cold = reinterpret_cast<const float*>(P.cold.get());
         b.resume_capacity = A.capacity;
         hipError_t me = hipMemsetAsync(A.q[wf::Q_ST].ctl_next, 0, 2 * sizeof(uint32_t), stream);      // what begin_drain does in the pipeline's kernels
         if (me == hipSuccess) me = hipMemsetAsync(b.work_counter, 0, sizeof(uint32_t), stream);
@@ -162,25 +162,23 @@ int v5_reserve(de_ctx* c, int idx, hipStream_t stream, size_t n_items) {
     const uint32_t pool_chunks = 1u << c->v5_pool_log2;
     if (!S.pool || !S.ctl || !S.rings || !S.free_ring || !S.d_args || !S.h_status || S.pool_chunks != pool_chunks || S.n_shards != (uint32_t)c->v5_shards) {      // all or none (a reservation that failed half way is redone)
         HIP_TRY(hipStreamSynchronize(stream));
-        if (S.pool) hipFree(S.pool); if (S.ctl) hipFree(S.ctl); if (S.rings) hipFree(S.rings); if (S.free_ring) hipFree(S.free_ring);
-        S.pool = nullptr; S.ctl = nullptr; S.rings = nullptr; S.free_ring = nullptr;
+        S.pool.release(); S.ctl.release(); S.rings.release(); S.free_ring.release();
         S.pool_chunks = pool_chunks; S.n_shards = (uint32_t)c->v5_shards;
         S.ring_cells = pool_chunks;
-        HIP_TRY(hipMalloc(&S.pool, (size_t)pool_chunks * DE_V5_CH * 64u));
-        HIP_TRY(hipMalloc(&S.ctl, (size_t)ps::C_WORDS * DE_V5_CTL_STRIDE * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&S.rings, (size_t)S.n_shards * wf::NQ * S.ring_cells * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(&S.free_ring, (size_t)pool_chunks * sizeof(uint32_t)));
-        if (!S.d_args) HIP_TRY(hipMalloc(&S.d_args, sizeof(RenderArgs)));
+        HIP_TRY(S.pool.ensure((size_t)pool_chunks * DE_V5_CH * 64u));
+        HIP_TRY(S.ctl.ensure((size_t)ps::C_WORDS * DE_V5_CTL_STRIDE * sizeof(uint32_t)));
+        HIP_TRY(S.rings.ensure((size_t)S.n_shards * wf::NQ * S.ring_cells * sizeof(uint32_t)));
+        HIP_TRY(S.free_ring.ensure((size_t)pool_chunks * sizeof(uint32_t)));
+        HIP_TRY(S.d_args.ensure(sizeof(RenderArgs)));
         if (!S.h_status) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&S.h_status), 64, hipHostMallocMapped));
+            HIP_TRY(S.h_status.ensure(64, hipHostMallocMapped));
             S.h_status[0] = 0u;
         }
     }
     if (n_items > S.cold_items) {
         HIP_TRY(hipStreamSynchronize(stream));
-        if (S.cold) hipFree(S.cold);
-        S.cold = nullptr; S.cold_items = 0;
-        if (hipMalloc(&S.cold, n_items * 64u) != hipSuccess) { (void)hipGetLastError(); return fail(DE_ERR_NOMEM, "no room for the cold records of a render_kernel_v5 launch (64 B per path): lower DE_V5_MAX_ITEMS"); }
+        S.cold_items = 0;
+        if (S.cold.ensure(n_items * 64u) != hipSuccess) { return fail(DE_ERR_NOMEM, "no room for the cold records of a render_kernel_v5 launch (64 B per path): lower DE_V5_MAX_ITEMS"); }
         S.cold_items = n_items;
     }
     return DE_OK;
@@ -494,9 +492,8 @@ int accumulate_legacy(de_ctx* c, RenderArgs& a, int spp, int first_index) {
                     LaunchSlot& sj = c->slot[j];
                     if (need <= sj.contrib_items) continue;
                     HIP_TRY(hipStreamSynchronize(sj.stream));      // the slot's previous launch still reads the old buffer
-                    if (sj.contrib) hipFree(sj.contrib);
-                    sj.contrib = nullptr; sj.contrib_items = 0;
-                    HIP_TRY(hipMalloc(&sj.contrib, need * sizeof(uint2)));
+                    sj.contrib_items = 0;
+                    HIP_TRY(sj.contrib.ensure(need * sizeof(uint2)));
                     sj.contrib_items = need;
                 }
             }
@@ -541,30 +538,16 @@ int accumulate_legacy(de_ctx* c, RenderArgs& a, int spp, int first_index) {
 }
 
 void free_queue_memory(de_ctx* c) {
-    for (auto& P : c->v3p) {
-        for (int i = 0; i < wf::NQ; ++i) { if (P.rec[i]) hipFree(P.rec[i]); P.rec[i] = nullptr; }
-        if (P.cold) hipFree(P.cold);
-        P.cold = nullptr; P.capacity = 0;
-    }
+    for (auto& P : c->v3p) v3_release_queues(P);
     for (auto& S : c->v5s) {
-        if (S.pool) hipFree(S.pool); if (S.rings) hipFree(S.rings); if (S.free_ring) hipFree(S.free_ring); if (S.cold) hipFree(S.cold);
-        S.pool = nullptr; S.rings = nullptr; S.free_ring = nullptr; S.cold = nullptr; S.cold_items = 0; S.pool_chunks = 0;
+        S.pool.release(); S.rings.release(); S.free_ring.release(); S.cold.release();
+        S.cold_items = 0; S.pool_chunks = 0;
     }
 }
-void legacy_destroy(de_ctx* c) {
+void destroy_legacy_events(de_ctx* c) {      // de_destroy; the pipes' and the scheduler's memory is freed by its members
     for (auto& P : c->v3p) {
-        for (int i = 0; i < wf::NQ; ++i) if (P.rec[i]) hipFree(P.rec[i]);
-        if (P.ctl) hipFree(P.ctl);
-        if (P.cold) hipFree(P.cold);
-        if (P.h_round2) hipHostFree(P.h_round2);
         if (P.stat_ev) hipEventDestroy(P.stat_ev);
         for (int i = 0; i < 3; ++i) if (P.ev_t[i]) hipEventDestroy(P.ev_t[i]);
-    }
-    for (auto& S : c->v5s) {
-        if (S.pool) hipFree(S.pool); if (S.ctl) hipFree(S.ctl); if (S.rings) hipFree(S.rings); if (S.free_ring) hipFree(S.free_ring);
-        if (S.cold) hipFree(S.cold);
-        if (S.d_args) hipFree(S.d_args);
-        if (S.h_status) hipHostFree(S.h_status);
     }
 }
 uint64_t legacy_memory_use(de_ctx* c) {
