@@ -106,8 +106,15 @@ class DeLook(ctypes.Structure):
                 ("size_3d", ctypes.c_int32), ("min_3d", ctypes.c_float * 3), ("max_3d", ctypes.c_float * 3)]
 
 
+class DeJpeg(ctypes.Structure):
+    """`de_jpeg` (include/digital_earth_jpeg.h): the quality and the restart interval of the JPEG output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("quality", ctypes.c_int32), ("restart_mcus", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
+DE_ERR_INTERNAL = -6
+JPEG_DEFAULT_RESTART = 2      # DE_JPEG_DEFAULT_RESTART of include/digital_earth_jpeg.h
 
 DE_FLAG_FIXED_WAVELENGTH = 1 << 0
 DE_FLAG_CLAMP_SAMPLER = 1 << 1
@@ -269,6 +276,21 @@ VIDEO_SYMBOLS = {
     "de_debug_video": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeVideo), ctypes.c_uint32, _P]),
 }
 
+# JPEG output: include/digital_earth_jpeg.h (same library, additions only; not part of the binder's header)
+_U64P = ctypes.POINTER(ctypes.c_uint64)
+JPEG_SYMBOLS = {
+    "de_set_jpeg": (ctypes.c_int, [_P, ctypes.POINTER(DeJpeg)]),
+    "de_get_jpeg": (ctypes.c_int, [_P, ctypes.POINTER(DeJpeg)]),
+    "de_jpeg_capacity": (ctypes.c_int, [_P, _U64P]),
+    "de_render_to_jpeg": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_jpeg": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _U64P]),
+    "de_fetch_jpeg_view": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_fetch_jpeg_begin": (ctypes.c_int, [_P]),
+    "de_fetch_jpeg_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_debug_jpeg": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeJpeg), _P, ctypes.c_uint64, _U64P]),
+    "de_debug_jpeg_framing": (ctypes.c_int, [ctypes.POINTER(DeJpeg), ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint64, _U64P, _U64P]),
+}
+
 # look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
 LOOK_SYMBOLS = {
     "de_set_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook), _P, _P]),
@@ -355,7 +377,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -107,7 +107,7 @@ int de_destroy(de_ctx* c) {
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
     // events and streams; the memory is the members' (de_memory.h): `delete c` frees what this context owns and leaves what it borrows
-    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) ring_destroy_events(*r);
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring}) ring_destroy_events(*r);
 #ifdef DE_LEGACY_VARIANTS
     destroy_legacy_events(c);
 #endif
@@ -1182,7 +1182,7 @@ int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
-    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
+    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
     c->os = *s;
     c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
     return DE_OK;
@@ -1344,6 +1344,120 @@ int de_debug_video(de_ctx* c, const float* image, int W, int H, const de_video* 
     const size_t bytes[2] = {(size_t)W * H * 3 * sizeof(float), vd_frame_bytes(W, H, *s)};
     const void* const in[2] = {image, nullptr};
     return debug_round_trip(c->stream, bytes, in, 1, out, [&](void* const* b) { vd_launch(c->stream, (const float*)b[0], (uint8_t*)b[1], W, H, *s, vd_make_consts(s->format, s->matrix, s->range), phase); return hipSuccess; });
+}
+
+/* ---- JPEG output: include/digital_earth_jpeg.h (jpeg_kernels.hip, jpeg_tables.h) */
+int de_set_jpeg(de_ctx* c, const de_jpeg* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = jp_settings_check(s); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->jp_ring); if (rc) return rc; }
+    c->jp = *s;
+    jp_make_tables(s->quality, &c->jp_tab);
+    c->jp_gen++; c->jp_tab_gen = c->jp_gen;
+    c->jp_w = out_w(c); c->jp_h = out_h(c);
+    jp_write_framing(c->jp_tab, c->jp_w, c->jp_h, s->restart_mcus, c->jp_framing);
+    packed_reset(c->jp_out);
+    return DE_OK;
+}
+int de_get_jpeg(de_ctx* c, de_jpeg* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->jp;
+    return DE_OK;
+}
+int de_jpeg_capacity(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    *bytes = (uint64_t)jp_ctx_geometry(c).capacity;
+    return DE_OK;
+}
+int de_render_to_jpeg(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    int rc = jp_render(c, c->jp_out.dev, c->jp_out_framed);
+    if (rc) return rc;
+    if (device_stream) *device_stream = c->jp_out.dev + JP_HEADER_WORD;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->jp_out.dev.get());
+    return DE_OK;
+}
+int de_fetch_jpeg_view(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = de_render_to_jpeg(c, nullptr, nullptr);
+    if (rc) return rc;
+    return fetch_staged_sized(c, c->jp_out.stage, c->jp_out.noun, c->jp_out.dev, JP_HEADER_WORD, jp_read_word, host, len);
+}
+int de_fetch_jpeg(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    const void* host = nullptr;
+    int rc = de_fetch_jpeg_view(c, &host, len);
+    if (rc) return rc;
+    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the frame (*len; de_jpeg_capacity bounds every frame)");
+    memcpy(out, host, (size_t)*len);
+    return DE_OK;
+}
+int de_fetch_jpeg_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = vd_even_check(c); if (rc) return rc; }
+    const JpegGeometry g = jp_ctx_geometry(c);
+    size_t prefix = c->jp_guess ? c->jp_guess : JP_HEADER_WORD + JP_FRAMING_BYTES + (size_t)g.W * (size_t)g.H / 4;      // the first: two bits per pixel
+    if (prefix > JP_HEADER_WORD + g.capacity) prefix = JP_HEADER_WORD + g.capacity;
+    return ring_begin_prefix(c, c->jp_ring, [c](int k, const uint8_t** src) {
+        int rc = jp_render(c, c->jp_cell[k].dev, c->jp_cell[k].framed);
+        *src = c->jp_cell[k].dev;
+        return rc;
+    }, prefix, c->jp_cell_copied);
+}
+int de_fetch_jpeg_end(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = ring_end_sized(c, c->jp_ring, [c](int k) { return (const uint8_t*)c->jp_cell[k].dev.get(); }, c->jp_cell_copied, JP_HEADER_WORD, jp_read_word, host, len);
+    if (!rc) c->jp_guess = ((JP_HEADER_WORD + (size_t)*len) * 5 / 4 + 4095) & ~(size_t)4095;      // the next prefix: a quarter more than this frame
+    return rc;
+}
+/* the conversion once on a host-given image of any even size.  Buffers of its own; the context's settings and streams are not touched. */
+int de_debug_jpeg(de_ctx* c, const float* image, int W, int H, const de_jpeg* s, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !image || !s || !out || !len || W <= 0 || H <= 0 || (W & 1) || (H & 1) || (long long)W * H > (1ll << 24))
+        return fail(DE_ERR_INVALID, "bad arguments (W and H positive and even, W * H at most 2^24)");
+    { int rc = jp_settings_check(s); if (rc) return rc; }
+    const JpegGeometry g = jp_geometry(W, H, s->restart_mcus);
+    { int rc = jp_geometry_check(g); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    JpegTables tab;
+    jp_make_tables(s->quality, &tab);
+    uint8_t framing[JP_FRAMING_BYTES];
+    jp_write_framing(tab, W, H, s->restart_mcus, framing);
+    de_ctx::JpegWork work;
+    Dev<float> d_image;
+    Dev<uint8_t> d_out;
+    const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
+    { int rc = jp_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_image.ensure(image_bytes));
+    HIP_TRY(d_out.ensure(jp_stream_bytes(g)));
+    HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(work.tab, &tab, sizeof(tab), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_out + JP_HEADER_WORD, framing, sizeof(framing), hipMemcpyHostToDevice, c->stream));
+    jp_launch(c->stream, d_image, work, g, d_out);
+    HIP_TRY(hipGetLastError());
+    uint32_t word[4];
+    HIP_TRY(hipMemcpyAsync(word, d_out, sizeof(word), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    { int rc = jp_read_word(word, len); if (rc) return rc; }
+    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the frame (*len)");
+    HIP_TRY(hipMemcpyAsync(out, d_out + JP_HEADER_WORD, (size_t)*len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+/* the host's part alone: no device, no context */
+int de_debug_jpeg_framing(const de_jpeg* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
+    if (!s || W <= 0 || H <= 0 || (W & 1) || (H & 1) || W > 65534 || H > 65534) return fail(DE_ERR_INVALID, "bad arguments (W and H positive, even and below 65535)");
+    { int rc = jp_settings_check(s); if (rc) return rc; }
+    if (len) *len = JP_FRAMING_BYTES;
+    if (capacity) *capacity = (uint64_t)jp_geometry(W, H, s->restart_mcus).capacity;
+    if (out || out_bytes) {
+        if (!out || out_bytes < JP_FRAMING_BYTES) return fail(DE_ERR_INVALID, "out_bytes is smaller than the framing (*len)");
+        JpegTables tab;
+        jp_make_tables(s->quality, &tab);
+        jp_write_framing(tab, W, H, s->restart_mcus, (uint8_t*)out);
+    }
+    return DE_OK;
 }
 
 /* ---- look LUTs: include/digital_earth_look.h (look_kernels.hip) */

@@ -10,6 +10,7 @@
 #include "../../include/digital_earth_hdr_output.h"
 #include "../../include/digital_earth_video.h"
 #include "../../include/digital_earth_look.h"
+#include "../../include/digital_earth_jpeg.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -41,6 +42,7 @@
 #include "hdr_output_kernels.hip"
 #include "videoframe_kernels.hip"
 #include "look_kernels.hip"
+#include "jpeg_kernels.hip"
 
 namespace {
 
@@ -306,6 +308,29 @@ struct de_ctx {
     bool lk_on = false;
     de_look lk = {};
     LookDev lk_dev;
+    // JPEG output (include/digital_earth_jpeg.h).  The tables of the settings are computed by de_set_jpeg on the host; they, the framing and
+    // every buffer reach the device on first use: the planes, coefficients, masks and interval slots of one conversion (JpegWork), the stream of the
+    // synchronous fetches (jp_out: its staging buffer grows to the longest frame fetched, not to the capacity) and, per ring cell, a stream on the device
+    // and a pinned cell — a lagged fetch copies a prefix at _begin and, should the frame be longer, the whole of it at _end, from its own device stream.
+    struct JpegWork {             // what one conversion passes through; re-allocated when a frame needs more
+        Dev<uint8_t> planes; Dev<int16_t> coef; Dev<unsigned long long> mask; Dev<uint8_t> slots; Dev<uint32_t> words; Dev<JpegTables> tab;
+    };
+    struct JpegStream {           // a stream on the device: the 16-byte word, the framing, the entropy-coded data
+        Dev<uint8_t> dev;
+        uint64_t framed = 0;      // jp_gen when the framing in it was written
+    };
+    de_jpeg jp = {(uint32_t)sizeof(de_jpeg), 90, DE_JPEG_DEFAULT_RESTART};
+    JpegTables jp_tab = {};         // of jp.quality: once per de_set_jpeg (and in de_create's stead on first use: jp_tab_gen = 0)
+    uint64_t jp_gen = 1, jp_tab_gen = 0, jp_tab_uploaded = 0;      // jp_gen: counts de_set_jpeg and changes of the output size
+    int jp_w = 0, jp_h = 0;         // the size the framing was written for
+    uint8_t jp_framing[JP_FRAMING_BYTES] = {};
+    JpegWork jp_work;
+    PackedOut jp_out = {"JPEG"};
+    uint64_t jp_out_framed = 0;
+    FetchRing jp_ring = {"JPEG", "de_fetch_jpeg"};
+    JpegStream jp_cell[DE_FETCH_RING];
+    size_t jp_cell_copied[DE_FETCH_RING] = {};      // bytes of the device stream that _begin copied into the pinned cell
+    size_t jp_guess = 0;            // the prefix a lagged fetch copies at _begin: a quarter more than the newest frame ended
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

@@ -2,7 +2,7 @@
 //   * the small helpers every entry point of that path shares: host <-> device layouts, a transposed fetch, a settings getter, device scratch buffers
 //     (how an output leaves the GPU — staging, the rings, the packed outputs' conversion frame — is de_fetch.h);
 //   * each opt-in stage's allocation and launch sequence (denoiser, auto-exposure, bloom, history reprojection, local exposure), the stages behind the
-//     display (look LUTs, output scaling, 8-bit and HDR pixels, video frames) and the two refusals;
+//     display (look LUTs, output scaling, 8-bit and HDR pixels, video frames, JPEG streams) and the two refusals;
 //   * display_chain: the ONE statement of the order denoise -> history -> meter -> bloom -> local exposure -> display and of its preconditions, which
 //     de_render_to_image and the four intermediate fetches of de_api.hip run up to their own stage.
 // The kernels are in *_kernels.hip; the tent pyramid the bloom and local exposure share is pyramid.h, what the packed outputs share pack.h, the source
@@ -448,6 +448,81 @@ void vd_launch(hipStream_t stream, const float* image, uint8_t* out, int W, int 
     VideoArgs a;
     a.image = image; a.out = out; a.W = W; a.H = H; a.format = s.format; a.siting = s.siting; a.mode = s.mode; a.seed = s.seed; a.phase = phase; a.k = k;
     hipLaunchKernelGGL(videoframe_pack_kernel, pack_grid(W, H), dim3(256), 0, stream, a);
+}
+// ---- JPEG output (include/digital_earth_jpeg.h, jpeg_kernels.hip, jpeg_tables.h)
+int jp_settings_check(const de_jpeg* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_jpeg)) return fail(DE_ERR_INVALID, "de_jpeg.struct_bytes does not match this library's struct");
+    if (s->quality < 1 || s->quality > 100) return fail(DE_ERR_INVALID, "de_jpeg.quality must lie in 1 ... 100");
+    if (s->restart_mcus < 1 || s->restart_mcus > 65535) return fail(DE_ERR_INVALID, "de_jpeg.restart_mcus must lie in 1 ... 65535");
+    return DE_OK;
+}
+int jp_geometry_check(const JpegGeometry& g) {      // the kernels count bytes in 32 bits
+    if (g.capacity + 64 >= (1ull << 32)) return fail(DE_ERR_INVALID, "the JPEG output's worst case does not fit 2^32 bytes at this size");
+    return DE_OK;
+}
+size_t jp_stream_bytes(const JpegGeometry& g) { return (JP_HEADER_WORD + g.capacity + 15) & ~(size_t)15; }      // a stream on the device
+// The buffers of one conversion of geometry g; `words` holds len[intervals], offset[intervals] and the status word.
+int jp_work_ensure(de_ctx::JpegWork& w, const JpegGeometry& g) {
+    int rc = w.planes.ensure((size_t)g.W * (size_t)g.H / 2 * 3, "JPEG buffers");
+    if (!rc) rc = w.coef.ensure(g.blocks * 64 * sizeof(int16_t), "JPEG buffers");
+    if (!rc) rc = w.mask.ensure(g.blocks * sizeof(unsigned long long), "JPEG buffers");
+    if (!rc) rc = w.slots.ensure(g.intervals * g.slot_bytes, "JPEG buffers");
+    if (!rc) rc = w.words.ensure((2 * g.intervals + 4) * sizeof(uint32_t), "JPEG buffers");
+    if (!rc) rc = w.tab.ensure(sizeof(JpegTables), "JPEG buffers");
+    return rc;
+}
+// image -> planes -> coefficients -> slots -> the stream at `out` (whose framing is in place or on its way on this stream).  w.tab holds the tables.
+void jp_launch(hipStream_t stream, const float* image, const de_ctx::JpegWork& w, const JpegGeometry& g, uint8_t* out) {
+    static const de_video jfif = {(uint32_t)sizeof(de_video), DE_VIDEO_I420, DE_VIDEO_MATRIX_BT601, DE_VIDEO_RANGE_FULL, DE_VIDEO_SITING_CENTER, DE_PIXELS_ROUND, 0u, 0};
+    vd_launch(stream, image, w.planes, g.W, g.H, jfif, vd_make_consts(jfif.format, jfif.matrix, jfif.range), 0u);
+    JpegArgs a;
+    a.planes = w.planes; a.tab = w.tab; a.coef = w.coef; a.mask = w.mask; a.slots = w.slots;
+    a.len = w.words; a.offset = w.words + g.intervals; a.status = w.words + 2 * g.intervals; a.out = out;
+    a.W = g.W; a.H = g.H; a.mcus_x = g.mcus_x; a.restart = g.restart;
+    a.blocks = (uint32_t)g.blocks; a.mcus = (uint32_t)g.mcus; a.intervals = (uint32_t)g.intervals; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.framing = JP_FRAMING_BYTES; a.capacity = (uint32_t)g.capacity;
+    hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((g.blocks + JP_WG_BLOCKS - 1) / JP_WG_BLOCKS)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((g.intervals + 63) / 64)), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(JP_SCAN_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(jpeg_compact_kernel, dim3((unsigned)g.intervals), dim3(256), 0, stream, a);
+}
+JpegGeometry jp_ctx_geometry(const de_ctx* c) { return jp_geometry(out_w(c), out_h(c), c->jp.restart_mcus); }
+// The 16-byte word as a fetch finds it on the host: the length, or DE_ERR_INTERNAL.
+int jp_read_word(const void* word, uint64_t* len) {
+    uint32_t w[4];
+    memcpy(w, word, sizeof(w));
+    *len = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    if (w[2]) return fail(DE_ERR_INTERNAL, w[2] & JP_STATUS_OVERFLOW ? "the JPEG encoder met a stream longer than its proven worst case: nothing was written past a buffer" : "the JPEG encoder met a coefficient outside the DCT's proven range");
+    return DE_OK;
+}
+// One conversion of the frame as it stands into `dev`, a stream on the device that is (re-)allocated and framed as needed.  Nothing is waited for.
+int jp_render(de_ctx* c, Dev<uint8_t>& dev, uint64_t& framed) {
+    HIP_TRY(hipSetDevice(c->device));
+    const JpegGeometry g = jp_ctx_geometry(c);
+    int rc = jp_geometry_check(g);
+    if (rc) return rc;
+    if (c->jp_w != g.W || c->jp_h != g.H || c->jp_tab_gen == 0) {      // the first conversion, or a new output size: tables (the defaults') and framing
+        if (c->jp_tab_gen == 0) jp_make_tables(c->jp.quality, &c->jp_tab);
+        c->jp_gen++; c->jp_tab_gen = c->jp_gen; c->jp_w = g.W; c->jp_h = g.H;
+        jp_write_framing(c->jp_tab, g.W, g.H, c->jp.restart_mcus, c->jp_framing);
+    }
+    const uint8_t* before = dev.get();
+    rc = dev.ensure(jp_stream_bytes(g), "JPEG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
+    if (rc) return rc;
+    if (dev.get() != before) framed = 0;
+    const JpegTables* tab_before = c->jp_work.tab.get();
+    rc = jp_work_ensure(c->jp_work, g);
+    if (rc) return rc;
+    if (c->jp_work.tab.get() != tab_before) c->jp_tab_uploaded = 0;
+    // pageable sources: the runtime has read them when the call returns; on the device they are ordered behind the conversions already enqueued
+    if (c->jp_tab_uploaded != c->jp_tab_gen) { HIP_TRY(hipMemcpyAsync(c->jp_work.tab, &c->jp_tab, sizeof(JpegTables), hipMemcpyHostToDevice, c->stream)); c->jp_tab_uploaded = c->jp_tab_gen; }
+    if (framed != c->jp_gen) { HIP_TRY(hipMemcpyAsync(dev + JP_HEADER_WORD, c->jp_framing, JP_FRAMING_BYTES, hipMemcpyHostToDevice, c->stream)); framed = c->jp_gen; }
+    rc = de_render_to_image(c, nullptr);
+    if (rc) return rc;
+    jp_launch(c->stream, shown_image(c), c->jp_work, g, dev);
+    HIP_TRY(hipGetLastError());
+    c->jp_out.count++;
+    return DE_OK;
 }
 // ---- look LUTs (include/digital_earth_look.h, look_kernels.hip): in place on the displayed image, directly behind the display launch
 // Everything de_set_look and de_debug_look refuse, in the header's order.

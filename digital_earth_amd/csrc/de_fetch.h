@@ -3,7 +3,8 @@
 //   * the ring arithmetic of the lagged fetches, plain integers;
 //   * copy_out: device -> caller's buffer through the context's staging buffer;
 //   * the conversion frame of the packed outputs (8-bit pixels, HDR pixels, video frames): allocate, display, phase, launch, count;
-//   * the synchronous path (render, copy, wait) and the lagged one (begin: render, copy, record; end: wait, hand out).
+//   * the synchronous path (render, copy, wait) and the lagged one (begin: render, copy, record; end: wait, hand out);
+//   * both once more for an output whose length the device decides (the JPEG stream): the length first, then exactly that many bytes.
 // The entry points of de_api.hip check their own arguments and call one of these.
 #pragma once
 
@@ -98,6 +99,65 @@ int ring_end(de_ctx* c, FetchRing& r, const H** host) {
     r.ended++;
     *host = (const H*)r.cell[k].get();
     return frame_status(c);
+}
+// ---- the same two paths for an output whose length the DEVICE decides (the JPEG stream, include/digital_earth_jpeg.h): on the device it is preceded
+// by a `word`-byte header that `length(header, &len)` reads.  A fetch copies the header and then exactly the stream — never the buffer's capacity.
+// Synchronous: the header, a wait, the stream, a wait; the staging buffer grows to the longest frame fetched, in steps of 1 MiB.
+template <class Length>
+int fetch_staged_sized(de_ctx* c, Pinned<void>& stage, const char* noun, const uint8_t* src, size_t word, Length length, const void** host, uint64_t* len) {
+    int rc = stage.ensure(word + 4096, std::string(noun) + " staging buffer");
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(stage, src, word, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    rc = frame_status(c);
+    if (!rc) rc = length(stage.get(), len);
+    if (rc) return rc;
+    rc = stage.ensure((word + (size_t)*len + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1), std::string(noun) + " staging buffer");
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(stage, src, word + (size_t)*len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *host = (const uint8_t*)stage.get() + word;
+    return DE_OK;
+}
+// Lagged: _begin cannot know the length without waiting, so it copies a PREFIX of `prefix` bytes (header included) of the stream `render(k)` enqueued
+// for cell k — each cell has a device stream of its own, which the next _begin does not touch; _end waits, reads the length and, only if the frame is
+// longer than the prefix, copies all of it from that cell's device stream (a wait for what has been enqueued since: the caller sizes the next prefix
+// from the lengths it sees, so a steady sequence never comes here).
+template <class Render>
+int ring_begin_prefix(de_ctx* c, FetchRing& r, Render render, size_t prefix, size_t* copied) {
+    if (ring_full(r.begun, r.ended, DE_FETCH_RING)) return fail(DE_ERR_STATE, std::string("four ") + r.noun + " fetches are in flight already: " + r.entry + "_end first");
+    const int k = ring_cell(r.begun, DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = r.cell[k].ensure(prefix, std::string(r.noun) + " ring");      // cell k is not in flight
+    if (rc) return rc;
+    if (!r.ev[k]) HIP_TRY(hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
+    const uint8_t* src = nullptr;
+    rc = render(k, &src);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(r.cell[k], src, prefix, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipEventRecord(r.ev[k], c->stream));
+    copied[k] = prefix;
+    r.begun++;
+    return DE_OK;
+}
+template <class Source, class Length>
+int ring_end_sized(de_ctx* c, FetchRing& r, Source source, const size_t* copied, size_t word, Length length, const void** host, uint64_t* len) {
+    if (ring_empty(r.begun, r.ended)) return fail(DE_ERR_STATE, std::string("no ") + r.noun + " fetch in flight: " + r.entry + "_begin first");
+    const int k = ring_cell(r.ended, DE_FETCH_RING);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipEventSynchronize(r.ev[k]));
+    r.ended++;
+    int rc = frame_status(c);
+    if (!rc) rc = length(r.cell[k].get(), len);
+    if (rc) return rc;
+    if (word + (size_t)*len > copied[k]) {
+        rc = r.cell[k].ensure((word + (size_t)*len + 4095) & ~(size_t)4095, std::string(r.noun) + " ring");
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(r.cell[k], source(k), word + (size_t)*len, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    *host = (const uint8_t*)r.cell[k].get() + word;
+    return DE_OK;
 }
 void ring_destroy_events(FetchRing& r) {      // de_destroy; the cells free themselves
     for (hipEvent_t& ev : r.ev) { if (ev) hipEventDestroy(ev); ev = nullptr; }

@@ -272,10 +272,16 @@ class EarthViewer:
         (H, W) or uint16 (H, W, 3) — always a copy, never pipelined: these pixels have no ring.  The HDR display output must be on.
         video=True (a keyword beside the sliders too): the iteration returns one video frame in the format of Renderer.set_video() — a flat
         uint8 array, Renderer.fetch_video — under the same copy / pipelined rules as pixels=True, through the video ring; finish(video=True)
-        ends that loop.  It goes with neither pixels=True nor hdr_pixels=True, and the picture save() holds is left as it was."""
+        ends that loop.  It goes with neither pixels=True nor hdr_pixels=True, and the picture save() holds is left as it was.
+        jpeg=True (a keyword beside the sliders too): the iteration returns one complete JPEG file in the settings of Renderer.set_jpeg() — bytes, or a
+        memoryview with copy=False; Renderer.fetch_jpeg — under the same rules as video=True, through the JPEG ring; finish(jpeg=True) ends that
+        loop.  It goes with none of pixels=True, hdr_pixels=True and video=True."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
         video = bool(sliders.pop("video", False))
+        jpeg = bool(sliders.pop("jpeg", False))
+        if jpeg and (pixels or hdr_pixels or video):
+            raise ValueError("jpeg=True goes with none of pixels=True, hdr_pixels=True and video=True")
         if hdr_pixels and (pixels or pipelined):
             raise ValueError("hdr_pixels=True goes with neither pixels=True nor pipelined")
         if video and (pixels or hdr_pixels):
@@ -288,7 +294,9 @@ class EarthViewer:
             should_reset = True
         r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
         frame = None
-        if video:
+        if jpeg:
+            frame = r.fetch_jpeg(copy=copy, lag=int(pipelined))
+        elif video:
             frame = r.fetch_video(copy=copy, lag=int(pipelined))
         elif hdr_pixels:
             self._pixels, self._image = r.fetch_hdr_pixels(), None
@@ -300,7 +308,7 @@ class EarthViewer:
         # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
         # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
         shown = self._pixels if (pixels or hdr_pixels) else self._image
-        if video:
+        if video or jpeg:
             pass                                # no picture of save()'s changed hands
         elif pipelined:
             self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
@@ -325,23 +333,46 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        if video:
+        if video or jpeg:
             return frame
         return self._pixels if (pixels or hdr_pixels) else self._image
+
+    def _record_jpeg(self, path, n, spp, fps, sliders_per_frame):
+        """record()'s Motion-JPEG side: frame(jpeg=True) through the pipelined JPEG ring into an AVI (.avi) or the bare concatenation (.mjpeg)."""
+        from . import mjpeg
+        r = self.renderer
+        size = r.jpeg()["size"]
+        w = mjpeg.AVIWriter(path, size[0], size[1], fps=fps) if path.endswith(".avi") else mjpeg.MJPEGWriter(path)
+        try:
+            for i in range(n):
+                now = {k: (v[i] if hasattr(v, "__len__") else v) for k, v in sliders_per_frame.items()}
+                got = self.frame(spp=spp, copy=False, pipelined=1, jpeg=True, **now)
+                if got is not None:
+                    w.write(got)
+                del got
+            for got in r.fetch_pending_jpeg(all_images=True):
+                w.write(got)
+        finally:
+            w.close()
+        return w.frames
 
     def record(self, path, frames, spp=1, fps=(TARGET_FPS, 1), **sliders_per_frame):
         """Write `frames` iterations of frame(video=True) to `path` as a Y4M file (digital_earth_amd/y4m.py) that every player opens, through the
         pipelined video ring: the GPU renders frame k + 1 while frame k is packed, copied and written.  The video output must be planar — "i420" or
         "i010" (Renderer.set_video; ValueError otherwise, before anything is rendered or written).  Every slider keyword is either a value, held
         for the whole recording, or a sequence of one value per frame (a sun angle per frame is a time-lapse); move the camera between calls, or
-        record in several calls.  Returns the number of frames written."""
+        record in several calls.  Returns the number of frames written.
+        A path ending in `.avi` writes a Motion-JPEG AVI instead (digital_earth_amd/mjpeg.py) and one ending in `.mjpeg` the concatenated JPEG files,
+        both from frame(jpeg=True) through the pipelined JPEG ring, in the settings of Renderer.set_jpeg()."""
         from . import y4m
         r = self.renderer
-        fmt = r.video()
         n = int(frames)
         for k, v in sliders_per_frame.items():
             if hasattr(v, "__len__") and len(v) != n:
                 raise ValueError("slider %r has %d values for %d frames" % (k, len(v), n))
+        if path.endswith((".avi", ".mjpeg")):
+            return self._record_jpeg(path, n, spp, fps, sliders_per_frame)
+        fmt = r.video()
         w = y4m.Y4MWriter(path, fmt["size"][0], fmt["size"][1], fps=fps, format=fmt["format"], range=fmt["range"], siting=fmt["siting"])
         try:
             for i in range(n):
@@ -356,9 +387,11 @@ class EarthViewer:
             w.close()
         return w.frames
 
-    def finish(self, copy=True, pixels=False, video=False):
+    def finish(self, copy=True, pixels=False, video=False, jpeg=False):
         """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop;
-        video=True: the frame of a frame(video=True) loop."""
+        video=True: the frame of a frame(video=True) loop; jpeg=True: the file of a frame(jpeg=True) loop."""
+        if jpeg:
+            return self.renderer.fetch_pending_jpeg(copy=copy)
         if video:
             return self.renderer.fetch_pending(copy=copy, video=True)
         img = self.renderer.fetch_pending(copy=copy, pixels=pixels)
@@ -392,7 +425,9 @@ class EarthViewer:
         linear / PQ / HLG, RGB, full range; digital_earth_amd/png16.py).  Here too nothing is displayed again and no setting or dither phase of the
         renderer is touched: "rgb16" pixels are written as they are, "rgb10a2" codes widened to 16 bits by bit replication, and a float signal held
         from render() / frame() is quantised on the host by rounding (png16.to_rgb16) — the setting's mode and dither belong to fetch_hdr_pixels().
-        Under the P3-D65 and Rec.2020 gamuts the label names the container, not a colorimetric picture: see Renderer.set_hdr_output."""
+        Under the P3-D65 and Rec.2020 gamuts the label names the container, not a colorimetric picture: see Renderer.set_hdr_output.
+        `.jpg` / `.jpeg` with a float image held (render, frame) and the HDR output off: the file is the GPU encoder's (Renderer.debug_jpeg on the
+        image held, in the settings of Renderer.set_jpeg) — no host encoder; with packed pixels held the image writer encodes them as before."""
         r = self.renderer
         if self._image is None and self._pixels is None:
             self.render(1)
@@ -403,6 +438,11 @@ class EarthViewer:
         if hdr is not None:
             held = self._pixels if self._pixels is not None else np.asarray(self._image, dtype=np.float32)
             png16.write_png16(path, png16.to_rgb16(held), png16.cicp_of(hdr["gamut"], hdr["transfer"]))
+            return
+        if path.endswith((".jpg", ".jpeg")) and self._image is not None:      # the GPU's encoder on the image held, in the settings of set_jpeg()
+            fmt = r.jpeg()
+            with open(path, "wb") as f:
+                f.write(r.debug_jpeg(self._image, quality=fmt["quality"], restart=fmt["restart"]))
             return
         px = self._pixels
         if px is None:

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -152,6 +152,7 @@ class Renderer:
                                       "lagged pixel fetches are in flight: fetch_pending(pixels=True) first")
         self._vd_ring = _FetchRing(self._lib, "de_fetch_videoframe", "de_fetch_video", ctypes.c_uint8, Renderer._vd_bytes, "fetch_video",
                                    "lagged video fetches are in flight: fetch_pending(video=True) first")
+        self._jp_in_flight, self._jp_view_ref = 0, None      # the lagged fetch_jpeg() calls; the last view handed out
         check(self._lib.de_create(int(device), self.image_res[0], self.image_res[1], ctypes.byref(self._h)))
         _native.apply_env_tuning(self._h)      # experiment overrides (DE_KERNEL, DE_V6_* ...): read HERE, not in the library
         self._params = DeParams()
@@ -199,6 +200,8 @@ class Renderer:
             for ring in (self._image_ring, self._pixel_ring, self._vd_ring):
                 if ring.referenced():
                     raise RuntimeError("a %s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % ring.name)
+            if self._jp_view_ref is not None and self._jp_view_ref() is not None:
+                raise RuntimeError("a fetch_jpeg(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
             check(self._lib.de_destroy(self._h))
             self._h = ctypes.c_void_p()
             self._lender = None
@@ -797,7 +800,7 @@ class Renderer:
         """End the pipelined window loop: wait for the fetches still in flight and return the newest image (None when there is none);
         all_images=True: the list of all of them, oldest first (copies).  pixels=True: the same for the lagged fetch_pixels() calls, which have a
         ring of their own; the float fetches are left alone, as the pixel fetches are without it.  video=True: the same for the lagged
-        fetch_video() calls and their ring."""
+        fetch_video() calls and their ring.  (The lagged fetch_jpeg() calls end in fetch_pending_jpeg().)"""
         if video and pixels:
             raise ValueError("pixels=True and video=True name two rings: one call each")
         ring, array = (self._vd_ring, self._vd_view) if video else (self._pixel_ring, self._pixel_view) if pixels else (self._image_ring, self._staging_view)
@@ -951,6 +954,93 @@ class Renderer:
         out = np.empty(max(W * H // 2, 1) * 3 * (2 if format in ("p010", "i010") else 1), dtype=np.uint8)
         check(self._lib.de_debug_video(self._h, image.ctypes.data, W, H, ctypes.byref(s), ctypes.c_uint32(int(phase) & 0xffffffff), out.ctypes.data))
         return out
+
+    # ------------------------------------------------------------------ JPEG output (include/digital_earth_jpeg.h)
+    def _jp_settings(self, quality, restart):
+        s = DeJpeg()
+        s.struct_bytes = ctypes.sizeof(DeJpeg)
+        s.quality, s.restart_mcus = int(quality), _native.JPEG_DEFAULT_RESTART if restart is None else int(restart)
+        return s
+
+    def set_jpeg(self, quality=90, restart=None):
+        """The settings of fetch_jpeg(): a baseline JFIF file (4:2:0, the typical Huffman tables) encoded on the GPU behind the display transform (and
+        behind the look and output scaling).  quality 1 ... 100 on the IJG scale; restart: MCUs (16 x 16 pixels) per restart interval, 1 ... 65535 —
+        the encoder's unit of parallelism; None: the measured default (profiles/jpeg.md).  Refused (DE_ERR_STATE) while lagged JPEG fetches are in
+        flight.  No other fetch is affected."""
+        check(self._lib.de_set_jpeg(self._h, ctypes.byref(self._jp_settings(quality, restart))))
+
+    def jpeg(self):
+        """The JPEG settings as a dict (set_jpeg's keywords, restart as a number) plus size = (width, height) and capacity, the upper bound of any
+        frame's length at these settings."""
+        s, n = DeJpeg(), ctypes.c_uint64()
+        check(self._lib.de_get_jpeg(self._h, ctypes.byref(s)))
+        check(self._lib.de_jpeg_capacity(self._h, ctypes.byref(n)))
+        return dict(quality=int(s.quality), restart=int(s.restart_mcus), size=self.output_size(), capacity=int(n.value))
+
+    def _jp_view(self, ptr, n, copy):
+        if copy:
+            return ctypes.string_at(ptr, n)
+        view = np.ctypeslib.as_array(ptr, shape=(n,)).view(_StagingView)
+        view.flags.writeable = False
+        view._owner = self
+        self._jp_view_ref = weakref.ref(view)
+        return memoryview(view)
+
+    def _jp_end(self, copy):
+        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        self._jp_in_flight -= 1
+        check(self._lib.de_fetch_jpeg_end(self._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return self._jp_view(ptr, int(n.value), copy)
+
+    def fetch_jpeg(self, copy=True, lag=0):
+        """The displayed image as one complete JPEG file: `bytes` that open(path, "wb").write() or a socket takes as they are.  Only the file's own
+        bytes cross the link.  copy=False: a read-only memoryview of the library's pinned buffer, valid until the next fetch_jpeg call (lag = 0) or
+        until the ring comes round (lag > 0).  lag=1, 2 or 3: pipelined like fetch_video(lag=...), through a ring of its own — the call returns the
+        file of the lag-th previous call (None until there is one); fetch_pending_jpeg() hands out the rest."""
+        if not self._textures_copied:
+            self.copy_textures()
+        if lag not in (0, 1, 2, 3):
+            raise ValueError("lag must be 0 ... 3")
+        if lag:
+            check(self._lib.de_fetch_jpeg_begin(self._h))
+            self._jp_in_flight += 1
+            return None if self._jp_in_flight <= lag else self._jp_end(copy)
+        if self._jp_in_flight:
+            raise RuntimeError("lagged JPEG fetches are in flight: fetch_pending_jpeg() first")
+        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        check(self._lib.de_fetch_jpeg_view(self._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return self._jp_view(ptr, int(n.value), copy)
+
+    def fetch_pending_jpeg(self, copy=True, all_images=False):
+        """fetch_pending() for the lagged fetch_jpeg() calls and their ring: wait for the JPEG fetches still in flight and return the newest file
+        (None when there is none) — bytes, or a memoryview with copy=False; all_images=True: the list of all of them, oldest first (bytes)."""
+        imgs = []
+        while self._jp_in_flight > 0:
+            imgs.append(self._jp_end(copy or all_images))
+        return imgs if all_images else (imgs[-1] if imgs else None)
+
+    def render_to_jpeg(self):
+        """Run the display and the encoder and leave the stream on the device (de_render_to_jpeg); returns (address of the stream, address of its
+        uint64 length).  Nothing is waited for."""
+        if not self._textures_copied:
+            self.copy_textures()
+        p, n = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.de_render_to_jpeg(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def debug_jpeg(self, image, quality=90, restart=None):
+        """The encoder once on a given (W, H, 3) float32 image (de_debug_jpeg), W and H even but free of this renderer's size; returns the file as
+        bytes.  The renderer's own settings and streams are not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (W, H, 3)")
+        W, H = image.shape[:2]
+        s = self._jp_settings(quality, restart)
+        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.de_debug_jpeg_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
+        out = ctypes.create_string_buffer(int(cap.value))
+        check(self._lib.de_debug_jpeg(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
+        return out.raw[:int(n.value)]
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)
     LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
