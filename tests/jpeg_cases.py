@@ -11,6 +11,20 @@ F = np.float32
 SIZES = [(16, 16, 8), (2, 2, 8), (34, 18, 8), (48, 40, 8), (160, 16, 1), (64, 32, 1), (64, 32, 3), (64, 32, 65535)]
 QUALITY = dict(black=100, white=100, checker77=50, impulse=100, noise100=100, noise1=1, specials=90)
 INPUTS = tuple(QUALITY)
+# Frames of more than 1024 restart intervals, where a thread of jpeg_scan_kernel owns more than one: a list of their own, so that the full input set does
+# not run at these sizes.  528 x 528 is 33 x 33 MCUs: two intervals per thread, the last owner has one and 479 threads none; 544 x 1040 is 34 x 65: three
+# per thread, the last owner has two.  noise100 gives every interval another length, so a wrong offset shows; black gives every interval the same.
+LARGE_SIZES = [(528, 528, 1), (544, 1040, 1)]
+LARGE_INPUTS = ("noise100", "black")
+SCAN_THREADS = 1024             # JP_SCAN_THREADS of csrc/jpeg_kernels.hip
+
+
+def scan_geometry(intervals):
+    """jpeg_scan_kernel's split of the intervals over its one workgroup, restated from jp_scan_chunk: (intervals per owning thread, owning threads,
+    threads that own none, intervals of the last owner)."""
+    chunk = -(-intervals // SCAN_THREADS)
+    owners = -(-intervals // chunk)
+    return chunk, owners, SCAN_THREADS - owners, intervals - (owners - 1) * chunk
 
 
 def _basis7(n):

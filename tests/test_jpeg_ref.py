@@ -11,6 +11,8 @@ import jpeg_f64 as j64
 import jpeg_ref as jr
 
 CASES = [(name, W, H, restart) for (W, H, restart) in jc.SIZES for name in jc.INPUTS]
+# the frames of more than 1024 intervals (tests/test_gpu_large_geometry.py): the reference is held to the decoder and to Pillow at these sizes too
+CASES += [(name, W, H, restart) for (W, H, restart) in jc.LARGE_SIZES for name in jc.LARGE_INPUTS]
 
 
 def _ids(case):

@@ -92,22 +92,34 @@ int main(int argc, char** argv) {
     if (argc != 1) return 2;
     static const int sizes[][2] = {{2, 2}, {16, 16}, {34, 18}, {48, 40}, {160, 16}, {64, 32}, {208, 120}};
     static const int qualities[] = {1, 50, 90, 100}, restarts[] = {1, 3, 8, 65535};
-    int runs = 0;
+    // More than JP_SCAN_THREADS intervals, where a thread of the scan owns two of them (528 x 528: 1089 intervals, the last owner has one, 479 threads none)
+    // or three (544 x 1040: 2210 intervals, the last owner has two).  Restart 1 and one quality only: the sweep stays about as long as it was.
+    static const int large[][2] = {{528, 528}, {544, 1040}};
+    struct Case { int W, H, quality, restart; };
+    std::vector<Case> cases;
     for (const auto& sz : sizes)
         for (int quality : qualities)
-            for (int restart : restarts)
-                for (int kind = 0; kind < 3; ++kind) {
-                    std::vector<float> image((size_t)sz[0] * sz[1] * 3);
-                    uint32_t r = 99u + (uint32_t)runs;
-                    for (float& x : image) { r = r * 1664525u + 1013904223u; x = kind == 0 ? (float)(r >> 8) * (1.2f / 16777216.0f) - 0.1f : kind == 1 ? 0.0f : ((r >> 30) & 1 ? 1.0f : 0.0f); }
-                    if (kind == 0) { image[1] = NAN; image[3] = -0.0f; image[5] = INFINITY; }
-                    const std::vector<uint8_t> s = run(image, sz[0], sz[1], quality, restart, &status);
-                    if (status || s.size() < JP_FRAMING_BYTES + 3 || s[s.size() - 2] != 0xff || s[s.size() - 1] != 0xd9) {
-                        fprintf(stderr, "%d x %d quality %d restart %d kind %d: status %u, %zu bytes, no EOI at the end\n", sz[0], sz[1], quality, restart, kind, status, s.size());
-                        return 1;
-                    }
-                    ++runs;
-                }
+            for (int restart : restarts) cases.push_back({sz[0], sz[1], quality, restart});
+    for (const auto& sz : large) {
+        const JpegGeometry g = jp_geometry(sz[0], sz[1], 1);
+        const size_t chunk = (g.intervals + JP_SCAN_THREADS - 1) / JP_SCAN_THREADS;
+        if (chunk < 2 || g.intervals % chunk == 0) { fprintf(stderr, "%d x %d: no ragged chunk of two intervals or more per thread\n", sz[0], sz[1]); return 1; }
+        cases.push_back({sz[0], sz[1], 90, 1});
+    }
+    int runs = 0;
+    for (const Case& c : cases)
+        for (int kind = 0; kind < 3; ++kind) {
+            std::vector<float> image((size_t)c.W * c.H * 3);
+            uint32_t r = 99u + (uint32_t)runs;
+            for (float& x : image) { r = r * 1664525u + 1013904223u; x = kind == 0 ? (float)(r >> 8) * (1.2f / 16777216.0f) - 0.1f : kind == 1 ? 0.0f : ((r >> 30) & 1 ? 1.0f : 0.0f); }
+            if (kind == 0) { image[1] = NAN; image[3] = -0.0f; image[5] = INFINITY; }
+            const std::vector<uint8_t> s = run(image, c.W, c.H, c.quality, c.restart, &status);
+            if (status || s.size() < JP_FRAMING_BYTES + 3 || s[s.size() - 2] != 0xff || s[s.size() - 1] != 0xd9) {
+                fprintf(stderr, "%d x %d quality %d restart %d kind %d: status %u, %zu bytes, no EOI at the end\n", c.W, c.H, c.quality, c.restart, kind, status, s.size());
+                return 1;
+            }
+            ++runs;
+        }
     printf("jpeg_host_check: %d conversions, every stream ends in EOI within its capacity, no sanitizer report\n", runs);
     return 0;
 }
