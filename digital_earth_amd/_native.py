@@ -111,10 +111,18 @@ class DeJpeg(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("quality", ctypes.c_int32), ("restart_mcus", ctypes.c_int32)]
 
 
+class DePng(ctypes.Structure):
+    """`de_png` (include/digital_earth_png.h): the source, the filter and the chunk size of the PNG output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("source", ctypes.c_int32), ("filter", ctypes.c_int32), ("chunk_bytes", ctypes.c_int32)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 DE_ERR_INTERNAL = -6
 JPEG_DEFAULT_RESTART = 2      # DE_JPEG_DEFAULT_RESTART of include/digital_earth_jpeg.h
+PNG_DEFAULT_CHUNK = 32768     # DE_PNG_DEFAULT_CHUNK of include/digital_earth_png.h
+PNG_SOURCES = ("pixels", "hdr_pixels")                                    # DE_PNG_SOURCE_*
+PNG_FILTERS = ("none", "sub", "up", "average", "paeth", "adaptive")       # DE_PNG_FILTER_*
 
 DE_FLAG_FIXED_WAVELENGTH = 1 << 0
 DE_FLAG_CLAMP_SAMPLER = 1 << 1
@@ -291,6 +299,20 @@ JPEG_SYMBOLS = {
     "de_debug_jpeg_framing": (ctypes.c_int, [ctypes.POINTER(DeJpeg), ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint64, _U64P, _U64P]),
 }
 
+# PNG output: include/digital_earth_png.h (same library, additions only; not part of the binder's header)
+PNG_SYMBOLS = {
+    "de_set_png": (ctypes.c_int, [_P, ctypes.POINTER(DePng)]),
+    "de_get_png": (ctypes.c_int, [_P, ctypes.POINTER(DePng)]),
+    "de_png_capacity": (ctypes.c_int, [_P, _U64P]),
+    "de_render_to_png": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_png": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _U64P]),
+    "de_fetch_png_view": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_fetch_png_begin": (ctypes.c_int, [_P]),
+    "de_fetch_png_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_debug_png": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePng), _P, ctypes.c_uint64, _U64P]),
+    "de_debug_png_framing": (ctypes.c_int, [ctypes.POINTER(DePng), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_uint64, _U64P, _U64P]),
+}
+
 # look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
 LOOK_SYMBOLS = {
     "de_set_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook), _P, _P]),
@@ -377,7 +399,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -107,7 +107,7 @@ int de_destroy(de_ctx* c) {
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
     // events and streams; the memory is the members' (de_memory.h): `delete c` frees what this context owns and leaves what it borrows
-    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring}) ring_destroy_events(*r);
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring, &c->pn_ring}) ring_destroy_events(*r);
 #ifdef DE_LEGACY_VARIANTS
     destroy_legacy_events(c);
 #endif
@@ -1182,7 +1182,7 @@ int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
-    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
+    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring, &c->pn_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
     c->os = *s;
     c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
     return DE_OK;
@@ -1456,6 +1456,111 @@ int de_debug_jpeg_framing(const de_jpeg* s, int W, int H, void* out, uint64_t ou
         JpegTables tab;
         jp_make_tables(s->quality, &tab);
         jp_write_framing(tab, W, H, s->restart_mcus, (uint8_t*)out);
+    }
+    return DE_OK;
+}
+
+/* ---- PNG output: include/digital_earth_png.h (png_kernels.hip, png_tables.h) */
+int de_set_png(de_ctx* c, const de_png* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = pn_settings_check(s); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->pn_ring); if (rc) return rc; }
+    c->pn = *s;
+    c->pn_guess = 0;
+    packed_reset(c->pn_out);
+    return DE_OK;
+}
+int de_get_png(de_ctx* c, de_png* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->pn;
+    return DE_OK;
+}
+int de_png_capacity(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = pn_source_check(c); if (rc) return rc; }
+    *bytes = (uint64_t)pn_ctx_geometry(c).capacity;
+    return DE_OK;
+}
+int de_render_to_png(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    int rc = pn_render(c, c->pn_out.dev);
+    if (rc) return rc;
+    if (device_stream) *device_stream = c->pn_out.dev + PNG_HEADER_WORD;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->pn_out.dev.get());
+    return DE_OK;
+}
+int de_fetch_png_view(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = de_render_to_png(c, nullptr, nullptr);
+    if (rc) return rc;
+    return fetch_staged_sized(c, c->pn_out.stage, c->pn_out.noun, c->pn_out.dev, PNG_HEADER_WORD, pn_read_word, host, len);
+}
+int de_fetch_png(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    const void* host = nullptr;
+    int rc = de_fetch_png_view(c, &host, len);
+    if (rc) return rc;
+    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the file (*len; de_png_capacity bounds every frame)");
+    memcpy(out, host, (size_t)*len);
+    return DE_OK;
+}
+int de_fetch_png_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = pn_source_check(c); if (rc) return rc; }
+    const PngGeometry g = pn_ctx_geometry(c);
+    size_t prefix = c->pn_guess ? c->pn_guess : PNG_HEADER_WORD + g.front + g.filtered / 4;      // the first: a quarter of the filtered bytes
+    if (prefix > PNG_HEADER_WORD + g.capacity) prefix = PNG_HEADER_WORD + g.capacity;
+    return ring_begin_prefix(c, c->pn_ring, [c](int k, const uint8_t** src) {
+        int rc = pn_render(c, c->pn_cell[k]);
+        *src = c->pn_cell[k];
+        return rc;
+    }, prefix, c->pn_cell_copied);
+}
+int de_fetch_png_end(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = ring_end_sized(c, c->pn_ring, [c](int k) { return (const uint8_t*)c->pn_cell[k].get(); }, c->pn_cell_copied, PNG_HEADER_WORD, pn_read_word, host, len);
+    if (!rc) c->pn_guess = ((PNG_HEADER_WORD + (size_t)*len) * 5 / 4 + 4095) & ~(size_t)4095;      // the next prefix: a quarter more than this frame
+    return rc;
+}
+/* the conversion once on host-given packed pixels of any size.  Buffers of its own; the context's settings and streams are not touched. */
+int de_debug_png(de_ctx* c, const void* pixels, int W, int H, int channels, int depth, const de_png* s, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !pixels || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = pn_shape_check(W, H, channels, depth); if (rc) return rc; }
+    { int rc = pn_settings_check(s); if (rc) return rc; }
+    const PngGeometry g = png_geometry(W, H, channels, depth, s->chunk_bytes);
+    HIP_TRY(hipSetDevice(c->device));
+    de_ctx::PngWork work;
+    Dev<uint8_t> d_out;
+    { int rc = pn_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_out.ensure(pn_stream_bytes(g)));
+    HIP_TRY(hipMemcpyAsync(work.pixels, pixels, (size_t)g.H * g.row_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(pn_tables_upload(c->stream, work));
+    const uint8_t cicp[4] = {1, 8, 0, 1};
+    pn_launch(c->stream, work, g, s->filter, cicp, d_out);
+    HIP_TRY(hipGetLastError());
+    uint32_t word[4];
+    HIP_TRY(hipMemcpyAsync(word, d_out, sizeof(word), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    { int rc = pn_read_word(word, len); if (rc) return rc; }
+    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the file (*len)");
+    HIP_TRY(hipMemcpyAsync(out, d_out + PNG_HEADER_WORD, (size_t)*len, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+/* the host's part alone: no device, no context */
+int de_debug_png_framing(const de_png* s, int W, int H, int channels, int depth, const uint8_t* cicp, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
+    if (!s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = pn_shape_check(W, H, channels, depth); if (rc) return rc; }
+    { int rc = pn_settings_check(s); if (rc) return rc; }
+    const PngGeometry g = png_geometry(W, H, channels, depth, s->chunk_bytes);
+    if (len) *len = g.front;
+    if (capacity) *capacity = (uint64_t)g.capacity;
+    if (out || out_bytes) {
+        if (!out || out_bytes < g.front) return fail(DE_ERR_INVALID, "out_bytes is smaller than the front (*len)");
+        static const uint8_t linear709[4] = {1, 8, 0, 1};
+        uint8_t front[PNG_FRONT_MAX];
+        png_write_front(pn_host_tables(), g, cicp ? cicp : linear709, front);
+        memcpy(out, front, g.front);
     }
     return DE_OK;
 }

@@ -11,6 +11,7 @@
 #include "../../include/digital_earth_video.h"
 #include "../../include/digital_earth_look.h"
 #include "../../include/digital_earth_jpeg.h"
+#include "../../include/digital_earth_png.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -43,6 +44,7 @@
 #include "videoframe_kernels.hip"
 #include "look_kernels.hip"
 #include "jpeg_kernels.hip"
+#include "png_kernels.hip"
 
 namespace {
 
@@ -331,6 +333,20 @@ struct de_ctx {
     JpegStream jp_cell[DE_FETCH_RING];
     size_t jp_cell_copied[DE_FETCH_RING] = {};      // bytes of the device stream that _begin copied into the pinned cell
     size_t jp_guess = 0;            // the prefix a lagged fetch copies at _begin: a quarter more than the newest frame ended
+    // PNG output (include/digital_earth_png.h).  Everything reaches the device on first use: the packed pixels, the filtered stream, the
+    // chunks' slots and words of one conversion (PngWork), the file of the synchronous fetches (pn_out) and, per ring cell, a file on the device and
+    // a pinned cell, as the JPEG ring.  The front travels in the kernels' arguments: no copy of it is tracked.
+    struct PngWork {              // what one conversion passes through; re-allocated when a frame needs more
+        Dev<uint8_t> pixels, filtered, slots; Dev<uint32_t> words; Dev<PngTables> tab;
+        bool tab_uploaded = false;
+    };
+    de_png pn = {(uint32_t)sizeof(de_png), DE_PNG_SOURCE_PIXELS, DE_PNG_FILTER_ADAPTIVE, DE_PNG_DEFAULT_CHUNK};
+    PngWork pn_work;
+    PackedOut pn_out = {"PNG"};
+    FetchRing pn_ring = {"PNG", "de_fetch_png"};
+    Dev<uint8_t> pn_cell[DE_FETCH_RING];
+    size_t pn_cell_copied[DE_FETCH_RING] = {};
+    size_t pn_guess = 0;            // the prefix a lagged fetch copies at _begin: a quarter more than the newest frame ended
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

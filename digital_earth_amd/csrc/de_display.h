@@ -524,6 +524,108 @@ int jp_render(de_ctx* c, Dev<uint8_t>& dev, uint64_t& framed) {
     c->jp_out.count++;
     return DE_OK;
 }
+// ---- PNG output (include/digital_earth_png.h, png_kernels.hip, png_tables.h)
+int pn_settings_check(const de_png* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_png)) return fail(DE_ERR_INVALID, "de_png.struct_bytes does not match this library's struct");
+    if (s->source < DE_PNG_SOURCE_PIXELS || s->source > DE_PNG_SOURCE_HDR_PIXELS) return fail(DE_ERR_INVALID, "de_png.source must be DE_PNG_SOURCE_PIXELS or _HDR_PIXELS");
+    if (s->filter < DE_PNG_FILTER_NONE || s->filter > DE_PNG_FILTER_ADAPTIVE) return fail(DE_ERR_INVALID, "de_png.filter must be DE_PNG_FILTER_NONE ... _PAETH or _ADAPTIVE");
+    if (s->chunk_bytes < 1024 || s->chunk_bytes > 65535) return fail(DE_ERR_INVALID, "de_png.chunk_bytes must lie in 1024 ... 65535");
+    return DE_OK;
+}
+int pn_shape_check(int W, int H, int channels, int depth) {      // what one conversion can take: the kernels count filtered bytes in 32 bits
+    if (W <= 0 || H <= 0 || !((depth == 8 && (channels == 3 || channels == 4)) || (depth == 16 && channels == 3)))
+        return fail(DE_ERR_INVALID, "a PNG frame needs W, H >= 1 and 3 or 4 channels of 8 bits or 3 of 16");
+    if ((unsigned long long)H * (1ull + (unsigned long long)W * (unsigned long long)(channels * depth / 8)) > PNG_MAX_FILTERED)
+        return fail(DE_ERR_INVALID, "the PNG output takes at most 2^27 filtered bytes, H (1 + W bpp)");
+    return DE_OK;
+}
+size_t pn_stream_bytes(const PngGeometry& g) { return (PNG_HEADER_WORD + g.capacity + 15) & ~(size_t)15; }      // a file on the device
+void pn_cicp(const de_hdr_output& ho, uint8_t cicp[4]) {      // as png16.cicp_of: {primaries, transfer, RGB, full range}
+    static const uint8_t primaries[3] = {1, 12, 9}, transfer[3] = {8, 16, 18};
+    cicp[0] = primaries[ho.gamut]; cicp[1] = transfer[ho.transfer]; cicp[2] = 0; cicp[3] = 1;
+}
+// The buffers of one conversion of geometry g; `words` holds len[chunks], offset[chunks], adler[chunks][2] and the status word.
+int pn_work_ensure(de_ctx::PngWork& w, const PngGeometry& g) {
+    const PngTables* before = w.tab.get();
+    int rc = w.pixels.ensure((size_t)g.H * g.row_bytes, "PNG buffers");
+    if (!rc) rc = w.filtered.ensure(g.filtered, "PNG buffers");
+    if (!rc) rc = w.slots.ensure(g.chunks * g.slot_bytes, "PNG buffers");
+    if (!rc) rc = w.words.ensure((4 * g.chunks + 4) * sizeof(uint32_t), "PNG buffers");
+    if (!rc) rc = w.tab.ensure(sizeof(PngTables), "PNG buffers");
+    if (w.tab.get() != before) w.tab_uploaded = false;
+    return rc;
+}
+// The tables onto the device, once per buffer.  The source is static: the copy may read it whenever it runs.
+const PngTables& pn_host_tables() { static const PngTables tables = [] { PngTables t; png_make_tables(&t); return t; }(); return tables; }
+hipError_t pn_tables_upload(hipStream_t stream, de_ctx::PngWork& w) {
+    if (w.tab_uploaded) return hipSuccess;
+    hipError_t e = hipMemcpyAsync(w.tab, &pn_host_tables(), sizeof(PngTables), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) w.tab_uploaded = true;
+    return e;
+}
+// w.pixels (packed, on this stream) -> filtered -> slots -> the file at `out`.  w.tab holds the tables.
+void pn_launch(hipStream_t stream, const de_ctx::PngWork& w, const PngGeometry& g, int filter, const uint8_t cicp[4], uint8_t* out) {
+    PngArgs a;
+    a.pixels = w.pixels; a.tab = w.tab; a.filtered = w.filtered; a.slots = w.slots;
+    a.len = w.words; a.offset = w.words + g.chunks; a.adler = w.words + 2 * g.chunks; a.status = w.words + 4 * g.chunks; a.out = out;
+    a.H = g.H; a.bpp = g.bpp; a.swap16 = g.depth == 16 ? 1 : 0; a.filter = filter; a.chunk_bytes = g.chunk_bytes;
+    a.row_bytes = (uint32_t)g.row_bytes; a.total = (uint32_t)g.filtered; a.chunks = (uint32_t)g.chunks; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.capacity = (uint32_t)g.capacity;
+    memset(a.front_bytes, 0, sizeof(a.front_bytes));
+    a.front = (uint32_t)png_write_front(pn_host_tables(), g, cicp, a.front_bytes);
+    hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)g.H), dim3(PNG_FILTER_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(png_deflate_kernel, dim3((unsigned)g.chunks), dim3(PNG_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(PNG_SCAN_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(png_compact_kernel, dim3((unsigned)g.chunks), dim3(256), 0, stream, a);
+}
+int pn_source_check(const de_ctx* c) {
+    if (c->pn.source == DE_PNG_SOURCE_HDR_PIXELS && !(c->ho.on && c->ho.pixel_format == DE_HDR_PIXELS_RGB16))
+        return fail(DE_ERR_STATE, "the PNG output's HDR source needs the HDR display output on at DE_HDR_PIXELS_RGB16");
+    return DE_OK;
+}
+PngGeometry pn_ctx_geometry(const de_ctx* c) {
+    const bool hdr = c->pn.source == DE_PNG_SOURCE_HDR_PIXELS;
+    return png_geometry(out_w(c), out_h(c), hdr ? 3 : c->px.channels, hdr ? 16 : 8, c->pn.chunk_bytes);
+}
+// The 16-byte word as a fetch finds it on the host: the length, or DE_ERR_INTERNAL.
+int pn_read_word(const void* word, uint64_t* len) {
+    uint32_t w[4];
+    memcpy(w, word, sizeof(w));
+    *len = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+    if (w[2]) return fail(DE_ERR_INTERNAL, "the PNG encoder met a chunk longer than its proven worst case: nothing was written past a buffer");
+    return DE_OK;
+}
+// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
+int pn_render(de_ctx* c, Dev<uint8_t>& dev) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = pn_source_check(c);
+    if (rc) return rc;
+    const PngGeometry g = pn_ctx_geometry(c);
+    rc = pn_shape_check(g.W, g.H, g.channels, g.depth);
+    if (rc) return rc;
+    rc = dev.ensure(pn_stream_bytes(g), "PNG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
+    if (rc) return rc;
+    rc = pn_work_ensure(c->pn_work, g);
+    if (rc) return rc;
+    HIP_TRY(pn_tables_upload(c->stream, c->pn_work));
+    rc = de_render_to_image(c, nullptr);
+    if (rc) return rc;
+    uint8_t cicp[4] = {1, 8, 0, 1};
+    if (g.depth == 16) {
+        const uint32_t phase = c->ho.animate ? c->pn_out.count : 0u;
+        hpx_launch(c->stream, shown_image(c), c->pn_work.pixels, g.W, g.H, c->ho, phase);
+        pn_cicp(c->ho, cicp);
+        c->pn_out.last_phase = phase;
+    } else {
+        const uint32_t phase = c->px.animate ? c->pn_out.count : 0u;
+        px_launch(c->stream, shown_image(c), c->pn_work.pixels, g.W, g.H, c->px, phase);
+        c->pn_out.last_phase = phase;
+    }
+    pn_launch(c->stream, c->pn_work, g, c->pn.filter, cicp, dev);
+    HIP_TRY(hipGetLastError());
+    c->pn_out.count++;
+    return DE_OK;
+}
 // ---- look LUTs (include/digital_earth_look.h, look_kernels.hip): in place on the displayed image, directly behind the display launch
 // Everything de_set_look and de_debug_look refuse, in the header's order.
 int lk_settings_check(const de_look* s, const float* t1, const float* t3) {

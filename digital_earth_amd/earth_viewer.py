@@ -275,11 +275,16 @@ class EarthViewer:
         ends that loop.  It goes with neither pixels=True nor hdr_pixels=True, and the picture save() holds is left as it was.
         jpeg=True (a keyword beside the sliders too): the iteration returns one complete JPEG file in the settings of Renderer.set_jpeg() — bytes, or a
         memoryview with copy=False; Renderer.fetch_jpeg — under the same rules as video=True, through the JPEG ring; finish(jpeg=True) ends that
-        loop.  It goes with none of pixels=True, hdr_pixels=True and video=True."""
+        loop.  It goes with none of pixels=True, hdr_pixels=True and video=True.
+        png=True (a keyword beside the sliders too): the same for one complete PNG file in the settings of Renderer.set_png() — Renderer.fetch_png,
+        through the PNG ring; finish_png() ends that loop.  It goes with none of the others."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
         video = bool(sliders.pop("video", False))
         jpeg = bool(sliders.pop("jpeg", False))
+        png = bool(sliders.pop("png", False))
+        if png and (pixels or hdr_pixels or video or jpeg):
+            raise ValueError("png=True goes with none of pixels=True, hdr_pixels=True, video=True and jpeg=True")
         if jpeg and (pixels or hdr_pixels or video):
             raise ValueError("jpeg=True goes with none of pixels=True, hdr_pixels=True and video=True")
         if hdr_pixels and (pixels or pipelined):
@@ -294,7 +299,9 @@ class EarthViewer:
             should_reset = True
         r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
         frame = None
-        if jpeg:
+        if png:
+            frame = r.fetch_png(copy=copy, lag=int(pipelined))
+        elif jpeg:
             frame = r.fetch_jpeg(copy=copy, lag=int(pipelined))
         elif video:
             frame = r.fetch_video(copy=copy, lag=int(pipelined))
@@ -308,7 +315,7 @@ class EarthViewer:
         # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
         # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
         shown = self._pixels if (pixels or hdr_pixels) else self._image
-        if video or jpeg:
+        if video or jpeg or png:
             pass                                # no picture of save()'s changed hands
         elif pipelined:
             self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
@@ -333,7 +340,7 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        if video or jpeg:
+        if video or jpeg or png:
             return frame
         return self._pixels if (pixels or hdr_pixels) else self._image
 
@@ -356,6 +363,26 @@ class EarthViewer:
             w.close()
         return w.frames
 
+    def _record_png(self, path, n, spp, sliders_per_frame):
+        """record()'s lossless side: frame(png=True) through the pipelined PNG ring into the numbered files path % 0, path % 1, ..."""
+        r = self.renderer
+        written = 0
+
+        def write(got):
+            nonlocal written
+            with open(path % written, "wb") as f:
+                f.write(got)
+            written += 1
+        for i in range(n):
+            now = {k: (v[i] if hasattr(v, "__len__") else v) for k, v in sliders_per_frame.items()}
+            got = self.frame(spp=spp, copy=False, pipelined=1, png=True, **now)
+            if got is not None:
+                write(got)
+            del got
+        for got in r.fetch_pending_png(all_images=True):
+            write(got)
+        return written
+
     def record(self, path, frames, spp=1, fps=(TARGET_FPS, 1), **sliders_per_frame):
         """Write `frames` iterations of frame(video=True) to `path` as a Y4M file (digital_earth_amd/y4m.py) that every player opens, through the
         pipelined video ring: the GPU renders frame k + 1 while frame k is packed, copied and written.  The video output must be planar — "i420" or
@@ -363,7 +390,9 @@ class EarthViewer:
         for the whole recording, or a sequence of one value per frame (a sun angle per frame is a time-lapse); move the camera between calls, or
         record in several calls.  Returns the number of frames written.
         A path ending in `.avi` writes a Motion-JPEG AVI instead (digital_earth_amd/mjpeg.py) and one ending in `.mjpeg` the concatenated JPEG files,
-        both from frame(jpeg=True) through the pipelined JPEG ring, in the settings of Renderer.set_jpeg()."""
+        both from frame(jpeg=True) through the pipelined JPEG ring, in the settings of Renderer.set_jpeg().
+        A path ending in `.png` is a pattern with one integer field ("frames/%05d.png"): a numbered lossless sequence, one complete PNG file per
+        frame from frame(png=True) through the pipelined PNG ring, in the settings of Renderer.set_png() (frames count from 0; `fps` is not used)."""
         from . import y4m
         r = self.renderer
         n = int(frames)
@@ -372,6 +401,14 @@ class EarthViewer:
                 raise ValueError("slider %r has %d values for %d frames" % (k, len(v), n))
         if path.endswith((".avi", ".mjpeg")):
             return self._record_jpeg(path, n, spp, fps, sliders_per_frame)
+        if path.endswith(".png"):
+            try:
+                numbered = path % 0 != path % 1
+            except (TypeError, ValueError):
+                numbered = False
+            if not numbered:
+                raise ValueError("a .png recording needs a pattern with one integer field, such as frames/%05d.png")
+            return self._record_png(path, n, spp, sliders_per_frame)
         fmt = r.video()
         w = y4m.Y4MWriter(path, fmt["size"][0], fmt["size"][1], fps=fps, format=fmt["format"], range=fmt["range"], siting=fmt["siting"])
         try:
@@ -387,9 +424,14 @@ class EarthViewer:
             w.close()
         return w.frames
 
+    def finish_png(self, copy=True):
+        """End a pipelined frame(png=True) loop: the file of its last iteration (None when nothing is in flight).  A method of its own, as
+        Renderer.fetch_pending_jpeg is: finish()'s signature is pinned."""
+        return self.renderer.fetch_pending_png(copy=copy)
+
     def finish(self, copy=True, pixels=False, video=False, jpeg=False):
         """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop;
-        video=True: the frame of a frame(video=True) loop; jpeg=True: the file of a frame(jpeg=True) loop."""
+        video=True: the frame of a frame(video=True) loop; jpeg=True: the file of a frame(jpeg=True) loop.  (A frame(png=True) loop ends in finish_png().)"""
         if jpeg:
             return self.renderer.fetch_pending_jpeg(copy=copy)
         if video:
@@ -427,7 +469,11 @@ class EarthViewer:
         from render() / frame() is quantised on the host by rounding (png16.to_rgb16) — the setting's mode and dither belong to fetch_hdr_pixels().
         Under the P3-D65 and Rec.2020 gamuts the label names the container, not a colorimetric picture: see Renderer.set_hdr_output.
         `.jpg` / `.jpeg` with a float image held (render, frame) and the HDR output off: the file is the GPU encoder's (Renderer.debug_jpeg on the
-        image held, in the settings of Renderer.set_jpeg) — no host encoder; with packed pixels held the image writer encodes them as before."""
+        image held, in the settings of Renderer.set_jpeg) — no host encoder; with packed pixels held the image writer encodes them as before.
+        `.png` once Renderer.set_png() has been called: the same picture under the same rules — the pixels held, or the image held through the pack
+        kernel at the phase it was shown with — filtered and deflated by the GPU's encoder (Renderer.debug_png, in the filter and chunk size of
+        set_png); a picture taken with the HDR output on is the 16-bit file with the cICP chunk of the setting it was taken with.  Without
+        set_png() the file is written the way it was before, byte for byte."""
         r = self.renderer
         if self._image is None and self._pixels is None:
             self.render(1)
@@ -435,6 +481,22 @@ class EarthViewer:
             np.save(path, self._image if self._image is not None else r.fetch_image())
             return
         hdr = self._held_hdr
+        gpu_png = path.endswith(".png") and r.png_is_set
+        if gpu_png:
+            fmt = r.png()
+            if hdr is not None:
+                held = self._pixels if self._pixels is not None else np.asarray(self._image, dtype=np.float32)
+                data = r.debug_png(np.ascontiguousarray(png16.to_rgb16(held)), filter=fmt["filter"], chunk_bytes=fmt["chunk_bytes"],
+                                   cicp=png16.cicp_of(hdr["gamut"], hdr["transfer"]))
+            else:
+                px = self._pixels
+                if px is None:
+                    pf = r.pixels()
+                    px = r.debug_pixels(self._image, channels=pf["channels"], mode=pf["mode"], seed=pf["seed"], phase=pf["last_phase"])
+                data = r.debug_png(px, filter=fmt["filter"], chunk_bytes=fmt["chunk_bytes"])
+            with open(path, "wb") as f:
+                f.write(data)
+            return
         if hdr is not None:
             held = self._pixels if self._pixels is not None else np.asarray(self._image, dtype=np.float32)
             png16.write_png16(path, png16.to_rgb16(held), png16.cicp_of(hdr["gamut"], hdr["transfer"]))

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -153,6 +153,7 @@ class Renderer:
         self._vd_ring = _FetchRing(self._lib, "de_fetch_videoframe", "de_fetch_video", ctypes.c_uint8, Renderer._vd_bytes, "fetch_video",
                                    "lagged video fetches are in flight: fetch_pending(video=True) first")
         self._jp_in_flight, self._jp_view_ref = 0, None      # the lagged fetch_jpeg() calls; the last view handed out
+        self._pn_in_flight, self._pn_view_ref, self._png_set = 0, None, False      # the same for fetch_png(); set_png() has been called
         check(self._lib.de_create(int(device), self.image_res[0], self.image_res[1], ctypes.byref(self._h)))
         _native.apply_env_tuning(self._h)      # experiment overrides (DE_KERNEL, DE_V6_* ...): read HERE, not in the library
         self._params = DeParams()
@@ -202,6 +203,8 @@ class Renderer:
                     raise RuntimeError("a %s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % ring.name)
             if self._jp_view_ref is not None and self._jp_view_ref() is not None:
                 raise RuntimeError("a fetch_jpeg(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
+            if self._pn_view_ref is not None and self._pn_view_ref() is not None:
+                raise RuntimeError("a fetch_png(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
             check(self._lib.de_destroy(self._h))
             self._h = ctypes.c_void_p()
             self._lender = None
@@ -1041,6 +1044,112 @@ class Renderer:
         out = ctypes.create_string_buffer(int(cap.value))
         check(self._lib.de_debug_jpeg(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
         return out.raw[:int(n.value)]
+
+    # ------------------------------------------------------------------ PNG output (include/digital_earth_png.h)
+    def _pn_settings(self, source, filter, chunk_bytes):
+        if source not in _native.PNG_SOURCES:
+            raise ValueError("source must be one of %s" % (_native.PNG_SOURCES,))
+        if filter not in _native.PNG_FILTERS:
+            raise ValueError("filter must be one of %s" % (_native.PNG_FILTERS,))
+        s = DePng()
+        s.struct_bytes = ctypes.sizeof(DePng)
+        s.source, s.filter = _native.PNG_SOURCES.index(source), _native.PNG_FILTERS.index(filter)
+        s.chunk_bytes = _native.PNG_DEFAULT_CHUNK if chunk_bytes is None else int(chunk_bytes)
+        return s
+
+    def set_png(self, source="pixels", filter="adaptive", chunk_bytes=None):
+        """The settings of fetch_png(): one complete, lossless PNG file filtered and deflated on the GPU behind the packed outputs.  source "pixels":
+        the 8-bit pixels of set_pixels() (RGB or RGBA); "hdr_pixels": the 16-bit RGB pixels of set_hdr_output(pixel_format="rgb16"), with a cICP
+        chunk.  filter: "adaptive" (per row, the lowest sum of absolute values) or a fixed "none" / "sub" / "up" / "average" / "paeth".  chunk_bytes:
+        filtered bytes per independent deflate chunk, 1024 ... 65535 — the encoder's unit of parallelism; None: the default.  Refused (DE_ERR_STATE)
+        while lagged PNG fetches are in flight.  No other fetch is affected."""
+        check(self._lib.de_set_png(self._h, ctypes.byref(self._pn_settings(source, filter, chunk_bytes))))
+        self._png_set = True
+
+    def png(self):
+        """The PNG settings as a dict (set_png's keywords) plus size = (width, height) and capacity, the proven bound of any frame's length."""
+        s, n = DePng(), ctypes.c_uint64()
+        check(self._lib.de_get_png(self._h, ctypes.byref(s)))
+        check(self._lib.de_png_capacity(self._h, ctypes.byref(n)))
+        return dict(source=_native.PNG_SOURCES[s.source], filter=_native.PNG_FILTERS[s.filter], chunk_bytes=int(s.chunk_bytes),
+                    size=self.output_size(), capacity=int(n.value))
+
+    @property
+    def png_is_set(self):
+        """True once set_png() has been called: EarthViewer.save("x.png") then writes the GPU's file."""
+        return self._png_set
+
+    def _pn_view(self, ptr, n, copy):
+        if copy:
+            return ctypes.string_at(ptr, n)
+        view = np.ctypeslib.as_array(ptr, shape=(n,)).view(_StagingView)
+        view.flags.writeable = False
+        view._owner = self
+        self._pn_view_ref = weakref.ref(view)
+        return memoryview(view)
+
+    def _pn_end(self, copy):
+        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        self._pn_in_flight -= 1
+        check(self._lib.de_fetch_png_end(self._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return self._pn_view(ptr, int(n.value), copy)
+
+    def fetch_png(self, copy=True, lag=0):
+        """The displayed image as one complete PNG file: `bytes` that open(path, "wb").write() takes as they are.  Only the file's own bytes cross
+        the link.  copy=False: a read-only memoryview of the library's pinned buffer, valid until the next fetch_png call (lag = 0) or until the
+        ring comes round (lag > 0).  lag=1, 2 or 3: pipelined like fetch_jpeg(lag=...), through a ring of its own — the call returns the file of
+        the lag-th previous call (None until there is one); fetch_pending_png() hands out the rest."""
+        if not self._textures_copied:
+            self.copy_textures()
+        if lag not in (0, 1, 2, 3):
+            raise ValueError("lag must be 0 ... 3")
+        if lag:
+            check(self._lib.de_fetch_png_begin(self._h))
+            self._pn_in_flight += 1
+            return None if self._pn_in_flight <= lag else self._pn_end(copy)
+        if self._pn_in_flight:
+            raise RuntimeError("lagged PNG fetches are in flight: fetch_pending_png() first")
+        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        check(self._lib.de_fetch_png_view(self._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return self._pn_view(ptr, int(n.value), copy)
+
+    def fetch_pending_png(self, copy=True, all_images=False):
+        """fetch_pending() for the lagged fetch_png() calls and their ring: wait for the PNG fetches still in flight and return the newest file
+        (None when there is none) — bytes, or a memoryview with copy=False; all_images=True: the list of all of them, oldest first (bytes)."""
+        imgs = []
+        while self._pn_in_flight > 0:
+            imgs.append(self._pn_end(copy or all_images))
+        return imgs if all_images else (imgs[-1] if imgs else None)
+
+    def render_to_png(self):
+        """Run the display, the pack and the encoder and leave the file on the device (de_render_to_png); returns (address of the file, address of
+        its uint64 length).  Nothing is waited for."""
+        if not self._textures_copied:
+            self.copy_textures()
+        p, n = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.de_render_to_png(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+    def debug_png(self, pixels, filter="adaptive", chunk_bytes=None, cicp=None):
+        """The encoder once on given packed pixels (de_debug_png): (H, W, 3 | 4) uint8 or (H, W, 3) uint16, rows top-down, of any size; returns the
+        file as bytes.  The renderer's own settings and streams are not touched.  cicp: four code points for a 16-bit file other than the call's
+        own (1, 8, 0, 1) — the front is the host's part (de_debug_png_framing), so the host exchanges it."""
+        pixels = np.ascontiguousarray(pixels)
+        if pixels.ndim != 3 or not ((pixels.dtype == np.uint8 and pixels.shape[2] in (3, 4)) or (pixels.dtype == np.uint16 and pixels.shape[2] == 3)):
+            raise ValueError("pixels must be (H, W, 3 | 4) uint8 or (H, W, 3) uint16")
+        H, W, ch = pixels.shape
+        depth = 8 * pixels.dtype.itemsize
+        s = self._pn_settings("pixels", filter, chunk_bytes)
+        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.de_debug_png_framing(ctypes.byref(s), W, H, ch, depth, None, None, 0, None, ctypes.byref(cap)))
+        out = ctypes.create_string_buffer(int(cap.value))
+        check(self._lib.de_debug_png(self._h, pixels.ctypes.data, W, H, ch, depth, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
+        data = out.raw[:int(n.value)]
+        if cicp is not None and depth == 16:
+            front, m = ctypes.create_string_buffer(64), ctypes.c_uint64()
+            check(self._lib.de_debug_png_framing(ctypes.byref(s), W, H, ch, depth, bytes(bytearray(cicp)), front, ctypes.c_uint64(64), ctypes.byref(m), None))
+            data = front.raw[:int(m.value)] + data[int(m.value):]
+        return data
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)
     LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
