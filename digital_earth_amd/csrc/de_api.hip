@@ -107,7 +107,7 @@ int de_destroy(de_ctx* c) {
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
     // events and streams; the memory is the members' (de_memory.h): `delete c` frees what this context owns and leaves what it borrows
-    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring, &c->pn_ring}) ring_destroy_events(*r);
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) ring_destroy_events(*r);
 #ifdef DE_LEGACY_VARIANTS
     destroy_legacy_events(c);
 #endif
@@ -1182,7 +1182,7 @@ int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
-    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_ring, &c->pn_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
+    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
     c->os = *s;
     c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
     return DE_OK;
@@ -1350,13 +1350,13 @@ int de_debug_video(de_ctx* c, const float* image, int W, int H, const de_video* 
 int de_set_jpeg(de_ctx* c, const de_jpeg* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     { int rc = jp_settings_check(s); if (rc) return rc; }
-    { int rc = refuse_in_flight(c->jp_ring); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->jp_coded.ring); if (rc) return rc; }
     c->jp = *s;
     jp_make_tables(s->quality, &c->jp_tab);
     c->jp_gen++; c->jp_tab_gen = c->jp_gen;
     c->jp_w = out_w(c); c->jp_h = out_h(c);
     jp_write_framing(c->jp_tab, c->jp_w, c->jp_h, s->restart_mcus, c->jp_framing);
-    packed_reset(c->jp_out);
+    packed_reset(c->jp_coded.out);
     return DE_OK;
 }
 int de_get_jpeg(de_ctx* c, de_jpeg* out) {
@@ -1373,44 +1373,34 @@ int de_jpeg_capacity(de_ctx* c, uint64_t* bytes) {
 int de_render_to_jpeg(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     { int rc = vd_even_check(c); if (rc) return rc; }
-    int rc = jp_render(c, c->jp_out.dev, c->jp_out_framed);
+    int rc = jp_render(c, c->jp_coded.out.dev, c->jp_out_framed);
     if (rc) return rc;
-    if (device_stream) *device_stream = c->jp_out.dev + JP_HEADER_WORD;
-    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->jp_out.dev.get());
+    if (device_stream) *device_stream = c->jp_coded.out.dev + CS_WORD_BYTES;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->jp_coded.out.dev.get());
     return DE_OK;
 }
 int de_fetch_jpeg_view(de_ctx* c, const void** host, uint64_t* len) {
     if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
     int rc = de_render_to_jpeg(c, nullptr, nullptr);
     if (rc) return rc;
-    return fetch_staged_sized(c, c->jp_out.stage, c->jp_out.noun, c->jp_out.dev, JP_HEADER_WORD, jp_read_word, host, len);
+    return coded_view(c, c->jp_coded, jp_length, host, len);
 }
 int de_fetch_jpeg(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
     if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
     const void* host = nullptr;
     int rc = de_fetch_jpeg_view(c, &host, len);
     if (rc) return rc;
-    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the frame (*len; de_jpeg_capacity bounds every frame)");
-    memcpy(out, host, (size_t)*len);
-    return DE_OK;
+    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the frame (*len; de_jpeg_capacity bounds every frame)");
 }
 int de_fetch_jpeg_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     { int rc = vd_even_check(c); if (rc) return rc; }
     const JpegGeometry g = jp_ctx_geometry(c);
-    size_t prefix = c->jp_guess ? c->jp_guess : JP_HEADER_WORD + JP_FRAMING_BYTES + (size_t)g.W * (size_t)g.H / 4;      // the first: two bits per pixel
-    if (prefix > JP_HEADER_WORD + g.capacity) prefix = JP_HEADER_WORD + g.capacity;
-    return ring_begin_prefix(c, c->jp_ring, [c](int k, const uint8_t** src) {
-        int rc = jp_render(c, c->jp_cell[k].dev, c->jp_cell[k].framed);
-        *src = c->jp_cell[k].dev;
-        return rc;
-    }, prefix, c->jp_cell_copied);
+    return coded_begin(c, c->jp_coded, JP_FRAMING_BYTES + (size_t)g.W * (size_t)g.H / 4, g.capacity, [c](int k) { return jp_render(c, c->jp_coded.cell[k], c->jp_cell_framed[k]); });      // the first: two bits per pixel
 }
 int de_fetch_jpeg_end(de_ctx* c, const void** host, uint64_t* len) {
     if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    int rc = ring_end_sized(c, c->jp_ring, [c](int k) { return (const uint8_t*)c->jp_cell[k].dev.get(); }, c->jp_cell_copied, JP_HEADER_WORD, jp_read_word, host, len);
-    if (!rc) c->jp_guess = ((JP_HEADER_WORD + (size_t)*len) * 5 / 4 + 4095) & ~(size_t)4095;      // the next prefix: a quarter more than this frame
-    return rc;
+    return coded_end(c, c->jp_coded, jp_length, host, len);
 }
 /* the conversion once on a host-given image of any even size.  Buffers of its own; the context's settings and streams are not touched. */
 int de_debug_jpeg(de_ctx* c, const float* image, int W, int H, const de_jpeg* s, void* out, uint64_t out_bytes, uint64_t* len) {
@@ -1430,20 +1420,12 @@ int de_debug_jpeg(de_ctx* c, const float* image, int W, int H, const de_jpeg* s,
     const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
     { int rc = jp_work_ensure(work, g); if (rc) return rc; }
     HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(jp_stream_bytes(g)));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
     HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(work.tab, &tab, sizeof(tab), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_out + JP_HEADER_WORD, framing, sizeof(framing), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_out + CS_WORD_BYTES, framing, sizeof(framing), hipMemcpyHostToDevice, c->stream));
     jp_launch(c->stream, d_image, work, g, d_out);
-    HIP_TRY(hipGetLastError());
-    uint32_t word[4];
-    HIP_TRY(hipMemcpyAsync(word, d_out, sizeof(word), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    { int rc = jp_read_word(word, len); if (rc) return rc; }
-    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the frame (*len)");
-    HIP_TRY(hipMemcpyAsync(out, d_out + JP_HEADER_WORD, (size_t)*len, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    return coded_debug_out(c->stream, d_out, jp_length, out, out_bytes, len, "out_bytes is smaller than the frame (*len)");
 }
 /* the host's part alone: no device, no context */
 int de_debug_jpeg_framing(const de_jpeg* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
@@ -1464,10 +1446,10 @@ int de_debug_jpeg_framing(const de_jpeg* s, int W, int H, void* out, uint64_t ou
 int de_set_png(de_ctx* c, const de_png* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     { int rc = pn_settings_check(s); if (rc) return rc; }
-    { int rc = refuse_in_flight(c->pn_ring); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->pn_coded.ring); if (rc) return rc; }
     c->pn = *s;
-    c->pn_guess = 0;
-    packed_reset(c->pn_out);
+    c->pn_coded.guess = 0;
+    packed_reset(c->pn_coded.out);
     return DE_OK;
 }
 int de_get_png(de_ctx* c, de_png* out) {
@@ -1483,44 +1465,34 @@ int de_png_capacity(de_ctx* c, uint64_t* bytes) {
 }
 int de_render_to_png(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
-    int rc = pn_render(c, c->pn_out.dev);
+    int rc = pn_render(c, c->pn_coded.out.dev);
     if (rc) return rc;
-    if (device_stream) *device_stream = c->pn_out.dev + PNG_HEADER_WORD;
-    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->pn_out.dev.get());
+    if (device_stream) *device_stream = c->pn_coded.out.dev + CS_WORD_BYTES;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->pn_coded.out.dev.get());
     return DE_OK;
 }
 int de_fetch_png_view(de_ctx* c, const void** host, uint64_t* len) {
     if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
     int rc = de_render_to_png(c, nullptr, nullptr);
     if (rc) return rc;
-    return fetch_staged_sized(c, c->pn_out.stage, c->pn_out.noun, c->pn_out.dev, PNG_HEADER_WORD, pn_read_word, host, len);
+    return coded_view(c, c->pn_coded, pn_length, host, len);
 }
 int de_fetch_png(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
     if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
     const void* host = nullptr;
     int rc = de_fetch_png_view(c, &host, len);
     if (rc) return rc;
-    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the file (*len; de_png_capacity bounds every frame)");
-    memcpy(out, host, (size_t)*len);
-    return DE_OK;
+    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the file (*len; de_png_capacity bounds every frame)");
 }
 int de_fetch_png_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
     { int rc = pn_source_check(c); if (rc) return rc; }
     const PngGeometry g = pn_ctx_geometry(c);
-    size_t prefix = c->pn_guess ? c->pn_guess : PNG_HEADER_WORD + g.front + g.filtered / 4;      // the first: a quarter of the filtered bytes
-    if (prefix > PNG_HEADER_WORD + g.capacity) prefix = PNG_HEADER_WORD + g.capacity;
-    return ring_begin_prefix(c, c->pn_ring, [c](int k, const uint8_t** src) {
-        int rc = pn_render(c, c->pn_cell[k]);
-        *src = c->pn_cell[k];
-        return rc;
-    }, prefix, c->pn_cell_copied);
+    return coded_begin(c, c->pn_coded, g.front + g.filtered / 4, g.capacity, [c](int k) { return pn_render(c, c->pn_coded.cell[k]); });      // the first: a quarter of the filtered bytes
 }
 int de_fetch_png_end(de_ctx* c, const void** host, uint64_t* len) {
     if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    int rc = ring_end_sized(c, c->pn_ring, [c](int k) { return (const uint8_t*)c->pn_cell[k].get(); }, c->pn_cell_copied, PNG_HEADER_WORD, pn_read_word, host, len);
-    if (!rc) c->pn_guess = ((PNG_HEADER_WORD + (size_t)*len) * 5 / 4 + 4095) & ~(size_t)4095;      // the next prefix: a quarter more than this frame
-    return rc;
+    return coded_end(c, c->pn_coded, pn_length, host, len);
 }
 /* the conversion once on host-given packed pixels of any size.  Buffers of its own; the context's settings and streams are not touched. */
 int de_debug_png(de_ctx* c, const void* pixels, int W, int H, int channels, int depth, const de_png* s, void* out, uint64_t out_bytes, uint64_t* len) {
@@ -1532,20 +1504,12 @@ int de_debug_png(de_ctx* c, const void* pixels, int W, int H, int channels, int 
     de_ctx::PngWork work;
     Dev<uint8_t> d_out;
     { int rc = pn_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_out.ensure(pn_stream_bytes(g)));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
     HIP_TRY(hipMemcpyAsync(work.pixels, pixels, (size_t)g.H * g.row_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(pn_tables_upload(c->stream, work));
     const uint8_t cicp[4] = {1, 8, 0, 1};
     pn_launch(c->stream, work, g, s->filter, cicp, d_out);
-    HIP_TRY(hipGetLastError());
-    uint32_t word[4];
-    HIP_TRY(hipMemcpyAsync(word, d_out, sizeof(word), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    { int rc = pn_read_word(word, len); if (rc) return rc; }
-    if (out_bytes < *len) return fail(DE_ERR_INVALID, "out_bytes is smaller than the file (*len)");
-    HIP_TRY(hipMemcpyAsync(out, d_out + PNG_HEADER_WORD, (size_t)*len, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return DE_OK;
+    return coded_debug_out(c->stream, d_out, pn_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
 }
 /* the host's part alone: no device, no context */
 int de_debug_png_framing(const de_png* s, int W, int H, int channels, int depth, const uint8_t* cicp, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {

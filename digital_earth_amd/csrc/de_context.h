@@ -96,6 +96,13 @@ struct PackedOut {                       // an output converted from the display
     Pinned<void> stage;                  // where a synchronous fetch lands
     uint32_t count = 0, last_phase = 0;  // conversions since the settings were set; the dither phase of the newest
 };
+struct CodedOut {                        // an output whose length the device decides (the JPEG stream, the PNG file): on the device, the 16-byte word, then the stream
+    PackedOut out;                       // the stream of the synchronous fetches; its staging buffer grows to the longest frame fetched, not to the capacity
+    FetchRing ring;                      // the lagged ones: a fetch copies a prefix at _begin and, should the frame be longer, the whole of it at _end ...
+    Dev<uint8_t> cell[DE_FETCH_RING];    // ... from a device stream of its own per ring cell, which the next _begin does not touch
+    size_t copied[DE_FETCH_RING] = {};   // bytes of cell k that _begin copied into the pinned cell
+    size_t guess = 0;                    // the prefix _begin copies: a quarter more than the newest frame ended; 0: the output's first estimate
+};
 
 struct DevTexture {
     int w = 0, h = 0, ch = 0;
@@ -311,15 +318,10 @@ struct de_ctx {
     de_look lk = {};
     LookDev lk_dev;
     // JPEG output (include/digital_earth_jpeg.h).  The tables of the settings are computed by de_set_jpeg on the host; they, the framing and
-    // every buffer reach the device on first use: the planes, coefficients, masks and interval slots of one conversion (JpegWork), the stream of the
-    // synchronous fetches (jp_out: its staging buffer grows to the longest frame fetched, not to the capacity) and, per ring cell, a stream on the device
-    // and a pinned cell — a lagged fetch copies a prefix at _begin and, should the frame be longer, the whole of it at _end, from its own device stream.
+    // every buffer reach the device on first use: the planes, coefficients, masks and interval slots of one conversion (JpegWork) and the streams of
+    // jp_coded, each with the generation of the framing in it beside it (jp_gen when it was written: jp_out_framed, jp_cell_framed).
     struct JpegWork {             // what one conversion passes through; re-allocated when a frame needs more
         Dev<uint8_t> planes; Dev<int16_t> coef; Dev<unsigned long long> mask; Dev<uint8_t> slots; Dev<uint32_t> words; Dev<JpegTables> tab;
-    };
-    struct JpegStream {           // a stream on the device: the 16-byte word, the framing, the entropy-coded data
-        Dev<uint8_t> dev;
-        uint64_t framed = 0;      // jp_gen when the framing in it was written
     };
     de_jpeg jp = {(uint32_t)sizeof(de_jpeg), 90, DE_JPEG_DEFAULT_RESTART};
     JpegTables jp_tab = {};         // of jp.quality: once per de_set_jpeg (and in de_create's stead on first use: jp_tab_gen = 0)
@@ -327,26 +329,17 @@ struct de_ctx {
     int jp_w = 0, jp_h = 0;         // the size the framing was written for
     uint8_t jp_framing[JP_FRAMING_BYTES] = {};
     JpegWork jp_work;
-    PackedOut jp_out = {"JPEG"};
-    uint64_t jp_out_framed = 0;
-    FetchRing jp_ring = {"JPEG", "de_fetch_jpeg"};
-    JpegStream jp_cell[DE_FETCH_RING];
-    size_t jp_cell_copied[DE_FETCH_RING] = {};      // bytes of the device stream that _begin copied into the pinned cell
-    size_t jp_guess = 0;            // the prefix a lagged fetch copies at _begin: a quarter more than the newest frame ended
+    CodedOut jp_coded = {{"JPEG"}, {"JPEG", "de_fetch_jpeg"}};
+    uint64_t jp_out_framed = 0, jp_cell_framed[DE_FETCH_RING] = {};
     // PNG output (include/digital_earth_png.h).  Everything reaches the device on first use: the packed pixels, the filtered stream, the
-    // chunks' slots and words of one conversion (PngWork), the file of the synchronous fetches (pn_out) and, per ring cell, a file on the device and
-    // a pinned cell, as the JPEG ring.  The front travels in the kernels' arguments: no copy of it is tracked.
+    // chunks' slots and words of one conversion (PngWork) and the files of pn_coded.  The front travels in the kernels' arguments: no copy of it is tracked.
     struct PngWork {              // what one conversion passes through; re-allocated when a frame needs more
         Dev<uint8_t> pixels, filtered, slots; Dev<uint32_t> words; Dev<PngTables> tab;
         bool tab_uploaded = false;
     };
     de_png pn = {(uint32_t)sizeof(de_png), DE_PNG_SOURCE_PIXELS, DE_PNG_FILTER_ADAPTIVE, DE_PNG_DEFAULT_CHUNK};
     PngWork pn_work;
-    PackedOut pn_out = {"PNG"};
-    FetchRing pn_ring = {"PNG", "de_fetch_png"};
-    Dev<uint8_t> pn_cell[DE_FETCH_RING];
-    size_t pn_cell_copied[DE_FETCH_RING] = {};
-    size_t pn_guess = 0;            // the prefix a lagged fetch copies at _begin: a quarter more than the newest frame ended
+    CodedOut pn_coded = {{"PNG"}, {"PNG", "de_fetch_png"}};
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

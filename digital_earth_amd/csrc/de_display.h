@@ -460,7 +460,6 @@ int jp_geometry_check(const JpegGeometry& g) {      // the kernels count bytes i
     if (g.capacity + 64 >= (1ull << 32)) return fail(DE_ERR_INVALID, "the JPEG output's worst case does not fit 2^32 bytes at this size");
     return DE_OK;
 }
-size_t jp_stream_bytes(const JpegGeometry& g) { return (JP_HEADER_WORD + g.capacity + 15) & ~(size_t)15; }      // a stream on the device
 // The buffers of one conversion of geometry g; `words` holds len[intervals], offset[intervals] and the status word.
 int jp_work_ensure(de_ctx::JpegWork& w, const JpegGeometry& g) {
     int rc = w.planes.ensure((size_t)g.W * (size_t)g.H / 2 * 3, "JPEG buffers");
@@ -479,21 +478,16 @@ void jp_launch(hipStream_t stream, const float* image, const de_ctx::JpegWork& w
     a.planes = w.planes; a.tab = w.tab; a.coef = w.coef; a.mask = w.mask; a.slots = w.slots;
     a.len = w.words; a.offset = w.words + g.intervals; a.status = w.words + 2 * g.intervals; a.out = out;
     a.W = g.W; a.H = g.H; a.mcus_x = g.mcus_x; a.restart = g.restart;
-    a.blocks = (uint32_t)g.blocks; a.mcus = (uint32_t)g.mcus; a.intervals = (uint32_t)g.intervals; a.slot_bytes = (uint32_t)g.slot_bytes;
-    a.framing = JP_FRAMING_BYTES; a.capacity = (uint32_t)g.capacity;
+    a.blocks = (uint32_t)g.blocks; a.mcus = (uint32_t)g.mcus; a.count = (uint32_t)g.intervals; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.front = JP_FRAMING_BYTES; a.extra = 2u; a.trailer = 0u; a.capacity = (uint32_t)g.capacity;
     hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((g.blocks + JP_WG_BLOCKS - 1) / JP_WG_BLOCKS)), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((g.intervals + 63) / 64)), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(JP_SCAN_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(CS_SCAN_THREADS), 0, stream, a);
     hipLaunchKernelGGL(jpeg_compact_kernel, dim3((unsigned)g.intervals), dim3(256), 0, stream, a);
 }
 JpegGeometry jp_ctx_geometry(const de_ctx* c) { return jp_geometry(out_w(c), out_h(c), c->jp.restart_mcus); }
-// The 16-byte word as a fetch finds it on the host: the length, or DE_ERR_INTERNAL.
-int jp_read_word(const void* word, uint64_t* len) {
-    uint32_t w[4];
-    memcpy(w, word, sizeof(w));
-    *len = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    if (w[2]) return fail(DE_ERR_INTERNAL, w[2] & JP_STATUS_OVERFLOW ? "the JPEG encoder met a stream longer than its proven worst case: nothing was written past a buffer" : "the JPEG encoder met a coefficient outside the DCT's proven range");
-    return DE_OK;
+int jp_length(const void* word, uint64_t* len) {
+    return coded_read_word(word, len, "the JPEG encoder met a stream longer than its proven worst case: nothing was written past a buffer", "the JPEG encoder met a coefficient outside the DCT's proven range");
 }
 // One conversion of the frame as it stands into `dev`, a stream on the device that is (re-)allocated and framed as needed.  Nothing is waited for.
 int jp_render(de_ctx* c, Dev<uint8_t>& dev, uint64_t& framed) {
@@ -507,7 +501,7 @@ int jp_render(de_ctx* c, Dev<uint8_t>& dev, uint64_t& framed) {
         jp_write_framing(c->jp_tab, g.W, g.H, c->jp.restart_mcus, c->jp_framing);
     }
     const uint8_t* before = dev.get();
-    rc = dev.ensure(jp_stream_bytes(g), "JPEG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
+    rc = dev.ensure(coded_stream_bytes(g.capacity), "JPEG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
     if (rc) return rc;
     if (dev.get() != before) framed = 0;
     const JpegTables* tab_before = c->jp_work.tab.get();
@@ -516,12 +510,12 @@ int jp_render(de_ctx* c, Dev<uint8_t>& dev, uint64_t& framed) {
     if (c->jp_work.tab.get() != tab_before) c->jp_tab_uploaded = 0;
     // pageable sources: the runtime has read them when the call returns; on the device they are ordered behind the conversions already enqueued
     if (c->jp_tab_uploaded != c->jp_tab_gen) { HIP_TRY(hipMemcpyAsync(c->jp_work.tab, &c->jp_tab, sizeof(JpegTables), hipMemcpyHostToDevice, c->stream)); c->jp_tab_uploaded = c->jp_tab_gen; }
-    if (framed != c->jp_gen) { HIP_TRY(hipMemcpyAsync(dev + JP_HEADER_WORD, c->jp_framing, JP_FRAMING_BYTES, hipMemcpyHostToDevice, c->stream)); framed = c->jp_gen; }
+    if (framed != c->jp_gen) { HIP_TRY(hipMemcpyAsync(dev + CS_WORD_BYTES, c->jp_framing, JP_FRAMING_BYTES, hipMemcpyHostToDevice, c->stream)); framed = c->jp_gen; }
     rc = de_render_to_image(c, nullptr);
     if (rc) return rc;
     jp_launch(c->stream, shown_image(c), c->jp_work, g, dev);
     HIP_TRY(hipGetLastError());
-    c->jp_out.count++;
+    c->jp_coded.out.count++;
     return DE_OK;
 }
 // ---- PNG output (include/digital_earth_png.h, png_kernels.hip, png_tables.h)
@@ -539,7 +533,6 @@ int pn_shape_check(int W, int H, int channels, int depth) {      // what one con
         return fail(DE_ERR_INVALID, "the PNG output takes at most 2^27 filtered bytes, H (1 + W bpp)");
     return DE_OK;
 }
-size_t pn_stream_bytes(const PngGeometry& g) { return (PNG_HEADER_WORD + g.capacity + 15) & ~(size_t)15; }      // a file on the device
 void pn_cicp(const de_hdr_output& ho, uint8_t cicp[4]) {      // as png16.cicp_of: {primaries, transfer, RGB, full range}
     static const uint8_t primaries[3] = {1, 12, 9}, transfer[3] = {8, 16, 18};
     cicp[0] = primaries[ho.gamut]; cicp[1] = transfer[ho.transfer]; cicp[2] = 0; cicp[3] = 1;
@@ -569,13 +562,13 @@ void pn_launch(hipStream_t stream, const de_ctx::PngWork& w, const PngGeometry& 
     a.pixels = w.pixels; a.tab = w.tab; a.filtered = w.filtered; a.slots = w.slots;
     a.len = w.words; a.offset = w.words + g.chunks; a.adler = w.words + 2 * g.chunks; a.status = w.words + 4 * g.chunks; a.out = out;
     a.H = g.H; a.bpp = g.bpp; a.swap16 = g.depth == 16 ? 1 : 0; a.filter = filter; a.chunk_bytes = g.chunk_bytes;
-    a.row_bytes = (uint32_t)g.row_bytes; a.total = (uint32_t)g.filtered; a.chunks = (uint32_t)g.chunks; a.slot_bytes = (uint32_t)g.slot_bytes;
-    a.capacity = (uint32_t)g.capacity;
+    a.row_bytes = (uint32_t)g.row_bytes; a.total = (uint32_t)g.filtered; a.count = (uint32_t)g.chunks; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.extra = 0u; a.trailer = PNG_TRAILER_BYTES; a.capacity = (uint32_t)g.capacity;
     memset(a.front_bytes, 0, sizeof(a.front_bytes));
     a.front = (uint32_t)png_write_front(pn_host_tables(), g, cicp, a.front_bytes);
     hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)g.H), dim3(PNG_FILTER_THREADS), 0, stream, a);
     hipLaunchKernelGGL(png_deflate_kernel, dim3((unsigned)g.chunks), dim3(PNG_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(PNG_SCAN_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(png_scan_kernel, dim3(1), dim3(CS_SCAN_THREADS), 0, stream, a);
     hipLaunchKernelGGL(png_compact_kernel, dim3((unsigned)g.chunks), dim3(256), 0, stream, a);
 }
 int pn_source_check(const de_ctx* c) {
@@ -587,13 +580,9 @@ PngGeometry pn_ctx_geometry(const de_ctx* c) {
     const bool hdr = c->pn.source == DE_PNG_SOURCE_HDR_PIXELS;
     return png_geometry(out_w(c), out_h(c), hdr ? 3 : c->px.channels, hdr ? 16 : 8, c->pn.chunk_bytes);
 }
-// The 16-byte word as a fetch finds it on the host: the length, or DE_ERR_INTERNAL.
-int pn_read_word(const void* word, uint64_t* len) {
-    uint32_t w[4];
-    memcpy(w, word, sizeof(w));
-    *len = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-    if (w[2]) return fail(DE_ERR_INTERNAL, "the PNG encoder met a chunk longer than its proven worst case: nothing was written past a buffer");
-    return DE_OK;
+int pn_length(const void* word, uint64_t* len) {      // its coders raise no range status
+    static const char* const text = "the PNG encoder met a chunk longer than its proven worst case: nothing was written past a buffer";
+    return coded_read_word(word, len, text, text);
 }
 // One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
 int pn_render(de_ctx* c, Dev<uint8_t>& dev) {
@@ -603,7 +592,7 @@ int pn_render(de_ctx* c, Dev<uint8_t>& dev) {
     const PngGeometry g = pn_ctx_geometry(c);
     rc = pn_shape_check(g.W, g.H, g.channels, g.depth);
     if (rc) return rc;
-    rc = dev.ensure(pn_stream_bytes(g), "PNG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
+    rc = dev.ensure(coded_stream_bytes(g.capacity), "PNG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
     if (rc) return rc;
     rc = pn_work_ensure(c->pn_work, g);
     if (rc) return rc;
@@ -612,18 +601,18 @@ int pn_render(de_ctx* c, Dev<uint8_t>& dev) {
     if (rc) return rc;
     uint8_t cicp[4] = {1, 8, 0, 1};
     if (g.depth == 16) {
-        const uint32_t phase = c->ho.animate ? c->pn_out.count : 0u;
+        const uint32_t phase = c->ho.animate ? c->pn_coded.out.count : 0u;
         hpx_launch(c->stream, shown_image(c), c->pn_work.pixels, g.W, g.H, c->ho, phase);
         pn_cicp(c->ho, cicp);
-        c->pn_out.last_phase = phase;
+        c->pn_coded.out.last_phase = phase;
     } else {
-        const uint32_t phase = c->px.animate ? c->pn_out.count : 0u;
+        const uint32_t phase = c->px.animate ? c->pn_coded.out.count : 0u;
         px_launch(c->stream, shown_image(c), c->pn_work.pixels, g.W, g.H, c->px, phase);
-        c->pn_out.last_phase = phase;
+        c->pn_coded.out.last_phase = phase;
     }
     pn_launch(c->stream, c->pn_work, g, c->pn.filter, cicp, dev);
     HIP_TRY(hipGetLastError());
-    c->pn_out.count++;
+    c->pn_coded.out.count++;
     return DE_OK;
 }
 // ---- look LUTs (include/digital_earth_look.h, look_kernels.hip): in place on the displayed image, directly behind the display launch

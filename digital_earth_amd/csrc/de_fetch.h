@@ -4,7 +4,7 @@
 //   * copy_out: device -> caller's buffer through the context's staging buffer;
 //   * the conversion frame of the packed outputs (8-bit pixels, HDR pixels, video frames): allocate, display, phase, launch, count;
 //   * the synchronous path (render, copy, wait) and the lagged one (begin: render, copy, record; end: wait, hand out);
-//   * both once more for an output whose length the device decides (the JPEG stream): the length first, then exactly that many bytes.
+//   * both once more for the outputs whose length the device decides (CodedOut: the JPEG stream, the PNG file), and the debug entry points' tail.
 // The entry points of de_api.hip check their own arguments and call one of these.
 #pragma once
 
@@ -100,7 +100,7 @@ int ring_end(de_ctx* c, FetchRing& r, const H** host) {
     *host = (const H*)r.cell[k].get();
     return frame_status(c);
 }
-// ---- the same two paths for an output whose length the DEVICE decides (the JPEG stream, include/digital_earth_jpeg.h): on the device it is preceded
+// ---- the same two paths for an output whose length the DEVICE decides (the coded outputs below): on the device it is preceded
 // by a `word`-byte header that `length(header, &len)` reads.  A fetch copies the header and then exactly the stream — never the buffer's capacity.
 // Synchronous: the header, a wait, the stream, a wait; the staging buffer grows to the longest frame fetched, in steps of 1 MiB.
 template <class Length>
@@ -157,6 +157,50 @@ int ring_end_sized(de_ctx* c, FetchRing& r, Source source, const size_t* copied,
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     *host = (const uint8_t*)r.cell[k].get() + word;
+    return DE_OK;
+}
+// ---- the coded outputs (CodedOut; the word and the failure rule: coded_stream.h).  An output brings its `length` — coded_read_word
+// with its two messages —, its render function, its first estimate, its capacity and its refusal texts; everything else is here.
+size_t coded_stream_bytes(size_t capacity) { return (CS_WORD_BYTES + capacity + 15) & ~(size_t)15; }      // a stream of that capacity on the device
+int coded_read_word(const void* word, uint64_t* len, const char* overflow, const char* range) {      // the length, or DE_ERR_INTERNAL with the status' message
+    uint32_t status;
+    cs_word_fields(word, len, &status);
+    if (status) return fail(DE_ERR_INTERNAL, status & CS_STATUS_OVERFLOW ? overflow : range);
+    return DE_OK;
+}
+template <class Length>      // the stream an output's de_render_to_* has just enqueued into o.out.dev
+int coded_view(de_ctx* c, CodedOut& o, Length length, const void** host, uint64_t* len) {
+    return fetch_staged_sized(c, o.out.stage, o.out.noun, o.out.dev, CS_WORD_BYTES, length, host, len);
+}
+int coded_copy_out(const void* host, uint64_t len, void* out, uint64_t out_bytes, const char* refusal) {
+    if (out_bytes < len) return fail(DE_ERR_INVALID, refusal);
+    memcpy(out, host, (size_t)len);
+    return DE_OK;
+}
+// begin: `first` bytes of stream are the estimate while no frame has ended; render(k) converts the frame as it stands into o.cell[k].
+template <class Render>
+int coded_begin(de_ctx* c, CodedOut& o, size_t first, size_t capacity, Render render) {
+    size_t prefix = o.guess ? o.guess : CS_WORD_BYTES + first;
+    if (prefix > CS_WORD_BYTES + capacity) prefix = CS_WORD_BYTES + capacity;
+    return ring_begin_prefix(c, o.ring, [&](int k, const uint8_t** src) { int rc = render(k); *src = o.cell[k]; return rc; }, prefix, o.copied);
+}
+template <class Length>
+int coded_end(de_ctx* c, CodedOut& o, Length length, const void** host, uint64_t* len) {
+    int rc = ring_end_sized(c, o.ring, [&o](int k) { return (const uint8_t*)o.cell[k].get(); }, o.copied, CS_WORD_BYTES, length, host, len);
+    if (!rc) o.guess = ((CS_WORD_BYTES + (size_t)*len) * 5 / 4 + 4095) & ~(size_t)4095;      // the next prefix: a quarter more than this frame
+    return rc;
+}
+// The tail of a debug conversion that has just been launched into d_out on `stream`: the word, the refusal of too small an `out`, the stream itself.
+template <class Length>
+int coded_debug_out(hipStream_t stream, const uint8_t* d_out, Length length, void* out, uint64_t out_bytes, uint64_t* len, const char* refusal) {
+    HIP_TRY(hipGetLastError());
+    uint32_t word[CS_WORD_BYTES / 4];
+    HIP_TRY(hipMemcpyAsync(word, d_out, sizeof(word), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    { int rc = length(word, len); if (rc) return rc; }
+    if (out_bytes < *len) return fail(DE_ERR_INVALID, refusal);
+    HIP_TRY(hipMemcpyAsync(out, d_out + CS_WORD_BYTES, (size_t)*len, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     return DE_OK;
 }
 void ring_destroy_events(FetchRing& r) {      // de_destroy; the cells free themselves

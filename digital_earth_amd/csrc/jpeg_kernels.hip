@@ -14,10 +14,10 @@
 //                           blocks' masks, so that only non-zero coefficients are loaded.  Bits are gathered MSB first in a 64-bit accumulator (at most
 //                           7 left over + 27 new), bytes leave it with a 0x00 behind every 0xFF, gathered again into 32-bit words and stored into the
 //                           interval's SLOT, whose start is 16-byte aligned; the last byte is padded with 1-bits.  The slot's length goes to len[i].
-//   jpeg_scan_kernel        one workgroup: the exclusive sum of (len[i] + 2) over the intervals (a chunk per thread, the 1024 chunk sums serially by
-//                           thread 0), the offsets, and the 16-byte word in front of the stream: {uint64 length, uint32 status, uint32 intervals}.
-//   jpeg_compact_kernel     one workgroup per interval: its slot's bytes to their final place behind the framing, consecutive threads consecutive bytes,
-//                           then RSTm (m = i mod 8) behind it, or EOI behind the last.
+//   jpeg_scan_kernel        one workgroup: the exclusive sum of (len[i] + 2) over the intervals, the offsets and the 16-byte word in front of the stream —
+//                           the coded tail every coded output shares (coded_stream.h), with 2 bytes behind every piece and no trailer.
+//   jpeg_compact_kernel     one workgroup per interval: the shared compaction of its slot to its final place behind the framing, then RSTm
+//                           (m = i mod 8) behind it, or EOI behind the last.
 // THE WORST CASE of a slot (jpeg_tables.h: JP_BLOCK_BITS, jp_geometry).  One block: its DC costs at most 11 bits of code (the longest of K.3 / K.4) + 11 of
 // magnitude (|difference| <= 2047) = 22.  Each of the 63 AC positions is paid for by exactly one symbol: a non-zero coefficient pays for itself and for the
 // run in front of it with at most 16 bits of code (the longest of K.5 / K.6) + 10 of magnitude (|q| <= 1023) = 26; a ZRL pays 11 bits for 16 positions;
@@ -30,25 +30,18 @@
 #include "de_kernels.h"
 #endif
 #include "jpeg_tables.h"
+#include "coded_stream.h"
 
 #define JP_WG_BLOCKS 32          // blocks per workgroup of the transform
 #define JP_LDS_STRIDE 9          // words per staged row of 8
-#define JP_SCAN_THREADS 1024
-#define JP_STATUS_RANGE 1u       // a coefficient outside the ranges the worst case assumes
-#define JP_STATUS_OVERFLOW 2u    // a store past its slot or past the stream's capacity
 
-struct JpegArgs {
+struct JpegArgs : CodedTail {    // the pieces are the restart intervals: count of them; front: the host's framing; extra: the marker behind each
     const uint8_t* planes;      // Y [H][W], Cb [H / 2][W / 2], Cr: rows top-down
     const JpegTables* tab;
     int16_t* coef;              // [blocks][64], zigzag order
     unsigned long long* mask;   // [blocks]
-    uint8_t* slots;             // [intervals][slot_bytes]
-    uint32_t* len;              // [intervals]
-    uint32_t* offset;           // [intervals]: where an interval's bytes start in the stream
-    uint32_t* status;           // one word: JP_STATUS_*; cleared by the transform
-    uint8_t* out;               // the 16-byte word, then the stream (its first `framing` bytes are the host's)
     int W, H, mcus_x, restart;
-    uint32_t blocks, mcus, intervals, slot_bytes, framing, capacity;      // capacity: of the stream, without the 16-byte word
+    uint32_t blocks, mcus;
 };
 
 struct JpegTile {               // the transform's LDS: 2 x 9216 + 4096 + 256 = 22 784 bytes
@@ -150,7 +143,7 @@ struct JpegBits {
 DE_DEV void jp_byte(JpegBits& w, uint32_t byte) {
     w.word |= byte << (8 * (w.at & 3u));
     if ((w.at & 3u) == 3u) {
-        if ((w.at >> 2) < w.words) w.slot[w.at >> 2] = w.word; else w.status |= JP_STATUS_OVERFLOW;
+        if ((w.at >> 2) < w.words) w.slot[w.at >> 2] = w.word; else w.status |= CS_STATUS_OVERFLOW;
         w.word = 0;
     }
     w.at++;
@@ -177,7 +170,7 @@ DE_DEV void jp_symbol(JpegBits& w, uint32_t entry, int v, int n) {
     jp_put(w, (code << n) | mag, (int)len + n);
 }
 DE_DEV void jp_encode_interval(const JpegArgs& a, uint32_t i) {
-    if (i >= a.intervals) return;
+    if (i >= a.count) return;
     JpegBits w;
     w.slot = reinterpret_cast<uint32_t*>(a.slots + (size_t)i * (size_t)a.slot_bytes);
     w.words = a.slot_bytes >> 2; w.at = 0; w.word = 0; w.acc = 0; w.n = 0; w.status = 0;
@@ -195,7 +188,7 @@ DE_DEV void jp_encode_interval(const JpegArgs& a, uint32_t i) {
             const int diff = dc - pred;
             if (b < 4) pred_y = dc; else if (b == 4) pred_cb = dc; else pred_cr = dc;
             const int n = jp_category(diff);
-            if (n > 11) { w.status |= JP_STATUS_RANGE; continue; }
+            if (n > 11) { w.status |= CS_STATUS_RANGE; continue; }
             jp_symbol(w, a.tab->dc[c][n], diff, n);
             unsigned long long m = mask >> 1;      // bit k - 1 = zigzag position k
             int prev = 0;
@@ -206,7 +199,7 @@ DE_DEV void jp_encode_interval(const JpegArgs& a, uint32_t i) {
                 prev = k;
                 const int v = (int)q[k];
                 const int na = jp_category(v);
-                if (na > 10 || na == 0) { w.status |= JP_STATUS_RANGE; continue; }
+                if (na > 10 || na == 0) { w.status |= CS_STATUS_RANGE; continue; }
                 for (; run >= 16; run -= 16) { const uint32_t zrl = a.tab->ac[c][0xF0]; jp_put(w, zrl & 0xffffu, (int)(zrl >> 16)); }
                 jp_symbol(w, a.tab->ac[c][(run << 4) | na], v, na);
             }
@@ -215,50 +208,16 @@ DE_DEV void jp_encode_interval(const JpegArgs& a, uint32_t i) {
     if (w.n) jp_put(w, (1u << (8 - w.n)) - 1u, 8 - w.n);      // pad with 1-bits
     const uint32_t bytes = w.at;
     while (w.at & 3u) jp_byte(w, 0u);                         // flush the last word
-    if (bytes > a.slot_bytes) w.status |= JP_STATUS_OVERFLOW;
+    if (bytes > a.slot_bytes) w.status |= CS_STATUS_OVERFLOW;
     a.len[i] = bytes <= a.slot_bytes ? bytes : 0u;
     if (w.status) *a.status = w.status;
 }
 
-// ---- the scan: thread t owns intervals [t chunk, (t + 1) chunk); `sums` is the workgroup's LDS, JP_SCAN_THREADS words
-DE_DEV uint32_t jp_scan_chunk(const JpegArgs& a) { return (a.intervals + JP_SCAN_THREADS - 1u) / JP_SCAN_THREADS; }
-DE_DEV void jp_scan_sum(const JpegArgs& a, uint32_t* sums, int t) {
-    const uint32_t chunk = jp_scan_chunk(a), lo = (uint32_t)t * chunk;
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < lo + chunk && i < a.intervals; ++i) s += a.len[i] + 2u;      // its bytes and the marker behind it
-    sums[t] = s;
+// ---- the marker behind interval i, by thread 0 of the workgroup that moved it
+DE_DEV void jp_marker(const JpegArgs& a, uint32_t i) {
+    uint8_t* dst = a.out + CS_WORD_BYTES + a.offset[i] + a.len[i];
+    dst[0] = 0xff; dst[1] = i + 1u < a.count ? (uint8_t)(0xd0u + (i & 7u)) : (uint8_t)0xd9u;
 }
-DE_DEV void jp_scan_total(const JpegArgs& a, uint32_t* sums, int t) {
-    if (t != 0) return;
-    unsigned long long run = a.framing;
-    for (int k = 0; k < JP_SCAN_THREADS; ++k) {
-        const uint32_t s = sums[k];
-        sums[k] = (uint32_t)(run < 0xffffffffull ? run : 0xffffffffull);
-        run += s;
-    }
-    uint32_t status = *a.status;
-    if (run > (unsigned long long)a.capacity) { status |= JP_STATUS_OVERFLOW; run = a.framing; }
-    uint32_t* head = reinterpret_cast<uint32_t*>(a.out);
-    head[0] = (uint32_t)run; head[1] = (uint32_t)(run >> 32); head[2] = status; head[3] = a.intervals;
-    if (status) *a.status = status;
-}
-DE_DEV void jp_scan_offsets(const JpegArgs& a, const uint32_t* sums, int t) {
-    const uint32_t chunk = jp_scan_chunk(a), lo = (uint32_t)t * chunk;
-    uint32_t at = sums[t];
-    for (uint32_t i = lo; i < lo + chunk && i < a.intervals; ++i) { a.offset[i] = at; at += a.len[i] + 2u; }
-}
-
-// ---- the compaction: thread t of the workgroup of interval i
-DE_DEV void jp_compact(const JpegArgs& a, uint32_t i, int t, int threads) {
-    if (i >= a.intervals || *a.status) return;      // a failed conversion leaves the framing alone behind a length of `framing`
-    const uint32_t n = a.len[i], at = a.offset[i];
-    if ((unsigned long long)at + n + 2ull > (unsigned long long)a.capacity || n > a.slot_bytes) return;      // (the scan has refused such a total already)
-    const uint8_t* src = a.slots + (size_t)i * (size_t)a.slot_bytes;
-    uint8_t* dst = a.out + JP_HEADER_WORD + at;
-    for (uint32_t k = (uint32_t)t; k < n; k += (uint32_t)threads) dst[k] = src[k];
-    if (t == 0) { dst[n] = 0xff; dst[n + 1] = i + 1u < a.intervals ? (uint8_t)(0xd0u + (i & 7u)) : (uint8_t)0xd9u; }
-}
-
 #ifndef DE_JPEG_STANDALONE
 __global__ void __launch_bounds__(256) jpeg_transform_kernel(JpegArgs a) {
     __shared__ JpegTile tile;
@@ -274,14 +233,16 @@ __global__ void __launch_bounds__(256) jpeg_transform_kernel(JpegArgs a) {
     jp_mask(a, tile, t, blockIdx.x);
 }
 __global__ void __launch_bounds__(64) jpeg_entropy_kernel(JpegArgs a) { jp_encode_interval(a, blockIdx.x * 64u + threadIdx.x); }
-__global__ void __launch_bounds__(JP_SCAN_THREADS) jpeg_scan_kernel(JpegArgs a) {
-    __shared__ uint32_t sums[JP_SCAN_THREADS];
+__global__ void __launch_bounds__(CS_SCAN_THREADS) jpeg_scan_kernel(JpegArgs a) {
+    __shared__ uint32_t sums[CS_SCAN_THREADS];
     const int t = (int)threadIdx.x;
-    jp_scan_sum(a, sums, t);
+    cs_scan_sum(a, sums, t);
     __syncthreads();
-    jp_scan_total(a, sums, t);
+    cs_scan_total(a, sums, t);
     __syncthreads();
-    jp_scan_offsets(a, sums, t);
+    cs_scan_offsets(a, sums, t);
 }
-__global__ void __launch_bounds__(256) jpeg_compact_kernel(JpegArgs a) { jp_compact(a, blockIdx.x, (int)threadIdx.x, 256); }
+__global__ void __launch_bounds__(256) jpeg_compact_kernel(JpegArgs a) {
+    if (cs_compact(a, blockIdx.x, (int)threadIdx.x, 256) && threadIdx.x == 0) jp_marker(a, blockIdx.x);
+}
 #endif

@@ -7,7 +7,6 @@
 #include <stdint.h>
 #include <string.h>
 
-#define JP_HEADER_WORD 16            // bytes in front of the stream on the device: uint64 length, uint32 status, uint32 intervals
 #define JP_BLOCK_BITS 1660           // worst case of one block before stuffing: 22 (DC) + 63 * 26 (AC): jpeg_kernels.hip
 #define JP_FRAMING_BYTES 629         // SOI .. SOS: jp_write_framing answers it
 

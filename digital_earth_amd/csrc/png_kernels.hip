@@ -12,10 +12,10 @@
 //                        (length, type, data, CRC) in LDS: no atomics on global memory.  The CRC-32 of the IDAT: a piece per thread through the byte
 //                        table, shifted behind the end by the host's shift-by-2^k-bytes operators, XORed together.  The Adler-32 partials (A, B) of the
 //                        chunk's bytes go to adler[2 k], adler[2 k + 1].  The image leaves LDS for the chunk's slot as whole words.
-//   png_scan_kernel      one workgroup: the exclusive sum of the slots' lengths (a run of chunks per thread, the 1024 sums serially by thread 0), the
-//                        Adler partials combined the same way, the front, the trailer (the IDAT that holds the Adler-32, IEND) and the 16-byte word
-//                        {uint64 length, uint32 status, uint32 chunks} in front of the file.  The twin of jpeg_scan_kernel, which is left as it is.
-//   png_compact_kernel   one workgroup per chunk: its slot's bytes to their final place, consecutive threads consecutive bytes.
+//   png_scan_kernel      one workgroup: the coded tail's scan (coded_stream.h, DESIGN.md §22: the exclusive sum of the slots' lengths, the offsets, the
+//                        16-byte word) with nothing behind a piece and a trailer of 28 bytes, and what is PNG's alone: the front, the Adler partials
+//                        joined along the same split (png_adler_join), the trailer (the IDAT that holds the Adler-32, IEND).
+//   png_compact_kernel   one workgroup per chunk: the shared compaction of its slot to its final place.
 // THE WORST CASE of a slot (png_tables.h: PNG_CHUNK_OVERHEAD).  A chunk of n filtered bytes is written as a dynamic block only if that takes FEWER than
 // n + 5 bytes — the stored block's size — so its deflate data is at most 2 (CMF / FLG) + n + 5 + 5 (the empty stored block behind a non-final chunk:
 // 3 bits, padding, LEN, NLEN) and the IDAT around it 12 more: n + 24.  Every store into the LDS image and into a slot is checked against that; one that
@@ -23,29 +23,23 @@
 // Included into de_api.hip's translation unit behind jpeg_kernels.hip; it touches no other kernel.
 #include "de_kernels.h"
 #include "png_tables.h"
+#include "coded_stream.h"
 
 #define PNG_FILTER_THREADS 256
 #define PNG_THREADS 512              // of the deflate kernel
-#define PNG_SCAN_THREADS 1024
 #define PNG_BUF_WORDS 16392          // the LDS image of one IDAT: 65535 + 24 bytes, rounded up
 #define PNG_SYMBOLS 286
 #define PNG_HEADER_BITS 1222         // of a dynamic block: 3 + 5 + 5 + 4 + 19 * 3 + 287 * 4
 #define PNG_FILTER_ADAPTIVE 5
-#define PNG_STATUS_OVERFLOW 2u       // a store past the LDS image, a slot or the file's capacity (JP_STATUS_OVERFLOW's value)
 #define PNG_NONE 0xffffffffu
 
-struct PngArgs {
+struct PngArgs : CodedTail {    // the pieces are the chunks' IDATs: count of them; front: the bytes of front_bytes; trailer: PNG_TRAILER_BYTES
     const uint8_t* pixels;      // [H][row_bytes], rows top-down; 16-bit samples little-endian (swap16: PNG wants them big-endian)
     const PngTables* tab;
     uint8_t* filtered;          // S: [H][1 + row_bytes]
-    uint8_t* slots;             // [chunks][slot_bytes]
-    uint32_t* len;              // [chunks]: the bytes of a chunk's IDAT
-    uint32_t* offset;           // [chunks]: where they start in the file
-    uint32_t* adler;            // [chunks][2]: A and B of the chunk's own bytes, from (0, 0)
-    uint32_t* status;           // one word; cleared by the filter kernel
-    uint8_t* out;               // the 16-byte word, then the file
+    uint32_t* adler;            // [count][2]: A and B of the chunk's own bytes, from (0, 0)
     int H, bpp, swap16, filter, chunk_bytes;
-    uint32_t row_bytes, total, chunks, slot_bytes, front, capacity;      // total: N; capacity: of the file, without the 16-byte word
+    uint32_t row_bytes, total;  // total: N
     uint8_t front_bytes[PNG_FRONT_MAX];
 };
 
@@ -217,10 +211,10 @@ DE_DEV void png_code_lengths(PngLds& s) {
 __global__ void __launch_bounds__(PNG_THREADS) png_deflate_kernel(PngArgs a) {
     __shared__ PngLds s;
     const uint32_t k = blockIdx.x, t = threadIdx.x;
-    if (k >= a.chunks) return;
+    if (k >= a.count) return;
     const uint32_t base = k * (uint32_t)a.chunk_bytes;
     const uint32_t n = a.total - base < (uint32_t)a.chunk_bytes ? a.total - base : (uint32_t)a.chunk_bytes;
-    const bool final_chunk = k + 1u == a.chunks;
+    const bool final_chunk = k + 1u == a.count;
     const uint8_t* c = a.filtered + base;
     const uint32_t seg = (n + PNG_THREADS - 1u) / PNG_THREADS;
     const uint32_t lo = t * seg < n ? t * seg : n, hi = lo + seg < n ? lo + seg : n;
@@ -357,68 +351,42 @@ __global__ void __launch_bounds__(PNG_THREADS) png_deflate_kernel(PngArgs a) {
         a.len[k] = fits ? bytes : 0u;
         a.adler[2u * k] = (uint32_t)(s.adler[0] % PNG_ADLER);
         a.adler[2u * k + 1u] = (uint32_t)(s.adler[1] % PNG_ADLER);
-        if (!fits) *a.status = PNG_STATUS_OVERFLOW;
+        if (!fits) *a.status = CS_STATUS_OVERFLOW;
     }
 }
 
 // ---- the scan: thread t owns chunks [t run, (t + 1) run)
-__global__ void __launch_bounds__(PNG_SCAN_THREADS) png_scan_kernel(PngArgs a) {
-    __shared__ uint32_t sums[PNG_SCAN_THREADS];
-    __shared__ uint32_t ad_a[PNG_SCAN_THREADS], ad_b[PNG_SCAN_THREADS], ad_n[PNG_SCAN_THREADS];
+__global__ void __launch_bounds__(CS_SCAN_THREADS) png_scan_kernel(PngArgs a) {
+    __shared__ uint32_t sums[CS_SCAN_THREADS];
+    __shared__ uint32_t ad_a[CS_SCAN_THREADS], ad_b[CS_SCAN_THREADS], ad_n[CS_SCAN_THREADS];
     const uint32_t t = threadIdx.x;
-    const uint32_t run = (a.chunks + PNG_SCAN_THREADS - 1u) / PNG_SCAN_THREADS, lo = t * run;
-    uint32_t sum = 0u, count = 0u;
-    unsigned long long A = 0ull, B = 0ull;      // the Adler state behind this thread's chunks, from (0, 0)
-    for (uint32_t i = lo; i < lo + run && i < a.chunks; ++i) {
-        sum += a.len[i];
+    const uint32_t run = cs_scan_run(a), lo = t * run;
+    cs_scan_sum(a, sums, (int)t);
+    unsigned long long A = 0ull, B = 0ull, count = 0ull;      // the Adler state behind this thread's chunks, from (0, 0), and their filtered bytes
+    for (uint32_t i = lo; i < lo + run && i < a.count; ++i) {
         const uint32_t n = a.total - i * (uint32_t)a.chunk_bytes < (uint32_t)a.chunk_bytes ? a.total - i * (uint32_t)a.chunk_bytes : (uint32_t)a.chunk_bytes;
-        B = (B + (unsigned long long)n * A + a.adler[2u * i + 1u]) % PNG_ADLER;
-        A = (A + a.adler[2u * i]) % PNG_ADLER;
+        png_adler_join(&A, &B, n, a.adler[2u * i], a.adler[2u * i + 1u]);
         count += n;
     }
-    sums[t] = sum; ad_a[t] = (uint32_t)A; ad_b[t] = (uint32_t)B; ad_n[t] = count;
-    if (t < a.front) a.out[PNG_HEADER_WORD + t] = a.front_bytes[t];
+    ad_a[t] = (uint32_t)A; ad_b[t] = (uint32_t)B; ad_n[t] = (uint32_t)count;
+    if (t < a.front) a.out[CS_WORD_BYTES + t] = a.front_bytes[t];
     __syncthreads();
-    if (t == 0u) {
-        unsigned long long at = a.front;
+    const unsigned long long length = cs_scan_total(a, sums, (int)t);
+    if (t == 0u && !*a.status) {      // the trailer, behind the last piece: the threads' Adler states joined from (1, 0)
         A = 1ull; B = 0ull;
-        for (uint32_t j = 0u; j < PNG_SCAN_THREADS; ++j) {
-            const uint32_t v = sums[j];
-            sums[j] = (uint32_t)(at < 0xffffffffull ? at : 0xffffffffull);
-            at += v;
-            B = (B + (unsigned long long)ad_n[j] * A + ad_b[j]) % PNG_ADLER;
-            A = (A + ad_a[j]) % PNG_ADLER;
-        }
-        uint32_t status = *a.status;
-        unsigned long long length = at + PNG_TRAILER_BYTES;
-        if (length > (unsigned long long)a.capacity) { status |= PNG_STATUS_OVERFLOW; }
-        if (status) length = a.front;
-        else {
-            const uint32_t adler = (uint32_t)((B << 16) | A);
-            uint8_t tr[PNG_TRAILER_BYTES] = {0, 0, 0, 4, 'I', 'D', 'A', 'T', (uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler, 0, 0, 0, 0,
-                                             0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
-            uint32_t r = 0xffffffffu;
-            for (int i = 4; i < 12; ++i) r = a.tab->crc[(r ^ tr[i]) & 0xffu] ^ (r >> 8);
-            r ^= 0xffffffffu;
-            tr[12] = (uint8_t)(r >> 24); tr[13] = (uint8_t)(r >> 16); tr[14] = (uint8_t)(r >> 8); tr[15] = (uint8_t)r;
-            for (int i = 0; i < PNG_TRAILER_BYTES; ++i) a.out[PNG_HEADER_WORD + at + (unsigned long long)i] = tr[i];
-        }
-        uint32_t* head = reinterpret_cast<uint32_t*>(a.out);
-        head[0] = (uint32_t)length; head[1] = (uint32_t)(length >> 32); head[2] = status; head[3] = a.chunks;
-        if (status) *a.status = status;
+        for (uint32_t j = 0u; j < CS_SCAN_THREADS; ++j) png_adler_join(&A, &B, ad_n[j], ad_a[j], ad_b[j]);
+        const uint32_t adler = (uint32_t)((B << 16) | A);
+        uint8_t tr[PNG_TRAILER_BYTES] = {0, 0, 0, 4, 'I', 'D', 'A', 'T', (uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler, 0, 0, 0, 0,
+                                         0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xae, 0x42, 0x60, 0x82};
+        uint32_t r = 0xffffffffu;
+        for (int i = 4; i < 12; ++i) r = a.tab->crc[(r ^ tr[i]) & 0xffu] ^ (r >> 8);
+        r ^= 0xffffffffu;
+        tr[12] = (uint8_t)(r >> 24); tr[13] = (uint8_t)(r >> 16); tr[14] = (uint8_t)(r >> 8); tr[15] = (uint8_t)r;
+        for (int i = 0; i < PNG_TRAILER_BYTES; ++i) a.out[CS_WORD_BYTES + length - PNG_TRAILER_BYTES + (unsigned long long)i] = tr[i];
     }
     __syncthreads();
-    uint32_t at = sums[t];
-    for (uint32_t i = lo; i < lo + run && i < a.chunks; ++i) { a.offset[i] = at; at += a.len[i]; }
+    cs_scan_offsets(a, sums, (int)t);
 }
 
 // ---- the compaction: the workgroup of chunk k
-__global__ void __launch_bounds__(256) png_compact_kernel(PngArgs a) {
-    const uint32_t k = blockIdx.x, t = threadIdx.x;
-    if (k >= a.chunks || *a.status) return;      // a failed conversion leaves the front alone behind a length of `front`
-    const uint32_t n = a.len[k], at = a.offset[k];
-    if ((unsigned long long)at + n + PNG_TRAILER_BYTES > (unsigned long long)a.capacity || n > a.slot_bytes) return;      // (the scan has refused such a total already)
-    const uint8_t* src = a.slots + (size_t)k * (size_t)a.slot_bytes;
-    uint8_t* dst = a.out + PNG_HEADER_WORD + at;
-    for (uint32_t i = t; i < n; i += 256u) dst[i] = src[i];
-}
+__global__ void __launch_bounds__(256) png_compact_kernel(PngArgs a) { cs_compact(a, blockIdx.x, (int)threadIdx.x, 256); }

@@ -12,7 +12,6 @@
 #define PNG_HD
 #endif
 
-#define PNG_HEADER_WORD 16           // bytes in front of the file on the device: uint64 length, uint32 status, uint32 chunks
 #define PNG_FRONT_MAX 64             // the front is 33 bytes (signature + IHDR), 49 with cICP
 #define PNG_TRAILER_BYTES 28         // the IDAT that holds the Adler-32 (16) and IEND (12)
 #define PNG_CHUNK_OVERHEAD 24        // per deflate chunk: IDAT length, type, CRC (12), CMF / FLG (2, the first only), a stored block's header (5), the sync block (5)
@@ -34,6 +33,11 @@ static inline PNG_HD uint32_t png_gf2_times(const uint32_t* mat, uint32_t vec) {
     for (int i = 0; vec; vec >>= 1, ++i)
         if (vec & 1u) sum ^= mat[i];
     return sum;
+}
+// The Adler-32 of a concatenation: (A, B) the state behind the bytes so far, (a, b) the sums of the next n < 2^28 bytes from (0, 0), all below 65521.
+static inline PNG_HD void png_adler_join(unsigned long long* A, unsigned long long* B, unsigned long long n, uint32_t a, uint32_t b) {
+    *B = (*B + n * *A + b) % PNG_ADLER;
+    *A = (*A + a) % PNG_ADLER;
 }
 static inline void png_gf2_square(uint32_t* square, const uint32_t* mat) {
     for (int i = 0; i < 32; ++i) square[i] = png_gf2_times(mat, mat[i]);

@@ -121,6 +121,68 @@ class _FetchRing:
         return self.view_ref is not None and self.view_ref() is not None
 
 
+class _CodedFetch:
+    """One coded output's fetches (fetch_jpeg, fetch_png; csrc/de_fetch.h's CodedOut is the native side): a whole file whose length the device
+    decides, as bytes or as a view of the library's pinned buffer, synchronous or lagged through the output's ring of four.  Parametrised by the
+    output: its library functions, its noun, and the names of its two attributes of the Renderer — the lagged fetches in flight (`_jp_in_flight`,
+    `_pn_in_flight`) and a weak reference to the last view handed out (close() refuses while it is referenced).  The Renderer is passed in, not kept."""
+
+    def __init__(self, lib, stem, noun, prefix):
+        self._view, self._begin, self._end = (getattr(lib, "de_fetch_%s_%s" % (stem, n)) for n in ("view", "begin", "end"))
+        self._render_to = getattr(lib, "de_render_to_" + stem)
+        self.stem, self._noun, self._counter, self._ref = stem, noun, prefix + "_in_flight", prefix + "_view_ref"
+
+    def in_flight(self, r, change=0):
+        setattr(r, self._counter, getattr(r, self._counter) + change)
+        return getattr(r, self._counter)
+
+    def referenced(self, r):
+        ref = getattr(r, self._ref)
+        return ref is not None and ref() is not None
+
+    def view(self, r, ptr, n, copy):
+        if copy:
+            return ctypes.string_at(ptr, n)
+        view = np.ctypeslib.as_array(ptr, shape=(n,)).view(_StagingView)
+        view.flags.writeable = False
+        view._owner = r
+        setattr(r, self._ref, weakref.ref(view))
+        return memoryview(view)
+
+    def end(self, r, copy):
+        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        self.in_flight(r, -1)
+        check(self._end(r._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return self.view(r, ptr, int(n.value), copy)
+
+    def fetch(self, r, copy, lag):
+        if not r._textures_copied:
+            r.copy_textures()
+        if lag not in (0, 1, 2, 3):
+            raise ValueError("lag must be 0 ... 3")
+        if lag:
+            check(self._begin(r._h))
+            return None if self.in_flight(r, +1) <= lag else self.end(r, copy)
+        if self.in_flight(r):
+            raise RuntimeError("lagged %s fetches are in flight: fetch_pending_%s() first" % (self._noun, self.stem))
+        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
+        check(self._view(r._h, ctypes.byref(ptr), ctypes.byref(n)))
+        return self.view(r, ptr, int(n.value), copy)
+
+    def pending(self, r, copy, all_images):
+        imgs = []
+        while self.in_flight(r) > 0:
+            imgs.append(self.end(r, copy or all_images))
+        return imgs if all_images else (imgs[-1] if imgs else None)
+
+    def render_to(self, r):
+        if not r._textures_copied:
+            r.copy_textures()
+        p, n = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._render_to(r._h, ctypes.byref(p), ctypes.byref(n)))
+        return p.value, n.value
+
+
 class Renderer:
     """GPU implementation of the reference `Renderer` (renderer.py:15-401).
 
@@ -152,6 +214,7 @@ class Renderer:
                                       "lagged pixel fetches are in flight: fetch_pending(pixels=True) first")
         self._vd_ring = _FetchRing(self._lib, "de_fetch_videoframe", "de_fetch_video", ctypes.c_uint8, Renderer._vd_bytes, "fetch_video",
                                    "lagged video fetches are in flight: fetch_pending(video=True) first")
+        self._jp_coded, self._pn_coded = _CodedFetch(self._lib, "jpeg", "JPEG", "_jp"), _CodedFetch(self._lib, "png", "PNG", "_pn")
         self._jp_in_flight, self._jp_view_ref = 0, None      # the lagged fetch_jpeg() calls; the last view handed out
         self._pn_in_flight, self._pn_view_ref, self._png_set = 0, None, False      # the same for fetch_png(); set_png() has been called
         check(self._lib.de_create(int(device), self.image_res[0], self.image_res[1], ctypes.byref(self._h)))
@@ -201,10 +264,9 @@ class Renderer:
             for ring in (self._image_ring, self._pixel_ring, self._vd_ring):
                 if ring.referenced():
                     raise RuntimeError("a %s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % ring.name)
-            if self._jp_view_ref is not None and self._jp_view_ref() is not None:
-                raise RuntimeError("a fetch_jpeg(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
-            if self._pn_view_ref is not None and self._pn_view_ref() is not None:
-                raise RuntimeError("a fetch_png(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()")
+            for coded in (self._jp_coded, self._pn_coded):
+                if coded.referenced(self):
+                    raise RuntimeError("a fetch_%s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % coded.stem)
             check(self._lib.de_destroy(self._h))
             self._h = ctypes.c_void_p()
             self._lender = None
@@ -980,56 +1042,22 @@ class Renderer:
         check(self._lib.de_jpeg_capacity(self._h, ctypes.byref(n)))
         return dict(quality=int(s.quality), restart=int(s.restart_mcus), size=self.output_size(), capacity=int(n.value))
 
-    def _jp_view(self, ptr, n, copy):
-        if copy:
-            return ctypes.string_at(ptr, n)
-        view = np.ctypeslib.as_array(ptr, shape=(n,)).view(_StagingView)
-        view.flags.writeable = False
-        view._owner = self
-        self._jp_view_ref = weakref.ref(view)
-        return memoryview(view)
-
-    def _jp_end(self, copy):
-        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
-        self._jp_in_flight -= 1
-        check(self._lib.de_fetch_jpeg_end(self._h, ctypes.byref(ptr), ctypes.byref(n)))
-        return self._jp_view(ptr, int(n.value), copy)
-
     def fetch_jpeg(self, copy=True, lag=0):
         """The displayed image as one complete JPEG file: `bytes` that open(path, "wb").write() or a socket takes as they are.  Only the file's own
         bytes cross the link.  copy=False: a read-only memoryview of the library's pinned buffer, valid until the next fetch_jpeg call (lag = 0) or
         until the ring comes round (lag > 0).  lag=1, 2 or 3: pipelined like fetch_video(lag=...), through a ring of its own — the call returns the
         file of the lag-th previous call (None until there is one); fetch_pending_jpeg() hands out the rest."""
-        if not self._textures_copied:
-            self.copy_textures()
-        if lag not in (0, 1, 2, 3):
-            raise ValueError("lag must be 0 ... 3")
-        if lag:
-            check(self._lib.de_fetch_jpeg_begin(self._h))
-            self._jp_in_flight += 1
-            return None if self._jp_in_flight <= lag else self._jp_end(copy)
-        if self._jp_in_flight:
-            raise RuntimeError("lagged JPEG fetches are in flight: fetch_pending_jpeg() first")
-        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
-        check(self._lib.de_fetch_jpeg_view(self._h, ctypes.byref(ptr), ctypes.byref(n)))
-        return self._jp_view(ptr, int(n.value), copy)
+        return self._jp_coded.fetch(self, copy, lag)
 
     def fetch_pending_jpeg(self, copy=True, all_images=False):
         """fetch_pending() for the lagged fetch_jpeg() calls and their ring: wait for the JPEG fetches still in flight and return the newest file
         (None when there is none) — bytes, or a memoryview with copy=False; all_images=True: the list of all of them, oldest first (bytes)."""
-        imgs = []
-        while self._jp_in_flight > 0:
-            imgs.append(self._jp_end(copy or all_images))
-        return imgs if all_images else (imgs[-1] if imgs else None)
+        return self._jp_coded.pending(self, copy, all_images)
 
     def render_to_jpeg(self):
         """Run the display and the encoder and leave the stream on the device (de_render_to_jpeg); returns (address of the stream, address of its
         uint64 length).  Nothing is waited for."""
-        if not self._textures_copied:
-            self.copy_textures()
-        p, n = ctypes.c_void_p(), ctypes.c_void_p()
-        check(self._lib.de_render_to_jpeg(self._h, ctypes.byref(p), ctypes.byref(n)))
-        return p.value, n.value
+        return self._jp_coded.render_to(self)
 
     def debug_jpeg(self, image, quality=90, restart=None):
         """The encoder once on a given (W, H, 3) float32 image (de_debug_jpeg), W and H even but free of this renderer's size; returns the file as
@@ -1079,56 +1107,22 @@ class Renderer:
         """True once set_png() has been called: EarthViewer.save("x.png") then writes the GPU's file."""
         return self._png_set
 
-    def _pn_view(self, ptr, n, copy):
-        if copy:
-            return ctypes.string_at(ptr, n)
-        view = np.ctypeslib.as_array(ptr, shape=(n,)).view(_StagingView)
-        view.flags.writeable = False
-        view._owner = self
-        self._pn_view_ref = weakref.ref(view)
-        return memoryview(view)
-
-    def _pn_end(self, copy):
-        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
-        self._pn_in_flight -= 1
-        check(self._lib.de_fetch_png_end(self._h, ctypes.byref(ptr), ctypes.byref(n)))
-        return self._pn_view(ptr, int(n.value), copy)
-
     def fetch_png(self, copy=True, lag=0):
         """The displayed image as one complete PNG file: `bytes` that open(path, "wb").write() takes as they are.  Only the file's own bytes cross
         the link.  copy=False: a read-only memoryview of the library's pinned buffer, valid until the next fetch_png call (lag = 0) or until the
         ring comes round (lag > 0).  lag=1, 2 or 3: pipelined like fetch_jpeg(lag=...), through a ring of its own — the call returns the file of
         the lag-th previous call (None until there is one); fetch_pending_png() hands out the rest."""
-        if not self._textures_copied:
-            self.copy_textures()
-        if lag not in (0, 1, 2, 3):
-            raise ValueError("lag must be 0 ... 3")
-        if lag:
-            check(self._lib.de_fetch_png_begin(self._h))
-            self._pn_in_flight += 1
-            return None if self._pn_in_flight <= lag else self._pn_end(copy)
-        if self._pn_in_flight:
-            raise RuntimeError("lagged PNG fetches are in flight: fetch_pending_png() first")
-        ptr, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_uint64()
-        check(self._lib.de_fetch_png_view(self._h, ctypes.byref(ptr), ctypes.byref(n)))
-        return self._pn_view(ptr, int(n.value), copy)
+        return self._pn_coded.fetch(self, copy, lag)
 
     def fetch_pending_png(self, copy=True, all_images=False):
         """fetch_pending() for the lagged fetch_png() calls and their ring: wait for the PNG fetches still in flight and return the newest file
         (None when there is none) — bytes, or a memoryview with copy=False; all_images=True: the list of all of them, oldest first (bytes)."""
-        imgs = []
-        while self._pn_in_flight > 0:
-            imgs.append(self._pn_end(copy or all_images))
-        return imgs if all_images else (imgs[-1] if imgs else None)
+        return self._pn_coded.pending(self, copy, all_images)
 
     def render_to_png(self):
         """Run the display, the pack and the encoder and leave the file on the device (de_render_to_png); returns (address of the file, address of
         its uint64 length).  Nothing is waited for."""
-        if not self._textures_copied:
-            self.copy_textures()
-        p, n = ctypes.c_void_p(), ctypes.c_void_p()
-        check(self._lib.de_render_to_png(self._h, ctypes.byref(p), ctypes.byref(n)))
-        return p.value, n.value
+        return self._pn_coded.render_to(self)
 
     def debug_png(self, pixels, filter="adaptive", chunk_bytes=None, cicp=None):
         """The encoder once on given packed pixels (de_debug_png): (H, W, 3 | 4) uint8 or (H, W, 3) uint16, rows top-down, of any size; returns the

@@ -39,14 +39,14 @@ static std::vector<uint8_t> run(const std::vector<float>& image, int W, int H, i
     std::vector<unsigned long long> mask(g.blocks, ~0ull);
     std::vector<uint32_t> slots(g.intervals * g.slot_bytes / 4, 0xA5A5A5A5u);
     std::vector<uint32_t> words(2 * g.intervals + 4, 0xA5A5A5A5u);
-    std::vector<uint32_t> out((JP_HEADER_WORD + g.capacity + 15) / 16 * 4, 0xA5A5A5A5u);
+    std::vector<uint32_t> out((CS_WORD_BYTES + g.capacity + 15) / 16 * 4, 0xA5A5A5A5u);
     JpegArgs a;
     a.planes = planes.data(); a.tab = &tab; a.coef = coef.data(); a.mask = mask.data(); a.slots = (uint8_t*)slots.data();
     a.len = words.data(); a.offset = words.data() + g.intervals; a.status = words.data() + 2 * g.intervals; a.out = (uint8_t*)out.data();
     a.W = W; a.H = H; a.mcus_x = g.mcus_x; a.restart = g.restart;
-    a.blocks = (uint32_t)g.blocks; a.mcus = (uint32_t)g.mcus; a.intervals = (uint32_t)g.intervals; a.slot_bytes = (uint32_t)g.slot_bytes;
-    a.framing = JP_FRAMING_BYTES; a.capacity = (uint32_t)g.capacity;
-    if (jp_write_framing(tab, W, H, restart, a.out + JP_HEADER_WORD) != JP_FRAMING_BYTES) { fprintf(stderr, "the framing is not JP_FRAMING_BYTES long\n"); exit(1); }
+    a.blocks = (uint32_t)g.blocks; a.mcus = (uint32_t)g.mcus; a.count = (uint32_t)g.intervals; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.front = JP_FRAMING_BYTES; a.extra = 2u; a.trailer = 0u; a.capacity = (uint32_t)g.capacity;
+    if (jp_write_framing(tab, W, H, restart, a.out + CS_WORD_BYTES) != JP_FRAMING_BYTES) { fprintf(stderr, "the framing is not JP_FRAMING_BYTES long\n"); exit(1); }
     for (uint32_t wg = 0; wg < (a.blocks + JP_WG_BLOCKS - 1) / JP_WG_BLOCKS; ++wg) {
         std::vector<JpegTile> lds(1);
         memset(&lds[0], 0xA5, sizeof(JpegTile));
@@ -56,18 +56,19 @@ static std::vector<uint8_t> run(const std::vector<float>& image, int W, int H, i
         for (int t = 0; t < 256; ++t) jp_store(a, lds[0], t, wg);
         for (int t = 0; t < 256; ++t) jp_mask(a, lds[0], t, wg);
     }
-    for (uint32_t i = 0; i < (a.intervals + 63) / 64 * 64; ++i) jp_encode_interval(a, i);
-    std::vector<uint32_t> sums(JP_SCAN_THREADS, 0xA5A5A5A5u);
-    for (int t = 0; t < JP_SCAN_THREADS; ++t) jp_scan_sum(a, sums.data(), t);
-    for (int t = 0; t < JP_SCAN_THREADS; ++t) jp_scan_total(a, sums.data(), t);
-    for (int t = 0; t < JP_SCAN_THREADS; ++t) jp_scan_offsets(a, sums.data(), t);
-    for (uint32_t i = 0; i < a.intervals; ++i)
-        for (int t = 0; t < 256; ++t) jp_compact(a, i, t, 256);
+    for (uint32_t i = 0; i < (a.count + 63) / 64 * 64; ++i) jp_encode_interval(a, i);
+    std::vector<uint32_t> sums(CS_SCAN_THREADS, 0xA5A5A5A5u);
+    for (int t = 0; t < CS_SCAN_THREADS; ++t) cs_scan_sum(a, sums.data(), t);
+    for (int t = 0; t < CS_SCAN_THREADS; ++t) cs_scan_total(a, sums.data(), t);
+    for (int t = 0; t < CS_SCAN_THREADS; ++t) cs_scan_offsets(a, sums.data(), t);
+    for (uint32_t i = 0; i < a.count; ++i)
+        for (int t = 0; t < 256; ++t)
+            if (cs_compact(a, i, t, 256) && t == 0) jp_marker(a, i);
     uint64_t len;
     memcpy(&len, out.data(), 8);
     *status = out[2];
     if (len > g.capacity) { fprintf(stderr, "the length passes the capacity\n"); exit(1); }
-    const uint8_t* s = (const uint8_t*)out.data() + JP_HEADER_WORD;
+    const uint8_t* s = (const uint8_t*)out.data() + CS_WORD_BYTES;
     return std::vector<uint8_t>(s, s + len);
 }
 
@@ -92,7 +93,7 @@ int main(int argc, char** argv) {
     if (argc != 1) return 2;
     static const int sizes[][2] = {{2, 2}, {16, 16}, {34, 18}, {48, 40}, {160, 16}, {64, 32}, {208, 120}};
     static const int qualities[] = {1, 50, 90, 100}, restarts[] = {1, 3, 8, 65535};
-    // More than JP_SCAN_THREADS intervals, where a thread of the scan owns two of them (528 x 528: 1089 intervals, the last owner has one, 479 threads none)
+    // More than CS_SCAN_THREADS intervals, where a thread of the scan owns two of them (528 x 528: 1089 intervals, the last owner has one, 479 threads none)
     // or three (544 x 1040: 2210 intervals, the last owner has two).  Restart 1 and one quality only: the sweep stays about as long as it was.
     static const int large[][2] = {{528, 528}, {544, 1040}};
     struct Case { int W, H, quality, restart; };
@@ -102,7 +103,7 @@ int main(int argc, char** argv) {
             for (int restart : restarts) cases.push_back({sz[0], sz[1], quality, restart});
     for (const auto& sz : large) {
         const JpegGeometry g = jp_geometry(sz[0], sz[1], 1);
-        const size_t chunk = (g.intervals + JP_SCAN_THREADS - 1) / JP_SCAN_THREADS;
+        const size_t chunk = (g.intervals + CS_SCAN_THREADS - 1) / CS_SCAN_THREADS;
         if (chunk < 2 || g.intervals % chunk == 0) { fprintf(stderr, "%d x %d: no ragged chunk of two intervals or more per thread\n", sz[0], sz[1]); return 1; }
         cases.push_back({sz[0], sz[1], 90, 1});
     }

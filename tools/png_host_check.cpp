@@ -4,7 +4,8 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/png_host_check.cpp -o png_host_check && ./png_host_check
 // Checks, each against an independent statement: the CRC of "123456789" is 0xCBF43926; shifting a register by n zero bytes with the operators equals
 // feeding n zero bytes through the byte table, for every n that sets one or several bits below 2^17; a CRC computed in pieces and combined the way
-// the deflate kernel combines them equals the CRC computed in one go; every match length 3 ... 258 lies in its code's range; the capacity is
+// the deflate kernel combines them equals the CRC computed in one go; Adler partials joined (png_adler_join) chunk by chunk and in the scan kernel's two
+// levels equal the serial Adler-32; every match length 3 ... 258 lies in its code's range; the capacity is
 // front + N + 24 per chunk + 28 and every slot holds a stored chunk with its overhead; the front has 33 or 49 bytes and its chunks' CRCs verify.
 #include <stdint.h>
 #include <stdio.h>
@@ -55,6 +56,35 @@ int main() {
         CHECK((combined ^ 0xffffffffu) == png_crc(t, data.data(), total), "the CRC of %zu bytes in pieces", total);
     }
 
+    // the Adler join: the chunks' partials taken from (0, 0) as the deflate kernel takes them, joined one by one from (1, 0), and joined in two levels
+    // as the scan kernel does (a run of chunks per thread from (0, 0), then the 1024 threads' states from (1, 0)), against the serial Adler-32
+    {
+        std::vector<uint8_t> bytes(2500u * 1024u + 77u);      // at 1024 per chunk: 2501 chunks, three per thread of the scan, the last owner has two
+        for (uint8_t& b : bytes) { lcg = lcg * 1664525u + 1013904223u; b = (lcg >> 28) == 0u ? 0xffu : (uint8_t)(lcg >> 16); }
+        uint32_t sa = 1u, sb = 0u;
+        for (uint8_t b : bytes) { sa = (sa + b) % PNG_ADLER; sb = (sb + sa) % PNG_ADLER; }
+        for (size_t chunk : {(size_t)1024, (size_t)16384, (size_t)65535}) {
+            const size_t chunks = (bytes.size() + chunk - 1) / chunk, threads = 1024, run = (chunks + threads - 1) / threads;
+            std::vector<uint32_t> pa(chunks), pb(chunks), pn(chunks);
+            for (size_t k = 0; k < chunks; ++k) {
+                const size_t base = k * chunk, n = bytes.size() - base < chunk ? bytes.size() - base : chunk;
+                unsigned long long a = 0, b = 0;
+                for (size_t i = 0; i < n; ++i) { a += bytes[base + i]; b += (unsigned long long)(n - i) * bytes[base + i]; }
+                pa[k] = (uint32_t)(a % PNG_ADLER); pb[k] = (uint32_t)(b % PNG_ADLER); pn[k] = (uint32_t)n;
+            }
+            unsigned long long A = 1, B = 0;
+            for (size_t k = 0; k < chunks; ++k) png_adler_join(&A, &B, pn[k], pa[k], pb[k]);
+            CHECK(A == sa && B == sb, "the Adler-32 of chunks of %zu joined one by one", chunk);
+            A = 1; B = 0;
+            for (size_t t = 0; t < threads; ++t) {
+                unsigned long long ta = 0, tb = 0, tn = 0;
+                for (size_t k = t * run; k < (t + 1) * run && k < chunks; ++k) { png_adler_join(&ta, &tb, pn[k], pa[k], pb[k]); tn += pn[k]; }
+                png_adler_join(&A, &B, tn, (uint32_t)ta, (uint32_t)tb);
+            }
+            CHECK(A == sa && B == sb, "the Adler-32 of chunks of %zu joined in the scan's groups of %zu", chunk, run);
+        }
+    }
+
     // deflate's length codes
     for (int L = 3; L <= 258; ++L) {
         const int i = t.len_code[L - 3];
@@ -85,6 +115,6 @@ int main() {
             CHECK(at == n, "the front's chunks end at its length");
         }
     if (failures) { fprintf(stderr, "%d checks failed\n", failures); return 1; }
-    printf("png_host_check: tables, CRC combination, length codes, geometry and front are clean\n");
+    printf("png_host_check: tables, CRC combination, Adler join, length codes, geometry and front are clean\n");
     return 0;
 }
