@@ -116,6 +116,12 @@ class DePng(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("source", ctypes.c_int32), ("filter", ctypes.c_int32), ("chunk_bytes", ctypes.c_int32)]
 
 
+class DeExr(ctypes.Structure):
+    """`de_exr` (include/digital_earth_exr.h): the source, the pixel type, the compression, the chunk size and the scale of the OpenEXR output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("source", ctypes.c_int32), ("pixel_type", ctypes.c_int32), ("compression", ctypes.c_int32),
+                ("chunk_bytes", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
 DE_ERR_INVALID = -1
 DE_ERR_STATE = -4
 DE_ERR_INTERNAL = -6
@@ -123,6 +129,10 @@ JPEG_DEFAULT_RESTART = 2      # DE_JPEG_DEFAULT_RESTART of include/digital_earth
 PNG_DEFAULT_CHUNK = 32768     # DE_PNG_DEFAULT_CHUNK of include/digital_earth_png.h
 PNG_SOURCES = ("pixels", "hdr_pixels")                                    # DE_PNG_SOURCE_*
 PNG_FILTERS = ("none", "sub", "up", "average", "paeth", "adaptive")       # DE_PNG_FILTER_*
+EXR_DEFAULT_CHUNK = 32768     # DE_EXR_DEFAULT_CHUNK of include/digital_earth_exr.h
+EXR_SOURCES = ("mean", "denoised", "history", "bloom", "local_exposure")  # DE_EXR_SOURCE_*
+EXR_PIXEL_TYPES = {"half": 1, "float": 2}                                 # DE_EXR_PIXEL_*: the file's own numbers
+EXR_COMPRESSIONS = {"none": 0, "zips": 2, "zip": 3}                       # DE_EXR_COMPRESSION_*: the file's own numbers
 
 DE_FLAG_FIXED_WAVELENGTH = 1 << 0
 DE_FLAG_CLAMP_SAMPLER = 1 << 1
@@ -312,6 +322,19 @@ PNG_SYMBOLS = {
     "de_debug_png": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePng), _P, ctypes.c_uint64, _U64P]),
     "de_debug_png_framing": (ctypes.c_int, [ctypes.POINTER(DePng), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_uint64, _U64P, _U64P]),
 }
+# OpenEXR output: include/digital_earth_exr.h (same library, additions only; not part of the binder's header)
+EXR_SYMBOLS = {
+    "de_set_exr": (ctypes.c_int, [_P, ctypes.POINTER(DeExr)]),
+    "de_get_exr": (ctypes.c_int, [_P, ctypes.POINTER(DeExr)]),
+    "de_exr_capacity": (ctypes.c_int, [_P, _U64P]),
+    "de_render_to_exr": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_exr": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _U64P]),
+    "de_fetch_exr_view": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_fetch_exr_begin": (ctypes.c_int, [_P]),
+    "de_fetch_exr_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_debug_exr": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeExr), _P, ctypes.c_uint64, _U64P]),
+    "de_debug_exr_framing": (ctypes.c_int, [ctypes.POINTER(DeExr), ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint64, _U64P, _U64P]),
+}
 
 # look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
 LOOK_SYMBOLS = {
@@ -399,7 +422,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -1,10 +1,11 @@
-// coded_stream.h — the tail of every coded output (the JPEG stream, the PNG file), plain C++ behind DE_DEV with no HIP in it: independent
-// PIECES (restart intervals, deflate chunks) have been coded into fixed-size slots, piece i into slots[i slot_bytes ..) with its length in len[i].  One
+// coded_stream.h — the tail of every coded output (the JPEG stream, the PNG file, the OpenEXR file), plain C++ behind DE_DEV with no
+// HIP in it: independent PIECES (restart intervals, deflate chunks) have been coded into fixed-size slots, piece i into slots[i slot_bytes ..) with its length in len[i].  One
 // workgroup of CS_SCAN_THREADS takes the exclusive sum of (len[i] + extra) from `front` on — thread t owns the pieces [t run, (t + 1) run), the 1024 sums
 // are taken serially by thread 0 — and writes the 16-byte word in front of the stream; a workgroup per piece then moves each slot to offset[i].
 // THE FAILURE RULE: any non-zero status — raised by a coder, or here where front + sum(len + extra) + trailer passes the capacity — means a length of
-// `front` and no piece moved.  Every load and store is range-checked; no atomics (whoever stores to the status word stores a failure, and the scan
-// keeps what it finds there), no inline assembly.  tools/coded_stream_host_check.cpp runs these leaves under the address and UB sanitizers.
+// `front` and no piece moved.  A piece may lie elsewhere than in its slot (an OpenEXR block that is written raw): alt_at[i] then says where in
+// `alt`.  Every load and store is range-checked; no atomics (whoever stores to the status word stores a failure, and the scan keeps what it finds
+// there), no inline assembly.  tools/coded_stream_host_check.cpp runs these leaves under the address and UB sanitizers.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -13,6 +14,7 @@
 #define CS_STATUS_RANGE 1u           // a value outside the range a coder's worst case assumes
 #define CS_STATUS_OVERFLOW 2u        // a store past a slot or past the stream's capacity
 #define CS_SCAN_THREADS 1024
+#define CS_NO_ALT 0xffffffffu        // alt_at[i]: piece i lies in its slot
 
 struct CodedTail {
     uint8_t* slots;             // [count][slot_bytes]
@@ -25,6 +27,9 @@ struct CodedTail {
     uint32_t extra;             // bytes the compaction's caller puts behind every piece (JPEG's marker: 2; PNG: 0)
     uint32_t trailer;           // bytes the scan kernel puts behind the last piece (PNG's Adler-32 IDAT and IEND: 28; JPEG: 0)
     uint32_t capacity;          // of the stream, without the 16-byte word
+    const uint8_t* alt = nullptr;         // where pieces lie that are not in their slots: piece i at alt[alt_at[i] ..) unless alt_at[i] is CS_NO_ALT
+    const uint32_t* alt_at = nullptr;     // [count]; null with alt (JPEG, PNG): every piece lies in its slot
+    uint32_t alt_bytes = 0;               // of `alt`
 };
 
 // ---- the word, written on the device and read on the host
@@ -73,8 +78,10 @@ DE_DEV void cs_scan_offsets(const CodedTail& a, const uint32_t* sums, int t) {
 DE_DEV bool cs_compact(const CodedTail& a, uint32_t i, int t, int threads) {
     if (i >= a.count || *a.status) return false;      // the failure rule
     const uint32_t n = a.len[i], at = a.offset[i];
-    if ((unsigned long long)at + n + a.extra + a.trailer > (unsigned long long)a.capacity || n > a.slot_bytes) return false;      // (the scan has refused such a total already)
-    const uint8_t* src = a.slots + (size_t)i * (size_t)a.slot_bytes;
+    const uint32_t alt_at = a.alt ? a.alt_at[i] : CS_NO_ALT;
+    if ((unsigned long long)at + n + a.extra + a.trailer > (unsigned long long)a.capacity) return false;      // (the scan has refused such a total already)
+    if (alt_at == CS_NO_ALT ? n > a.slot_bytes : (unsigned long long)alt_at + n > (unsigned long long)a.alt_bytes) return false;
+    const uint8_t* src = alt_at == CS_NO_ALT ? a.slots + (size_t)i * (size_t)a.slot_bytes : a.alt + alt_at;
     uint8_t* dst = a.out + CS_WORD_BYTES + at;
     for (uint32_t k = (uint32_t)t; k < n; k += (uint32_t)threads) dst[k] = src[k];
     return true;

@@ -107,7 +107,7 @@ int de_destroy(de_ctx* c) {
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
     // events and streams; the memory is the members' (de_memory.h): `delete c` frees what this context owns and leaves what it borrows
-    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) ring_destroy_events(*r);
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring, &c->ex_coded.ring}) ring_destroy_events(*r);
 #ifdef DE_LEGACY_VARIANTS
     destroy_legacy_events(c);
 #endif
@@ -1525,6 +1525,97 @@ int de_debug_png_framing(const de_png* s, int W, int H, int channels, int depth,
         uint8_t front[PNG_FRONT_MAX];
         png_write_front(pn_host_tables(), g, cicp ? cicp : linear709, front);
         memcpy(out, front, g.front);
+    }
+    return DE_OK;
+}
+
+/* ---- OpenEXR output: include/digital_earth_exr.h (exr_kernels.hip, exr_tables.h) */
+int de_set_exr(de_ctx* c, const de_exr* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ex_settings_check(s); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->ex_coded.ring); if (rc) return rc; }
+    c->ex = *s;
+    c->ex_coded.guess = 0;
+    packed_reset(c->ex_coded.out);
+    return DE_OK;
+}
+int de_get_exr(de_ctx* c, de_exr* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->ex;
+    return DE_OK;
+}
+int de_exr_capacity(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ex_shape_check(c->W, c->H, c->ex.pixel_type); if (rc) return rc; }
+    *bytes = (uint64_t)ex_ctx_geometry(c).capacity;
+    return DE_OK;
+}
+int de_render_to_exr(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    int rc = ex_render(c, c->ex_coded.out.dev);
+    if (rc) return rc;
+    if (device_stream) *device_stream = c->ex_coded.out.dev + CS_WORD_BYTES;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->ex_coded.out.dev.get());
+    return DE_OK;
+}
+int de_fetch_exr_view(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = de_render_to_exr(c, nullptr, nullptr);
+    if (rc) return rc;
+    return coded_view(c, c->ex_coded, ex_length, host, len);
+}
+int de_fetch_exr(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    const void* host = nullptr;
+    int rc = de_fetch_exr_view(c, &host, len);
+    if (rc) return rc;
+    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the file (*len; de_exr_capacity bounds every frame)");
+}
+int de_fetch_exr_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = ex_shape_check(c->W, c->H, c->ex.pixel_type); if (rc) return rc; }
+    const ExrGeometry g = ex_ctx_geometry(c);
+    return coded_begin(c, c->ex_coded, g.front + g.raw / 2, g.capacity, [c](int k) { return ex_render(c, c->ex_coded.cell[k]); });      // the first: the front and half the raw bytes
+}
+int de_fetch_exr_end(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    return coded_end(c, c->ex_coded, ex_length, host, len);
+}
+/* the conversion once on a host-given image of any size, rows top-down.  Buffers of its own; the context's settings and streams are not touched. */
+int de_debug_exr(de_ctx* c, const float* image, int W, int H, const de_exr* s, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !image || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ex_settings_check(s); if (rc) return rc; }
+    { int rc = ex_shape_check(W, H, s->pixel_type); if (rc) return rc; }
+    const ExrGeometry g = ex_geometry(W, H, *s);
+    HIP_TRY(hipSetDevice(c->device));
+    de_ctx::ExrWork work;
+    Dev<float> d_image;
+    Dev<uint8_t> d_out;
+    const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
+    { int rc = ex_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_image.ensure(image_bytes));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
+    HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(ex_tables_upload(c->stream, work));
+    DisplaySrc src;
+    src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;      // x / 1.0f == x
+    { int rc = ex_launch(c->stream, work, g, src, false, s->scale, d_out, [] { return (int)DE_OK; }); if (rc) return rc; }
+    return coded_debug_out(c->stream, d_out, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+}
+/* the host's part alone: no device, no context */
+int de_debug_exr_framing(const de_exr* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
+    if (!s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ex_settings_check(s); if (rc) return rc; }
+    { int rc = ex_shape_check(W, H, s->pixel_type); if (rc) return rc; }
+    const ExrGeometry g = ex_geometry(W, H, *s);
+    if (len) *len = g.front;
+    if (capacity) *capacity = (uint64_t)g.capacity;
+    if (out || out_bytes) {
+        if (!out || out_bytes < g.front) return fail(DE_ERR_INVALID, "out_bytes is smaller than the front (*len)");
+        uint8_t front[EXR_FRONT_MAX];
+        exr_write_front(g, front);
+        memcpy(out, front, EXR_FRONT_FIXED);
+        memset((uint8_t*)out + EXR_FRONT_FIXED, 0, g.front - EXR_FRONT_FIXED);
     }
     return DE_OK;
 }

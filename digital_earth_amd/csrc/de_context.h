@@ -12,6 +12,7 @@
 #include "../../include/digital_earth_look.h"
 #include "../../include/digital_earth_jpeg.h"
 #include "../../include/digital_earth_png.h"
+#include "../../include/digital_earth_exr.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -45,6 +46,7 @@
 #include "look_kernels.hip"
 #include "jpeg_kernels.hip"
 #include "png_kernels.hip"
+#include "exr_kernels.hip"
 
 namespace {
 
@@ -96,7 +98,7 @@ struct PackedOut {                       // an output converted from the display
     Pinned<void> stage;                  // where a synchronous fetch lands
     uint32_t count = 0, last_phase = 0;  // conversions since the settings were set; the dither phase of the newest
 };
-struct CodedOut {                        // an output whose length the device decides (the JPEG stream, the PNG file): on the device, the 16-byte word, then the stream
+struct CodedOut {                        // an output whose length the device decides (the JPEG stream, the PNG file, the OpenEXR file): on the device, the 16-byte word, then the stream
     PackedOut out;                       // the stream of the synchronous fetches; its staging buffer grows to the longest frame fetched, not to the capacity
     FetchRing ring;                      // the lagged ones: a fetch copies a prefix at _begin and, should the frame be longer, the whole of it at _end ...
     Dev<uint8_t> cell[DE_FETCH_RING];    // ... from a device stream of its own per ring cell, which the next _begin does not touch
@@ -340,6 +342,15 @@ struct de_ctx {
     de_png pn = {(uint32_t)sizeof(de_png), DE_PNG_SOURCE_PIXELS, DE_PNG_FILTER_ADAPTIVE, DE_PNG_DEFAULT_CHUNK};
     PngWork pn_work;
     CodedOut pn_coded = {{"PNG"}, {"PNG", "de_fetch_png"}};
+    // OpenEXR output (include/digital_earth_exr.h).  Everything reaches the device on first use: the framed raw blocks, the predicted
+    // bytes, the chunks' slots and words of one conversion (ExrWork) and the files of ex_coded.  The front travels in the kernels' arguments.
+    struct ExrWork {              // what one conversion passes through; re-allocated when a frame needs more
+        Dev<uint8_t> raw, pred, slots; Dev<uint32_t> words; Dev<PngTables> tab;
+        bool tab_uploaded = false;
+    };
+    de_exr ex = {(uint32_t)sizeof(de_exr), DE_EXR_SOURCE_MEAN, DE_EXR_PIXEL_HALF, DE_EXR_COMPRESSION_ZIP, DE_EXR_DEFAULT_CHUNK, 1.0f};
+    ExrWork ex_work;
+    CodedOut ex_coded = {{"EXR"}, {"EXR", "de_fetch_exr"}};
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

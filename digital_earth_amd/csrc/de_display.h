@@ -734,4 +734,113 @@ int display_chain(de_ctx* c, DisplayStop stop, DisplayArgs* d, bool* per_tile) {
     if (c->lx_on) { rc = run_local_exposure(c, *d, *per_tile); if (rc) return rc; }
     return DE_OK;
 }
+
+// ---- OpenEXR output (include/digital_earth_exr.h, exr_kernels.hip, exr_tables.h): in FRONT of the display, behind the chain's stages
+int ex_settings_check(const de_exr* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_exr)) return fail(DE_ERR_INVALID, "de_exr.struct_bytes does not match this library's struct");
+    if (s->source < DE_EXR_SOURCE_MEAN || s->source > DE_EXR_SOURCE_LOCAL_EXPOSURE) return fail(DE_ERR_INVALID, "de_exr.source must be DE_EXR_SOURCE_MEAN, _DENOISED, _HISTORY, _BLOOM or _LOCAL_EXPOSURE");
+    if (s->pixel_type != DE_EXR_PIXEL_HALF && s->pixel_type != DE_EXR_PIXEL_FLOAT) return fail(DE_ERR_INVALID, "de_exr.pixel_type must be DE_EXR_PIXEL_HALF or _FLOAT");
+    if (s->compression != DE_EXR_COMPRESSION_NONE && s->compression != DE_EXR_COMPRESSION_ZIPS && s->compression != DE_EXR_COMPRESSION_ZIP)
+        return fail(DE_ERR_INVALID, "de_exr.compression must be DE_EXR_COMPRESSION_NONE, _ZIPS or _ZIP");
+    if (s->chunk_bytes < 1024 || s->chunk_bytes > 65535) return fail(DE_ERR_INVALID, "de_exr.chunk_bytes must lie in 1024 ... 65535");
+    if (!(s->scale > 0.0f) || !(s->scale < INFINITY)) return fail(DE_ERR_INVALID, "de_exr.scale must be finite and greater than 0");      // NaN fails the first
+    return DE_OK;
+}
+int ex_shape_check(int W, int H, int pixel_type) {      // what one conversion can take: the kernels count bytes in 32 bits
+    if (W <= 0 || H <= 0) return fail(DE_ERR_INVALID, "an EXR frame needs W, H >= 1");
+    if ((unsigned long long)W * (unsigned long long)H * 3ull * (pixel_type == DE_EXR_PIXEL_FLOAT ? 4ull : 2ull) > EXR_MAX_RAW)
+        return fail(DE_ERR_INVALID, "the EXR output takes at most 2^27 raw bytes, H W 3 bps");
+    return DE_OK;
+}
+ExrGeometry ex_geometry(int W, int H, const de_exr& s) { return exr_geometry(W, H, s.pixel_type, s.compression, s.chunk_bytes); }
+// The buffers of one conversion of geometry g; `words` holds len[pieces], offset[pieces], alt_at[pieces], adler[pieces][2] and the status word.
+int ex_work_ensure(de_ctx::ExrWork& w, const ExrGeometry& g) {
+    const PngTables* before = w.tab.get();
+    const bool zip = g.compression != DE_EXR_COMPRESSION_NONE;
+    int rc = w.raw.ensure(g.blocks * g.r_stride, "EXR buffers");
+    if (!rc && zip) rc = w.pred.ensure(g.blocks * g.p_stride, "EXR buffers");
+    if (!rc) rc = w.slots.ensure(zip ? g.pieces * g.slot_bytes : 16, "EXR buffers");
+    if (!rc) rc = w.words.ensure((5 * g.pieces + 4) * sizeof(uint32_t), "EXR buffers");
+    if (!rc) rc = w.tab.ensure(sizeof(PngTables), "EXR buffers");
+    if (w.tab.get() != before) w.tab_uploaded = false;
+    return rc;
+}
+hipError_t ex_tables_upload(hipStream_t stream, de_ctx::ExrWork& w) {      // deflate's length codes: the PNG output's tables, static on the host
+    if (w.tab_uploaded) return hipSuccess;
+    hipError_t e = hipMemcpyAsync(w.tab, &pn_host_tables(), sizeof(PngTables), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) w.tab_uploaded = true;
+    return e;
+}
+// src (on this stream) -> framed raw blocks -> predicted bytes -> slots -> the file at `out`.  w.tab holds the tables.  `after_layout` runs behind
+// the one kernel that reads `src`.
+template <class AfterLayout>
+int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g, const DisplaySrc& src, bool flip, float scale, uint8_t* out, AfterLayout after_layout) {
+    ExrArgs a;
+    a.src = src; a.flip = flip ? 1 : 0; a.scale = scale; a.tab = w.tab; a.raw = w.raw; a.pred = w.pred; a.slots = w.slots;
+    a.len = w.words; a.offset = w.words + g.pieces; a.alt_w = w.words + 2 * g.pieces; a.adler = w.words + 3 * g.pieces; a.status = w.words + 5 * g.pieces; a.out = out;
+    a.alt = w.raw; a.alt_at = a.alt_w; a.alt_bytes = (uint32_t)(g.blocks * g.r_stride);
+    a.pixel_type = g.pixel_type; a.compression = g.compression;
+    a.W = (uint32_t)g.W; a.H = (uint32_t)g.H; a.L = (uint32_t)g.L; a.line_bytes = (uint32_t)g.line_bytes; a.block_bytes = (uint32_t)g.block_bytes;
+    a.blocks = (uint32_t)g.blocks; a.chunk = (uint32_t)g.chunk; a.cpb = (uint32_t)g.cpb; a.r_stride = (uint32_t)g.r_stride; a.p_stride = (uint32_t)g.p_stride;
+    a.count = (uint32_t)g.pieces; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.front = (uint32_t)g.front; a.extra = 0u; a.trailer = 0u; a.capacity = (uint32_t)g.capacity;
+    memset(a.front_bytes, 0, sizeof(a.front_bytes));
+    exr_write_front(g, a.front_bytes);
+    const unsigned row_wgs = (unsigned)((((size_t)g.W + 3) / 4 + 255) / 256), block_wgs = (unsigned)(((g.block_bytes + 3) / 4 + 255) / 256);      // exr_row_workgroups, exr_block_workgroups
+    if (src_aligned(src) && (g.W & 3) == 0) hipLaunchKernelGGL(exr_layout_kernel<true>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(exr_layout_kernel<false>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    { int rc = after_layout(); if (rc) return rc; }
+    if (g.compression != DE_EXR_COMPRESSION_NONE) {
+        hipLaunchKernelGGL(exr_predict_kernel, dim3(block_wgs * (unsigned)g.blocks), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(exr_deflate_kernel, dim3((unsigned)g.pieces), dim3(PNG_THREADS), 0, stream, a);
+    }
+    hipLaunchKernelGGL(exr_block_kernel, dim3((unsigned)((g.blocks + 255) / 256)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(exr_scan_kernel, dim3(1), dim3(CS_SCAN_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(exr_compact_kernel, dim3((unsigned)g.pieces), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return DE_OK;
+}
+ExrGeometry ex_ctx_geometry(const de_ctx* c) { return ex_geometry(c->W, c->H, c->ex); }
+int ex_length(const void* word, uint64_t* len) {      // its coders raise no range status
+    static const char* const text = "the EXR encoder met a piece longer than its proven worst case: nothing was written past a buffer";
+    return coded_read_word(word, len, text, text);
+}
+// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.  MEAN reads what
+// the display launch would read with every stage off; the other sources are the chain left at their stage — its refusals, its side effects.
+int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
+    static const DisplayStop stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
+    HIP_TRY(hipSetDevice(c->device));
+    const ExrGeometry g = ex_ctx_geometry(c);
+    int rc = ex_shape_check(g.W, g.H, g.pixel_type);
+    if (rc) return rc;
+    const bool mean = c->ex.source == DE_EXR_SOURCE_MEAN;
+    if (!mean) { rc = display_chain_refusal(c, stop_of[c->ex.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
+    rc = dev.ensure(coded_stream_bytes(g.capacity), "EXR buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
+    if (rc) return rc;
+    rc = ex_work_ensure(c->ex_work, g);
+    if (rc) return rc;
+    HIP_TRY(ex_tables_upload(c->stream, c->ex_work));
+    DisplayArgs d;
+    bool per_tile;
+    if (mean) {
+        rc = join_slots(c);      // the launches in flight first, and the next accumulate_kernel must not overwrite what this reads
+        if (rc) return rc;
+        touched_hdr(c);
+        d.hdr = c->display_src ? c->display_src : c->d_hdr; d.tile_spp = c->d_tile_spp; d.samples = c->current_spp; d.W = c->W; d.H = c->H;
+        per_tile = c->frame_kind == DE_FRAME_ADAPTIVE;
+    } else {
+        rc = display_chain(c, stop_of[c->ex.source], &d, &per_tile);
+        if (rc) return rc;
+    }
+    rc = ex_launch(c->stream, c->ex_work, g, display_src(d, per_tile), true, c->ex.scale, dev, [c]() {
+        // what the next accumulate_kernel must wait for ends behind the layout (it has read the sums), as behind the display launch in de_render_to_image
+        HIP_TRY(hipEventRecord(c->ev_main, c->stream));
+        c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
+        return (int)DE_OK;
+    });
+    if (rc) return rc;
+    c->ex_coded.out.count++;
+    return DE_OK;
+}
 }  // namespace

@@ -277,12 +277,17 @@ class EarthViewer:
         memoryview with copy=False; Renderer.fetch_jpeg — under the same rules as video=True, through the JPEG ring; finish(jpeg=True) ends that
         loop.  It goes with none of pixels=True, hdr_pixels=True and video=True.
         png=True (a keyword beside the sliders too): the same for one complete PNG file in the settings of Renderer.set_png() — Renderer.fetch_png,
-        through the PNG ring; finish_png() ends that loop.  It goes with none of the others."""
+        through the PNG ring; finish_png() ends that loop.  It goes with none of the others.
+        exr=True (a keyword beside the sliders too): the same for one complete OpenEXR file of the scene-linear frame in the settings of
+        Renderer.set_exr() — Renderer.fetch_exr, through the EXR ring; finish_exr() ends that loop.  It goes with none of the others."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
         video = bool(sliders.pop("video", False))
         jpeg = bool(sliders.pop("jpeg", False))
         png = bool(sliders.pop("png", False))
+        exr = bool(sliders.pop("exr", False))
+        if exr and (pixels or hdr_pixels or video or jpeg or png):
+            raise ValueError("exr=True goes with none of pixels=True, hdr_pixels=True, video=True, jpeg=True and png=True")
         if png and (pixels or hdr_pixels or video or jpeg):
             raise ValueError("png=True goes with none of pixels=True, hdr_pixels=True, video=True and jpeg=True")
         if jpeg and (pixels or hdr_pixels or video):
@@ -299,7 +304,9 @@ class EarthViewer:
             should_reset = True
         r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
         frame = None
-        if png:
+        if exr:
+            frame = r.fetch_exr(copy=copy, lag=int(pipelined))
+        elif png:
             frame = r.fetch_png(copy=copy, lag=int(pipelined))
         elif jpeg:
             frame = r.fetch_jpeg(copy=copy, lag=int(pipelined))
@@ -315,7 +322,7 @@ class EarthViewer:
         # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
         # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
         shown = self._pixels if (pixels or hdr_pixels) else self._image
-        if video or jpeg or png:
+        if video or jpeg or png or exr:
             pass                                # no picture of save()'s changed hands
         elif pipelined:
             self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
@@ -340,7 +347,7 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        if video or jpeg or png:
+        if video or jpeg or png or exr:
             return frame
         return self._pixels if (pixels or hdr_pixels) else self._image
 
@@ -363,10 +370,12 @@ class EarthViewer:
             w.close()
         return w.frames
 
-    def _record_png(self, path, n, spp, sliders_per_frame):
-        """record()'s lossless side: frame(png=True) through the pipelined PNG ring into the numbered files path % 0, path % 1, ..."""
+    def _record_png(self, path, n, spp, sliders_per_frame, exr=False):
+        """record()'s lossless side: frame(png=True) through the pipelined PNG ring into the numbered files path % 0, path % 1, ...; exr=True: the
+        scene-linear side, frame(exr=True) through the EXR ring."""
         r = self.renderer
         written = 0
+        which = {"exr": True} if exr else {"png": True}
 
         def write(got):
             nonlocal written
@@ -375,11 +384,11 @@ class EarthViewer:
             written += 1
         for i in range(n):
             now = {k: (v[i] if hasattr(v, "__len__") else v) for k, v in sliders_per_frame.items()}
-            got = self.frame(spp=spp, copy=False, pipelined=1, png=True, **now)
+            got = self.frame(spp=spp, copy=False, pipelined=1, **which, **now)
             if got is not None:
                 write(got)
             del got
-        for got in r.fetch_pending_png(all_images=True):
+        for got in (r.fetch_pending_exr if exr else r.fetch_pending_png)(all_images=True):
             write(got)
         return written
 
@@ -392,7 +401,9 @@ class EarthViewer:
         A path ending in `.avi` writes a Motion-JPEG AVI instead (digital_earth_amd/mjpeg.py) and one ending in `.mjpeg` the concatenated JPEG files,
         both from frame(jpeg=True) through the pipelined JPEG ring, in the settings of Renderer.set_jpeg().
         A path ending in `.png` is a pattern with one integer field ("frames/%05d.png"): a numbered lossless sequence, one complete PNG file per
-        frame from frame(png=True) through the pipelined PNG ring, in the settings of Renderer.set_png() (frames count from 0; `fps` is not used)."""
+        frame from frame(png=True) through the pipelined PNG ring, in the settings of Renderer.set_png() (frames count from 0; `fps` is not used).
+        A path ending in `.exr` is such a pattern too ("frames/%05d.exr"): one complete OpenEXR file of the scene-linear frame per iteration, from
+        frame(exr=True) through the pipelined EXR ring, in the settings of Renderer.set_exr()."""
         from . import y4m
         r = self.renderer
         n = int(frames)
@@ -401,14 +412,15 @@ class EarthViewer:
                 raise ValueError("slider %r has %d values for %d frames" % (k, len(v), n))
         if path.endswith((".avi", ".mjpeg")):
             return self._record_jpeg(path, n, spp, fps, sliders_per_frame)
-        if path.endswith(".png"):
+        if path.endswith((".png", ".exr")):
+            suffix = path[-4:]
             try:
                 numbered = path % 0 != path % 1
             except (TypeError, ValueError):
                 numbered = False
             if not numbered:
-                raise ValueError("a .png recording needs a pattern with one integer field, such as frames/%05d.png")
-            return self._record_png(path, n, spp, sliders_per_frame)
+                raise ValueError("a %s recording needs a pattern with one integer field, such as frames/%%05d%s" % (suffix, suffix))
+            return self._record_png(path, n, spp, sliders_per_frame, exr=suffix == ".exr")
         fmt = r.video()
         w = y4m.Y4MWriter(path, fmt["size"][0], fmt["size"][1], fps=fps, format=fmt["format"], range=fmt["range"], siting=fmt["siting"])
         try:
@@ -428,6 +440,10 @@ class EarthViewer:
         """End a pipelined frame(png=True) loop: the file of its last iteration (None when nothing is in flight).  A method of its own, as
         Renderer.fetch_pending_jpeg is: finish()'s signature is pinned."""
         return self.renderer.fetch_pending_png(copy=copy)
+
+    def finish_exr(self, copy=True):
+        """End a pipelined frame(exr=True) loop: the file of its last iteration (None when nothing is in flight)."""
+        return self.renderer.fetch_pending_exr(copy=copy)
 
     def finish(self, copy=True, pixels=False, video=False, jpeg=False):
         """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop;
@@ -473,8 +489,17 @@ class EarthViewer:
         `.png` once Renderer.set_png() has been called: the same picture under the same rules — the pixels held, or the image held through the pack
         kernel at the phase it was shown with — filtered and deflated by the GPU's encoder (Renderer.debug_png, in the filter and chunk size of
         set_png); a picture taken with the HDR output on is the 16-bit file with the cICP chunk of the setting it was taken with.  Without
-        set_png() the file is written the way it was before, byte for byte."""
+        set_png() the file is written the way it was before, byte for byte.
+        `.exr`: not a picture held but the scene-linear frame of the CURRENT accumulation, as one OpenEXR file converted and deflated on the GPU
+        (Renderer.fetch_exr) in the settings of Renderer.set_exr(), or the defaults (half, ZIP, the mean) if that was never called; a sample is
+        rendered first if the frame holds none.  digital_earth_amd.exr.read opens it again."""
         r = self.renderer
+        if path.endswith(".exr"):
+            if r.current_spp == 0:
+                self.render(1)
+            with open(path, "wb") as f:
+                f.write(r.fetch_exr())
+            return
         if self._image is None and self._pixels is None:
             self.render(1)
         if path.endswith(".npy"):

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -122,7 +122,7 @@ class _FetchRing:
 
 
 class _CodedFetch:
-    """One coded output's fetches (fetch_jpeg, fetch_png; csrc/de_fetch.h's CodedOut is the native side): a whole file whose length the device
+    """One coded output's fetches (fetch_jpeg, fetch_png, fetch_exr; csrc/de_fetch.h's CodedOut is the native side): a whole file whose length the device
     decides, as bytes or as a view of the library's pinned buffer, synchronous or lagged through the output's ring of four.  Parametrised by the
     output: its library functions, its noun, and the names of its two attributes of the Renderer — the lagged fetches in flight (`_jp_in_flight`,
     `_pn_in_flight`) and a weak reference to the last view handed out (close() refuses while it is referenced).  The Renderer is passed in, not kept."""
@@ -217,6 +217,7 @@ class Renderer:
         self._jp_coded, self._pn_coded = _CodedFetch(self._lib, "jpeg", "JPEG", "_jp"), _CodedFetch(self._lib, "png", "PNG", "_pn")
         self._jp_in_flight, self._jp_view_ref = 0, None      # the lagged fetch_jpeg() calls; the last view handed out
         self._pn_in_flight, self._pn_view_ref, self._png_set = 0, None, False      # the same for fetch_png(); set_png() has been called
+        self._ex_coded, self._ex_in_flight, self._ex_view_ref = _CodedFetch(self._lib, "exr", "EXR", "_ex"), 0, None      # the same for fetch_exr()
         check(self._lib.de_create(int(device), self.image_res[0], self.image_res[1], ctypes.byref(self._h)))
         _native.apply_env_tuning(self._h)      # experiment overrides (DE_KERNEL, DE_V6_* ...): read HERE, not in the library
         self._params = DeParams()
@@ -264,7 +265,7 @@ class Renderer:
             for ring in (self._image_ring, self._pixel_ring, self._vd_ring):
                 if ring.referenced():
                     raise RuntimeError("a %s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % ring.name)
-            for coded in (self._jp_coded, self._pn_coded):
+            for coded in (self._jp_coded, self._pn_coded, self._ex_coded):
                 if coded.referenced(self):
                     raise RuntimeError("a fetch_%s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % coded.stem)
             check(self._lib.de_destroy(self._h))
@@ -1144,6 +1145,72 @@ class Renderer:
             check(self._lib.de_debug_png_framing(ctypes.byref(s), W, H, ch, depth, bytes(bytearray(cicp)), front, ctypes.c_uint64(64), ctypes.byref(m), None))
             data = front.raw[:int(m.value)] + data[int(m.value):]
         return data
+
+    # ------------------------------------------------------------------ OpenEXR output (include/digital_earth_exr.h)
+    def _ex_settings(self, source, pixel_type, compression, chunk_bytes, scale):
+        if source not in _native.EXR_SOURCES:
+            raise ValueError("source must be one of %s" % (_native.EXR_SOURCES,))
+        if pixel_type not in _native.EXR_PIXEL_TYPES:
+            raise ValueError("pixel_type must be one of %s" % (tuple(_native.EXR_PIXEL_TYPES),))
+        if compression not in _native.EXR_COMPRESSIONS:
+            raise ValueError("compression must be one of %s" % (tuple(_native.EXR_COMPRESSIONS),))
+        s = DeExr()
+        s.struct_bytes = ctypes.sizeof(DeExr)
+        s.source, s.pixel_type, s.compression = _native.EXR_SOURCES.index(source), _native.EXR_PIXEL_TYPES[pixel_type], _native.EXR_COMPRESSIONS[compression]
+        s.chunk_bytes = _native.EXR_DEFAULT_CHUNK if chunk_bytes is None else int(chunk_bytes)
+        s.scale = float(scale)
+        return s
+
+    def set_exr(self, source="mean", pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0):
+        """The settings of fetch_exr(): one complete OpenEXR scan-line file of the SCENE-LINEAR frame, converted and deflated on the GPU in front of
+        the display transform.  source "mean": the sums divided by the sample count (per tile inside an adaptive frame); "denoised" / "history" /
+        "bloom" / "local_exposure": the image fetch_denoised_hdr() / fetch_history_hdr() / fetch_bloom_hdr() / fetch_local_exposure_hdr() hand
+        out, refused as those are while the stage is off.  pixel_type "half" (clamped to +-65504, nearest even) or "float"; compression "zip"
+        (16 lines per block), "zips" (one) or "none"; chunk_bytes: predicted bytes per independent deflate chunk, 1024 ... 65535 (None: the
+        default); scale: finite, > 0, multiplied into every sample.  The file is always the context's size: output scaling and the look do not
+        apply.  Refused (DE_ERR_STATE) while lagged EXR fetches are in flight.  No other fetch is affected."""
+        check(self._lib.de_set_exr(self._h, ctypes.byref(self._ex_settings(source, pixel_type, compression, chunk_bytes, scale))))
+
+    def exr(self):
+        """The EXR settings as a dict (set_exr's keywords) plus size = (width, height) and capacity, the proven bound of any frame's length."""
+        s, n = DeExr(), ctypes.c_uint64()
+        check(self._lib.de_get_exr(self._h, ctypes.byref(s)))
+        check(self._lib.de_exr_capacity(self._h, ctypes.byref(n)))
+        name = lambda table, v: next(k for k, x in table.items() if x == v)
+        return dict(source=_native.EXR_SOURCES[s.source], pixel_type=name(_native.EXR_PIXEL_TYPES, s.pixel_type),
+                    compression=name(_native.EXR_COMPRESSIONS, s.compression), chunk_bytes=int(s.chunk_bytes), scale=float(s.scale),
+                    size=self.image_res, capacity=int(n.value))
+
+    def fetch_exr(self, copy=True, lag=0):
+        """The scene-linear frame as one complete OpenEXR file: `bytes` that open(path, "wb").write() takes as they are (digital_earth_amd.exr.read
+        opens them again).  Only the file's own bytes cross the link.  copy=False: a read-only memoryview of the library's pinned buffer, valid
+        until the next fetch_exr call (lag = 0) or until the ring comes round (lag > 0).  lag=1, 2 or 3: pipelined like fetch_png(lag=...), through
+        a ring of its own — the call returns the file of the lag-th previous call (None until there is one); fetch_pending_exr() hands out the rest."""
+        return self._ex_coded.fetch(self, copy, lag)
+
+    def fetch_pending_exr(self, copy=True, all_images=False):
+        """fetch_pending() for the lagged fetch_exr() calls and their ring: wait for the EXR fetches still in flight and return the newest file
+        (None when there is none) — bytes, or a memoryview with copy=False; all_images=True: the list of all of them, oldest first (bytes)."""
+        return self._ex_coded.pending(self, copy, all_images)
+
+    def render_to_exr(self):
+        """Run the stages up to the source's and the encoder and leave the file on the device (de_render_to_exr); returns (address of the file,
+        address of its uint64 length).  Nothing is waited for."""
+        return self._ex_coded.render_to(self)
+
+    def debug_exr(self, image, pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0):
+        """The encoder once on a given (H, W, 3) float32 image in R, G, B order, rows top-down, of any size (de_debug_exr); returns the file as
+        bytes.  The renderer's own settings and streams are not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (H, W, 3)")
+        H, W = image.shape[:2]
+        s = self._ex_settings("mean", pixel_type, compression, chunk_bytes, scale)
+        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.de_debug_exr_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
+        out = ctypes.create_string_buffer(int(cap.value))
+        check(self._lib.de_debug_exr(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
+        return out.raw[:int(n.value)]
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)
     LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
