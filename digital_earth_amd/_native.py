@@ -322,6 +322,15 @@ PNG_SYMBOLS = {
     "de_debug_png": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePng), _P, ctypes.c_uint64, _U64P]),
     "de_debug_png_framing": (ctypes.c_int, [ctypes.POINTER(DePng), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_uint64, _U64P, _U64P]),
 }
+# EXR AOV channels: include/digital_earth_exr_aovs.h (same library, additions only; not part of the binder's header)
+EXR_AOVS = {"depth": 1, "normal": 2, "albedo": 4, "coverage": 8, "transmittance": 16, "variance": 32, "samples": 64}      # DE_EXR_AOV_*
+EXR_AOV_ALL = 127
+EXR_AOV_SYMBOLS = {
+    "de_set_exr_aovs": (ctypes.c_int, [_P, ctypes.c_uint32]),
+    "de_get_exr_aovs": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32)]),
+    "de_debug_exr_aovs": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeExr), ctypes.c_uint32, _P, ctypes.c_uint64, _U64P]),
+    "de_debug_exr_aov_framing": (ctypes.c_int, [ctypes.POINTER(DeExr), ctypes.c_uint32, ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint64, _U64P, _U64P]),
+}
 # OpenEXR output: include/digital_earth_exr.h (same library, additions only; not part of the binder's header)
 EXR_SYMBOLS = {
     "de_set_exr": (ctypes.c_int, [_P, ctypes.POINTER(DeExr)]),
@@ -422,7 +431,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -17,7 +17,7 @@ DEPS = ["de_api.hip", "de_fast.hip", "de_rccl.h", "de_display.h", "de_fetch.h", 
         os.path.join("..", "..", "include", "digital_earth_local_exposure.h"), os.path.join("..", "..", "include", "digital_earth_output_scale.h"),
         os.path.join("..", "..", "include", "digital_earth_hdr_output.h"), os.path.join("..", "..", "include", "digital_earth_video.h"),
         os.path.join("..", "..", "include", "digital_earth_look.h"), os.path.join("..", "..", "include", "digital_earth_jpeg.h"),
-        os.path.join("..", "..", "include", "digital_earth_png.h"), os.path.join("..", "..", "include", "digital_earth_exr.h")]
+        os.path.join("..", "..", "include", "digital_earth_png.h"), os.path.join("..", "..", "include", "digital_earth_exr.h"), os.path.join("..", "..", "include", "digital_earth_exr_aovs.h")]
 DEPS_LEGACY = DEPS + [os.path.join("legacy", f) for f in ("render_kernel_v3.hip", "render_kernel_v5.hip", "de_launch_legacy.h", "de_ctx_legacy_members.inc")]
 # -ffp-contract=off is part of the arithmetic contract (de_math.h): fused operations only where written.
 # -fno-slp-vectorize: the SLP vectoriser packs pairs of scalar f32 operations into v_pk_* instructions; on gfx950 the

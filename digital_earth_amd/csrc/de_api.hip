@@ -1533,6 +1533,7 @@ int de_debug_png_framing(const de_png* s, int W, int H, int channels, int depth,
 int de_set_exr(de_ctx* c, const de_exr* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     { int rc = ex_settings_check(s); if (rc) return rc; }
+    if (c->ex_aovs) { int rc = ex_shape_check(c->W, c->H, s->pixel_type, c->ex_aovs); if (rc) return rc; }      // the AOV channels in force count at the new pixel type
     { int rc = refuse_in_flight(c->ex_coded.ring); if (rc) return rc; }
     c->ex = *s;
     c->ex_coded.guess = 0;
@@ -1546,7 +1547,7 @@ int de_get_exr(de_ctx* c, de_exr* out) {
 }
 int de_exr_capacity(de_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
-    { int rc = ex_shape_check(c->W, c->H, c->ex.pixel_type); if (rc) return rc; }
+    { int rc = ex_ctx_shape_check(c); if (rc) return rc; }
     *bytes = (uint64_t)ex_ctx_geometry(c).capacity;
     return DE_OK;
 }
@@ -1573,7 +1574,7 @@ int de_fetch_exr(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
 }
 int de_fetch_exr_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
-    { int rc = ex_shape_check(c->W, c->H, c->ex.pixel_type); if (rc) return rc; }
+    { int rc = ex_ctx_shape_check(c); if (rc) return rc; }
     const ExrGeometry g = ex_ctx_geometry(c);
     return coded_begin(c, c->ex_coded, g.front + g.raw / 2, g.capacity, [c](int k) { return ex_render(c, c->ex_coded.cell[k]); });      // the first: the front and half the raw bytes
 }
@@ -1616,6 +1617,100 @@ int de_debug_exr_framing(const de_exr* s, int W, int H, void* out, uint64_t out_
         exr_write_front(g, front);
         memcpy(out, front, EXR_FRONT_FIXED);
         memset((uint8_t*)out + EXR_FRONT_FIXED, 0, g.front - EXR_FRONT_FIXED);
+    }
+    return DE_OK;
+}
+
+/* ---- EXR AOV channels: include/digital_earth_exr_aovs.h (exr_kernels.hip: exr_aov_layout_kernel, exr_tables.h) */
+int de_set_exr_aovs(de_ctx* c, uint32_t mask) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = ex_mask_check(mask); if (rc) return rc; }
+    { int rc = ex_shape_check(c->W, c->H, c->ex.pixel_type, mask); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->ex_coded.ring); if (rc) return rc; }
+    c->ex_aovs = mask;
+    c->ex_coded.guess = 0;
+    return DE_OK;
+}
+int de_get_exr_aovs(de_ctx* c, uint32_t* mask) {
+    if (!c || !mask) return fail(DE_ERR_INVALID, "null argument");
+    *mask = c->ex_aovs;
+    return DE_OK;
+}
+/* the conversion with AOV channels once on host-given arrays of any size, rows top-down.  Buffers of its own; the context's settings are not touched. */
+int de_debug_exr_aovs(de_ctx* c, const float* image, const float* guides, const float* s2, const float* counts, int W, int H, const de_exr* s, uint32_t mask,
+                      void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !image || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ex_settings_check(s); if (rc) return rc; }
+    { int rc = ex_mask_check(mask); if (rc) return rc; }
+    { int rc = ex_shape_check(W, H, s->pixel_type, mask); if (rc) return rc; }
+    const ExrGeometry g = ex_geometry(W, H, *s, mask);
+    uint32_t need = 0u;
+    for (int k = 0; k < g.channels; ++k) need |= exr_slot_need(g.ch[k].slot);
+    if ((need & (EXR_NEED_NC | EXR_NEED_AT | EXR_NEED_DIST)) && !guides) return fail(DE_ERR_INVALID, "the mask selects guide channels: `guides` is null");
+    if ((need & EXR_NEED_MOMENTS) && !s2) return fail(DE_ERR_INVALID, "the mask selects the variance: `s2` is null");
+    if ((need & EXR_NEED_DIVISOR) && !counts) return fail(DE_ERR_INVALID, "the mask selects the variance or the samples: `counts` is null");
+    HIP_TRY(hipSetDevice(c->device));
+    // behind the first enqueued copy every way out waits for the stream: the copies read the caller's arrays and the local vectors below
+    #define SYNC_TRY(expr) do { hipError_t se_ = (expr); if (se_ != hipSuccess) { (void)hipStreamSynchronize(c->stream); HIP_TRY(se_); } } while (0)
+    de_ctx::ExrWork work;
+    Dev<float> d_image, d_s2, d_counts, d_dist;
+    Dev<float4> d_nc, d_at;
+    Dev<uint8_t> d_out;
+    const size_t npx = (size_t)W * H, image_bytes = npx * 3 * sizeof(float);
+    { int rc = ex_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_image.ensure(image_bytes));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
+    SYNC_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
+    std::vector<float4> nc, at;      // alive until the copies have been waited for
+    std::vector<float> dist;
+    ExrAovSrc av;
+    if (need & (EXR_NEED_NC | EXR_NEED_AT | EXR_NEED_DIST)) {      // the nine guides of a pixel side by side, in de_fetch_guides' order, into the device's three buffers
+        nc.resize(npx); at.resize(npx); dist.resize(npx);
+        for (size_t p = 0; p < npx; ++p) {
+            const float* q = guides + p * 9;
+            nc[p] = make_float4(q[2], q[3], q[4], q[0]); at[p] = make_float4(q[5], q[6], q[7], q[8]); dist[p] = q[1];
+        }
+        SYNC_TRY(d_nc.ensure(npx * sizeof(float4)));
+        SYNC_TRY(d_at.ensure(npx * sizeof(float4)));
+        SYNC_TRY(d_dist.ensure(npx * sizeof(float)));
+        SYNC_TRY(hipMemcpyAsync(d_nc, nc.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        SYNC_TRY(hipMemcpyAsync(d_at, at.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        SYNC_TRY(hipMemcpyAsync(d_dist, dist.data(), npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        av.nc = d_nc; av.at = d_at; av.dist = d_dist;
+    }
+    if (need & EXR_NEED_MOMENTS) {
+        SYNC_TRY(d_s2.ensure(image_bytes));
+        SYNC_TRY(hipMemcpyAsync(d_s2, s2, image_bytes, hipMemcpyHostToDevice, c->stream));
+        av.s1 = d_image; av.s2 = d_s2;
+    }
+    if (counts) {      // the divisor of B, G, R too: `image` is read as the sums
+        SYNC_TRY(d_counts.ensure(npx * sizeof(float)));
+        SYNC_TRY(hipMemcpyAsync(d_counts, counts, npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        av.counts = d_counts;
+    }
+    SYNC_TRY(ex_tables_upload(c->stream, work));
+    DisplaySrc src;
+    src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;      // without counts: x / 1.0f == x
+    { int rc = ex_launch(c->stream, work, g, src, false, s->scale, d_out, [] { return (int)DE_OK; }, av); if (rc) { (void)hipStreamSynchronize(c->stream); return rc; } }
+    #undef SYNC_TRY
+    return coded_debug_out(c->stream, d_out, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+}
+/* the host's part alone: no device, no context */
+int de_debug_exr_aov_framing(const de_exr* s, uint32_t mask, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
+    if (!s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ex_settings_check(s); if (rc) return rc; }
+    { int rc = ex_mask_check(mask); if (rc) return rc; }
+    { int rc = ex_shape_check(W, H, s->pixel_type, mask); if (rc) return rc; }
+    const ExrGeometry g = ex_geometry(W, H, *s, mask);
+    if (len) *len = g.front;
+    if (capacity) *capacity = (uint64_t)g.capacity;
+    if (out || out_bytes) {
+        if (!out || out_bytes < g.front) return fail(DE_ERR_INVALID, "out_bytes is smaller than the front (*len)");
+        uint8_t front[EXR_FRONT_MAX];
+        const size_t n = exr_write_front(g, front);
+        if (n != g.front_fixed) return fail(DE_ERR_INTERNAL, "the EXR front's length is not the geometry's");
+        memcpy(out, front, n);
+        memset((uint8_t*)out + n, 0, g.front - n);
     }
     return DE_OK;
 }

@@ -13,6 +13,7 @@
 #include "../../include/digital_earth_jpeg.h"
 #include "../../include/digital_earth_png.h"
 #include "../../include/digital_earth_exr.h"
+#include "../../include/digital_earth_exr_aovs.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -349,6 +350,7 @@ struct de_ctx {
         bool tab_uploaded = false;
     };
     de_exr ex = {(uint32_t)sizeof(de_exr), DE_EXR_SOURCE_MEAN, DE_EXR_PIXEL_HALF, DE_EXR_COMPRESSION_ZIP, DE_EXR_DEFAULT_CHUNK, 1.0f};
+    uint32_t ex_aovs = 0;         // DE_EXR_AOV_* (include/digital_earth_exr_aovs.h): the channels beside B, G, R; 0: none, the file of §23
     ExrWork ex_work;
     CodedOut ex_coded = {{"EXR"}, {"EXR", "de_fetch_exr"}};
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then

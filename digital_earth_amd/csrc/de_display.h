@@ -673,6 +673,13 @@ void lk_launch(hipStream_t stream, float* image, uint64_t n_pixels, const de_loo
     hipLaunchKernelGGL(look_apply_kernel, dim3((unsigned)((lk_threads(n_pixels) + 255u) / 256u)), dim3(256), 0, stream, a);
 }
 
+// The guides of the frame as it stands, for a consumer outside the denoiser (the EXR output's AOV channels, §24): de_fetch_guides' two steps, its refusals.
+int guides_of_the_frame(de_ctx* c) {
+    int rc = run_setup(c);
+    if (rc) return rc;
+    return dn_ensure_guides(c);
+}
+
 // ---- the chain.  Where a caller leaves it: behind the stage it hands out (an intermediate fetch), or in front of the display launch.
 enum DisplayStop { STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE, STOP_IMAGE };
 
@@ -746,13 +753,26 @@ int ex_settings_check(const de_exr* s) {
     if (!(s->scale > 0.0f) || !(s->scale < INFINITY)) return fail(DE_ERR_INVALID, "de_exr.scale must be finite and greater than 0");      // NaN fails the first
     return DE_OK;
 }
-int ex_shape_check(int W, int H, int pixel_type) {      // what one conversion can take: the kernels count bytes in 32 bits
-    if (W <= 0 || H <= 0) return fail(DE_ERR_INVALID, "an EXR frame needs W, H >= 1");
-    if ((unsigned long long)W * (unsigned long long)H * 3ull * (pixel_type == DE_EXR_PIXEL_FLOAT ? 4ull : 2ull) > EXR_MAX_RAW)
-        return fail(DE_ERR_INVALID, "the EXR output takes at most 2^27 raw bytes, H W 3 bps");
+int ex_mask_check(uint32_t mask) {
+    if (mask & ~(uint32_t)DE_EXR_AOV_ALL) return fail(DE_ERR_INVALID, "unknown DE_EXR_AOV_* bit");
     return DE_OK;
 }
-ExrGeometry ex_geometry(int W, int H, const de_exr& s) { return exr_geometry(W, H, s.pixel_type, s.compression, s.chunk_bytes); }
+int ex_shape_check(int W, int H, int pixel_type, uint32_t mask = 0u) {      // what one conversion can take: the kernels count bytes in 32 bits
+    if (W <= 0 || H <= 0) return fail(DE_ERR_INVALID, "an EXR frame needs W, H >= 1");
+    if (!mask) {
+        if ((unsigned long long)W * (unsigned long long)H * 3ull * (pixel_type == DE_EXR_PIXEL_FLOAT ? 4ull : 2ull) > EXR_MAX_RAW)
+            return fail(DE_ERR_INVALID, "the EXR output takes at most 2^27 raw bytes, H W 3 bps");
+        return DE_OK;
+    }
+    ExrChannel ch[EXR_MAX_CHANNELS];
+    const int n = exr_channel_list(mask, pixel_type, 1, ch);
+    unsigned long long sum = 0ull;
+    for (int k = 0; k < n; ++k) sum += (unsigned long long)ch[k].bps;
+    if ((unsigned long long)W * (unsigned long long)H * sum > EXR_MAX_RAW)
+        return fail(DE_ERR_INVALID, "the EXR output takes at most 2^27 raw bytes, H W times the channels' bytes per pixel (fewer AOV channels, or HALF, make a frame smaller)");
+    return DE_OK;
+}
+ExrGeometry ex_geometry(int W, int H, const de_exr& s, uint32_t mask = 0u) { return exr_geometry(W, H, s.pixel_type, s.compression, s.chunk_bytes, mask); }
 // The buffers of one conversion of geometry g; `words` holds len[pieces], offset[pieces], alt_at[pieces], adler[pieces][2] and the status word.
 int ex_work_ensure(de_ctx::ExrWork& w, const ExrGeometry& g) {
     const PngTables* before = w.tab.get();
@@ -773,9 +793,36 @@ hipError_t ex_tables_upload(hipStream_t stream, de_ctx::ExrWork& w) {      // de
 }
 // src (on this stream) -> framed raw blocks -> predicted bytes -> slots -> the file at `out`.  w.tab holds the tables.  `after_layout` runs behind
 // the one kernel that reads `src`.
+// What the AOV planes of geometry g read: the guides, the sums with S2 and the divisor, each null (0) where no selected channel needs it.
+struct ExrAovSrc {
+    const float4* nc = nullptr; const float4* at = nullptr; const float* dist = nullptr;
+    const float* s1 = nullptr; const float* s2 = nullptr;
+    const int32_t* tile_spp = nullptr; const float* counts = nullptr; int samples = 1;
+};
 template <class AfterLayout>
-int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g, const DisplaySrc& src, bool flip, float scale, uint8_t* out, AfterLayout after_layout) {
+int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g, const DisplaySrc& src, bool flip, float scale, uint8_t* out, AfterLayout after_layout,
+              const ExrAovSrc& av = ExrAovSrc()) {
     ExrArgs a;
+    a.front_fixed = (uint32_t)g.front_fixed; a.rgb_bps = (uint32_t)g.bps; a.counts = av.counts;
+    a.aov = ExrAov();
+    for (int k = 0; k < g.channels; ++k) {
+        const ExrChannel& ch = g.ch[k];
+        if (ch.slot <= EXR_SLOT_B) { a.rgb_offset[ch.slot] = (uint32_t)ch.offset; continue; }
+        if (a.aov.planes >= EXR_MAX_AOV_PLANES) return fail(DE_ERR_INTERNAL, "the EXR output's channel list holds more AOV planes than the kernel takes");
+        ExrPlane& pl = a.aov.plane[a.aov.planes++];
+        pl.slot = (uint32_t)ch.slot; pl.bps = (uint32_t)ch.bps; pl.offset = (uint32_t)ch.offset;
+        a.aov.need |= exr_slot_need(ch.slot);
+    }
+    const uint32_t need = a.aov.need;
+    a.aov.nc = (need & EXR_NEED_NC) ? reinterpret_cast<const ExrF4*>(av.nc) : nullptr;
+    a.aov.at = (need & EXR_NEED_AT) ? reinterpret_cast<const ExrF4*>(av.at) : nullptr;
+    a.aov.dist = (need & EXR_NEED_DIST) ? av.dist : nullptr;
+    a.aov.s1 = (need & EXR_NEED_MOMENTS) ? av.s1 : nullptr;
+    a.aov.s2 = (need & EXR_NEED_MOMENTS) ? av.s2 : nullptr;
+    a.aov.tile_spp = av.tile_spp; a.aov.counts = av.counts; a.aov.samples = av.samples;
+    if (((need & EXR_NEED_NC) && !a.aov.nc) || ((need & EXR_NEED_AT) && !a.aov.at) || ((need & EXR_NEED_DIST) && !a.aov.dist) ||
+        ((need & EXR_NEED_MOMENTS) && (!a.aov.s1 || !a.aov.s2)))
+        return fail(DE_ERR_INTERNAL, "the EXR output's AOV channels were given no buffer to read");
     a.src = src; a.flip = flip ? 1 : 0; a.scale = scale; a.tab = w.tab; a.raw = w.raw; a.pred = w.pred; a.slots = w.slots;
     a.len = w.words; a.offset = w.words + g.pieces; a.alt_w = w.words + 2 * g.pieces; a.adler = w.words + 3 * g.pieces; a.status = w.words + 5 * g.pieces; a.out = out;
     a.alt = w.raw; a.alt_at = a.alt_w; a.alt_bytes = (uint32_t)(g.blocks * g.r_stride);
@@ -790,6 +837,12 @@ int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g
     if (src_aligned(src) && (g.W & 3) == 0) hipLaunchKernelGGL(exr_layout_kernel<true>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(exr_layout_kernel<false>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
+    if (a.aov.planes) {      // the same grid; it reads the sums too, so ahead of after_layout
+        const uintptr_t bits = reinterpret_cast<uintptr_t>(a.aov.dist) | reinterpret_cast<uintptr_t>(a.aov.s1) | reinterpret_cast<uintptr_t>(a.aov.s2);
+        if ((bits & 15u) == 0u && (g.W & 3) == 0) hipLaunchKernelGGL(exr_aov_layout_kernel<true>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(exr_aov_layout_kernel<false>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+    }
     { int rc = after_layout(); if (rc) return rc; }
     if (g.compression != DE_EXR_COMPRESSION_NONE) {
         hipLaunchKernelGGL(exr_predict_kernel, dim3(block_wgs * (unsigned)g.blocks), dim3(256), 0, stream, a);
@@ -801,7 +854,21 @@ int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g
     HIP_TRY(hipGetLastError());
     return DE_OK;
 }
-ExrGeometry ex_ctx_geometry(const de_ctx* c) { return ex_geometry(c->W, c->H, c->ex); }
+ExrGeometry ex_ctx_geometry(const de_ctx* c) { return ex_geometry(c->W, c->H, c->ex, c->ex_aovs); }
+int ex_ctx_shape_check(const de_ctx* c) { return ex_shape_check(c->W, c->H, c->ex.pixel_type, c->ex_aovs); }
+// What the AOV channels in force refuse before anything is enqueued.  The variance is this context's own sums beside its own S2: not with a display
+// source (the sums shown are another buffer's, S2 is not) and not under a tile or sample partition (this rank's S2 is a part's), as the denoiser,
+// S2's other reader, refuses (denoise_refusal); and not without a complete S2.  The guides' own refusal, before maps and LUTs, is de_fetch_guides'.
+int ex_aov_refusal(de_ctx* c) {
+    if (c->ex_aovs & DE_EXR_AOV_VARIANCE) {
+        if (c->display_src) return fail(DE_ERR_STATE, "the EXR variance channels describe this context's own frame: not with a display source or after de_reduce_progressive");
+        if (c->tiles_world > 1) return fail(DE_ERR_STATE, "the EXR variance channels describe whole frames: not under a tile partition");
+        if (c->sample_world > 1) return fail(DE_ERR_STATE, "the EXR variance channels describe whole frames: not under a sample partition");
+    }
+    if ((c->ex_aovs & DE_EXR_AOV_VARIANCE) && !(c->d_s2 && (c->dn_s2_complete || c->frame_kind == DE_FRAME_ADAPTIVE)))
+        return fail(DE_ERR_STATE, "the EXR variance channels need the sums of squares of every sample of this frame: turn the denoiser on (de_set_denoise) before the frame's first sample, or render adaptively");
+    return DE_OK;
+}
 int ex_length(const void* word, uint64_t* len) {      // its coders raise no range status
     static const char* const text = "the EXR encoder met a piece longer than its proven worst case: nothing was written past a buffer";
     return coded_read_word(word, len, text, text);
@@ -812,10 +879,17 @@ int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
     static const DisplayStop stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
     HIP_TRY(hipSetDevice(c->device));
     const ExrGeometry g = ex_ctx_geometry(c);
-    int rc = ex_shape_check(g.W, g.H, g.pixel_type);
+    int rc = ex_ctx_shape_check(c);
     if (rc) return rc;
     const bool mean = c->ex.source == DE_EXR_SOURCE_MEAN;
     if (!mean) { rc = display_chain_refusal(c, stop_of[c->ex.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
+    rc = ex_aov_refusal(c);
+    if (rc) return rc;
+    const bool guides = (c->ex_aovs & (DE_EXR_AOV_DEPTH | DE_EXR_AOV_NORMAL | DE_EXR_AOV_ALBEDO | DE_EXR_AOV_COVERAGE | DE_EXR_AOV_TRANSMITTANCE)) != 0u;
+    if (guides) {      // the guides of the frame's geometry, whatever the source: made if stale, as for de_fetch_guides and the denoiser
+        rc = guides_of_the_frame(c);
+        if (rc) return rc;
+    }
     rc = dev.ensure(coded_stream_bytes(g.capacity), "EXR buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
     if (rc) return rc;
     rc = ex_work_ensure(c->ex_work, g);
@@ -833,12 +907,18 @@ int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
         rc = display_chain(c, stop_of[c->ex.source], &d, &per_tile);
         if (rc) return rc;
     }
+    ExrAovSrc av;      // the frame's own sums and counts, whatever the source: a stage's mean has no S2
+    if (c->ex_aovs) {
+        av.nc = c->d_dn_nc; av.at = c->d_dn_at; av.dist = c->d_dn_dist;
+        av.s1 = c->d_hdr; av.s2 = c->d_s2;      // the context's own sums beside its own S2 (ex_aov_refusal: no display source)
+        av.tile_spp = c->frame_kind == DE_FRAME_ADAPTIVE ? c->d_tile_spp : nullptr; av.samples = c->current_spp;
+    }
     rc = ex_launch(c->stream, c->ex_work, g, display_src(d, per_tile), true, c->ex.scale, dev, [c]() {
         // what the next accumulate_kernel must wait for ends behind the layout (it has read the sums), as behind the display launch in de_render_to_image
         HIP_TRY(hipEventRecord(c->ev_main, c->stream));
         c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
         return (int)DE_OK;
-    });
+    }, av);
     if (rc) return rc;
     c->ex_coded.out.count++;
     return DE_OK;

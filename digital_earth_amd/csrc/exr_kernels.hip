@@ -1,10 +1,15 @@
 // exr_kernels.hip — the opt-in OpenEXR output in front of the display transform (include/digital_earth_exr.h): the frame's mean, or
-// the mean a stage of the display chain made of it, becomes one complete scan-line file behind the front the host composed.  Six kernels, one after
-// the other on the context stream, no atomics on global memory and no host synchronisation between them:
+// the mean a stage of the display chain made of it, becomes one complete scan-line file behind the front the host composed.  Six kernels (seven with
+// AOV channels: include/digital_earth_exr_aovs.h), one after the other on the context stream, no atomics on global memory and no host
+// synchronisation between them:
 //   exr_layout_kernel    one thread per group of four pixels of a file row (display_source.h: src_load4, src_samples): the division, the scale, the
 //                        conversion (exr_tables.h: exr_sample_bits, exr_half_bits), and the samples into the row's three planes B, G, R of the FRAMED
 //                        raw buffer — per block its 8-byte header {y0, P} and its raw bytes r, which is what a raw block is in the file.  Consecutive
-//                        threads store consecutive samples of one plane.
+//                        threads store consecutive samples of one plane.  The planes' offsets within a line are the host's (exr_tables.h).
+//   exr_aov_layout_kernel  only with AOV channels, on the same flat grid: a thread loads its four pixels' guides (two float4 and a float each, 16-byte
+//                        loads), S1, S2 and the divisor — only what the mask selects; an unselected buffer may be null — and stores four
+//                        consecutive samples into each selected plane of the same line (exr_tables.h: exr_aov_thread, every store checked
+//                        against line_bytes).
 //   exr_predict_kernel   ZIP / ZIPS: four bytes of p per thread from r (exr_predicted: the reorder and the predictor), one dword store.
 //   exr_deflate_kernel   ZIP / ZIPS: one 512-thread workgroup per chunk of a block's p; the chunk's deflate data is the shared coder's
 //                        (png_deflate.h: png_code_chunk) in the same LDS image, which keeps two workgroups per CU.  What is this file's alone: a
@@ -37,6 +42,11 @@ struct ExrArgs : CodedTail {    // the pieces are the blocks' chunks (NONE: the 
     uint32_t* alt_w;            // alt_at, to be written
     int pixel_type, compression;
     uint32_t W, H, L, line_bytes, block_bytes, blocks, chunk, cpb, r_stride, p_stride;
+    uint32_t front_fixed;       // the header's bytes in front_bytes: 313 with B, G, R alone
+    uint32_t rgb_offset[3];     // of the planes of R, G, B within a line (B, G, R alone: 2 W bps, W bps, 0), each of W bps bytes
+    uint32_t rgb_bps;
+    const float* counts;        // the divisor per pixel, [H][W] (de_debug_exr_aovs), else null: src_samples
+    ExrAov aov;                 // the AOV planes and what they read; aov.planes == 0: none, exr_aov_layout_kernel does not run
     uint8_t front_bytes[EXR_FRONT_MAX];
 };
 
@@ -68,18 +78,35 @@ __global__ void __launch_bounds__(256) exr_layout_kernel(ExrArgs a) {
     float px[12];
     if (VEC) src_load4<true>(p, px);      // (W is a multiple of 4 and the buffer 16-byte aligned)
     else for (uint32_t k = 0u; k < 3u * n; ++k) px[k] = p[k];
-    const float samples = src_samples(a.src, (int)x0, (int)j);
+    float samples[4];
+    samples[0] = src_samples(a.src, (int)x0, (int)j);
+    for (uint32_t k = 1u; k < 4u; ++k) samples[k] = samples[0];
+    if (a.counts) for (uint32_t k = 0u; k < n; ++k) samples[k] = a.counts[(size_t)j * (size_t)a.W + x0 + k];
     uint8_t* row = block + EXR_BLOCK_HEADER + (size_t)line * (size_t)a.line_bytes;
-    for (uint32_t ch = 0u; ch < 3u; ++ch) {      // the planes B, G, R
-        const uint32_t plane = 2u - ch;
+    for (uint32_t ch = 0u; ch < 3u; ++ch) {      // the planes of R, G, B where the host's sort put them
+        const uint32_t off = a.rgb_offset[ch];
+        if ((size_t)off + (size_t)a.W * (size_t)a.rgb_bps > (size_t)a.line_bytes) continue;      // (the host's offsets lie inside the line)
         if (a.pixel_type == EXR_PIXEL_HALF) {
-            uint16_t* dst = reinterpret_cast<uint16_t*>(row + (size_t)plane * (size_t)a.W * 2u) + x0;
-            for (uint32_t k = 0u; k < n; ++k) dst[k] = (uint16_t)exr_half_bits(exr_sample_bits(px[3u * k + ch] / samples, a.scale));
+            uint16_t* dst = reinterpret_cast<uint16_t*>(row + off) + x0;
+            for (uint32_t k = 0u; k < n; ++k) dst[k] = (uint16_t)exr_half_bits(exr_sample_bits(px[3u * k + ch] / samples[k], a.scale));
         } else {
-            uint32_t* dst = reinterpret_cast<uint32_t*>(row + (size_t)plane * (size_t)a.W * 4u) + x0;
-            for (uint32_t k = 0u; k < n; ++k) dst[k] = exr_sample_bits(px[3u * k + ch] / samples, a.scale);
+            uint32_t* dst = reinterpret_cast<uint32_t*>(row + off) + x0;
+            for (uint32_t k = 0u; k < n; ++k) dst[k] = exr_sample_bits(px[3u * k + ch] / samples[k], a.scale);
         }
     }
+}
+
+// ---- the AOV planes of the same line: the layout's grid, thread for thread; it writes no plane the layout writes and no block header
+template <bool VEC>
+__global__ void __launch_bounds__(256) exr_aov_layout_kernel(ExrArgs a) {
+    const uint32_t wgs = exr_row_workgroups(a), y = blockIdx.x / wgs;
+    const uint32_t g = (blockIdx.x - y * wgs) * 256u + threadIdx.x, x0 = 4u * g;
+    if (y >= a.H || x0 >= a.W) return;
+    const uint32_t j = a.flip ? a.H - 1u - y : y;
+    const uint32_t b = y / a.L, line = y - b * a.L;
+    if (b >= a.blocks || (size_t)EXR_BLOCK_HEADER + (size_t)(line + 1u) * (size_t)a.line_bytes > (size_t)a.r_stride) return;      // the line lies in its block
+    uint8_t* row = a.raw + (size_t)b * (size_t)a.r_stride + EXR_BLOCK_HEADER + (size_t)line * (size_t)a.line_bytes;
+    if (!exr_aov_thread<VEC>(a.aov, row, a.line_bytes, a.W, x0, j)) *a.status = CS_STATUS_OVERFLOW;
 }
 
 // ---- the reorder and the predictor: thread g of a block owns p[4 g .. 4 g + 4); a flat grid, as the layout's
@@ -179,7 +206,7 @@ __global__ void __launch_bounds__(CS_SCAN_THREADS) exr_scan_kernel(ExrArgs a) {
     __shared__ uint32_t sums[CS_SCAN_THREADS];
     const uint32_t t = threadIdx.x;
     cs_scan_sum(a, sums, (int)t);
-    if (t < EXR_FRONT_FIXED && t < a.capacity) a.out[CS_WORD_BYTES + t] = a.front_bytes[t];
+    if (t < a.front_fixed && t < EXR_FRONT_MAX && t < a.capacity) a.out[CS_WORD_BYTES + t] = a.front_bytes[t];      // front_fixed <= 626 < CS_SCAN_THREADS
     __syncthreads();
     cs_scan_total(a, sums, (int)t);
     __syncthreads();
@@ -193,7 +220,7 @@ __global__ void __launch_bounds__(256) exr_compact_kernel(ExrArgs a) {
     if (!moved || threadIdx.x != 0u) return;
     const uint32_t b = i / a.cpb;
     if (i != b * a.cpb) return;
-    const uint32_t at = EXR_FRONT_FIXED + 8u * b;
+    const uint32_t at = a.front_fixed + 8u * b;
     if (at + 8u > a.front || a.front > a.capacity) return;
     uint8_t* entry = a.out + CS_WORD_BYTES + at;
     const uint32_t offset = a.offset[i];

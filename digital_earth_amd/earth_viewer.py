@@ -184,7 +184,7 @@ def _rgb_picture(px):
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, look=None, look_strength=1.0, **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, look=None, look_strength=1.0, exr_aovs=(), **renderer_kwargs):
         """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
         in frame()'s loop instead of restarting at one sample per pixel.  local_exposure: the same for Renderer.set_local_exposure — every frame is
         dodged and burned on the GPU ahead of the display transform.  output_res: None, or the (width, height) at which frames are delivered and
@@ -192,7 +192,9 @@ class EarthViewer:
         hdr_output: None / False, True (Renderer.set_hdr_output's defaults: 1000-nit Rec.2020 PQ) or a dict of its keywords — frames are then the HDR
         signal, frame(hdr_pixels=True) hands out 10 / 16-bit pixels and save() writes a 16-bit PNG that names its colour space.
         look: None, the path of a 3D .cube file or a digital_earth_amd.cube.Cube — every frame is graded through it on the GPU behind the display
-        transform, mixed with the ungraded frame by look_strength (Renderer.set_look; a shaper or trilinear interpolation: call that directly)."""
+        transform, mixed with the ungraded frame by look_strength (Renderer.set_look; a shaper or trilinear interpolation: call that directly).
+        exr_aovs: names of channel groups ("depth", "normal", "albedo", "coverage", "transmittance", "variance", "samples", or "all") that
+        save("x.exr"), frame(exr=True) and record("f%05d.exr") write beside B, G, R (Renderer.set_exr's aovs)."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
@@ -208,6 +210,8 @@ class EarthViewer:
             self.renderer.set_hdr_output(True, **(hdr_output if isinstance(hdr_output, dict) else {}))
         if look is not None:
             self.renderer.set_look(look, strength=look_strength)
+        if exr_aovs:
+            self.renderer.set_exr(aovs=exr_aovs)
         self.config = None
         if config is not None:
             self.load_config(config)

@@ -1,7 +1,9 @@
 """A minimal reader of the OpenEXR files this project's GPU encoder writes (include/digital_earth_exr.h): single-part scan-line files with the
-channels B, G, R of one pixel type (HALF or FLOAT), compression NONE, ZIPS or ZIP, increasing line order, no subsampling.  Written from the file
-layout, not from the encoder: it is the tests' independent decoder and the user's way back in.  Inflate is zlib.decompress (which checks the
-Adler-32); numpy only assembles the array.  Anything else — tiles, multi-part, deep data, other channels or compressions — is refused by name."""
+channels B, G, R of one pixel type (HALF or FLOAT) and, beside them, any further channels of HALF or FLOAT type each (the AOV channels of
+include/digital_earth_exr_aovs.h: a line holds every channel's samples in the channel list's order, which must be sorted by name as bytes),
+compression NONE, ZIPS or ZIP, increasing line order, no subsampling.  Written from the file layout, not from the encoder: it is the tests' independent decoder and the user's way back in.  Inflate is zlib.decompress (which checks the
+Adler-32); numpy only assembles the array.  Anything else — tiles, multi-part, deep data, UINT or subsampled channels, a channel list without B, G, R or out of order, other compressions — is
+refused by name."""
 import struct
 import zlib
 
@@ -80,8 +82,9 @@ def unpredict(p):
 
 def read(data):
     """An OpenEXR file of this encoder's kind -> (array [H][W][3] float16 | float32 in R, G, B order, rows top-down; info).  info: width, height,
-    pixel_type ("half" | "float"), compression ("none" | "zips" | "zip"), lines_per_block, blocks (per block: y, offset, data_size, raw), attributes
-    (the header's names in file order).  Raises ExrError naming what it refuses."""
+    pixel_type ("half" | "float": of B, G, R), compression ("none" | "zips" | "zip"), lines_per_block, blocks (per block: y, offset, data_size, raw),
+    attributes (the header's names in file order), channel_names (in file order), channel_types (name -> "half" | "float") and channels: every
+    channel of the file, B, G and R included, as name -> array [H][W] of its own type.  Raises ExrError naming what it refuses."""
     data = bytes(data)
     if len(data) < 8 or data[:4] != MAGIC:
         raise ExrError("not an OpenEXR file: the magic number is missing")
@@ -103,13 +106,19 @@ def read(data):
     if "channels" not in attrs or attrs["channels"][0] != "chlist":
         raise ExrError("the required attribute 'channels' is missing")
     chans = _channels(attrs["channels"][1])
-    if [c[0] for c in chans] != ["B", "G", "R"]:
-        raise ExrError("channels %s, not B, G, R" % ", ".join(c[0] for c in chans))
-    if len({c[1] for c in chans}) != 1 or chans[0][1] not in PIXEL_TYPES:
-        raise ExrError("the channels' pixel types %s are not all HALF or all FLOAT" % [c[1] for c in chans])
+    names = [c[0] for c in chans]
+    if not {"B", "G", "R"} <= set(names):
+        raise ExrError("channels %s hold no B, G, R" % ", ".join(names))
+    if len(set(names)) != len(names) or [n.encode("latin-1") for n in names] != sorted(n.encode("latin-1") for n in names):
+        raise ExrError("channels %s are not sorted by name" % ", ".join(names))
+    colour = [c for c in chans if c[0] in ("B", "G", "R")]
+    if len({c[1] for c in colour}) != 1 or any(c[1] not in PIXEL_TYPES for c in chans):
+        raise ExrError("the channels' pixel types %s: B, G, R must share one, and every channel be HALF or FLOAT" % [c[1] for c in chans])
     if any(c[3] != 1 or c[4] != 1 for c in chans):
         raise ExrError("subsampled channels are not supported")
-    type_name, dtype = PIXEL_TYPES[chans[0][1]]
+    type_name, dtype = PIXEL_TYPES[colour[0][1]]
+    dtypes = [PIXEL_TYPES[c[1]][1] for c in chans]
+    pixel_bytes = sum(d.itemsize for d in dtypes)
     comp = need("compression", "compression", 1)[0]
     if comp not in COMPRESSIONS:
         raise ExrError("compression %s is not supported" % _REFUSED_COMPRESSIONS.get(comp, comp))
@@ -122,19 +131,19 @@ def read(data):
     for name, kind, size in (("pixelAspectRatio", "float", 4), ("screenWindowCenter", "v2f", 8), ("screenWindowWidth", "float", 4)):
         need(name, kind, size)
     W, H = x1 + 1, y1 + 1
-    bps = dtype.itemsize
     nb = (H + L - 1) // L
     if at + 8 * nb > len(data):
         raise ExrError("the offset table passes the end of the file")
     offsets = struct.unpack_from("<%dQ" % nb, data, at)
     out = np.empty((H, W, 3), dtype)
+    planes = {n: np.empty((H, W), d) for n, d in zip(names, dtypes)}
     blocks = []
     for b, off in enumerate(offsets):
         if off + 8 > len(data):
             raise ExrError("block %d lies behind the end of the file" % b)
         y, size = struct.unpack_from("<ii", data, off)
         lines = min(L, H - b * L)
-        P = lines * W * 3 * bps
+        P = lines * W * pixel_bytes
         if y != b * L:
             raise ExrError("the offset table's entry %d points at a block of line %d" % (b, y))
         if size < 0 or size > P or off + 8 + size > len(data):
@@ -147,7 +156,13 @@ def read(data):
             body = unpredict(zlib.decompress(body))
             if len(body) != P:
                 raise ExrError("block %d inflates to %d bytes, not %d" % (b, len(body), P))
-        planes = np.frombuffer(body, dtype).reshape(lines, 3, W)      # per line: B, G, R
-        out[b * L:b * L + lines] = planes[:, ::-1, :].transpose(0, 2, 1)
+        rows = np.frombuffer(body, np.uint8).reshape(lines, W * pixel_bytes)      # per line: every channel's W samples, in the list's order
+        at = 0
+        for n, d in zip(names, dtypes):
+            planes[n][b * L:b * L + lines] = np.ascontiguousarray(rows[:, at:at + W * d.itemsize]).view(d)
+            at += W * d.itemsize
         blocks.append(dict(y=y, offset=off, data_size=size, raw=raw))
-    return out, dict(width=W, height=H, pixel_type=type_name, compression=comp_name, lines_per_block=L, blocks=blocks, attributes=order)
+    for k, n in enumerate("RGB"):
+        out[:, :, k] = planes[n]
+    return out, dict(width=W, height=H, pixel_type=type_name, compression=comp_name, lines_per_block=L, blocks=blocks, attributes=order,
+                     channel_names=names, channel_types={n: PIXEL_TYPES[c[1]][0] for n, c in zip(names, chans)}, channels=planes)

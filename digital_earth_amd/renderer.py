@@ -1161,15 +1161,46 @@ class Renderer:
         s.scale = float(scale)
         return s
 
-    def set_exr(self, source="mean", pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0):
+    @staticmethod
+    def _ex_aov_mask(aovs):
+        """Names of AOV groups (or "all", or one name) -> the DE_EXR_AOV_* mask."""
+        if isinstance(aovs, str):
+            aovs = (aovs,)
+        mask = 0
+        for name in aovs or ():
+            if name == "all":
+                mask |= _native.EXR_AOV_ALL
+            elif name in _native.EXR_AOVS:
+                mask |= _native.EXR_AOVS[name]
+            else:
+                raise ValueError("aovs must be names of %s, or \"all\"" % (tuple(_native.EXR_AOVS),))
+        return mask
+
+    def set_exr(self, source="mean", pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0, aovs=()):
         """The settings of fetch_exr(): one complete OpenEXR scan-line file of the SCENE-LINEAR frame, converted and deflated on the GPU in front of
         the display transform.  source "mean": the sums divided by the sample count (per tile inside an adaptive frame); "denoised" / "history" /
         "bloom" / "local_exposure": the image fetch_denoised_hdr() / fetch_history_hdr() / fetch_bloom_hdr() / fetch_local_exposure_hdr() hand
         out, refused as those are while the stage is off.  pixel_type "half" (clamped to +-65504, nearest even) or "float"; compression "zip"
         (16 lines per block), "zips" (one) or "none"; chunk_bytes: predicted bytes per independent deflate chunk, 1024 ... 65535 (None: the
         default); scale: finite, > 0, multiplied into every sample.  The file is always the context's size: output scaling and the look do not
-        apply.  Refused (DE_ERR_STATE) while lagged EXR fetches are in flight.  No other fetch is affected."""
-        check(self._lib.de_set_exr(self._h, ctypes.byref(self._ex_settings(source, pixel_type, compression, chunk_bytes, scale))))
+        apply.  Refused (DE_ERR_STATE) while lagged EXR fetches are in flight.  No other fetch is affected.
+        aovs: names of channel groups written beside B, G, R in the same file (include/digital_earth_exr_aovs.h) — "depth" (Z, metres,
+        always float), "normal" (N.X, N.Y, N.Z), "albedo" (albedo.R, .G, .B), "coverage", "transmittance", "variance" (variance.R, .G, .B of the
+        mean, always float: needs the denoiser on since before the frame's first sample, or an adaptive frame), "samples" (always float) — or "all".
+        () : none, the three-channel file.  digital_earth_amd.exr.read returns them in info["channels"].  A refused call changes nothing."""
+        s, mask = self._ex_settings(source, pixel_type, compression, chunk_bytes, scale), self._ex_aov_mask(aovs)
+        W, H = self.image_res
+        if mask:      # what de_set_exr_aovs could refuse behind the new settings, first (without AOVs a frame past the limit is refused at the fetch, as before)
+            check(self._lib.de_debug_exr_aov_framing(ctypes.byref(s), mask, int(W), int(H), None, 0, None, None))
+        check(self._lib.de_set_exr_aovs(self._h, 0))      # refuses while fetches are in flight, as de_set_exr does; the mask goes on behind the settings it is checked against
+        check(self._lib.de_set_exr(self._h, ctypes.byref(s)))
+        check(self._lib.de_set_exr_aovs(self._h, mask))
+
+    def exr_aovs(self):
+        """The names of the AOV channel groups in force (set_exr's aovs), in the order of their bits."""
+        mask = ctypes.c_uint32()
+        check(self._lib.de_get_exr_aovs(self._h, ctypes.byref(mask)))
+        return tuple(name for name, bit in _native.EXR_AOVS.items() if mask.value & bit)
 
     def exr(self):
         """The EXR settings as a dict (set_exr's keywords) plus size = (width, height) and capacity, the proven bound of any frame's length."""
@@ -1210,6 +1241,36 @@ class Renderer:
         check(self._lib.de_debug_exr_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
         out = ctypes.create_string_buffer(int(cap.value))
         check(self._lib.de_debug_exr(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
+        return out.raw[:int(n.value)]
+
+    def debug_exr_aovs(self, image, guides=None, s2=None, counts=None, aovs=(), pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0):
+        """The encoder with AOV channels once on given arrays, rows top-down, of any size (de_debug_exr_aovs): image (H, W, 3) is read as the sums,
+        guides (H, W, 9) in fetch_guides' order, s2 (H, W, 3), counts (H, W) the divisor per pixel (None: 1).  An array no selected channel reads
+        may be None.  aovs: names as for set_exr, or the mask itself.  Returns the file as bytes."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (H, W, 3)")
+        H, W = image.shape[:2]
+        keep = []
+
+        def arg(a, shape, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError("%s must have shape %s" % (what, shape))
+            keep.append(a)
+            return a.ctypes.data
+        mask = int(aovs) if isinstance(aovs, (int, np.integer)) else self._ex_aov_mask(aovs)
+        s = self._ex_settings("mean", pixel_type, compression, chunk_bytes, scale)
+        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.de_debug_exr_aov_framing(ctypes.byref(s), mask, W, H, None, 0, None, ctypes.byref(cap)))
+        sentinel = 64
+        out = ctypes.create_string_buffer(b"\xA5" * (int(cap.value) + sentinel), int(cap.value) + sentinel)
+        check(self._lib.de_debug_exr_aovs(self._h, image.ctypes.data, arg(guides, (H, W, 9), "guides"), arg(s2, (H, W, 3), "s2"), arg(counts, (H, W), "counts"),
+                                          W, H, ctypes.byref(s), mask, out, ctypes.c_uint64(int(cap.value)), ctypes.byref(n)))
+        if out.raw[int(cap.value):] != b"\xA5" * sentinel or out.raw[int(n.value):int(cap.value)] != b"\xA5" * (int(cap.value) - int(n.value)):
+            raise RuntimeError("de_debug_exr_aovs wrote behind the file's length")
         return out.raw[:int(n.value)]
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)

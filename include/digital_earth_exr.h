@@ -51,8 +51,9 @@
  * bytes, by the raw fallback).  Every store is checked against its slot and the capacity: one that would pass is not made, raises the status word and
  * ends the conversion with DE_ERR_INTERNAL.  LIMIT: H W 3 bps <= 2^27 (DE_ERR_INVALID otherwise): 3840 x 2160 at FLOAT fits.
  * DE_EXR_DEFAULT_CHUNK = 32768 is the PNG output's measured default; for this output it is UNMEASURED (the rule: profiles/exr.md).
- * OUT OF SCOPE: PIZ / PXR24 / B44 / DWA compression, tiles, multi-part and deep files, alpha, extra layers (guides, variance, depth), luminance /
+ * OUT OF SCOPE: PIZ / PXR24 / B44 / DWA compression, tiles, multi-part and deep files, alpha, luminance /
  * chroma, the `chromaticities` attribute (absent means Rec.709 primaries and D65, which is what the sums are), LZ77 beyond distance 1.
+ * Extra channels beside B, G, R (depth, normal, albedo, coverage, transmittance, variance, samples) are digital_earth_exr_aovs.h's.
  *
  * The conversion runs on the context stream with no host synchronisation in it.  Every other fetch and its buffers are untouched; the EXR fetches have
  * device buffers, a pinned staging buffer and a four-deep pinned ring of their own, all allocated on first use.  With none of the calls below made,
