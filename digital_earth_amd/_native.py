@@ -87,6 +87,12 @@ class DeOutputScale(ctypes.Structure):
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("enabled", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("filter", ctypes.c_int32)]
 
 
+class DePanorama(ctypes.Structure):
+    """`de_panorama` (include/digital_earth_panorama.h): the projection, size, apron, supersampling and frame of the 360° output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("on", ctypes.c_int32), ("projection", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("aperture_deg", ctypes.c_float), ("apron", ctypes.c_int32), ("supersample", ctypes.c_int32), ("basis", ctypes.c_float * 9)]
+
+
 class DeHdrOutput(ctypes.Structure):
     """`de_hdr_output` (include/digital_earth_hdr_output.h): the HDR display output — peak luminance, gamut, transfer, and the format of its pixels."""
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("on", ctypes.c_int32), ("peak_nits", ctypes.c_float), ("gamut", ctypes.c_int32), ("transfer", ctypes.c_int32),
@@ -194,6 +200,7 @@ DEBUG_SYMBOLS = {
     "de_debug_pixels": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DePixels), ctypes.c_uint32, _P]),
     "de_debug_output_scale": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeOutputScale), _P]),
     "de_debug_output_scale_weights": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, ctypes.POINTER(ctypes.c_int)]),
+    "de_debug_panorama": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), _P]),
     "de_debug_hdr_consts": (ctypes.c_int, [_P, ctypes.POINTER(DeHdrOutput), _P]),
     "de_texture_info": (ctypes.c_int, [_P, ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 3),
     "de_last_reduce_ms": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_float)]),
@@ -270,6 +277,16 @@ OUTPUT_SCALE_SYMBOLS = {
     "de_set_output_scale": (ctypes.c_int, [_P, ctypes.POINTER(DeOutputScale)]),
     "de_get_output_scale": (ctypes.c_int, [_P, ctypes.POINTER(DeOutputScale)]),
     "de_output_size": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+}
+
+# panorama output: include/digital_earth_panorama.h (same library, additions only; not part of the binder's header)
+_F3 = ctypes.POINTER(ctypes.c_float)
+PANORAMA_SYMBOLS = {
+    "de_set_panorama": (ctypes.c_int, [_P, ctypes.POINTER(DePanorama)]),
+    "de_get_panorama": (ctypes.c_int, [_P, ctypes.POINTER(DePanorama)]),
+    "de_panorama_face_camera": (ctypes.c_int, [_P, ctypes.c_int, _F3, _F3, _F3, _F3]),
+    "de_panorama_capture": (ctypes.c_int, [_P, ctypes.c_int]),
+    "de_panorama_captured": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32)]),
 }
 
 # HDR display output: include/digital_earth_hdr_output.h (same library, additions only; not part of the binder's header)
@@ -431,7 +448,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

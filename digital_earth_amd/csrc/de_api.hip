@@ -406,8 +406,24 @@ int de_flush(de_ctx* c) {
     return frame_status(c);  // an abort already known (the words are host-visible): a host framework's own collective must not ship that frame
 }
 
-int de_render_to_image(de_ctx* c, const float** device_image) {
+/* de_render_to_image (capture_face < 0), and de_panorama_capture's half of it (capture_face = 0 ... 5: the chain, the display launch and the look as
+ * they stand, then the displayed image into that face's slot instead of the stage that makes the shown image; include/digital_earth_panorama.h). */
+static int render_to_image_or_slot(de_ctx* c, const float** device_image, int capture_face);
+
+int de_render_to_image(de_ctx* c, const float** device_image) { return render_to_image_or_slot(c, device_image, -1); }
+
+static int render_to_image_or_slot(de_ctx* c, const float** device_image, int capture_face) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
+    const bool capture = capture_face >= 0;
+    if (!capture && c->pano.on) {      // the shown image is made of the six captured faces alone: the frame as it stands is not displayed, nothing of it is read
+        int rc = pano_refusal(c);      // ahead of everything: a refused call changes nothing
+        if (rc) return rc;
+        HIP_TRY(hipSetDevice(c->device));
+        rc = run_panorama(c);
+        if (rc) return rc;
+        if (device_image) *device_image = shown_image(c);
+        return DE_OK;
+    }
     DisplayArgs d;
     bool per_tile;
     int rc = display_chain(c, STOP_IMAGE, &d, &per_tile);
@@ -427,6 +443,12 @@ int de_render_to_image(de_ctx* c, const float** device_image) {
     if (c->lk_on) {              // the look LUTs, in place on d_image; behind ev_main too: the stage reads nothing the next frame's sums write
         lk_launch(c->stream, c->d_image, (uint64_t)c->W * (uint64_t)c->H, c->lk, c->lk_dev);
         HIP_TRY(hipGetLastError());
+    }
+    if (capture) {               // behind the look, ahead of any pack: the displayed image into the face's slot
+        const size_t n = (size_t)c->W * (size_t)c->W * 3;
+        HIP_TRY(hipMemcpyAsync(c->pano_faces + (size_t)capture_face * n, c->d_image, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        c->pano_mask |= 1u << capture_face;
+        return DE_OK;
     }
     if (os_active(c)) { rc = run_output_scale(c); if (rc) return rc; }      // behind ev_main: the next frame's sums do not wait for the resampling
     if (device_image) *device_image = shown_image(c);
@@ -1182,6 +1204,7 @@ int de_set_output_scale(de_ctx* c, const de_output_scale* s) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
     int ow = 0, oh = 0;
     { int rc = os_settings_check(s, c->W, c->H, &ow, &oh); if (rc) return rc; }
+    if (s->enabled && c->pano.on) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): it makes the shown image, and a context has one");
     for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
     c->os = *s;
     c->os.enabled = s->enabled ? 1 : 0; c->os.width = ow; c->os.height = oh;
@@ -1198,6 +1221,77 @@ int de_output_size(de_ctx* c, int* width, int* height) {
     *width = out_w(c); *height = out_h(c);
     return DE_OK;
 }
+/* ---- the panorama output: include/digital_earth_panorama.h (panorama_kernels.hip, panorama_body.h) */
+int de_set_panorama(de_ctx* c, const de_panorama* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    if (c->W != c->H) return fail(DE_ERR_INVALID, "a panorama's face camera is square: the context needs W == H");
+    { int rc = pano_settings_check(s, c->W); if (rc) return rc; }
+    if (s->on && c->os.enabled) return fail(DE_ERR_STATE, "output scaling is on (de_set_output_scale): it makes the shown image, and a context has one");
+    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = c->pano_faces.ensure((size_t)DE_PANO_FACES * (size_t)c->W * (size_t)c->W * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
+    { int rc = c->pano_out.ensure((size_t)s->width * (size_t)s->height * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
+    c->pano = *s;
+    c->pano.on = s->on ? 1 : 0;
+    c->pano_mask = 0u;
+    pano_make_consts(c->pano, c->W, &c->pano_consts);
+    return DE_OK;
+}
+int de_get_panorama(de_ctx* c, de_panorama* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->pano;
+    return DE_OK;
+}
+int de_panorama_face_camera(de_ctx* c, int face, const float* pos, float* look_at, float* up, float* fov) {
+    if (!c || !pos || !look_at || !up || !fov) return fail(DE_ERR_INVALID, "null argument");
+    if (face < 0 || face >= DE_PANO_FACES) return fail(DE_ERR_INVALID, "face must lie in 0 ... 5");
+    if (c->W != c->H) return fail(DE_ERR_INVALID, "a panorama's face camera is square: the context needs W == H");
+    double look[3], u[3];
+    pano_face_frame(c->pano.basis, face, look, u);
+    const double len = sqrt((double)pos[0] * pos[0] + (double)pos[1] * pos[1] + (double)pos[2] * pos[2]), L = len > 1.0 ? len : 1.0;
+    for (int k = 0; k < 3; ++k) { look_at[k] = (float)((double)pos[k] + L * look[k]); up[k] = (float)u[k]; }
+    *fov = (float)((double)c->W / (double)(c->W - 2 * c->pano.apron));
+    return DE_OK;
+}
+int de_panorama_capture(de_ctx* c, int face) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (face < 0 || face >= DE_PANO_FACES) return fail(DE_ERR_INVALID, "face must lie in 0 ... 5");
+    if (!c->pano.on) return fail(DE_ERR_STATE, "the panorama is off (de_set_panorama)");
+    // what would print the face's border into the picture: a seam along every cube edge
+    if (c->p.vignette_strength != 0.0f) return fail(DE_ERR_STATE, "a panorama face cannot be captured with a vignette (vignette_strength != 0): it darkens every face's border");
+    if (c->ae_on) return fail(DE_ERR_STATE, "a panorama face cannot be captured under auto-exposure: every face would be metered on its own");
+    if (c->bl_on) return fail(DE_ERR_STATE, "a panorama face cannot be captured under bloom: the glare ends at the face's border");
+    if (c->lx_on) return fail(DE_ERR_STATE, "a panorama face cannot be captured under local exposure: its pyramid ends at the face's border");
+    if (c->hs_on) return fail(DE_ERR_STATE, "a panorama face cannot be captured under history reprojection: the history belongs to another face's camera");
+    return render_to_image_or_slot(c, nullptr, face);
+}
+int de_panorama_captured(de_ctx* c, uint32_t* mask) {
+    if (!c || !mask) return fail(DE_ERR_INVALID, "null argument");
+    *mask = c->pano_mask;
+    return DE_OK;
+}
+/* include/digital_earth_debug.h: the kernel once on host-given faces.  Buffers and tables of its own; the context's setting and slots are not touched.
+ * The arguments and the settings are checked before the context is read. */
+int de_debug_panorama(de_ctx* c, const float* faces, int n, const de_panorama* s, float* out) {
+    if (!c || !faces || !s || !out || n < 4 || n > 16384) return fail(DE_ERR_INVALID, "bad arguments (faces of 4 ... 16384 pixels a side)");
+    { int rc = pano_settings_check(s, n); if (rc) return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<float> d_faces, d_out;
+    de_ctx::PanoTab tab;
+    PanoArgs k = {};
+    pano_make_consts(*s, n, &k);
+    const size_t in_bytes = (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float), out_bytes = (size_t)s->width * (size_t)s->height * 3 * sizeof(float);
+    HIP_TRY(d_faces.ensure(in_bytes));
+    HIP_TRY(d_out.ensure(out_bytes));
+    if (s->projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, tab, s->width, s->height, s->supersample); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(d_faces, faces, in_bytes, hipMemcpyHostToDevice, c->stream));
+    int rc = pano_launch(c->stream, *s, k, n, d_faces, tab, d_out);
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return DE_OK;
+}
+
 /* include/digital_earth_debug.h: the stage once on a host-given image.  Buffers and tables of its own; the context's setting is not touched. */
 int de_debug_output_scale(de_ctx* c, const float* image, int W, int H, const de_output_scale* s, float* out) {
     if (!c || !image || !s || !out || W <= 0 || H <= 0 || (W % 16) != 0 || (H % 8) != 0 || (long long)W * H > (1ll << 28))
@@ -1574,6 +1668,7 @@ int de_fetch_exr(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
 }
 int de_fetch_exr_begin(de_ctx* c) {
     if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = ex_pano_refusal(c); if (rc) return rc; }
     { int rc = ex_ctx_shape_check(c); if (rc) return rc; }
     const ExrGeometry g = ex_ctx_geometry(c);
     return coded_begin(c, c->ex_coded, g.front + g.raw / 2, g.capacity, [c](int k) { return ex_render(c, c->ex_coded.cell[k]); });      // the first: the front and half the raw bytes

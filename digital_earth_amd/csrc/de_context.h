@@ -7,6 +7,7 @@
 #include "../../include/digital_earth_pixels.h"
 #include "../../include/digital_earth_local_exposure.h"
 #include "../../include/digital_earth_output_scale.h"
+#include "../../include/digital_earth_panorama.h"
 #include "../../include/digital_earth_hdr_output.h"
 #include "../../include/digital_earth_video.h"
 #include "../../include/digital_earth_look.h"
@@ -41,6 +42,7 @@
 #include "history_kernels.hip"
 #include "pixels_kernels.hip"
 #include "output_scale_kernels.hip"
+#include "panorama_kernels.hip"
 #include "local_exposure_kernels.hip"
 #include "hdr_output_kernels.hip"
 #include "videoframe_kernels.hip"
@@ -297,6 +299,13 @@ struct de_ctx {
         int n_src = 0, n_dst = 0, filter = -1, taps = 0;
     } os_tab[2];                    // [0] along v, [1] along u
     Dev<float> os_mid, os_out;
+    // Panorama output (include/digital_earth_panorama.h).  Allocated by the first de_set_panorama that succeeds: six face slots of N x N x 3
+    // floats in one buffer and the output (width, height, 3); the equirect's four tables on first use, rebuilt when the size or S changes.  Per context.
+    de_panorama pano = {(uint32_t)sizeof(de_panorama), 0, DE_PANO_EQUIRECT, 0, 0, 180.0f, 1, 2, {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}};
+    uint32_t pano_mask = 0;         // bit k: slot k holds a face (cleared by de_set_panorama alone)
+    PanoArgs pano_consts = {};      // of `pano`: fov, scale, half_aperture, m — once per de_set_panorama; the pointers are filled at the launch
+    Dev<float> pano_faces, pano_out;
+    struct PanoTab { Dev<float> t[4]; int width = 0, height = 0, S = 0; } pano_tab;      // sin lon, cos lon, sin lat, cos lat
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.

@@ -329,10 +329,11 @@ int lx_run(de_ctx* c, const de_local_exposure& x, DisplayArgs& d, bool& per_tile
 int run_local_exposure(de_ctx* c, DisplayArgs& d, bool& per_tile) { return lx_run(c, c->lx, d, per_tile); }
 // ---- output scaling (include/digital_earth_output_scale.h, output_scale_kernels.hip): every call that hands out the displayed image sizes itself from these
 bool os_active(const de_ctx* c) { return c->os.enabled && c->os.width > 0 && (c->os.width != c->W || c->os.height != c->H); }      // on at W x H is the identity: nothing runs
-int out_w(const de_ctx* c) { return os_active(c) ? c->os.width : c->W; }
-int out_h(const de_ctx* c) { return os_active(c) ? c->os.height : c->H; }
+// the panorama (include/digital_earth_panorama.h, below) stands in the same place; de_set_output_scale and de_set_panorama refuse each other, so at most one of the two is on
+int out_w(const de_ctx* c) { return c->pano.on ? c->pano.width : os_active(c) ? c->os.width : c->W; }
+int out_h(const de_ctx* c) { return c->pano.on ? c->pano.height : os_active(c) ? c->os.height : c->H; }
 size_t out_image_bytes(const de_ctx* c) { return (size_t)out_w(c) * (size_t)out_h(c) * 3 * sizeof(float); }
-const float* shown_image(const de_ctx* c) { return os_active(c) ? c->os_out : c->d_image; }
+const float* shown_image(const de_ctx* c) { return c->pano.on ? c->pano_out : os_active(c) ? c->os_out : c->d_image; }
 // The settings against a source size; *ow, *oh = the output size they ask for (0, 0: the source's).
 int os_settings_check(const de_output_scale* s, int W, int H, int* ow, int* oh) {
     if (s->struct_bytes != (uint32_t)sizeof(de_output_scale)) return fail(DE_ERR_INVALID, "de_output_scale.struct_bytes does not match this library's struct");
@@ -392,6 +393,89 @@ int run_output_scale(de_ctx* c) {
     rc = c->os_out.ensure((size_t)ow * (size_t)oh * 3 * sizeof(float), "output scaling's buffers");
     if (rc) return rc;
     return os_launch(c->stream, c->d_image, W, H, ow, oh, c->os_tab[0], c->os_tab[1], c->os_mid, c->os_out);
+}
+// ---- the panorama output (include/digital_earth_panorama.h, panorama_kernels.hip, panorama_body.h)
+// The settings against a face size N (the context's W = H, or de_debug_panorama's n).
+int pano_settings_check(const de_panorama* s, int N) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_panorama)) return fail(DE_ERR_INVALID, "de_panorama.struct_bytes does not match this library's struct");
+    if (s->projection != DE_PANO_EQUIRECT && s->projection != DE_PANO_FISHEYE) return fail(DE_ERR_INVALID, "de_panorama.projection must be DE_PANO_EQUIRECT or DE_PANO_FISHEYE");
+    if (s->width <= 0 || s->height <= 0 || (s->width % 16) != 0 || (s->height % 8) != 0) return fail(DE_ERR_INVALID, "de_panorama: width must be a positive multiple of 16 and height of 8");
+    if ((long long)s->width * s->height > (1ll << 28)) return fail(DE_ERR_INVALID, "de_panorama: width * height must not exceed 2^28");
+    if (s->projection == DE_PANO_FISHEYE) {
+        if (s->width != s->height) return fail(DE_ERR_INVALID, "de_panorama: a fisheye frame needs width == height");
+        if (!(s->aperture_deg > 0.0f && s->aperture_deg <= 360.0f)) return fail(DE_ERR_INVALID, "de_panorama.aperture_deg must lie in (0, 360]");      // NaN fails both
+    }
+    if (s->apron < 1 || s->apron > N / 4) return fail(DE_ERR_INVALID, "de_panorama.apron must lie in 1 ... N / 4");
+    if (s->supersample < 1 || s->supersample > PANO_MAX_S) return fail(DE_ERR_INVALID, "de_panorama.supersample must lie in 1 ... 4");
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)s->basis[3 * i + k] * (double)s->basis[3 * j + k];
+            if (!(fabs(d - (i == j ? 1.0 : 0.0)) <= 1e-4)) return fail(DE_ERR_INVALID, "de_panorama.basis must be orthonormal within 1e-4");      // NaN fails
+        }
+    return DE_OK;
+}
+// The header's face table: look and up of face 0 ... 5 from basis = r, u, f, in double.
+void pano_face_frame(const float* basis, int face, double look[3], double up[3]) {
+    static const int look_of[6] = {0, 0, 1, 1, 2, 2}, up_of[6] = {1, 1, 2, 2, 1, 1};
+    static const double look_sign[6] = {1, -1, 1, -1, 1, -1}, up_sign[6] = {1, 1, -1, 1, 1, 1};
+    for (int k = 0; k < 3; ++k) { look[k] = look_sign[face] * (double)basis[3 * look_of[face] + k]; up[k] = up_sign[face] * (double)basis[3 * up_of[face] + k]; }
+}
+// What the kernel reads of the settings beside the sizes: fov, scale, the half aperture and every face's m, as the header defines them.
+void pano_make_consts(const de_panorama& s, int N, PanoArgs* k) {
+    const double pi = 3.14159265358979323846;
+    k->fov = (float)((double)N / (double)(N - 2 * s.apron));
+    k->scale = (float)((double)N / (2.0 * (double)k->fov));
+    k->half_aperture = (float)((double)s.aperture_deg * pi / 360.0);
+    for (int face = 0; face < 6; ++face) {
+        double d[3], up[3], du[3], dv[3];
+        pano_face_frame(s.basis, face, d, up);
+        auto cross = [](const double* a, const double* b, double* o) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
+        auto normalize = [](double* v) { const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); v[0] /= n; v[1] /= n; v[2] /= n; };
+        cross(d, up, du); normalize(du);
+        cross(du, d, dv); normalize(dv);
+        const int axis = face / 2, e1 = axis == 0 ? 1 : 0, e2 = axis == 2 ? 1 : 2;      // the other two, in r, u, f order
+        double m[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int c = 0; c < 3; ++c) {
+            m[0] += (double)s.basis[3 * e1 + c] * du[c]; m[1] += (double)s.basis[3 * e2 + c] * du[c];
+            m[2] += (double)s.basis[3 * e1 + c] * dv[c]; m[3] += (double)s.basis[3 * e2 + c] * dv[c];
+        }
+        for (int c = 0; c < 4; ++c) k->m[face][c] = (float)m[c];
+    }
+}
+// The equirect's tables on the device, rebuilt only when the size or S changed.  The upload reads pageable host memory that dies with this call: waited for.
+int pano_tables_ensure(hipStream_t stream, de_ctx::PanoTab& d, int width, int height, int S) {
+    if (d.t[0] && d.width == width && d.height == height && d.S == S) return DE_OK;
+    std::vector<float> h[4];
+    const double pi = 3.14159265358979323846;
+    pano_build_tables(width, S, 2.0 * pi, &h[0], &h[1]);
+    pano_build_tables(height, S, pi, &h[2], &h[3]);
+    d.S = 0;
+    for (int k = 0; k < 4; ++k) { int rc = d.t[k].ensure(h[k].size() * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(d.t[k], h[k].data(), h[k].size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    d.width = width; d.height = height; d.S = S;
+    return DE_OK;
+}
+// faces [6][N][N][3] -> out (width, height, 3) on `stream`; `k` carries the settings' constants (pano_make_consts), `tab` the equirect's tables.
+int pano_launch(hipStream_t stream, const de_panorama& s, const PanoArgs& k, int N, const float* faces, const de_ctx::PanoTab& tab, float* out) {
+    PanoArgs a = k;
+    a.faces = faces; a.out = out; a.N = N; a.width = s.width; a.height = s.height; a.S = s.supersample; a.fisheye = s.projection == DE_PANO_FISHEYE ? 1 : 0;
+    a.sin_lon = tab.t[0]; a.cos_lon = tab.t[1]; a.sin_lat = tab.t[2]; a.cos_lat = tab.t[3];
+    const unsigned long long blocks = (unsigned long long)pano_tiles(s.width) * (unsigned long long)pano_tiles(s.height);      // at most 2^28 / 128 + ...: one dimension holds it
+    hipLaunchKernelGGL(panorama_kernel, dim3((unsigned)blocks), dim3(PANO_THREADS), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return DE_OK;
+}
+// What every call that hands out the shown image answers before anything is enqueued while the stage is on without its six faces.
+int pano_refusal(const de_ctx* c) {
+    if (c->pano.on && c->pano_mask != 63u) return fail(DE_ERR_STATE, "the panorama is on and fewer than six faces are captured (de_panorama_capture)");
+    return DE_OK;
+}
+// Behind the display on the context stream: the six slots -> pano_out.
+int run_panorama(de_ctx* c) {
+    if (c->pano.projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, c->pano_tab, c->pano.width, c->pano.height, c->pano.supersample); if (rc) return rc; }
+    return pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->pano_faces, c->pano_tab, c->pano_out);
 }
 // ---- the packed outputs (pack.h): their settings share the quantiser's mode, their launches the grid (pack_grid).  `who`: the settings struct's name.
 int pack_mode_check(int mode, const char* who) {
@@ -869,6 +953,11 @@ int ex_aov_refusal(de_ctx* c) {
         return fail(DE_ERR_STATE, "the EXR variance channels need the sums of squares of every sample of this frame: turn the denoiser on (de_set_denoise) before the frame's first sample, or render adaptively");
     return DE_OK;
 }
+// The EXR output sits in FRONT of the display: a face's scene-linear frame is not the panorama, and a scene-linear panorama does not exist.
+int ex_pano_refusal(const de_ctx* c) {
+    if (c->pano.on) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): the EXR output reads the frame in front of the display, where no panorama exists");
+    return DE_OK;
+}
 int ex_length(const void* word, uint64_t* len) {      // its coders raise no range status
     static const char* const text = "the EXR encoder met a piece longer than its proven worst case: nothing was written past a buffer";
     return coded_read_word(word, len, text, text);
@@ -877,6 +966,7 @@ int ex_length(const void* word, uint64_t* len) {      // its coders raise no ran
 // the display launch would read with every stage off; the other sources are the chain left at their stage — its refusals, its side effects.
 int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
     static const DisplayStop stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
+    { int rc = ex_pano_refusal(c); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
     const ExrGeometry g = ex_ctx_geometry(c);
     int rc = ex_ctx_shape_check(c);

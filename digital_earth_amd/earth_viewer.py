@@ -184,7 +184,7 @@ def _rgb_picture(px):
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, look=None, look_strength=1.0, exr_aovs=(), **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, look=None, look_strength=1.0, exr_aovs=(), panorama=None, **renderer_kwargs):
         """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
         in frame()'s loop instead of restarting at one sample per pixel.  local_exposure: the same for Renderer.set_local_exposure — every frame is
         dodged and burned on the GPU ahead of the display transform.  output_res: None, or the (width, height) at which frames are delivered and
@@ -194,7 +194,10 @@ class EarthViewer:
         look: None, the path of a 3D .cube file or a digital_earth_amd.cube.Cube — every frame is graded through it on the GPU behind the display
         transform, mixed with the ungraded frame by look_strength (Renderer.set_look; a shaper or trilinear interpolation: call that directly).
         exr_aovs: names of channel groups ("depth", "normal", "albedo", "coverage", "transmittance", "variance", "samples", or "all") that
-        save("x.exr"), frame(exr=True) and record("f%05d.exr") write beside B, G, R (Renderer.set_exr's aovs)."""
+        save("x.exr"), frame(exr=True) and record("f%05d.exr") write beside B, G, R (Renderer.set_exr's aovs).
+        panorama: None / False, True (Renderer.set_panorama's defaults: a 4 N x 2 N equirectangular frame) or a dict of its keywords — screen_res must
+        be square, (N, N), and the vignette is turned off (it would print every face's border); frame(panorama=True) then renders the six cube faces around the camera and hands out the 360° frame, and save() and
+        record() write it through the writers as they are."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
@@ -212,6 +215,9 @@ class EarthViewer:
             self.renderer.set_look(look, strength=look_strength)
         if exr_aovs:
             self.renderer.set_exr(aovs=exr_aovs)
+        if panorama:
+            self.renderer.vignette_strength = 0.0      # a vignette would darken every face's border: a capture under one is refused
+            self.renderer.set_panorama(**(panorama if isinstance(panorama, dict) else {}))
         self.config = None
         if config is not None:
             self.load_config(config)
@@ -283,13 +289,20 @@ class EarthViewer:
         png=True (a keyword beside the sliders too): the same for one complete PNG file in the settings of Renderer.set_png() — Renderer.fetch_png,
         through the PNG ring; finish_png() ends that loop.  It goes with none of the others.
         exr=True (a keyword beside the sliders too): the same for one complete OpenEXR file of the scene-linear frame in the settings of
-        Renderer.set_exr() — Renderer.fetch_exr, through the EXR ring; finish_exr() ends that loop.  It goes with none of the others."""
+        Renderer.set_exr() — Renderer.fetch_exr, through the EXR ring; finish_exr() ends that loop.  It goes with none of the others.
+        panorama=True (a keyword beside the sliders too; the viewer was made with panorama=...): step 2 is Renderer.render_panorama(spp) — the six
+        cube faces around the camera, `spp` each, never accumulated over iterations — and what is handed out (the float field, or with pixels /
+        hdr_pixels / video / jpeg / png = True that output, pipelined or not) is the 360° frame at Renderer.output_size() — so
+        record(path, n, panorama=True) writes a 360° Y4M, Motion-JPEG or PNG sequence through the writers as they are.  Not with exr=True."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
         video = bool(sliders.pop("video", False))
         jpeg = bool(sliders.pop("jpeg", False))
         png = bool(sliders.pop("png", False))
         exr = bool(sliders.pop("exr", False))
+        panorama = bool(sliders.pop("panorama", False))
+        if panorama and exr:
+            raise ValueError("panorama=True does not go with exr=True: the EXR output sits in front of the display, where no panorama exists")
         if exr and (pixels or hdr_pixels or video or jpeg or png):
             raise ValueError("exr=True goes with none of pixels=True, hdr_pixels=True, video=True, jpeg=True and png=True")
         if png and (pixels or hdr_pixels or video or jpeg):
@@ -306,7 +319,10 @@ class EarthViewer:
             r.set_look_at(*self.camera.look_at)
             r.set_up(*self.camera._up)
             should_reset = True
-        r.accumulate(int(spp))                  # == accumulate() x spp, bit for bit
+        if panorama:
+            r.render_panorama(int(spp))         # six faces around the camera, `spp` each; the camera is put back and the frame left empty
+        else:
+            r.accumulate(int(spp))              # == accumulate() x spp, bit for bit
         frame = None
         if exr:
             frame = r.fetch_exr(copy=copy, lag=int(pipelined))

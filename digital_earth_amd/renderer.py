@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -845,6 +845,111 @@ class Renderer:
         first, w = np.empty(int(n_dst), np.int32), np.empty((int(n_dst), int(taps.value)), np.float32)
         check(self._lib.de_debug_output_scale_weights(self._h, int(n_src), int(n_dst), f, first.ctypes.data, w.ctypes.data, ctypes.byref(taps)))
         return first, w
+
+    # ------------------------------------------------------------------ panorama output (include/digital_earth_panorama.h)
+    PANORAMA_PROJECTIONS = ("equirect", "fisheye")
+    PANORAMA_FACES = ("+r", "-r", "+u", "-u", "+f", "-f")
+
+    def _panorama_settings(self, size, projection, aperture, apron, supersample, basis, on):
+        if projection not in self.PANORAMA_PROJECTIONS:
+            raise ValueError("projection must be one of %s" % (self.PANORAMA_PROJECTIONS,))
+        s = DePanorama()
+        s.struct_bytes = ctypes.sizeof(DePanorama)
+        s.on = 1 if on else 0
+        s.projection = self.PANORAMA_PROJECTIONS.index(projection)
+        s.width, s.height = int(size[0]), int(size[1])
+        s.aperture_deg, s.apron, s.supersample = float(aperture), int(apron), int(supersample)
+        b = np.asarray(np.eye(3) if basis is None else basis, dtype=np.float32).reshape(9)
+        for k in range(9):
+            s.basis[k] = float(b[k])
+        return s
+
+    def camera_basis(self):
+        """The current camera's right, up and forward as a (3, 3) float64 array, rows r, u, f: forward = look_at - camera_pos, right = forward x up,
+        up = right x forward, each normalised — the axes the renderer casts with."""
+        pos, at, up = (np.array([v[0], v[1], v[2]], dtype=np.float64) for v in (self._params.camera_pos, self._params.look_at, self._params.up))
+        f = at - pos
+        f /= np.linalg.norm(f)
+        r = np.cross(f, up)
+        r /= np.linalg.norm(r)
+        u = np.cross(r, f)
+        return np.stack([r, u / np.linalg.norm(u), f])
+
+    def set_panorama(self, size=None, projection="equirect", aperture=180.0, apron=1, supersample=2, basis=None, on=True):
+        """Deliver a 360° frame instead of the pinhole rectangle: while this is on and six cube faces are captured (render_panorama), fetch_image,
+        fetch_pixels, fetch_hdr_pixels, fetch_video, fetch_jpeg, fetch_png and render_to_image_device hand out `size` = (width, height): the faces
+        resampled on the GPU to an "equirect" frame (a VR player, a video site, an environment map; size=None: (4 N, 2 N)) or a "fisheye" dome master
+        of `aperture` degrees (width == height; size=None: (2 N, 2 N)).  The renderer must be square, image_res = (N, N).  apron: face pixels rendered
+        beyond 90° on every side (1 ... N / 4) so that no bilinear tap crosses a cube edge; supersample: S x S sub-positions per output pixel
+        (1 ... 4).  basis: the panorama's right, up and forward, (3, 3) rows r, u, f, orthonormal; None: the world axes — render_panorama(basis=None)
+        sets the current camera's.  Every call clears the captured faces.  Refused (DE_ERR_STATE) while output scaling is on or lagged fetches are in
+        flight; fetch_exr is refused while this is on.  on=False: every fetch returns the bytes it returned before."""
+        N = self.image_res[0]
+        if size is None:
+            size = (2 * N, 2 * N) if projection == "fisheye" else (4 * N, 2 * N)
+        check(self._lib.de_set_panorama(self._h, ctypes.byref(self._panorama_settings(size, projection, aperture, apron, supersample, basis, on))))
+
+    @property
+    def panorama(self):
+        """The panorama settings as a dict (set_panorama's keywords) plus captured, the tuple of the faces (0 ... 5 = +r, -r, +u, -u, +f, -f) held."""
+        s, mask = DePanorama(), ctypes.c_uint32()
+        check(self._lib.de_get_panorama(self._h, ctypes.byref(s)))
+        check(self._lib.de_panorama_captured(self._h, ctypes.byref(mask)))
+        return dict(size=(int(s.width), int(s.height)), projection=self.PANORAMA_PROJECTIONS[s.projection], aperture=float(s.aperture_deg), apron=int(s.apron),
+                    supersample=int(s.supersample), basis=np.array(list(s.basis), dtype=np.float32).reshape(3, 3), on=bool(s.on),
+                    captured=tuple(k for k in range(6) if mask.value >> k & 1))
+
+    def panorama_face_camera(self, face):
+        """The camera of cube face `face` under the current settings, at the current camera position: dict(look_at, up, fov) — set these with
+        aspect_scale = 1, reset, accumulate, capture_panorama_face(face)."""
+        pos, at, up, fov = (ctypes.c_float * 3)(*[float(v) for v in self._params.camera_pos]), (ctypes.c_float * 3)(), (ctypes.c_float * 3)(), ctypes.c_float()
+        check(self._lib.de_panorama_face_camera(self._h, int(face), pos, at, up, ctypes.byref(fov)))
+        return dict(look_at=tuple(float(v) for v in at), up=tuple(float(v) for v in up), fov=float(fov.value))
+
+    def capture_panorama_face(self, face):
+        """Display the frame as it stands and keep the image as cube face `face` (de_panorama_capture).  Refused (DE_ERR_STATE) under a vignette,
+        auto-exposure, bloom, local exposure or history: each would print the face's border into the picture."""
+        if not self._textures_copied:
+            self.copy_textures()
+        check(self._lib.de_panorama_capture(self._h, int(face)))
+
+    def render_panorama(self, spp, basis=None):
+        """The six faces of the panorama, `spp` samples per pixel each: for every face set its camera, reset, accumulate and capture; then put the
+        caller's camera, fov and aspect scale back (and reset: the frame left is the last face's).  basis=None: the current camera's right, up and
+        forward become the panorama's frame; otherwise (3, 3) rows r, u, f.  The settings are those of set_panorama(), which must be on."""
+        held = self.panorama
+        if not held["on"]:
+            raise RuntimeError("the panorama is off: set_panorama() first")
+        b = self.camera_basis() if basis is None else np.asarray(basis, dtype=np.float64).reshape(3, 3)
+        if not np.array_equal(b.astype(np.float32), held["basis"]):      # a new frame is a new setting (refused while lagged fetches are in flight); the same one keeps its slots, overwritten below
+            self.set_panorama(held["size"], held["projection"], held["aperture"], held["apron"], held["supersample"], b, True)
+        p = self._params
+        keep = (tuple(p.look_at), tuple(p.up), float(p.fov), float(p.aspect_scale))
+        try:
+            for face in range(6):
+                cam = self.panorama_face_camera(face)
+                p.look_at[0], p.look_at[1], p.look_at[2] = cam["look_at"]
+                p.up[0], p.up[1], p.up[2] = cam["up"]
+                p.fov, p.aspect_scale = cam["fov"], 1.0
+                self._push_params()
+                self.reset_framebuffer()
+                self.accumulate(int(spp))
+                self.capture_panorama_face(face)
+        finally:
+            (p.look_at[0], p.look_at[1], p.look_at[2]), (p.up[0], p.up[1], p.up[2]), p.fov, p.aspect_scale = keep[0], keep[1], keep[2], keep[3]
+            self._push_params()
+            self.reset_framebuffer()
+
+    def debug_panorama(self, faces, size, projection="equirect", aperture=180.0, apron=1, supersample=2, basis=None):
+        """The kernel once on given faces, (6, n, n, 3) float32, face k as fetch_image() returns the render of face k's camera (de_debug_panorama);
+        any n >= 4, free of this renderer's size; returns (width, height, 3) float32.  The renderer's own setting and faces are not touched."""
+        faces = np.ascontiguousarray(faces, dtype=np.float32)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 3:
+            raise ValueError("faces must have shape (6, n, n, 3)")
+        s = self._panorama_settings(size, projection, aperture, apron, supersample, basis, True)
+        out = np.empty((max(int(size[0]), 0), max(int(size[1]), 0), 3), dtype=np.float32)
+        check(self._lib.de_debug_panorama(self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(s), out.ctypes.data))
+        return out
 
     def _staging_view(self, ptr, _=None):
         ow, oh = self.output_size()

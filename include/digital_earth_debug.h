@@ -101,6 +101,13 @@ int de_debug_pixels(de_ctx* ctx, const float* image, int W, int H, const struct 
 struct de_output_scale;
 int de_debug_output_scale(de_ctx* ctx, const float* image, int W, int H, const struct de_output_scale* settings, float* out);
 int de_debug_output_scale_weights(de_ctx* ctx, int n_src, int n_dst, int filter, int32_t* first, float* weights, int* taps);
+/* The panorama kernel (include/digital_earth_panorama.h) once on host-given faces: faces[6][n][n][3] floats, face k as de_fetch_image returns the
+ * render of face k's camera ((n, n, 3), index (u n + v) 3 + c); any n in 4 ... 16384, free of the context's size; settings as de_set_panorama takes
+ * them (`on` is not read), checked against n; out (width, height, 3) floats.  Buffers and tables of its own: the context's setting and slots are not
+ * touched.  The arguments and the settings are checked before the context is read.  For the tests' restatement (tests/panorama_ref.py), which is
+ * handed the device's de_sincos through de_debug_math: functions 2 and 3, de_sin and de_cos, ARE its two outputs, and 8 is its square root. */
+struct de_panorama;
+int de_debug_panorama(de_ctx* ctx, const float* faces, int n, const struct de_panorama* settings, float* out);
 /* de_debug_hdr_consts: the constants the HDR display kernel is handed for `settings` (include/digital_earth_hdr_output.h), evaluated on
  * the host in double and rounded to f32 exactly as de_set_hdr_output does — no device work, `ctx` is not read and may be NULL.  out19 = m, s, fl, ds,
  * clamp_max, dch_s, the nine entries of the XYZ -> display matrix (row-major, as lib/OpenDRT.py:72-74 writes them), h_a, h_b, h_c, (1 - h_g) / h_g.
