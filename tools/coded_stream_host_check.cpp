@@ -8,6 +8,10 @@
 // status is overflow, with a status found set it is kept, and either way the length is `front` and no byte behind the front is written (the buffer
 // ends there: one would be the sanitizer's to find); and saturation: five pieces of 2^30 bytes, whose slots do not exist, leave the last offset at
 // 2^32 - 1 and the status at overflow.
+// And the one serial leaf of the deflate coder that fills the pieces (csrc/png_deflate.h: png_code_lengths, thread 0's part), over host stand-ins for
+// the four device calls the header's other functions name: the chain histograms of tests/deflate_cases.py (unlimited depth 16, 17, 21), 40 Fibonacci
+// counts, 286 equal counts and 285 ones beside a million, on a heap PngLds.  Checked: every length in 1 .. 15, the Kraft sum exactly 1, no symbol's
+// code longer than a rarer one's, the canonical first codes, and for the depth-16 chain the one repair step worked out by hand.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -16,6 +20,18 @@
 
 #define DE_DEV static inline
 #include "../digital_earth_amd/csrc/coded_stream.h"
+
+// the deflate coder's header as it stands; the device calls it names outside png_code_lengths, for one thread
+static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { const uint32_t old = *p; *p |= v; return old; }
+static inline uint32_t atomicAdd(uint32_t* p, uint32_t v) { const uint32_t old = *p; *p += v; return old; }
+static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { const unsigned long long old = *p; *p += v; return old; }
+static inline void __syncthreads() {}
+#if !defined(__clang__)
+static inline uint32_t host_bitreverse32(uint32_t v) { uint32_t r = 0u; for (int i = 0; i < 32; ++i) r |= ((v >> i) & 1u) << (31 - i); return r; }
+#define __builtin_bitreverse32 host_bitreverse32
+#endif
+#include "../digital_earth_amd/csrc/png_tables.h"
+#include "../digital_earth_amd/csrc/png_deflate.h"
 
 static int failures = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { if (++failures <= 20) { fprintf(stderr, "FAILED %s:%d: ", __FILE__, __LINE__); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } } } while (0)
@@ -130,6 +146,67 @@ static void saturation(uint32_t extra, uint32_t trailer) {
     CHECK(offset[count - 1] == 0xffffffffu, "the last offset is not saturated");
 }
 
+// counts in ascending order (the rank sort's result) through png_code_lengths.  `deep`: the unlimited tree is deeper than 15, so the longest code is 15.
+static void code_lengths(const std::vector<uint32_t>& counts, bool deep, const uint32_t* want_count, const char* what) {
+    std::vector<PngLds> heap(1);      // on the heap: one index past the struct is the sanitizer's to find
+    PngLds& s = heap[0];
+    memset(&s, 0xA5, sizeof(s));
+    const uint32_t n = (uint32_t)counts.size();
+    CHECK(n >= 2u && n <= PNG_SYMBOLS, "%s: %u symbols", what, n);
+    for (uint32_t i = 0; i < 288u; ++i) s.len[i] = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        CHECK(i == 0u || counts[i - 1u] <= counts[i], "%s: the counts are not sorted", what);
+        s.key[i] = counts[i];
+        s.sorted[i] = (uint16_t)i;      // symbol i at rank i: ties are by symbol already
+    }
+    s.used = n;
+    png_code_lengths(s);
+    uint32_t kraft = 0u, handed = 0u, longest = 0u;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t l = s.len[i];
+        CHECK(l >= 1u && l <= 15u, "%s: symbol %u has length %u", what, i, l);
+        if (l >= 1u && l <= 15u) kraft += 1u << (15u - l);
+        if (i) CHECK(s.len[i - 1u] >= l, "%s: symbol %u (count %u) has a longer code than the rarer symbol %u", what, i, counts[i], i - 1u);
+        if (l > longest) longest = l;
+    }
+    for (uint32_t i = n; i < 288u; ++i) CHECK(s.len[i] == 0, "%s: a length was handed to the unused symbol %u", what, i);
+    CHECK(kraft == (1u << 15), "%s: the Kraft sum is %u / 32768", what, kraft);
+    CHECK(!deep || longest == 15u, "%s: the longest code is %u, not 15", what, longest);
+    uint32_t code = 0u;
+    for (uint32_t l = 1; l <= 15u; ++l) {
+        handed += s.count[l];
+        code = (code + (l > 1u ? s.count[l - 1u] : 0u)) << 1;
+        CHECK(s.next[l] == code, "%s: the first code of length %u is %u, not %u", what, l, s.next[l], code);
+        if (want_count) CHECK(s.count[l] == want_count[l], "%s: %u codes of length %u, not %u", what, s.count[l], l, want_count[l]);
+    }
+    CHECK(handed == n, "%s: %u lengths for %u symbols", what, handed, n);
+}
+
+static std::vector<uint32_t> chain_counts(uint32_t nsym) {      // tests/deflate_cases.py: chain_counts, end-of-block's one occurrence in front
+    std::vector<uint32_t> c{1u, 1u};
+    uint32_t s_prev = 1u, sum = 2u;
+    while (c.size() < nsym + 1u) { const uint32_t next = s_prev + 1u; c.push_back(next); s_prev = sum; sum += next; }
+    return c;
+}
+
+static int code_length_runs() {
+    // depth 16: the lengths 1 .. 16, 16 clamp to one code each of 1 .. 14 and three of 15, a Kraft sum of 2^15 + 1; the one repair step takes a code of
+    // 15 away and splits the code of 14 into two of 15
+    static const uint32_t chain16[16] = {0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 4};
+    code_lengths(chain_counts(16), true, chain16, "the chain of 16 literals");
+    code_lengths(chain_counts(17), true, nullptr, "the chain of 17 literals");
+    code_lengths(chain_counts(21), true, nullptr, "the chain of 21 literals");
+    std::vector<uint32_t> fib{1u, 1u};
+    while (fib.size() < 40u) fib.push_back(fib[fib.size() - 1u] + fib[fib.size() - 2u]);
+    code_lengths(fib, true, nullptr, "40 Fibonacci counts");
+    code_lengths(std::vector<uint32_t>(PNG_SYMBOLS, 1u), false, nullptr, "286 equal counts");
+    std::vector<uint32_t> skew(PNG_SYMBOLS, 1u);
+    skew.back() = 1000000u;
+    code_lengths(skew, false, nullptr, "285 ones beside a million");
+    code_lengths(std::vector<uint32_t>{1u, 5u}, false, nullptr, "two symbols");
+    return 7;
+}
+
 int main() {
     static const uint32_t modes[2][2] = {{2u, 0u}, {0u, 28u}}, counts[] = {1, 2, 1023, 1024, 1025, 2049, 3000};
     int runs = 0;
@@ -137,7 +214,9 @@ int main() {
         for (uint32_t count : counts) { sweep(m[0], m[1], count, 4711u + (uint32_t)runs); ++runs; }
         saturation(m[0], m[1]);
     }
+    const int histograms = code_length_runs();
     if (failures) { fprintf(stderr, "%d checks failed\n", failures); return 1; }
-    printf("coded_stream_host_check: %d sweeps of offsets, word, stream and the failure rule, saturation at 2^32 - 1, no sanitizer report\n", runs);
+    printf("coded_stream_host_check: %d sweeps of offsets, word, stream and the failure rule, saturation at 2^32 - 1, code lengths of %d histograms "
+           "within 15 bits and complete, no sanitizer report\n", runs, histograms);
     return 0;
 }
