@@ -57,6 +57,7 @@ DE_DEV void pano_fisheye(const PanoArgs& a, int ki, int kj, float* rgb) {
     if (rho > 1.0f) { rgb[0] = 0.0f; rgb[1] = 0.0f; rgb[2] = 0.0f; return; }
     float st, ct;
     PANO_SINCOS(rho * a.half_aperture, &st, &ct);
+    // rho == 0 cannot be reached under the size rule: the width is a multiple of 16, so 2 ki + 1 == width S has no solution; the branch is the header's definition
     if (rho == 0.0f) pano_sample(a, 0.0f, 0.0f, 1.0f, rgb);
     else pano_sample(a, st * (px / rho), st * (py / rho), ct, rgb);
 }

@@ -7,6 +7,8 @@
 2. `f64_*`: an independent float64 statement of the GEOMETRY alone — the direction of an output position, the face cameras of the header's table,
    and the renderer's cast through such a camera (get_cast_dir's formula, the jitter replaced by the fractional position, its 1e-5 offset dropped as
    the stage's header drops it).  It shares no code with 1.
+3. `f64_linear_*`: an independent float64 statement of the IMAGE: six faces filled with a field that is linear on every face, built from 2. alone,
+   and the closed form of what any correct resampling of them holds at a direction.  It knows of no tap, no face index and no table.
 """
 import numpy as np
 
@@ -17,6 +19,21 @@ STRUCT_BYTES = 68
 # face 0 ... 5 = +r, -r, +u, -u, +f, -f: (row of the basis, sign) of its look and of its up
 LOOK = ((0, 1), (0, -1), (1, 1), (1, -1), (2, 1), (2, -1))
 UP = ((1, 1), (1, 1), (2, -1), (2, 1), (1, 1), (1, 1))
+TILE, MAX_S = 32, 4            # panorama_body.h's PANO_TILE and PANO_MAX_S: one workgroup's square of the output, the largest supersample
+# Outputs of more than one tile along the second axis (tests/test_panorama_ref.py states in numpy what each is there for; the GPU tests run them):
+MULTI_TILE = [((96, 40), "equirect", 180.0),      # 3 x 2 tiles: a swapped / and % in the tile decode lands elsewhere; the last tile row has 8 rows
+              ((48, 72), "equirect", 180.0),      # 2 x 3 tiles, partial on both axes (16 columns, 8 rows)
+              ((48, 48), "fisheye", 90.0),        # 2 x 2 tiles, partial on both axes; every sample on +f or one of its four neighbours
+              ((80, 80), "fisheye", 220.0)]       # 3 x 3 tiles, partial; directions behind the equator of the frame
+# Face sizes and aprons of those runs: de_create's smallest square with the smallest and the largest apron, and one N that is no power of two and exceeds
+# a tile (its face rows have a 120-float stride)
+FACE_SIZES = ((16, 1), (16, 4), (40, 10))
+# The float32 restatement of f64_linear_faces against f64_linear_image, the largest absolute error over every case of tests/test_panorama_ref.py's
+# linear-field test (values reach about 2): measured on the restatement alone with numpy's leaves, per supersample.  The bound of that test and of the
+# GPU's is FOUR times this: the device's de_sincos may differ from the port's by an ulp in the fisheye.  A half-pixel or a transposition is an error of
+# about fov / N = 0.07 at N = 16, five orders above.
+LINEAR_MEASURED = {1: 5.7e-7, 4: 4.1e-7}      # 5.64e-7 (80 x 80 fisheye at 220°, apron 1) and 4.05e-7 (32 x 32 fisheye at 360°, apron 1), rounded up
+LINEAR_BOUND = {S: 4.0 * m for S, m in LINEAR_MEASURED.items()}      # 2.28e-6 and 1.64e-6
 
 
 # ---------------------------------------------------------------- the leaves
@@ -228,6 +245,40 @@ def f64_cast_dir(look, up, fov, N, X, Y):
     fv = 2.0 * fov * (np.asarray(Y, np.float64) + 0.5) / N - fov
     v = d + fu[..., None] * du + fv[..., None] * dv
     return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def f64_linear_faces(N, apron, basis=None):
+    """Six faces whose CONTENT has a closed form on the sphere: pixel (u, v) of face k holds the float64 cast direction of its centre divided by the
+    direction's component along the face's look, d / (d . look) = look + fu du + fv dv in world coordinates — linear in (u, v) on every face, so a
+    correct bilinear tap reproduces it exactly but for float32 rounding.  (6, N, N, 3), rounded to float32 once."""
+    idx = np.arange(N, dtype=np.float64)
+    X, Y = np.meshgrid(idx, idx, indexing="ij")
+    out = np.empty((6, N, N, 3), np.float64)
+    for face in range(6):
+        look, up, fov = f64_face_camera(face, N, apron, basis)
+        d = f64_cast_dir(look, up, fov, N, X, Y)
+        out[face] = d / (d @ look)[..., None]
+    return out.astype(F)
+
+
+def f64_linear_image(size, projection, aperture=180.0, basis=None, S=1):
+    """What a panorama of f64_linear_faces holds, in float64 and free of any face, tap or table: at an output direction D the value is
+    D / max |component of D in the panorama's frame|, in world coordinates — the same on both sides of a cube edge — and 0 beyond the fisheye's
+    circle; the mean over the S x S sub-positions of a pixel.  Returns (image (width, height, 3), inside, outside): the pixels all of whose
+    sub-positions lie inside the image, and those all of whose lie beyond the circle."""
+    w, h = size
+    B = np.eye(3) if basis is None else np.asarray(basis, np.float64).reshape(3, 3)
+    total = np.zeros((w, h, 3))
+    every, none = np.ones((w, h), bool), np.ones((w, h), bool)
+    for b in range(S):
+        for a in range(S):
+            x, y = np.meshgrid(np.arange(w) + (a + 0.5) / S, np.arange(h) + (b + 0.5) / S, indexing="ij")
+            d, inside = f64_direction(x, y, size, projection, aperture, basis)
+            v = d / np.abs(d @ B.T).max(-1, keepdims=True)
+            total += np.where(inside[..., None], v, 0.0)
+            every &= inside
+            none &= ~inside
+    return total / float(S * S), every, none
 
 
 def f64_major_axis(direction, basis=None):

@@ -5,7 +5,10 @@ held to the float64 sphere; a context that turns the stage off again returns the
 
 Shapes, the smallest at which each thing can go wrong: faces of N = 16 (de_create's smallest square); 64 x 32 equirect (two whole tiles), 48 x 24
 equirect (a partial 32 x 32 tile on both axes), 32 x 32 fisheye at 180° (five faces) and 360° (six, the pole at the rim); S = 1, 2, 3 (3: a
-sub-position count that is no power of two); aprons 1 and 4 (the largest N / 4 admits); the world axes and an oblique frame."""
+sub-position count that is no power of two); aprons 1 and 4 (the largest N / 4 admits); the world axes and an oblique frame.  More than one tile
+along the second axis (panorama_ref.MULTI_TILE): 96 x 40 and 48 x 72 equirect (3 x 2 and 2 x 3 tiles, the last partial), 48 x 48 fisheye at 90° and
+80 x 80 at 220° (2 x 2 and 3 x 3, partial), S = 1, 3, 4 (4: the LDS tables full), and faces of N = 40 with apron 10 beside N = 16.  The same shapes
+with faces of a linear content against its float64 closed form: the kernel's image held to something not written from the header."""
 import ctypes
 
 import numpy as np
@@ -78,6 +81,46 @@ def test_kernel_equals_the_restatement_bit_for_bit(ctx, output):
     assert now["on"] == held["on"] and now["size"] == held["size"] and now["captured"] == held["captured"]      # the debug entry point leaves the context alone
     odd = random_faces(5, seed=7)                                   # any n >= 4: de_create's size rule does not bind the debug entry point
     _same(ctx.debug_panorama(odd, size, projection, aperture, 1, 2), ref.panorama(odd, size, projection, aperture, 1, 2, sincos=sincos, sqrt=sqrt), "n = 5")
+
+
+@pytest.mark.parametrize("output", ref.MULTI_TILE)
+def test_kernel_equals_the_restatement_on_more_than_one_tile_per_axis(ctx, output):
+    """Outputs of 3 x 2, 2 x 3, 2 x 2 and 3 x 3 tiles, the last tile partial (tests/test_panorama_ref.py states in numpy what each reaches): the tile
+    decode's / and %, the latitude tables' base j0 S and their [b][jl] layout, the in_i and in_j guards, and the fisheye's ki, kj beyond the first
+    tile.  S = 4 fills the LDS tables to their 128 entries on random faces; N = 40 with apron 10 is a face larger than a tile whose rows are 120 floats."""
+    size, projection, aperture = output
+    sincos, sqrt = device_leaves(ctx)
+    for n, apron in ref.FACE_SIZES:
+        for S in (1, 3, 4):
+            for basis in (None, OBLIQUE):
+                faces = random_faces(n, seed=S + 10 * apron + n)
+                got = ctx.debug_panorama(faces, size, projection, aperture, apron, S, basis)
+                want = ref.panorama(faces, size, projection, aperture, apron, S, basis, sincos=sincos, sqrt=sqrt)
+                _same(got, want, (output, n, apron, S, basis is not None))
+                assert got.min() >= 0.0 and got.max() < 1.0 and len(np.unique(got)) > got.size // 8
+
+
+@pytest.mark.parametrize("S", (1, 4))
+@pytest.mark.parametrize("output", ref.MULTI_TILE + [((32, 32), "fisheye", 360.0)])
+def test_linear_faces_come_out_as_the_float64_direction_field_on_the_device(ctx, output, S):
+    """The one comparison of the kernel with something that is not written from the header: faces whose content is linear in (u, v), built from the
+    float64 face cameras alone (ref.f64_linear_faces), come out at every pixel inside the image as D / max |component of D| of the pixel's float64
+    direction D (at S = 4: the mean over the sixteen sub-positions, a 0 for each beyond the fisheye's circle), and as exactly 0 outside.  The bound is
+    the CPU test's (tests/test_panorama_ref.py): four times the restatement's own largest error, 2.28e-6 at S = 1 and 1.64e-6 at S = 4, where a
+    transposed or half-pixel-shifted tap errs by 0.07."""
+    size, projection, aperture = output
+    worst = 0.0
+    for apron in APRONS:
+        for basis in (None, OBLIQUE):
+            got = ctx.debug_panorama(ref.f64_linear_faces(N, apron, basis), size, projection, aperture, apron, S, basis)
+            want, inside, outside = ref.f64_linear_image(size, projection, aperture, basis, S)
+            assert got.dtype == F and got.shape == want.shape and inside.sum() > inside.size // 2
+            assert (got[outside] == 0).all(), (output, S, apron)
+            assert outside.any() == (projection == "fisheye") and (inside | outside).all() == (projection == "equirect" or S == 1)
+            err = float(np.abs(got.astype(np.float64) - want)[~outside].max())
+            print("linear field on the device %s S %d apron %d %s: max error %.3e" % (output, S, apron, "oblique" if basis is not None else "axes", err))
+            worst = max(worst, err)
+    assert 0.0 < worst <= ref.LINEAR_BOUND[S], (worst, ref.LINEAR_BOUND[S])      # 4 x ref.LINEAR_MEASURED[S], the restatement alone on the CPU
 
 
 def test_constant_faces_survive_exactly_on_the_device(ctx):

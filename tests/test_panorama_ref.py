@@ -1,6 +1,8 @@
 """The panorama stage's restatement (tests/panorama_ref.py) held to an independent float64 statement of its geometry, without a GPU:
 the resampler inverts the renderer's own camera, picks the face the float64 direction picks, keeps constants exactly, and the float64 sphere of the
-orientation test stays under that test's cap."""
+orientation test stays under that test's cap; the shapes of more than one tile that the GPU tests run reach what they are there for; and the resampled
+IMAGE of faces with a linear content equals the float64 closed form at every pixel, which holds the tap addressing to something not written from the
+header."""
 import numpy as np
 import pytest
 
@@ -128,3 +130,97 @@ def test_the_float64_sphere_stays_under_the_orientation_tests_cap(sign):
     assert between.mean() < 0.10
     assert (ang[got == 1] <= radius + margin).all() and (ang[got == 0] >= radius - margin).all()
     assert (got == 1).sum() > 100 and (got == 0).sum() > 1000
+
+
+# ---------------------------------------------------------------- the multi-tile shapes reach what they are there for
+def _ceil_div(a, b):
+    return -(-a // b)
+
+
+def test_the_multi_tile_shapes_reach_what_they_are_there_for():
+    """tests/test_gpu_panorama.py runs ref.MULTI_TILE through the kernel; here, in numpy, what each shape is there for (panorama_kernel decodes its
+    one-dimensional grid as i0 = (block / tiles_j) 32, j0 = (block % tiles_j) 32 and stages 32 S table entries per axis)."""
+    T = ref.TILE
+    want = {((96, 40), "equirect"): ((3, 2), (0, 8)), ((48, 72), "equirect"): ((2, 3), (16, 8)),
+            ((48, 48), "fisheye"): ((2, 2), (16, 16)), ((80, 80), "fisheye"): ((3, 3), (16, 16))}
+    assert len(ref.MULTI_TILE) == 4
+    for size, projection, aperture in ref.MULTI_TILE:
+        w, h = size
+        tiles, rest = want[(size, projection)]
+        assert (_ceil_div(w, T), _ceil_div(h, T)) == tiles and (w % T, h % T) == rest
+        assert tiles[1] > 1                                        # more than one tile along the second axis: j0 > 0 runs
+        assert w % 16 == 0 and h % 8 == 0                          # the header's size rule
+        if projection == "equirect":
+            assert tiles[0] != tiles[1]                            # a swapped / and % leaves a tile of the output unwritten
+            assert rest[1] != 0                                    # the last tile row is partial: the in_j guard decides
+        else:
+            assert rest[0] != 0 and rest[1] != 0
+    assert any(r[0] != 0 and r[1] != 0 for (_, p), (_, r) in want.items() if p == "equirect")      # an equirect partial on both axes
+    assert T * ref.MAX_S == 128                                    # S = 4: a tile's table span is 128 entries, the LDS tables' size
+    for size in ((96, 40), (48, 72)):                              # ... and the last tile of either axis reaches past the tables' end at S = 4, or ends on it
+        for n in size:
+            assert (_ceil_div(n, T) - 1) * T * ref.MAX_S + 128 >= n * ref.MAX_S
+    assert {n for n, _ in ref.FACE_SIZES} == {16, 40} and 40 > T and 40 & 39 and 40 * 3 == 120 and all(1 <= a <= n // 4 for n, a in ref.FACE_SIZES)
+    # the fisheyes: at 90° no sample leaves +f and its four neighbours; at 220° some lie behind the equator of the frame (cf < 0)
+    for basis in (None, OBLIQUE):
+        k = ref.consts(N, 1, 90.0, basis)
+        cr, cu, cf, outside = ref.sub_direction((48, 48), "fisheye", 1, 0, 0, k)
+        face, _, _ = ref.locate(cr, cu, cf, N, k)
+        seen = set(np.unique(face[~outside]).tolist())
+        assert 4 in seen and 5 not in seen and (face[~outside] == 4).mean() > 0.5
+        k = ref.consts(N, 1, 220.0, basis)
+        cr, cu, cf, outside = ref.sub_direction((80, 80), "fisheye", 1, 0, 0, k)
+        face, _, _ = ref.locate(cr, cu, cf, N, k)
+        assert (cf[~outside] < 0).sum() > 100 and set(np.unique(face[~outside]).tolist()) == {0, 1, 2, 3, 4}
+        assert outside.any() and not outside[40, 40]
+
+
+# ---------------------------------------------------------------- the resampled IMAGE against float64
+LINEAR_CASES = ref.MULTI_TILE + [((32, 32), "fisheye", 360.0)]
+
+
+def linear_error(got, size, projection, aperture, basis, S):
+    """`got`, a panorama of ref.f64_linear_faces, against ref.f64_linear_image: the largest absolute error over the pixels all of whose sub-positions
+    lie inside the image; every pixel all of whose sub-positions lie beyond the fisheye's circle must be exactly 0."""
+    want, inside, outside = ref.f64_linear_image(size, projection, aperture, basis, S)
+    assert got.shape == want.shape and got.dtype == F
+    assert inside.sum() > inside.size // 2
+    assert (got[outside] == 0).all()
+    if projection == "fisheye":
+        assert outside.sum() > 50
+        cut = ~inside & ~outside                                   # pixels the circle cuts (none at S = 1): the mean counts a 0 per sub-position beyond it
+        assert (S > 1) == bool(cut.any())
+        return float(np.abs(got.astype(np.float64) - want)[~outside].max())
+    assert inside.all()
+    return float(np.abs(got.astype(np.float64) - want).max())
+
+
+@pytest.mark.parametrize("S", (1, 4))
+@pytest.mark.parametrize("case", LINEAR_CASES)
+def test_linear_faces_come_out_as_the_float64_direction_field(case, S):
+    """The tap addressing (u N + v) 3 + c, the choice of the four taps and the order of the two lerps, held to something that is not written from
+    the header: faces whose content is linear in (u, v) (ref.f64_linear_faces, from the float64 face cameras alone) come out, at every pixel inside
+    the image, as D / max |component of D| of the pixel's float64 direction D — on both sides of every cube edge, so no pixel is excluded.  A
+    transposed or shifted tap is an error of fov / N = 0.07 at N = 16.  The bound: ref.LINEAR_BOUND, four times the largest error of this very
+    restatement over all of these cases (measured 5.7e-7 at S = 1 where values reach 2)."""
+    size, projection, aperture = case
+    worst = 0.0
+    for apron in (1, 4):
+        for basis in (None, OBLIQUE):
+            faces = ref.f64_linear_faces(N, apron, basis)
+            assert 1.0 < np.abs(faces).max() <= 2.0 * np.sqrt(3.0) and len(np.unique(faces.reshape(-1, 3), axis=0)) == faces.size // 3      # no two pixels alike
+            got = ref.panorama(faces, size, projection, aperture, apron, S, basis)
+            err = linear_error(got, size, projection, aperture, basis, S)
+            print("linear field %s S %d apron %d %s: max error %.3e" % (case, S, apron, "oblique" if basis is not None else "axes", err))
+            worst = max(worst, err)
+    assert worst <= ref.LINEAR_BOUND[S], (worst, ref.LINEAR_BOUND[S])      # 4 x the measured maximum of the restatement alone (ref.LINEAR_MEASURED)
+    assert worst > 0.0                                             # float32 did round: the comparison is not of a thing with itself
+
+
+def test_the_linear_field_catches_a_transposed_face():
+    """The check's own strength: faces handed over with u and v exchanged — every tap read at (v, u), what a transposition shared by the header,
+    the kernel and the restatement would be — miss the float64 field by four orders more than the bound."""
+    size, projection, aperture = (96, 40), "equirect", 180.0
+    faces = ref.f64_linear_faces(N, 1)
+    err = linear_error(ref.panorama(np.ascontiguousarray(faces.transpose(0, 2, 1, 3)), size, projection, aperture, 1, 1), size, projection, aperture, None, 1)
+    assert err > 1e4 * ref.LINEAR_BOUND[1]
