@@ -289,6 +289,14 @@ PANORAMA_SYMBOLS = {
     "de_panorama_captured": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32)]),
 }
 
+# scene-linear panorama: include/digital_earth_environment.h (same library, additions only; not part of the binder's header)
+ENVIRONMENT_SYMBOLS = {
+    "de_environment_capture": (ctypes.c_int, [_P, ctypes.c_int]),
+    "de_environment_captured": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32)]),
+    "de_fetch_environment_face": (ctypes.c_int, [_P, ctypes.c_int, _P]),
+    "de_debug_environment_exr": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), ctypes.POINTER(DeExr), _P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+}
+
 # HDR display output: include/digital_earth_hdr_output.h (same library, additions only; not part of the binder's header)
 HDR_OUTPUT_SYMBOLS = {
     "de_set_hdr_output": (ctypes.c_int, [_P, ctypes.POINTER(DeHdrOutput)]),
@@ -448,7 +456,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -1228,12 +1228,14 @@ int de_set_panorama(de_ctx* c, const de_panorama* s) {
     { int rc = pano_settings_check(s, c->W); if (rc) return rc; }
     if (s->on && c->os.enabled) return fail(DE_ERR_STATE, "output scaling is on (de_set_output_scale): it makes the shown image, and a context has one");
     for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
+    // an EXR fetch of the scene-linear panorama reads the linear slots and the tables (include/digital_earth_environment.h); one of the pinhole frame reads nothing of this stage
+    if (ring_any_in_flight(c->ex_coded.ring, [c](int k) { return c->ex_cell_env[k]; })) return refuse_in_flight(c->ex_coded.ring);
     HIP_TRY(hipSetDevice(c->device));
     { int rc = c->pano_faces.ensure((size_t)DE_PANO_FACES * (size_t)c->W * (size_t)c->W * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
     { int rc = c->pano_out.ensure((size_t)s->width * (size_t)s->height * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
     c->pano = *s;
     c->pano.on = s->on ? 1 : 0;
-    c->pano_mask = 0u;
+    c->pano_mask = 0u; c->env_mask = 0u;
     pano_make_consts(c->pano, c->W, &c->pano_consts);
     return DE_OK;
 }
@@ -1290,6 +1292,76 @@ int de_debug_panorama(de_ctx* c, const float* faces, int n, const de_panorama* s
     HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return DE_OK;
+}
+
+/* ---- the scene-linear panorama: include/digital_earth_environment.h (environment_kernels.hip, environment_body.h) */
+int de_environment_capture(de_ctx* c, int face) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (face < 0 || face >= DE_PANO_FACES) return fail(DE_ERR_INVALID, "face must lie in 0 ... 5");
+    if (!c->pano.on) return fail(DE_ERR_STATE, "the panorama is off (de_set_panorama)");
+    const int source = c->ex.source;
+    // what would print the face's border or another face's camera into the environment; a vignette and auto-exposure live behind the display and do not
+    if (source == DE_EXR_SOURCE_HISTORY) return fail(DE_ERR_STATE, "a linear panorama face cannot be captured from the history (de_exr.source): the history belongs to another face's camera");
+    if (source == DE_EXR_SOURCE_BLOOM) return fail(DE_ERR_STATE, "a linear panorama face cannot be captured from the bloom (de_exr.source): its pyramid ends at the face's border");
+    if (source == DE_EXR_SOURCE_LOCAL_EXPOSURE) return fail(DE_ERR_STATE, "a linear panorama face cannot be captured from local exposure (de_exr.source): its pyramid ends at the face's border");
+    if (source != DE_EXR_SOURCE_MEAN) { int rc = display_chain_refusal(c, ex_stop_of[source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
+    HIP_TRY(hipSetDevice(c->device));
+    { int rc = c->env_faces.ensure((size_t)DE_PANO_FACES * env_face_floats(c) * sizeof(float), "the environment's buffers"); if (rc) return rc; }
+    DisplayArgs d;
+    bool per_tile;
+    int rc = ex_source(c, source, &d, &per_tile);
+    if (rc) return rc;
+    rc = env_capture_launch(c->stream, display_src(d, per_tile), c->env_faces + (size_t)face * env_face_floats(c));
+    if (rc) return rc;
+    rc = ex_sums_read(c);      // behind the capture: it has read the sums
+    if (rc) return rc;
+    c->env_mask |= 1u << face;
+    return DE_OK;
+}
+int de_environment_captured(de_ctx* c, uint32_t* mask) {
+    if (!c || !mask) return fail(DE_ERR_INVALID, "null argument");
+    *mask = c->env_mask;
+    return DE_OK;
+}
+int de_fetch_environment_face(de_ctx* c, int face, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (face < 0 || face >= DE_PANO_FACES) return fail(DE_ERR_INVALID, "face must lie in 0 ... 5");
+    if (!(c->env_mask >> face & 1u)) return fail(DE_ERR_STATE, "that linear face is not held (de_environment_capture)");
+    HIP_TRY(hipSetDevice(c->device));
+    return copy_out(c, out, c->env_faces + (size_t)face * env_face_floats(c), env_face_floats(c) * sizeof(float));
+}
+/* The resampling and the conversion once on host-given linear faces.  Buffers and tables of its own; the context's settings and slots are not touched.
+ * The arguments and both settings are checked before the context is read. */
+int de_debug_environment_exr(de_ctx* c, const float* faces, int n, const de_panorama* p, const de_exr* s, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !faces || !p || !s || !out || !len || n < 4 || n > 16384) return fail(DE_ERR_INVALID, "bad arguments (faces of 4 ... 16384 pixels a side)");
+    { int rc = pano_settings_check(p, n); if (rc) return rc; }
+    { int rc = ex_settings_check(s); if (rc) return rc; }
+    { int rc = ex_shape_check(p->width, p->height, s->pixel_type); if (rc) return rc; }
+    const ExrGeometry g = ex_geometry(p->width, p->height, *s);
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<float> d_faces, d_image;
+    Dev<uint8_t> d_out;
+    de_ctx::PanoTab tab;
+    de_ctx::ExrWork work;
+    PanoArgs k = {};
+    pano_make_consts(*p, n, &k);
+    const size_t in_bytes = (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float), image_bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
+    { int rc = ex_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_faces.ensure(in_bytes));
+    HIP_TRY(d_image.ensure(image_bytes));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
+    if (p->projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, tab, p->width, p->height, p->supersample); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(d_faces, faces, in_bytes, hipMemcpyHostToDevice, c->stream));      // behind it every way out waits for the stream: the copy reads the caller's array
+    hipError_t e = ex_tables_upload(c->stream, work);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); HIP_TRY(e); }
+    int rc = pano_launch(c->stream, *p, k, n, d_faces, tab, d_image, true);
+    if (!rc) {
+        DisplaySrc src;
+        src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = p->width; src.H = p->height;      // x / 1.0f == x
+        rc = ex_launch(c->stream, work, g, src, true, s->scale, d_out, [] { return (int)DE_OK; });
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    return coded_debug_out(c->stream, d_out, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
 }
 
 /* include/digital_earth_debug.h: the stage once on a host-given image.  Buffers and tables of its own; the context's setting is not touched. */
@@ -1671,7 +1743,10 @@ int de_fetch_exr_begin(de_ctx* c) {
     { int rc = ex_pano_refusal(c); if (rc) return rc; }
     { int rc = ex_ctx_shape_check(c); if (rc) return rc; }
     const ExrGeometry g = ex_ctx_geometry(c);
-    return coded_begin(c, c->ex_coded, g.front + g.raw / 2, g.capacity, [c](int k) { return ex_render(c, c->ex_coded.cell[k]); });      // the first: the front and half the raw bytes
+    const int cell = ring_next_cell(c->ex_coded.ring);
+    int rc = coded_begin(c, c->ex_coded, g.front + g.raw / 2, g.capacity, [c](int k) { return ex_render(c, c->ex_coded.cell[k]); });      // the first: the front and half the raw bytes
+    if (!rc) c->ex_cell_env[cell] = env_active(c);      // de_set_panorama waits for a fetch of the scene-linear panorama
+    return rc;
 }
 int de_fetch_exr_end(de_ctx* c, const void** host, uint64_t* len) {
     if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");

@@ -15,6 +15,7 @@
 #include "../../include/digital_earth_png.h"
 #include "../../include/digital_earth_exr.h"
 #include "../../include/digital_earth_exr_aovs.h"
+#include "../../include/digital_earth_environment.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -43,6 +44,7 @@
 #include "pixels_kernels.hip"
 #include "output_scale_kernels.hip"
 #include "panorama_kernels.hip"
+#include "environment_kernels.hip"
 #include "local_exposure_kernels.hip"
 #include "hdr_output_kernels.hip"
 #include "videoframe_kernels.hip"
@@ -306,6 +308,12 @@ struct de_ctx {
     PanoArgs pano_consts = {};      // of `pano`: fov, scale, half_aperture, m — once per de_set_panorama; the pointers are filled at the launch
     Dev<float> pano_faces, pano_out;
     struct PanoTab { Dev<float> t[4]; int width = 0, height = 0, S = 0; } pano_tab;      // sin lon, cos lon, sin lat, cos lat
+    // Scene-linear panorama (include/digital_earth_environment.h).  Allocated by the first de_environment_capture that succeeds: six
+    // linear face slots of N x N x 3 floats in one buffer; the row-major image [height][width][3] by the first EXR conversion of the panorama.  The
+    // settings are `pano` and `ex`; the equirect's tables are pano_tab.
+    uint32_t env_mask = 0;          // bit k: linear slot k holds a face (cleared by de_set_panorama alone)
+    Dev<float> env_faces, env_out;
+    bool ex_cell_env[DE_FETCH_RING] = {};      // lagged EXR fetch in ring cell k was begun with the panorama on: it reads env_faces and env_out
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.

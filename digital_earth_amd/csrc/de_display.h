@@ -458,12 +458,14 @@ int pano_tables_ensure(hipStream_t stream, de_ctx::PanoTab& d, int width, int he
     return DE_OK;
 }
 // faces [6][N][N][3] -> out (width, height, 3) on `stream`; `k` carries the settings' constants (pano_make_consts), `tab` the equirect's tables.
-int pano_launch(hipStream_t stream, const de_panorama& s, const PanoArgs& k, int N, const float* faces, const de_ctx::PanoTab& tab, float* out) {
+// rows: environment_kernel instead (include/digital_earth_environment.h) — the same arithmetic into out [height][width][3].
+int pano_launch(hipStream_t stream, const de_panorama& s, const PanoArgs& k, int N, const float* faces, const de_ctx::PanoTab& tab, float* out, bool rows = false) {
     PanoArgs a = k;
     a.faces = faces; a.out = out; a.N = N; a.width = s.width; a.height = s.height; a.S = s.supersample; a.fisheye = s.projection == DE_PANO_FISHEYE ? 1 : 0;
     a.sin_lon = tab.t[0]; a.cos_lon = tab.t[1]; a.sin_lat = tab.t[2]; a.cos_lat = tab.t[3];
     const unsigned long long blocks = (unsigned long long)pano_tiles(s.width) * (unsigned long long)pano_tiles(s.height);      // at most 2^28 / 128 + ...: one dimension holds it
-    hipLaunchKernelGGL(panorama_kernel, dim3((unsigned)blocks), dim3(PANO_THREADS), 0, stream, a);
+    if (rows) hipLaunchKernelGGL(environment_kernel, dim3((unsigned)blocks), dim3(PANO_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL(panorama_kernel, dim3((unsigned)blocks), dim3(PANO_THREADS), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return DE_OK;
 }
@@ -476,6 +478,17 @@ int pano_refusal(const de_ctx* c) {
 int run_panorama(de_ctx* c) {
     if (c->pano.projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, c->pano_tab, c->pano.width, c->pano.height, c->pano.supersample); if (rc) return rc; }
     return pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->pano_faces, c->pano_tab, c->pano_out);
+}
+// ---- the scene-linear panorama (include/digital_earth_environment.h, environment_kernels.hip, environment_body.h)
+// The EXR output is the panorama's: the stage on and all six LINEAR slots held.  (On with fewer, the EXR calls refuse: ex_pano_refusal.)
+bool env_active(const de_ctx* c) { return c->pano.on && c->env_mask == 63u; }
+size_t env_face_floats(const de_ctx* c) { return (size_t)c->W * (size_t)c->W * 3; }
+// src ([N][N][3] and its divisor) -> one linear slot on `stream`: the division and the transposition.
+int env_capture_launch(hipStream_t stream, const DisplaySrc& src, float* slot) {
+    const unsigned tiles = (unsigned)((src.W + ENV_TILE - 1) / ENV_TILE);      // a face is square
+    hipLaunchKernelGGL(environment_capture_kernel, dim3(tiles * tiles), dim3(ENV_THREADS), 0, stream, src, slot);
+    HIP_TRY(hipGetLastError());
+    return DE_OK;
 }
 // ---- the packed outputs (pack.h): their settings share the quantiser's mode, their launches the grid (pack_grid).  `who`: the settings struct's name.
 int pack_mode_check(int mode, const char* who) {
@@ -938,8 +951,9 @@ int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g
     HIP_TRY(hipGetLastError());
     return DE_OK;
 }
-ExrGeometry ex_ctx_geometry(const de_ctx* c) { return ex_geometry(c->W, c->H, c->ex, c->ex_aovs); }
-int ex_ctx_shape_check(const de_ctx* c) { return ex_shape_check(c->W, c->H, c->ex.pixel_type, c->ex_aovs); }
+// of the context's frame, or of the scene-linear panorama while that is what the EXR calls deliver (B, G, R alone: no AOV channel exists there)
+ExrGeometry ex_ctx_geometry(const de_ctx* c) { return env_active(c) ? ex_geometry(c->pano.width, c->pano.height, c->ex) : ex_geometry(c->W, c->H, c->ex, c->ex_aovs); }
+int ex_ctx_shape_check(const de_ctx* c) { return env_active(c) ? ex_shape_check(c->pano.width, c->pano.height, c->ex.pixel_type) : ex_shape_check(c->W, c->H, c->ex.pixel_type, c->ex_aovs); }
 // What the AOV channels in force refuse before anything is enqueued.  The variance is this context's own sums beside its own S2: not with a display
 // source (the sums shown are another buffer's, S2 is not) and not under a tile or sample partition (this rank's S2 is a part's), as the denoiser,
 // S2's other reader, refuses (denoise_refusal); and not without a complete S2.  The guides' own refusal, before maps and LUTs, is de_fetch_guides'.
@@ -953,26 +967,70 @@ int ex_aov_refusal(de_ctx* c) {
         return fail(DE_ERR_STATE, "the EXR variance channels need the sums of squares of every sample of this frame: turn the denoiser on (de_set_denoise) before the frame's first sample, or render adaptively");
     return DE_OK;
 }
-// The EXR output sits in FRONT of the display: a face's scene-linear frame is not the panorama, and a scene-linear panorama does not exist.
+// The EXR output sits in FRONT of the display: a face's scene-linear frame is not the panorama.  The scene-linear panorama is made of the six LINEAR
+// slots alone (include/digital_earth_environment.h); without all six there is none, and it has no AOV channels.
 int ex_pano_refusal(const de_ctx* c) {
-    if (c->pano.on) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): the EXR output reads the frame in front of the display, where no panorama exists");
+    if (!c->pano.on) return DE_OK;
+    if (c->env_mask != 63u) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): the EXR output reads the frame in front of the display, where a panorama exists only once six linear faces are captured (de_environment_capture)");
+    if (c->ex_aovs) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): a scene-linear panorama has no AOV channels (de_set_exr_aovs(ctx, 0) first)");
     return DE_OK;
 }
 int ex_length(const void* word, uint64_t* len) {      // its coders raise no range status
     static const char* const text = "the EXR encoder met a piece longer than its proven worst case: nothing was written past a buffer";
     return coded_read_word(word, len, text, text);
 }
-// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.  MEAN reads what
-// the display launch would read with every stage off; the other sources are the chain left at their stage — its refusals, its side effects.
+static const DisplayStop ex_stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
+// What a scene-linear output of `source` reads of the frame as it stands, on the context stream: MEAN reads what the display launch would read with
+// every stage off; the other sources are the chain left at their stage — its refusals, its side effects.  (de_environment_capture reads the same.)
+int ex_source(de_ctx* c, int source, DisplayArgs* d, bool* per_tile) {
+    if (source != DE_EXR_SOURCE_MEAN) return display_chain(c, ex_stop_of[source], d, per_tile);
+    int rc = join_slots(c);      // the launches in flight first, and the next accumulate_kernel must not overwrite what this reads
+    if (rc) return rc;
+    touched_hdr(c);
+    d->hdr = c->display_src ? c->display_src : c->d_hdr; d->tile_spp = c->d_tile_spp; d->samples = c->current_spp; d->W = c->W; d->H = c->H;
+    *per_tile = c->frame_kind == DE_FRAME_ADAPTIVE;
+    return DE_OK;
+}
+// what the next accumulate_kernel must wait for ends behind the kernel that has read the sums, as behind the display launch in de_render_to_image
+int ex_sums_read(de_ctx* c) {
+    HIP_TRY(hipEventRecord(c->ev_main, c->stream));
+    c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
+    return DE_OK;
+}
+// One conversion of the scene-linear panorama into `dev` (env_active): the six linear slots resampled into env_out, [height][width][3] with row 0 at
+// the bottom, which the unchanged layout reads with its rows flipped and a divisor of 1.  The frame as it stands is not read.  Nothing is waited for.
+int ex_render_environment(de_ctx* c, Dev<uint8_t>& dev) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = ex_ctx_shape_check(c);
+    if (rc) return rc;
+    const ExrGeometry g = ex_ctx_geometry(c);
+    rc = c->env_out.ensure((size_t)g.W * (size_t)g.H * 3 * sizeof(float), "the environment's buffers");      // its size changes with de_set_panorama alone, which waits for the fetches that read it
+    if (rc) return rc;
+    rc = dev.ensure(coded_stream_bytes(g.capacity), "EXR buffers");
+    if (rc) return rc;
+    rc = ex_work_ensure(c->ex_work, g);
+    if (rc) return rc;
+    HIP_TRY(ex_tables_upload(c->stream, c->ex_work));
+    if (c->pano.projection == DE_PANO_EQUIRECT) { rc = pano_tables_ensure(c->stream, c->pano_tab, c->pano.width, c->pano.height, c->pano.supersample); if (rc) return rc; }
+    rc = pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->env_faces, c->pano_tab, c->env_out, true);
+    if (rc) return rc;
+    DisplaySrc src;
+    src.hdr = c->env_out; src.tile_spp = nullptr; src.samples = 1; src.W = g.W; src.H = g.H;      // x / 1.0f == x
+    rc = ex_launch(c->stream, c->ex_work, g, src, true, c->ex.scale, dev, [] { return (int)DE_OK; });
+    if (rc) return rc;
+    c->ex_coded.out.count++;
+    return DE_OK;
+}
+// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
 int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
-    static const DisplayStop stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
     { int rc = ex_pano_refusal(c); if (rc) return rc; }
+    if (env_active(c)) return ex_render_environment(c, dev);
     HIP_TRY(hipSetDevice(c->device));
     const ExrGeometry g = ex_ctx_geometry(c);
     int rc = ex_ctx_shape_check(c);
     if (rc) return rc;
     const bool mean = c->ex.source == DE_EXR_SOURCE_MEAN;
-    if (!mean) { rc = display_chain_refusal(c, stop_of[c->ex.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
+    if (!mean) { rc = display_chain_refusal(c, ex_stop_of[c->ex.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
     rc = ex_aov_refusal(c);
     if (rc) return rc;
     const bool guides = (c->ex_aovs & (DE_EXR_AOV_DEPTH | DE_EXR_AOV_NORMAL | DE_EXR_AOV_ALBEDO | DE_EXR_AOV_COVERAGE | DE_EXR_AOV_TRANSMITTANCE)) != 0u;
@@ -987,28 +1045,15 @@ int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
     HIP_TRY(ex_tables_upload(c->stream, c->ex_work));
     DisplayArgs d;
     bool per_tile;
-    if (mean) {
-        rc = join_slots(c);      // the launches in flight first, and the next accumulate_kernel must not overwrite what this reads
-        if (rc) return rc;
-        touched_hdr(c);
-        d.hdr = c->display_src ? c->display_src : c->d_hdr; d.tile_spp = c->d_tile_spp; d.samples = c->current_spp; d.W = c->W; d.H = c->H;
-        per_tile = c->frame_kind == DE_FRAME_ADAPTIVE;
-    } else {
-        rc = display_chain(c, stop_of[c->ex.source], &d, &per_tile);
-        if (rc) return rc;
-    }
+    rc = ex_source(c, c->ex.source, &d, &per_tile);
+    if (rc) return rc;
     ExrAovSrc av;      // the frame's own sums and counts, whatever the source: a stage's mean has no S2
     if (c->ex_aovs) {
         av.nc = c->d_dn_nc; av.at = c->d_dn_at; av.dist = c->d_dn_dist;
         av.s1 = c->d_hdr; av.s2 = c->d_s2;      // the context's own sums beside its own S2 (ex_aov_refusal: no display source)
         av.tile_spp = c->frame_kind == DE_FRAME_ADAPTIVE ? c->d_tile_spp : nullptr; av.samples = c->current_spp;
     }
-    rc = ex_launch(c->stream, c->ex_work, g, display_src(d, per_tile), true, c->ex.scale, dev, [c]() {
-        // what the next accumulate_kernel must wait for ends behind the layout (it has read the sums), as behind the display launch in de_render_to_image
-        HIP_TRY(hipEventRecord(c->ev_main, c->stream));
-        c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
-        return (int)DE_OK;
-    }, av);
+    rc = ex_launch(c->stream, c->ex_work, g, display_src(d, per_tile), true, c->ex.scale, dev, [c]() { return ex_sums_read(c); }, av);      // behind the layout: it has read the sums
     if (rc) return rc;
     c->ex_coded.out.count++;
     return DE_OK;

@@ -74,6 +74,12 @@ int refuse_in_flight(const FetchRing& r) {      // what changes the size or the 
     if (in_flight(r)) return fail(DE_ERR_STATE, std::string(r.noun) + " fetches are in flight: " + r.entry + "_end first");
     return DE_OK;
 }
+int ring_next_cell(const FetchRing& r) { return ring_cell(r.begun, DE_FETCH_RING); }      // the cell the next _begin fills
+template <class Pred>
+bool ring_any_in_flight(const FetchRing& r, Pred pred) {      // pred(cell) of any fetch begun and not ended, oldest first
+    for (unsigned n = r.ended; n != r.begun; ++n) if (pred(ring_cell(n, DE_FETCH_RING))) return true;
+    return false;
+}
 template <class T>
 int ring_begin(de_ctx* c, FetchRing& r, int (*render)(de_ctx*, const T**), size_t capacity, size_t size) {
     if (ring_full(r.begun, r.ended, DE_FETCH_RING)) return fail(DE_ERR_STATE, std::string("four ") + r.noun + " fetches are in flight already: " + r.entry + "_end first");

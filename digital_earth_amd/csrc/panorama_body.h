@@ -1,4 +1,5 @@
-// panorama_body.h — the per-pixel body of panorama_kernel (panorama_kernels.hip, include/digital_earth_panorama.h) and its arguments,
+// panorama_body.h — the per-pixel body of panorama_kernel and of environment_kernel (panorama_kernels.hip, include/digital_earth_panorama.h and
+// include/digital_earth_environment.h) and its arguments,
 // free of anything of the device, so that a host build (tools/panorama_host_check.cpp) runs it pixel by pixel under the sanitizers.  The includer
 // brings DE_DEV and the three leaves PANO_SINCOS(x, &s, &c), PANO_SQRT(x), PANO_FLOOR(x): de_math.h's on the device.
 // Every operation is a float32 operation rounded on its own (the unit is compiled with -ffp-contract=off); the header carries the definition, and
@@ -12,7 +13,7 @@
 
 struct PanoArgs {
     const float* faces;           // [6][N][N][3]: slot f at f N N 3, each as the display writes it: index (u N + v) 3 + c
-    float* out;                   // (width, height, 3): index (i height + j) 3 + c
+    float* out;                   // (width, height, 3): index (i height + j) 3 + c; environment_kernel: [height][width][3], index (j width + i) 3 + c
     const float* sin_lon;         // equirect: [width S], [width S], [height S], [height S]; fisheye: not read
     const float* cos_lon;
     const float* sin_lat;
@@ -62,10 +63,10 @@ DE_DEV void pano_fisheye(const PanoArgs& a, int ki, int kj, float* rgb) {
     else pano_sample(a, st * (px / rho), st * (py / rho), ct, rgb);
 }
 
-// Output pixel (i, j), inside the image.  The four tables' entries of the pixel come through `sl`, `cl` (lon: [S]) and `st`, `ct` (lat: [S]) — the
-// kernel hands its LDS copies, the host check the tables themselves.
-DE_DEV void pano_pixel(const PanoArgs& a, int i, int j, const float* sin_lon, const float* cos_lon, const float* sin_lat, const float* cos_lat, int lat_stride) {
-    float mean[3] = {0.0f, 0.0f, 0.0f};
+// The running mean of output pixel (i, j), inside the image, into mean[3].  The four tables' entries of the pixel come through `sin_lon`, `cos_lon`
+// (entry s at s lon_stride) and `sin_lat`, `cos_lat` (entry b at b lat_stride) — a kernel hands its LDS copies, the host check the tables themselves.
+DE_DEV void pano_pixel_mean(const PanoArgs& a, int i, int j, const float* sin_lon, const float* cos_lon, int lon_stride, const float* sin_lat, const float* cos_lat, int lat_stride, float* mean) {
+    mean[0] = 0.0f; mean[1] = 0.0f; mean[2] = 0.0f;
     int k = 0;
     for (int b = 0; b < a.S; ++b)
         for (int s = 0; s < a.S; ++s) {
@@ -73,7 +74,7 @@ DE_DEV void pano_pixel(const PanoArgs& a, int i, int j, const float* sin_lon, co
             if (a.fisheye) pano_fisheye(a, i * a.S + s, j * a.S + b, v);
             else {
                 const float cl = cos_lat[b * lat_stride];
-                pano_sample(a, cl * sin_lon[s], sin_lat[b * lat_stride], cl * cos_lon[s], v);
+                pano_sample(a, cl * sin_lon[s * lon_stride], sin_lat[b * lat_stride], cl * cos_lon[s * lon_stride], v);
             }
             ++k;
             if (k == 1) { mean[0] = v[0]; mean[1] = v[1]; mean[2] = v[2]; }
@@ -82,6 +83,21 @@ DE_DEV void pano_pixel(const PanoArgs& a, int i, int j, const float* sin_lon, co
                 for (int ch = 0; ch < 3; ++ch) mean[ch] = mean[ch] + (v[ch] - mean[ch]) * w;
             }
         }
+}
+
+// panorama_kernel's pixel: the display's layout, (width, height, 3) with the pixels of a column contiguous.
+DE_DEV void pano_pixel(const PanoArgs& a, int i, int j, const float* sin_lon, const float* cos_lon, const float* sin_lat, const float* cos_lat, int lat_stride) {
+    float mean[3];
+    pano_pixel_mean(a, i, j, sin_lon, cos_lon, 1, sin_lat, cos_lat, lat_stride, mean);
     float* o = a.out + ((size_t)i * (size_t)a.height + (size_t)j) * 3;
+    o[0] = mean[0]; o[1] = mean[1]; o[2] = mean[2];
+}
+
+// environment_kernel's pixel (include/digital_earth_environment.h): the same mean into [height][width][3], the pixels of a ROW contiguous
+// and j = 0 still the bottom row — what the EXR layout reads with its rows flipped.
+DE_DEV void pano_pixel_rows(const PanoArgs& a, int i, int j, const float* sin_lon, const float* cos_lon, int lon_stride, const float* sin_lat, const float* cos_lat, int lat_stride) {
+    float mean[3];
+    pano_pixel_mean(a, i, j, sin_lon, cos_lon, lon_stride, sin_lat, cos_lat, lat_stride, mean);
+    float* o = a.out + ((size_t)j * (size_t)a.width + (size_t)i) * 3;
     o[0] = mean[0]; o[1] = mean[1]; o[2] = mean[2];
 }

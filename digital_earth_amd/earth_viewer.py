@@ -293,7 +293,9 @@ class EarthViewer:
         panorama=True (a keyword beside the sliders too; the viewer was made with panorama=...): step 2 is Renderer.render_panorama(spp) — the six
         cube faces around the camera, `spp` each, never accumulated over iterations — and what is handed out (the float field, or with pixels /
         hdr_pixels / video / jpeg / png = True that output, pipelined or not) is the 360° frame at Renderer.output_size() — so
-        record(path, n, panorama=True) writes a 360° Y4M, Motion-JPEG or PNG sequence through the writers as they are.  Not with exr=True."""
+        record(path, n, panorama=True) writes a 360° Y4M, Motion-JPEG or PNG sequence through the writers as they are.  With exr=True step 2 is
+        Renderer.render_environment(spp) instead — the same six renders captured in FRONT of the display — and the file handed out, through the EXR
+        ring when pipelined, is the scene-linear 360° frame, an HDR environment map: record("env/%05d.exr", n, panorama=True) writes a sequence."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
         video = bool(sliders.pop("video", False))
@@ -301,8 +303,6 @@ class EarthViewer:
         png = bool(sliders.pop("png", False))
         exr = bool(sliders.pop("exr", False))
         panorama = bool(sliders.pop("panorama", False))
-        if panorama and exr:
-            raise ValueError("panorama=True does not go with exr=True: the EXR output sits in front of the display, where no panorama exists")
         if exr and (pixels or hdr_pixels or video or jpeg or png):
             raise ValueError("exr=True goes with none of pixels=True, hdr_pixels=True, video=True, jpeg=True and png=True")
         if png and (pixels or hdr_pixels or video or jpeg):
@@ -319,7 +319,9 @@ class EarthViewer:
             r.set_look_at(*self.camera.look_at)
             r.set_up(*self.camera._up)
             should_reset = True
-        if panorama:
+        if panorama and exr:
+            r.render_environment(int(spp))      # the same six renders, captured in front of the display (include/digital_earth_environment.h)
+        elif panorama:
             r.render_panorama(int(spp))         # six faces around the camera, `spp` each; the camera is put back and the frame left empty
         else:
             r.accumulate(int(spp))              # == accumulate() x spp, bit for bit
@@ -512,10 +514,11 @@ class EarthViewer:
         set_png() the file is written the way it was before, byte for byte.
         `.exr`: not a picture held but the scene-linear frame of the CURRENT accumulation, as one OpenEXR file converted and deflated on the GPU
         (Renderer.fetch_exr) in the settings of Renderer.set_exr(), or the defaults (half, ZIP, the mean) if that was never called; a sample is
-        rendered first if the frame holds none.  digital_earth_amd.exr.read opens it again."""
+        rendered first if the frame holds none.  digital_earth_amd.exr.read opens it again.  Behind frame(panorama=True, exr=True) or
+        Renderer.render_environment() the file is whatever fetch_exr() delivers then: the scene-linear panorama."""
         r = self.renderer
         if path.endswith(".exr"):
-            if r.current_spp == 0:
+            if r.current_spp == 0 and not (r.panorama["on"] and len(r.environment["captured"]) == 6):      # the panorama is made of its slots, not of the frame
                 self.render(1)
             with open(path, "wb") as f:
                 f.write(r.fetch_exr())

@@ -882,8 +882,10 @@ class Renderer:
         of `aperture` degrees (width == height; size=None: (2 N, 2 N)).  The renderer must be square, image_res = (N, N).  apron: face pixels rendered
         beyond 90° on every side (1 ... N / 4) so that no bilinear tap crosses a cube edge; supersample: S x S sub-positions per output pixel
         (1 ... 4).  basis: the panorama's right, up and forward, (3, 3) rows r, u, f, orthonormal; None: the world axes — render_panorama(basis=None)
-        sets the current camera's.  Every call clears the captured faces.  Refused (DE_ERR_STATE) while output scaling is on or lagged fetches are in
-        flight; fetch_exr is refused while this is on.  on=False: every fetch returns the bytes it returned before."""
+        sets the current camera's.  Every call clears the captured faces, the linear ones too.  Refused (DE_ERR_STATE) while output scaling is on or
+        lagged fetches are in flight (of the EXR output: those of a scene-linear panorama).  The scene-linear side is
+        include/digital_earth_environment.h's: while this is on fetch_exr is refused until six LINEAR faces are captured (render_environment), and
+        then hands out the HDR environment map.  on=False: every fetch returns the bytes it returned before."""
         N = self.image_res[0]
         if size is None:
             size = (2 * N, 2 * N) if projection == "fisheye" else (4 * N, 2 * N)
@@ -917,6 +919,10 @@ class Renderer:
         """The six faces of the panorama, `spp` samples per pixel each: for every face set its camera, reset, accumulate and capture; then put the
         caller's camera, fov and aspect scale back (and reset: the frame left is the last face's).  basis=None: the current camera's right, up and
         forward become the panorama's frame; otherwise (3, 3) rows r, u, f.  The settings are those of set_panorama(), which must be on."""
+        self._render_faces(spp, basis, (self.capture_panorama_face,))
+
+    def _render_faces(self, spp, basis, captures):
+        """render_panorama's and render_environment's loop: every face rendered once and handed to each of `captures`."""
         held = self.panorama
         if not held["on"]:
             raise RuntimeError("the panorama is off: set_panorama() first")
@@ -934,7 +940,8 @@ class Renderer:
                 self._push_params()
                 self.reset_framebuffer()
                 self.accumulate(int(spp))
-                self.capture_panorama_face(face)
+                for capture in captures:
+                    capture(face)
         finally:
             (p.look_at[0], p.look_at[1], p.look_at[2]), (p.up[0], p.up[1], p.up[2]), p.fov, p.aspect_scale = keep[0], keep[1], keep[2], keep[3]
             self._push_params()
@@ -950,6 +957,53 @@ class Renderer:
         out = np.empty((max(int(size[0]), 0), max(int(size[1]), 0), 3), dtype=np.float32)
         check(self._lib.de_debug_panorama(self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(s), out.ctypes.data))
         return out
+
+    # ------------------------------------------------------------------ scene-linear panorama (include/digital_earth_environment.h)
+    def capture_environment_face(self, face):
+        """Keep the frame as it stands, in FRONT of the display, as LINEAR cube face `face` (de_environment_capture): what fetch_exr() would write
+        with the panorama off — the mean, or with set_exr(source="denoised") the filtered mean; the other sources are refused (DE_ERR_STATE), a
+        vignette and auto-exposure are not.  The panorama must be on."""
+        if not self._textures_copied:
+            self.copy_textures()
+        check(self._lib.de_environment_capture(self._h, int(face)))
+
+    def fetch_environment_face(self, face):
+        """Linear face `face` as (N, N, 3) float32 in fetch_image's orientation: fetch_hdr() / spp of that face's render — one face of a linear
+        cube map.  DE_ERR_STATE if it is not held."""
+        N = self.image_res[0]
+        out = np.empty((N, N, 3), dtype=np.float32)
+        check(self._lib.de_fetch_environment_face(self._h, int(face), out.ctypes.data))
+        return out
+
+    @property
+    def environment(self):
+        """dict(captured=...): the tuple of the LINEAR faces (0 ... 5 = +r, -r, +u, -u, +f, -f) held.  With all six and the panorama on, fetch_exr()
+        hands out the environment map at panorama["size"]."""
+        mask = ctypes.c_uint32()
+        check(self._lib.de_environment_captured(self._h, ctypes.byref(mask)))
+        return dict(captured=tuple(k for k in range(6) if mask.value >> k & 1))
+
+    def render_environment(self, spp, basis=None, display=False):
+        """render_panorama's six renders, each captured LINEARLY (capture_environment_face): afterwards fetch_exr() — and save("x.exr"),
+        frame(panorama=True, exr=True) — deliver one OpenEXR file of the scene-linear 360° frame, an HDR environment map, in the settings of
+        set_exr().  display=True: every face is captured through the display too (capture_panorama_face), so that fetch_image, fetch_png, ... hand
+        out the tone-mapped panorama of the same renders."""
+        self._render_faces(spp, basis, (self.capture_environment_face, self.capture_panorama_face) if display else (self.capture_environment_face,))
+
+    def debug_environment_exr(self, faces, size, projection="equirect", aperture=180.0, apron=1, supersample=2, basis=None,
+                              pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0):
+        """The resampling and the EXR conversion once on given LINEAR faces, (6, n, n, 3) float32 as debug_panorama takes them
+        (de_debug_environment_exr); returns the file as bytes.  The renderer's own settings and faces are not touched."""
+        faces = np.ascontiguousarray(faces, dtype=np.float32)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 3:
+            raise ValueError("faces must have shape (6, n, n, 3)")
+        p = self._panorama_settings(size, projection, aperture, apron, supersample, basis, True)
+        s = self._ex_settings("mean", pixel_type, compression, chunk_bytes, scale)
+        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.de_debug_exr_framing(ctypes.byref(s), int(size[0]), int(size[1]), None, 0, None, ctypes.byref(cap)))
+        out = ctypes.create_string_buffer(int(cap.value))
+        check(self._lib.de_debug_environment_exr(self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
+        return out.raw[:int(n.value)]
 
     def _staging_view(self, ptr, _=None):
         ow, oh = self.output_size()
@@ -1308,14 +1362,19 @@ class Renderer:
         return tuple(name for name, bit in _native.EXR_AOVS.items() if mask.value & bit)
 
     def exr(self):
-        """The EXR settings as a dict (set_exr's keywords) plus size = (width, height) and capacity, the proven bound of any frame's length."""
+        """The EXR settings as a dict (set_exr's keywords) plus size = (width, height) and capacity, the proven bound of any frame's length — of the
+        panorama's size while fetch_exr() delivers the scene-linear panorama (render_environment)."""
         s, n = DeExr(), ctypes.c_uint64()
         check(self._lib.de_get_exr(self._h, ctypes.byref(s)))
         check(self._lib.de_exr_capacity(self._h, ctypes.byref(n)))
         name = lambda table, v: next(k for k, x in table.items() if x == v)
         return dict(source=_native.EXR_SOURCES[s.source], pixel_type=name(_native.EXR_PIXEL_TYPES, s.pixel_type),
                     compression=name(_native.EXR_COMPRESSIONS, s.compression), chunk_bytes=int(s.chunk_bytes), scale=float(s.scale),
-                    size=self.image_res, capacity=int(n.value))
+                    size=self._exr_size(), capacity=int(n.value))
+
+    def _exr_size(self):
+        p = self.panorama
+        return p["size"] if p["on"] and len(self.environment["captured"]) == 6 else self.image_res
 
     def fetch_exr(self, copy=True, lag=0):
         """The scene-linear frame as one complete OpenEXR file: `bytes` that open(path, "wb").write() takes as they are (digital_earth_amd.exr.read

@@ -47,7 +47,9 @@
  *     and DE_PIXELS_TRUNCATE still gives 255.
  * tests/panorama_ref.py restates all of this in numpy, and the GPU equals it bit for bit.
  *
- * EXR sits in front of the display: a scene-linear panorama is out of scope, and the EXR calls answer DE_ERR_STATE while the stage is on.
+ * EXR sits in front of the display, where these slots do not reach: the scene-linear panorama is include/digital_earth_environment.h's, a second set
+ * of slots captured in front of the display (de_environment_capture).  Until all six of THOSE are held the EXR calls answer DE_ERR_STATE while the
+ * stage is on.
  */
 #ifndef DIGITAL_EARTH_PANORAMA_H
 #define DIGITAL_EARTH_PANORAMA_H

@@ -3,9 +3,11 @@
 // drives this).  The body runs pixel by pixel over the whole output on heap blocks of exactly their sizes: the six face slots
 // (6 N N 3 floats), the four tables and the output.  The leaves are restated here for the host: de_math.h's de_sincos with the C library's fmaf
 // (a correctly rounded fused multiply-add), sqrtf and floorf.
-//   panorama_host_check IN OUT
+//   panorama_host_check IN OUT [rows]
+// rows: environment_kernel's side — pano_pixel_rows into [height][width][3], tile by tile with the tables staged as that kernel
+// stages them in LDS, here in heap blocks of exactly the LDS arrays' sizes: longitude [s][il], latitude [jl S + b].
 // IN: int32 N, width, height, S, fisheye; f32 fov, scale, half_aperture, m[6][4]; f32 sin_lon[width S], cos_lon[width S], sin_lat[height S],
-// cos_lat[height S]; the faces [6][N][N][3] f32.  OUT: (width, height, 3) f32.
+// cos_lat[height S]; the faces [6][N][N][3] f32.  OUT: (width, height, 3) f32; rows: [height][width][3] f32.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -52,7 +54,8 @@ static std::vector<T> take(FILE* f, size_t n) {
 }
 
 int main(int argc, char** argv) {
-    if (argc != 3) return 2;
+    if (argc != 3 && !(argc == 4 && strcmp(argv[3], "rows") == 0)) return 2;
+    const bool rows = argc == 4;
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     const std::vector<int32_t> head = take<int32_t>(f, 5);
@@ -69,7 +72,23 @@ int main(int argc, char** argv) {
     std::vector<float> out((size_t)a.width * a.height * 3);
     a.faces = faces.data(); a.out = out.data();
     a.sin_lon = sin_lon.data(); a.cos_lon = cos_lon.data(); a.sin_lat = sin_lat.data(); a.cos_lat = cos_lat.data();
-    for (int i = 0; i < a.width; ++i)
+    if (rows) {
+        for (int j0 = 0; j0 < a.height; j0 += PANO_TILE)
+            for (int i0 = 0; i0 < a.width; i0 += PANO_TILE) {
+                std::vector<float> lon_s((size_t)PANO_MAX_S * PANO_TILE), lon_c(lon_s.size()), lat_s(lon_s.size()), lat_c(lon_s.size());
+                for (int t = 0; t < PANO_TILE * a.S; ++t) {      // the kernel's staging, thread t
+                    const long long ki = (long long)i0 * a.S + t, kj = (long long)j0 * a.S + t;
+                    const bool in_i = ki < (long long)a.width * a.S, in_j = kj < (long long)a.height * a.S;
+                    const int at = (t % a.S) * PANO_TILE + t / a.S;
+                    lon_s[at] = in_i ? sin_lon[ki] : 0.0f; lon_c[at] = in_i ? cos_lon[ki] : 0.0f;
+                    lat_s[t] = in_j ? sin_lat[kj] : 0.0f; lat_c[t] = in_j ? cos_lat[kj] : 0.0f;
+                }
+                for (int jl = 0; jl < PANO_TILE && j0 + jl < a.height; ++jl)
+                    for (int il = 0; il < PANO_TILE && i0 + il < a.width; ++il)
+                        pano_pixel_rows(a, i0 + il, j0 + jl, lon_s.data() + il, lon_c.data() + il, PANO_TILE, lat_s.data() + jl * a.S, lat_c.data() + jl * a.S, 1);
+            }
+    }
+    else for (int i = 0; i < a.width; ++i)
         for (int j = 0; j < a.height; ++j)      // the tables' entries of the pixel, where the kernel hands its LDS copies: [S] along each axis, stride 1
             pano_pixel(a, i, j, sin_lon.data() + (size_t)i * a.S, cos_lon.data() + (size_t)i * a.S, sin_lat.data() + (size_t)j * a.S, cos_lat.data() + (size_t)j * a.S, 1);
     f = fopen(argv[2], "wb");
