@@ -26,11 +26,13 @@
 #include <string>
 #include <vector>
 
-// single translation unit: the kernels are compiled together with the host API
-#include "render_kernel.hip"
-#include "render_kernel_v2.hip"
-#include "de_stages.h"
+// single translation unit: the kernels are compiled together with the host API.  pt_leaves.h (the integrator's leaves) comes in through each of
+// the first three; the per-lane path tracer is in the legacy library only.
+#include "render_kernel.hip"          // the ray marcher, the per-lane pieces (Tracer) and kernel body
+#include "render_kernel_v2.hip"       // path_tracer as a wave-level state machine
+#include "de_stages.h"                // path_tracer in stage form, under render_kernel_v6.hip
 #ifdef DE_LEGACY_VARIANTS
+#include "legacy/render_kernel_v1.hip"
 #include "legacy/render_kernel_v3.hip"
 #include "legacy/render_kernel_v5.hip"
 #endif
@@ -190,7 +192,7 @@ struct de_ctx {
     void* comm = nullptr;        // the context's own RCCL communicator (de_comm_init)
     int comm_rank = 0, comm_world = 1;
     bool trace = false;          // env DE_AUTO_TRACE, read once in de_create: print what the launch policy measured and chose
-    int kernel_variant = 4;      // 4 = automatic (default): large launches run the first vertex rounds in the wavefront pipeline and finish in the state machine, small ones run the state machine alone; 1 = per-lane loops (render_kernel.hip), 2 = wave-level state machine (render_kernel_v2.hip), 3 = wavefront pipeline through HBM queues (render_kernel_v3.hip)
+    int kernel_variant = 4;      // 4 = automatic (default): large launches run the first vertex rounds in the wavefront pipeline and finish in the state machine, small ones run the state machine alone; 1 = per-lane loops (legacy/render_kernel_v1.hip), 2 = wave-level state machine (render_kernel_v2.hip), 3 = wavefront pipeline through HBM queues (render_kernel_v3.hip)
     // render_kernel_v6 (kernel variant 6): one persistent launch per call, one workgroup per CU, stage queues in LDS.  Per launch slot:
     // the control words, one cold record per record slot of every workgroup, the launch's RenderArgs.
     struct V6State {

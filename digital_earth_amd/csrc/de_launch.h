@@ -367,8 +367,8 @@ hipError_t launch_render(de_ctx* c, const RenderArgs& a, hipStream_t stream, Pre
         else hipLaunchKernelGGL((ray_march_kernel<false, MODE>), grid, block, 0, stream, a);
     }
 #ifdef DE_LEGACY_VARIANTS
-    else if (clamp) hipLaunchKernelGGL((render_kernel<true, false, MODE>), grid, block, 0, stream, a);      // kernel variant 1: per-lane loops
-    else hipLaunchKernelGGL((render_kernel<false, false, MODE>), grid, block, 0, stream, a);
+    else if (clamp) hipLaunchKernelGGL((render_kernel<true, MODE>), grid, block, 0, stream, a);      // kernel variant 1: per-lane loops
+    else hipLaunchKernelGGL((render_kernel<false, MODE>), grid, block, 0, stream, a);
 #endif
     return hipGetLastError();
 }

@@ -8,13 +8,12 @@
 // integers in one word); what the loops do not need (throughput, radiance so far, incoming direction, normal, material) is its COLD record
 // (wf::Cold).  The three loop stages (StStage, GasStage, CloudStage) are structs with begin / step / finish (+ suspend / restore: the loop's
 // state between two steps, bit for bit); the four straight-line stages are functions from a record to the stage it goes to next.
-// Written once, used by render_kernel_v6.hip (the product: one persistent launch, stage queues in LDS) and by the two legacy statements of
+// Written once, on the leaves of pt_leaves.h, used by render_kernel_v6.hip (the product: one persistent launch, stage queues in LDS) and by the two legacy statements of
 // the same integrator (legacy/render_kernel_v3.hip: level-synchronous kernels over HBM queues; legacy/render_kernel_v5.hip: one persistent
 // launch over HBM queues).  Every path executes the same arithmetic in the same order on its own RNG stream whichever of them runs it.
 // (Until round 5 this text lived in render_kernel_v3.hip.)
 #pragma once
-#include "de_kernels.h"
-#include "render_kernel_v2.hip"      // namespace v2: the leaf helpers the stage bodies share with the state machine (cloud limits, camera ray, phase evaluation / sampling)
+#include "pt_leaves.h"      // namespace pt: the leaves the stage bodies share with the other statements of the integrator (events, cloud limits, camera ray, phase, colour, bisection)
 
 namespace wf {
 
@@ -27,7 +26,6 @@ template <typename T> DE_DEV const T* opaque_ptr(const T* p) {
 }
 
 enum { Q_ST = 0, Q_GAS, Q_CLOUD, Q_EVENT, Q_SURF, Q_SCFIN, Q_SURFFIN, NQ };
-enum { EV_NULL = 0, EV_ABSORB = 1, EV_SCATTER = 2 };
 
 // per-path state outside the loops (64 bytes, one sector per access)
 struct Cold { float thr, Ls, dx, dy, dz, nx, ny, nz, alb, ocean, bathy, pad0, pad1, pad2, pad3, pad4; };
@@ -54,11 +52,6 @@ DE_DEV uint32_t m_make(int kind, int node, int sc, int below, int ev_id, int eve
 DE_DEV float asf(uint32_t u) { return __builtin_bit_cast(float, u); }
 DE_DEV uint32_t asu(float f) { return __builtin_bit_cast(uint32_t, f); }
 
-// pathtracer.py:145-168 without the `land_isection` line (the caller applies it through c_below): shared with v2
-DE_DEV void cloud_limits_of_ray(vec3 ray_pos, vec3 ray_dir, float* t_start_out, float* t_max_out, int* below_out) {
-    v2::cloud_limits_of_ray(ray_pos, ray_dir, t_start_out, t_max_out, below_out);
-}
-
 // ---- stage glue (pathtracer.py:180-205, 219-232): the same statements v2 executes "in place" when a loop ends
 // enter the cloud-shell segment of the ray in p (kind in meta).  aux = rmo_t (kind 0) or trg (kinds 1, 2); X = isect / li.
 // Returns the queue the record goes to, with p.x laid out for it.
@@ -67,7 +60,7 @@ DE_DEV int enter_cloud(Path& p, float c_ts, float c_tm, float aux, float X) {
     const float t_start = c_ts;
     const float t_max = (m_below(p.meta) && X > 0.0f) ? -1.0f : c_tm;                      // pathtracer.py:166
     bool run = true;
-    if (kind == 0) run = ((m_event(p.meta) & 15) == EV_NULL) || (aux > t_start);          // pathtracer.py:195
+    if (kind == 0) run = ((m_event(p.meta) & 15) == pt::EV_NULL) || (aux > t_start);          // pathtracer.py:195
     const bool enter = run && (t_start < t_max);
     if (enter) { p.x[0] = t_start; p.x[1] = t_max; p.x[2] = aux; p.x[3] = X; return Q_CLOUD; }
     if (kind == 0) { p.x[0] = t_start; p.x[1] = aux; p.x[2] = X; return Q_EVENT; }        // EVENT: t, rmo_t, isect
@@ -91,7 +84,7 @@ DE_DEV int after_sphere_trace(Path& p, float t, float max_ray_dist) {
 DE_DEV void ray_head(Path& p) {
     const vec2_ atmos = rsi(p.P, p.W, DE_ATMOS_UPPER);
     float c_ts, c_tm; int below;
-    cloud_limits_of_ray(p.P, p.W, &c_ts, &c_tm, &below);
+    pt::cloud_limits_of_ray(p.P, p.W, &c_ts, &c_tm, &below);
     p.x[0] = (atmos.x > 0.0f) ? atmos.x : 0.0f;
     p.x[1] = atmos.x; p.x[2] = atmos.y; p.x[3] = c_ts; p.x[4] = c_tm;
     p.meta = (p.meta & ~(1u << 16)) | ((uint32_t)below << 16);
@@ -123,8 +116,7 @@ DE_DEV float sphere_trace(const RenderArgs& a, const Path& p, float land_height_
 }
 
 DE_DEV void write_contrib(const RenderArgs& a, uint32_t pid, float Ls, int node) {
-    if (__builtin_isinf(Ls) || Ls != Ls || Ls < 0.0f) Ls = 0.0f;                          // pathtracer.py:466-467
-    a.contrib[pid] = make_uint2(asu(Ls), (uint32_t)node);
+    a.contrib[pid] = make_uint2(asu(pt::clean_radiance(Ls)), (uint32_t)node);
 }
 
 
@@ -141,7 +133,7 @@ DE_DEV void new_path(const RenderArgs& a, const FrameConsts& fc, const float* s_
     const uint32_t pixel = (uint32_t)(v * a.W + u);
     rng_seed(p.rng, a.seed_lo, a.seed_hi, pixel, (uint32_t)(a.spp_begin + s_idx * a.spp_stride));
     int node = 0;
-    if (!a.fixed_wavelength) {
+    if (!a.fixed_wavelength) {      // pt::spectrum_node<6> written out: called as a function it changes the primary stage's machine code (see pt_leaves.h on the land grading)
         const float sample = rng_next(p.rng);
         node = 1;
 #pragma unroll
@@ -153,7 +145,7 @@ DE_DEV void new_path(const RenderArgs& a, const FrameConsts& fc, const float* s_
         }
     }
     p.pid = w;
-    p.W = v2::get_cast_dir(p.rng, fc, a.H, u, v);
+    p.W = pt::get_cast_dir(p.rng, fc, a.H, u, v);
     p.P = fc.cam_pos;
     p.meta = m_make(0, node, 0, 0, 0, 0);
     p.x[5] = 0.0f;
@@ -175,7 +167,7 @@ DE_DEV int event_body(const RenderArgs& a, const FrameConsts& fc, const ColdT& c
     int event = gas_event;
     float tt = rmo_t;
     int id = m_evid(p.meta);
-    if (cloud_event > 0 && (t < rmo_t || gas_event == EV_NULL)) { tt = t; id = CLOUD_ID; event = cloud_event; }
+    if (cloud_event > 0 && (t < rmo_t || gas_event == pt::EV_NULL)) { tt = t; id = CLOUD_ID; event = cloud_event; }
     if (sc > 9 && id == CLOUD_ID) id = ISOTROPIC_CLOUD_ID;
     vec3 LD;
     {   // sample_cone_oriented (lib/sampling.py:25-28), the light direction's basis from the frame constants
@@ -184,9 +176,9 @@ DE_DEV int event_body(const RenderArgs& a, const FrameConsts& fc, const ColdT& c
         LD = v3((bx.x * cv.x + by.x * cv.y) + bn.x * cv.z, (bx.y * cv.x + by.y * cv.y) + bn.y * cv.z, (bx.z * cv.x + by.z * cv.y) + bn.z * cv.z);
     }
     bool end = false, miss = false;
-    if (event == EV_ABSORB) {
+    if (event == pt::EV_ABSORB) {
         end = true;
-    } else if (event == EV_SCATTER) {
+    } else if (event == pt::EV_SCATTER) {
         p.P = p.P + tt * D;
         if (sc == 0) cold.set_thr_ls(p.pid, 1.0f, 0.0f);
         cold.set_dir(p.pid, D);
@@ -199,7 +191,7 @@ DE_DEV int event_body(const RenderArgs& a, const FrameConsts& fc, const ColdT& c
         } else {
             const vec2_ atmos = rsi(p.P, LD, DE_ATMOS_UPPER);
             float c_ts, c_tm; int below;
-            cloud_limits_of_ray(p.P, LD, &c_ts, &c_tm, &below);
+            pt::cloud_limits_of_ray(p.P, LD, &c_ts, &c_tm, &below);
             p.meta = m_make(1, node, sc, below, id, 0);
             const float t_start = de_max(0.0f, atmos.x);
             float t_max = atmos.y;                                  // land_isection = -1
@@ -227,9 +219,7 @@ DE_DEV int event_body(const RenderArgs& a, const FrameConsts& fc, const ColdT& c
         float Ls = (sc == 0) ? 0.0f : cold.get_ls(p.pid);
         if (miss) {                                                  // pathtracer.py:455-463; D is still the primary direction
             if (dot(fc.light_dir, D) > fc.sun_cos_angle) Ls += L.sun_power;
-            const vec3 stars_srgb = sphere_tap_rgb<CLAMP>(a.stars, normalized(D));
-            const float stars_power = v2::srgb_to_spectrum(L, stars_srgb);
-            Ls += stars_power * L.sun_power * 0.0000001f;
+            Ls += pt::stars_term(L, sphere_tap_rgb<CLAMP>(a.stars, normalized(D)));
         }
         write_contrib(a, p.pid, Ls, node);
     }
@@ -267,7 +257,7 @@ DE_DEV int surf_body(const RenderArgs& a, const FrameConsts& fc, const ColdT& co
     const vec3 albedo_srgb = mix3(land, ocean_albedo, ocean);
     const float bathy = tap_r8<CLAMP>(a.bathy, uu, vv);
     const float emissive = tap_r8<CLAMP>(a.emissive, uu, vv);
-    const float alb = v2::srgb_to_spectrum(L, albedo_srgb);
+    const float alb = pt::srgb_to_spectrum(L, albedo_srgb);
     float thr, Ls;
     cold.get_thr_ls(p.pid, thr, Ls);
     cold.set_thr_ls(p.pid, thr, Ls + thr * emissive * L.night_power);
@@ -311,10 +301,10 @@ DE_DEV int scfin_body(const RenderArgs& a, const FrameConsts& fc, const ColdT& c
     const vec3 D = cold.get_dir(p.pid), LD = p.W;
     const float trg = p.x[0], trn = p.x[1], li = p.x[2];
     const float direct_tr = (li > 0.0f) ? 0.0f : trg * trn;
-    const float direct_phase = v2::evaluate_phase(fc, D, LD, ev_id, sc > 0);
+    const float direct_phase = pt::evaluate_phase(fc, D, LD, ev_id, sc > 0);
     Ls += thr * direct_tr * L.sun_irradiance * direct_phase;
     float phase_div_pdf;
-    const vec3 nd = v2::sample_phase(fc, p.rng, D, ev_id, sc > 0, &phase_div_pdf);
+    const vec3 nd = pt::sample_phase(fc, p.rng, D, ev_id, sc > 0, &phase_div_pdf);
     thr *= phase_div_pdf;
     return vertex_end(a, cold, p, node, sc, thr, Ls, nd);
 }
@@ -401,7 +391,7 @@ struct GasStage {
         kind = wf::m_kind(p.meta);
         t = p.x[0]; tmax = p.x[1];
         C = p.P + t * p.W;
-        trn = 1.0f; event = wf::EV_NULL; ev_id = 0;
+        trn = 1.0f; event = pt::EV_NULL; ev_id = 0;
     }
     DE_DEV bool step(wf::Path& p) {
         const float neg_log = -de_log_unit(rng_next(p.rng));
@@ -451,7 +441,7 @@ struct GasStage {
                 }
             }
             const float albedo = (id == 0) ? 1.0f : ((id == 1) ? 0.95f : ((id == 2) ? 0.0f : 0.99f));
-            event = (rng_next(p.rng) < albedo) ? wf::EV_SCATTER : wf::EV_ABSORB;
+            event = (rng_next(p.rng) < albedo) ? pt::EV_SCATTER : pt::EV_ABSORB;
             ev_id = id;
             done = true;
         }
@@ -573,7 +563,7 @@ struct CloudStage {
         const float trn_r = trn * (1.0f - pr);
         trn = delta ? trn : trn_r;
         bool done = !delta & (trn_r < 1e-5f);
-        if (delta & (rand < pr)) { cloud_event = (rng_next(p.rng) < 0.99f) ? wf::EV_SCATTER : wf::EV_ABSORB; done = true; }
+        if (delta & (rand < pr)) { cloud_event = (rng_next(p.rng) < 0.99f) ? pt::EV_SCATTER : pt::EV_ABSORB; done = true; }
         return done | !(t < tmax);
     }
     DE_DEV bool step(wf::Path& p) { Tok k; return issue(p, k) || resolve(p, k); }

@@ -1,5 +1,5 @@
 // legacy/de_launch_legacy.h — host side of the kernel families the product no longer runs (library built with -DDE_LEGACY_VARIANTS only:
-// libdigitalearth_hip_legacy.so, loaded by the cross-check tests through DE_LIB_PATH): render_kernel (per-lane loops, variant 1), the wavefront
+// libdigitalearth_hip_legacy.so, loaded by the cross-check tests through DE_LIB_PATH): render_kernel (per-lane loops, variant 1: legacy/render_kernel_v1.hip), the wavefront
 // pipeline through HBM queues with its launch policy of rounds 3-4 (variants 3 and, with DE_AUTO_V6=0, 4) and the HBM-queue stage scheduler
 // (variant 5).  They are three further statements of path_tracer that must give the product's bits; nothing here is product surface.  This
 // library reads its experiment knobs from the environment as rounds 1-4 did (the product library reads none: de_set_tuning).

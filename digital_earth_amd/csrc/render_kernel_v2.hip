@@ -1,6 +1,6 @@
 // render_kernel_v2.hip — path_tracer (pathtracer.py:316-469) as a WAVEFRONT-LEVEL STATE MACHINE.
 //
-// Why: in the straightforward kernel (render_kernel.hip) every lane walks the reference's nested loops
+// Why: in the straightforward kernel (legacy/render_kernel_v1.hip) every lane walks the reference's nested loops
 // (250-step sphere trace, two delta-tracking loops, two ratio-tracking loops per light sample, 25 vertices) and the
 // 64 lanes of a wave serialise on each other's trip counts: rocprofv3 measured 11.5 % VALU lane utilisation
 // (profiles/r1a_summary.md).  Here each lane carries an explicit `state`; every trip of the wave loop advances
@@ -15,14 +15,12 @@
 // consecutive transitions in one pass.  Lanes start their next sample immediately when a path ends (path
 // regeneration), so short paths do not idle the lane.
 //
-// Results are IDENTICAL to render_kernel.hip and to the CPU oracle: each lane executes the same arithmetic in the
+// Results are IDENTICAL to the per-lane loops and to the CPU oracle: each lane executes the same arithmetic in the
 // same order on its own RNG stream; only the interleaving between lanes changes.
 #pragma once
-#include "de_kernels.h"
+#include "pt_leaves.h"      // namespace pt: the leaves shared with the other statements of the integrator (events, cloud limits, phase, colour, camera ray, bisection)
 
 namespace v2 {
-
-enum { EV_NULL = 0, EV_ABSORB = 1, EV_SCATTER = 2 };
 
 // lane states.  Loop states first (class tests are range tests).
 enum : int {
@@ -55,99 +53,6 @@ DE_DEV bool is_cloud_tap(int s) { return s >= S_DT_C && s <= S_RT_C_S; }
 
 struct Work2 { uint32_t taps_r8, taps_rgb, sphere_steps, tracking_steps, vertices, draws; };
 
-// pathtracer.py:145-169
-DE_DEV void intersect_cloud_limits(vec3 ray_pos, vec3 ray_dir, float land_isection, float* t_start_out, float* t_max_out) {
-    float t_start = 0.0f, t_max = 0.0f;
-    float elevation = length(ray_pos);
-    vec2_ lower = rsi(ray_pos, ray_dir, DE_CLOUDS_LOWER);
-    vec2_ upper = rsi(ray_pos, ray_dir, DE_CLOUDS_UPPER);
-    if (elevation >= DE_CLOUDS_UPPER) {
-        t_start = de_max(0.0f, upper.x);
-        t_max = (lower.y >= 0.0f) ? lower.x : upper.y;
-        if (upper.y < 0.0f) t_max = -1.0f;
-    } else if (elevation >= DE_CLOUDS_LOWER) {
-        t_start = 0.0f;
-        t_max = (lower.y >= 0.0f) ? lower.x : upper.y;
-    } else {
-        t_start = lower.y;
-        t_max = upper.y;
-        if (land_isection > 0.0f) t_max = -1.0f;
-    }
-    *t_start_out = t_start; *t_max_out = t_max;
-}
-// pathtracer.py:145-168 up to (not including) the `if land_isection > 0.0: t_max = -1.0` of the below-cloud branch:
-// everything that depends on the ray alone, computed when the ray is set up.  `below` tells the caller to apply that line.
-DE_DEV void cloud_limits_of_ray(vec3 ray_pos, vec3 ray_dir, float* t_start_out, float* t_max_out, int* below_out) {
-    float t_start = 0.0f, t_max = 0.0f;
-    int below = 0;
-    float elevation = length_nr(ray_pos);
-    vec2_ lower = rsi(ray_pos, ray_dir, DE_CLOUDS_LOWER);
-    vec2_ upper = rsi(ray_pos, ray_dir, DE_CLOUDS_UPPER);
-    if (elevation >= DE_CLOUDS_UPPER) {
-        t_start = de_max(0.0f, upper.x);
-        t_max = (lower.y >= 0.0f) ? lower.x : upper.y;
-        if (upper.y < 0.0f) t_max = -1.0f;
-    } else if (elevation >= DE_CLOUDS_LOWER) {
-        t_start = 0.0f;
-        t_max = (lower.y >= 0.0f) ? lower.x : upper.y;
-    } else {
-        t_start = lower.y;
-        t_max = upper.y;
-        below = 1;
-    }
-    *t_start_out = t_start; *t_max_out = t_max; *below_out = below;
-}
-// pathtracer.py:235-247
-DE_DEV float evaluate_phase(const FrameConsts& fc, vec3 ray_dir, vec3 light_dir, int id, bool reduce_peak) {
-    float phase = 0.0f;
-    float c = dot(ray_dir, light_dir);
-    if (id == RAYLEIGH_ID) phase += rayleigh_phase(c);
-    else if (id == MIE_ID) phase += klein_nishina_phase(c, DE_MIE_ASYMMETRY, fc.kn_log);
-    else if (id == CLOUD_ID) phase += cloud_phase(fc.cloud, c, reduce_peak);
-    else if (id == ISOTROPIC_CLOUD_ID) phase += (float)(1.0 / (4.0 * M_PI));
-    return phase;
-}
-// pathtracer.py:249-261
-DE_DEV vec3 sample_phase(const FrameConsts& fc, Rng& rng, vec3 ray_dir, int id, bool reduce_peak, float* phase_div_pdf) {
-    *phase_div_pdf = 1.0f;
-    if (id == RAYLEIGH_ID || id == ISOTROPIC_CLOUD_ID) {
-        float r0 = rng_next(rng);
-        float r1 = rng_next(rng);
-        vec3 d = sample_sphere(r0, r1);
-        *phase_div_pdf = evaluate_phase(fc, ray_dir, d, id, reduce_peak) * (float)(4.0 * M_PI);
-        return d;
-    } else if (id == MIE_ID) {
-        return sample_klein_nishina_phase(rng, ray_dir, DE_MIE_ASYMMETRY);
-    }
-    return sample_cloud_phase(fc.cloud, rng, ray_dir, reduce_peak);
-}
-DE_DEV float srgb_to_spectrum(const LambdaNode& L, vec3 rgb) {
-    return (L.s2s_valid != 0.0f) ? dot(rgb, v3(L.c0, L.c1, L.c2)) : 0.0f;
-}
-// lib/colour.py:21-39.  The first DE_V2_LDS_TREE_LEVELS levels of the bisection tree are read from the wave's LDS copy, the
-// rest from global memory (measured per frame: 0 levels 232 ms, 5 levels 230 ms, 6 levels 228 ms, 7 levels 238 ms — the LDS
-// they take is what limits the waves per CU; reading the last two levels with one 32-byte block read changed nothing).
-#ifndef DE_V2_LDS_TREE_LEVELS
-#define DE_V2_LDS_TREE_LEVELS 6
-#endif
-DE_DEV int spectrum_node(const float* lds_val, const float* node_val, float sample) {
-    int n = 1;
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        float val = (it < DE_V2_LDS_TREE_LEVELS) ? lds_val[n] : node_val[n];
-        if (val < sample) n = 2 * n + 1;
-        else if (val > sample) n = 2 * n;
-        else break;
-    }
-    return n;
-}
-DE_DEV vec3 get_cast_dir(Rng& rng, const FrameConsts& fc, int H, int u, int v) {   // renderer.py:269-279
-    float fov = fc.fov;
-    float fu = (2.0f * fov * ((float)u + rng_next(rng)) / (float)H - fov * fc.aspect_ratio - 1e-5f) * fc.aspect_scale;
-    float fv = 2.0f * fov * ((float)v + rng_next(rng)) / (float)H - fov - 1e-5f;
-    return normalized(fc.d + fu * fc.du + fv * fc.dv);
-}
-
 }  // namespace v2
 
 #ifndef DE_V2_CHUNK
@@ -169,7 +74,8 @@ template <bool CLAMP, int MODE>
 __attribute__((amdgpu_num_vgpr(DE_V2_NUM_VGPR)))
 #endif
 __global__ void __launch_bounds__(DE_V2_BLOCK, DE_V2_MIN_WAVES) render_kernel_v2(RenderArgs a, const FrameConsts* __restrict__ fcp) {
-    using namespace v2;
+    using namespace v2;      // the state machine's own: lane states, class tests, Work2
+    using namespace pt;      // the integrator's leaves (pt_leaves.h)
     // Persistent waves over WORK ITEMS = single samples.  Item w of the launch is sample (w / 64) % spp of lane-pixel
     // (w & 63) of owned tile a.tiles[w / (64 * spp)].  A wave takes chunks of DE_V2_CHUNK consecutive items from a
     // device-wide counter (one atomic per chunk) and hands them to its lanes one by one as paths end, so no lane idles
@@ -576,11 +482,9 @@ __global__ void __launch_bounds__(DE_V2_BLOCK, DE_V2_MIN_WAVES) render_kernel_v2
                 if (state == S_END_MISS) {
                     if (dot(fc.light_dir, D) > fc.sun_cos_angle) Ls += L.sun_power;     // D is still the primary direction
                     if (MODE) wk.taps_rgb += 1;
-                    vec3 stars_srgb = sphere_tap_rgb<CLAMP>(a.stars, normalized(D));
-                    float stars_power = srgb_to_spectrum(L, stars_srgb);
-                    Ls += stars_power * L.sun_power * 0.0000001f;
+                    Ls += stars_term(L, sphere_tap_rgb<CLAMP>(a.stars, normalized(D)));
                 }
-                if (__builtin_isinf(Ls) || Ls != Ls || Ls < 0.0f) Ls = 0.0f;
+                Ls = clean_radiance(Ls);
                 if (MODE != 2) a.contrib[w] = make_uint2(__builtin_bit_cast(uint32_t, Ls), (uint32_t)node);
                 if (MODE) wk.draws += rng.draws;
                 if (MODE == 2) {
@@ -779,10 +683,10 @@ __global__ void __launch_bounds__(DE_V2_BLOCK, DE_V2_MIN_WAVES) render_kernel_v2
                     const uint32_t pixel = (uint32_t)(v * a.W + u);
                     rng_seed(rng, a.seed_lo, a.seed_hi, pixel, (uint32_t)(a.spp_begin + s_idx * a.spp_stride));
                     node = 0;
-                    if (!a.fixed_wavelength) node = v2::spectrum_node(s_node_val, a.node_val, rng_next(rng));
+                    if (!a.fixed_wavelength) node = spectrum_node<DE_V2_LDS_TREE_LEVELS>(s_node_val, a.node_val, rng_next(rng));
                     const LambdaNode& L = a.nodes[node];
                     ext_r = L.ext_r; ext_m = L.ext_m; ext_o = L.ext_o; rmaxr = L.inv_max_ext_rmo;
-                    D = v2::get_cast_dir(rng, fc, a.H, u, v);
+                    D = get_cast_dir(rng, fc, a.H, u, v);
                     P = fc.cam_pos;
                     thr = 1.0f; Ls = 0.0f; sc = 0;
                     path_vertices = 0;
@@ -810,13 +714,7 @@ __global__ void __launch_bounds__(DE_V2_BLOCK, DE_V2_MIN_WAVES) render_kernel_v2
     }
 
     if (MODE == 1) {
-        atomicAdd(&a.counters[0], (unsigned long long)n_samples);
-        atomicAdd(&a.counters[1], (unsigned long long)wk.taps_r8);
-        atomicAdd(&a.counters[2], (unsigned long long)wk.taps_rgb);
-        atomicAdd(&a.counters[3], (unsigned long long)wk.sphere_steps);
-        atomicAdd(&a.counters[4], (unsigned long long)wk.tracking_steps);
-        atomicAdd(&a.counters[5], (unsigned long long)wk.vertices);
-        atomicAdd(&a.counters[6], (unsigned long long)wk.draws);
+        flush_work_counters(a.counters, n_samples, wk.taps_r8, wk.taps_rgb, wk.sphere_steps, wk.tracking_steps, wk.vertices, wk.draws);
         if (lane == 0) {   // per-wave scheduler statistics: trips, passes, section cycle counters (s_memtime)
             atomicAdd(&a.counters[7], (unsigned long long)st[0]);
             atomicAdd(&a.counters[8], (unsigned long long)st[1]);
