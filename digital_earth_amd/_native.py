@@ -135,6 +135,12 @@ JPEG_DEFAULT_RESTART = 2      # DE_JPEG_DEFAULT_RESTART of include/digital_earth
 PNG_DEFAULT_CHUNK = 32768     # DE_PNG_DEFAULT_CHUNK of include/digital_earth_png.h
 PNG_SOURCES = ("pixels", "hdr_pixels")                                    # DE_PNG_SOURCE_*
 PNG_FILTERS = ("none", "sub", "up", "average", "paeth", "adaptive")       # DE_PNG_FILTER_*
+class DeRgbe(ctypes.Structure):
+    """`de_rgbe` (include/digital_earth_rgbe.h): the source, the row coding, the rounding and the scale of the Radiance HDR output."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("source", ctypes.c_int32), ("rle", ctypes.c_int32), ("rounding", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
+RGBE_ROUNDINGS = {"trunc": 0, "round": 1}                                 # DE_RGBE_ROUND_TRUNC, _NEAREST
 EXR_DEFAULT_CHUNK = 32768     # DE_EXR_DEFAULT_CHUNK of include/digital_earth_exr.h
 EXR_SOURCES = ("mean", "denoised", "history", "bloom", "local_exposure")  # DE_EXR_SOURCE_*
 EXR_PIXEL_TYPES = {"half": 1, "float": 2}                                 # DE_EXR_PIXEL_*: the file's own numbers
@@ -370,6 +376,21 @@ EXR_SYMBOLS = {
     "de_debug_exr_framing": (ctypes.c_int, [ctypes.POINTER(DeExr), ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint64, _U64P, _U64P]),
 }
 
+# Radiance HDR output: include/digital_earth_rgbe.h (same library, additions only; not part of the binder's header)
+RGBE_SYMBOLS = {
+    "de_set_rgbe": (ctypes.c_int, [_P, ctypes.POINTER(DeRgbe)]),
+    "de_get_rgbe": (ctypes.c_int, [_P, ctypes.POINTER(DeRgbe)]),
+    "de_rgbe_capacity": (ctypes.c_int, [_P, _U64P]),
+    "de_render_to_rgbe": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
+    "de_fetch_rgbe": (ctypes.c_int, [_P, _P, ctypes.c_uint64, _U64P]),
+    "de_fetch_rgbe_view": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_fetch_rgbe_begin": (ctypes.c_int, [_P]),
+    "de_fetch_rgbe_end": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), _U64P]),
+    "de_debug_rgbe": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeRgbe), _P, ctypes.c_uint64, _U64P]),
+    "de_debug_rgbe_framing": (ctypes.c_int, [ctypes.POINTER(DeRgbe), ctypes.c_int, ctypes.c_int, _P, ctypes.c_uint64, _U64P, _U64P]),
+    "de_debug_environment_rgbe": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), ctypes.POINTER(DeRgbe), _P, ctypes.c_uint64, _U64P]),
+}
+
 # look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
 LOOK_SYMBOLS = {
     "de_set_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook), _P, _P]),
@@ -456,7 +477,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()) + list(RGBE_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -107,7 +107,7 @@ int de_destroy(de_ctx* c) {
     if (c->comm && g_rccl.CommDestroy) { g_rccl.CommDestroy(c->comm); c->comm = nullptr; }
     release_loan(c);
     // events and streams; the memory is the members' (de_memory.h): `delete c` frees what this context owns and leaves what it borrows
-    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring, &c->ex_coded.ring}) ring_destroy_events(*r);
+    for (FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring, &c->ex_coded.ring, &c->rg_coded.ring}) ring_destroy_events(*r);
 #ifdef DE_LEGACY_VARIANTS
     destroy_legacy_events(c);
 #endif
@@ -1230,6 +1230,7 @@ int de_set_panorama(de_ctx* c, const de_panorama* s) {
     for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
     // an EXR fetch of the scene-linear panorama reads the linear slots and the tables (include/digital_earth_environment.h); one of the pinhole frame reads nothing of this stage
     if (ring_any_in_flight(c->ex_coded.ring, [c](int k) { return c->ex_cell_env[k]; })) return refuse_in_flight(c->ex_coded.ring);
+    if (ring_any_in_flight(c->rg_coded.ring, [c](int k) { return c->rg_cell_env[k]; })) return refuse_in_flight(c->rg_coded.ring);      // the same of an RGBE fetch (include/digital_earth_rgbe.h)
     HIP_TRY(hipSetDevice(c->device));
     { int rc = c->pano_faces.ensure((size_t)DE_PANO_FACES * (size_t)c->W * (size_t)c->W * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
     { int rc = c->pano_out.ensure((size_t)s->width * (size_t)s->height * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
@@ -1883,6 +1884,128 @@ int de_debug_exr_aov_framing(const de_exr* s, uint32_t mask, int W, int H, void*
         memset((uint8_t*)out + n, 0, g.front - n);
     }
     return DE_OK;
+}
+
+/* ---- Radiance HDR output: include/digital_earth_rgbe.h (rgbe_kernels.hip, rgbe_tables.h) */
+int de_set_rgbe(de_ctx* c, const de_rgbe* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = rg_settings_check(s); if (rc) return rc; }
+    { int rc = refuse_in_flight(c->rg_coded.ring); if (rc) return rc; }
+    c->rg = *s;
+    c->rg_coded.guess = 0;
+    packed_reset(c->rg_coded.out);
+    return DE_OK;
+}
+int de_get_rgbe(de_ctx* c, de_rgbe* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->rg;
+    return DE_OK;
+}
+int de_rgbe_capacity(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = rg_ctx_shape_check(c); if (rc) return rc; }
+    *bytes = (uint64_t)rg_ctx_geometry(c).capacity;
+    return DE_OK;
+}
+int de_render_to_rgbe(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    int rc = rg_render(c, c->rg_coded.out.dev);
+    if (rc) return rc;
+    if (device_stream) *device_stream = c->rg_coded.out.dev + CS_WORD_BYTES;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->rg_coded.out.dev.get());
+    return DE_OK;
+}
+int de_fetch_rgbe_view(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = de_render_to_rgbe(c, nullptr, nullptr);
+    if (rc) return rc;
+    return coded_view(c, c->rg_coded, rg_length, host, len);
+}
+int de_fetch_rgbe(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    const void* host = nullptr;
+    int rc = de_fetch_rgbe_view(c, &host, len);
+    if (rc) return rc;
+    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the file (*len; de_rgbe_capacity bounds every frame)");
+}
+int de_fetch_rgbe_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = rg_pano_refusal(c); if (rc) return rc; }
+    { int rc = rg_ctx_shape_check(c); if (rc) return rc; }
+    const RgbeGeometry g = rg_ctx_geometry(c);
+    const int cell = ring_next_cell(c->rg_coded.ring);
+    int rc = coded_begin(c, c->rg_coded, g.header + 2 * (size_t)g.W * (size_t)g.H, g.capacity, [c](int k) { return rg_render(c, c->rg_coded.cell[k]); });      // the first: the front and half the flat bytes
+    if (!rc) c->rg_cell_env[cell] = env_active(c);      // de_set_panorama waits for a fetch of the scene-linear panorama
+    return rc;
+}
+int de_fetch_rgbe_end(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    return coded_end(c, c->rg_coded, rg_length, host, len);
+}
+/* the conversion once on a host-given image of any size, rows top-down.  Buffers of its own; the context's settings and streams are not touched. */
+int de_debug_rgbe(de_ctx* c, const float* image, int W, int H, const de_rgbe* s, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !image || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = rg_settings_check(s); if (rc) return rc; }
+    { int rc = rg_shape_check(W, H); if (rc) return rc; }
+    const RgbeGeometry g = rg_geometry(W, H, *s);
+    HIP_TRY(hipSetDevice(c->device));
+    de_ctx::RgbeWork work;
+    Dev<float> d_image;
+    Dev<uint8_t> d_out;
+    const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
+    { int rc = rg_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_image.ensure(image_bytes));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
+    HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));      // behind it every way out waits for the stream: the copy reads the caller's array
+    DisplaySrc src;
+    src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;      // x / 1.0f == x
+    { int rc = rg_launch(c->stream, work, g, src, false, s->rounding, d_out, [] { return (int)DE_OK; }); if (rc) { (void)hipStreamSynchronize(c->stream); return rc; } }
+    return coded_debug_out(c->stream, d_out, rg_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+}
+/* the host's part alone: no device, no context */
+int de_debug_rgbe_framing(const de_rgbe* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
+    if (!s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = rg_settings_check(s); if (rc) return rc; }
+    { int rc = rg_shape_check(W, H); if (rc) return rc; }
+    const RgbeGeometry g = rg_geometry(W, H, *s);
+    if (len) *len = g.header;
+    if (capacity) *capacity = (uint64_t)g.capacity;
+    if (out || out_bytes) {
+        if (!out || out_bytes < g.header) return fail(DE_ERR_INVALID, "out_bytes is smaller than the front (*len)");
+        memcpy(out, g.text, g.header);
+    }
+    return DE_OK;
+}
+/* The resampling and the conversion once on host-given linear faces, as de_debug_environment_exr.  Buffers and tables of its own; the context's
+ * settings and slots are not touched.  The arguments and both settings are checked before the context is read. */
+int de_debug_environment_rgbe(de_ctx* c, const float* faces, int n, const de_panorama* p, const de_rgbe* s, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !faces || !p || !s || !out || !len || n < 4 || n > 16384) return fail(DE_ERR_INVALID, "bad arguments (faces of 4 ... 16384 pixels a side)");
+    { int rc = pano_settings_check(p, n); if (rc) return rc; }
+    { int rc = rg_settings_check(s); if (rc) return rc; }
+    { int rc = rg_shape_check(p->width, p->height); if (rc) return rc; }
+    const RgbeGeometry g = rg_geometry(p->width, p->height, *s);
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<float> d_faces, d_image;
+    Dev<uint8_t> d_out;
+    de_ctx::PanoTab tab;
+    de_ctx::RgbeWork work;
+    PanoArgs k = {};
+    pano_make_consts(*p, n, &k);
+    const size_t in_bytes = (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float), image_bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
+    { int rc = rg_work_ensure(work, g); if (rc) return rc; }
+    HIP_TRY(d_faces.ensure(in_bytes));
+    HIP_TRY(d_image.ensure(image_bytes));
+    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
+    if (p->projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, tab, p->width, p->height, p->supersample); if (rc) return rc; }
+    HIP_TRY(hipMemcpyAsync(d_faces, faces, in_bytes, hipMemcpyHostToDevice, c->stream));      // behind it every way out waits for the stream: the copy reads the caller's array
+    int rc = pano_launch(c->stream, *p, k, n, d_faces, tab, d_image, true);
+    if (!rc) {
+        DisplaySrc src;
+        src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = p->width; src.H = p->height;      // x / 1.0f == x
+        rc = rg_launch(c->stream, work, g, src, true, s->rounding, d_out, [] { return (int)DE_OK; });
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    return coded_debug_out(c->stream, d_out, rg_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
 }
 
 /* ---- look LUTs: include/digital_earth_look.h (look_kernels.hip) */

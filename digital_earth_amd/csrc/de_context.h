@@ -16,6 +16,7 @@
 #include "../../include/digital_earth_exr.h"
 #include "../../include/digital_earth_exr_aovs.h"
 #include "../../include/digital_earth_environment.h"
+#include "../../include/digital_earth_rgbe.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -54,6 +55,7 @@
 #include "jpeg_kernels.hip"
 #include "png_kernels.hip"
 #include "exr_kernels.hip"
+#include "rgbe_kernels.hip"
 
 namespace {
 
@@ -372,6 +374,15 @@ struct de_ctx {
     uint32_t ex_aovs = 0;         // DE_EXR_AOV_* (include/digital_earth_exr_aovs.h): the channels beside B, G, R; 0: none, the file of §23
     ExrWork ex_work;
     CodedOut ex_coded = {{"EXR"}, {"EXR", "de_fetch_exr"}};
+    // Radiance HDR output (include/digital_earth_rgbe.h).  Everything reaches the device on first use: the planar bytes, the planes'
+    // slots and words of one conversion (RgbeWork) and the files of rg_coded.  The front travels in the kernels' arguments.
+    struct RgbeWork {             // what one conversion passes through; re-allocated when a frame needs more
+        Dev<uint8_t> planes, slots; Dev<uint32_t> words;
+    };
+    de_rgbe rg = {(uint32_t)sizeof(de_rgbe), DE_EXR_SOURCE_MEAN, 1, DE_RGBE_ROUND_TRUNC, 1.0f};
+    RgbeWork rg_work;
+    CodedOut rg_coded = {{"RGBE"}, {"RGBE", "de_fetch_rgbe"}};
+    bool rg_cell_env[DE_FETCH_RING] = {};      // lagged RGBE fetch in ring cell k was begun with the panorama on: it reads env_faces and env_out
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

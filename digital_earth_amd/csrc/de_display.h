@@ -1058,4 +1058,106 @@ int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
     c->ex_coded.out.count++;
     return DE_OK;
 }
+
+// ---- Radiance HDR output (include/digital_earth_rgbe.h, rgbe_kernels.hip, rgbe_tables.h): where the EXR output sits, another file
+int rg_settings_check(const de_rgbe* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_rgbe)) return fail(DE_ERR_INVALID, "de_rgbe.struct_bytes does not match this library's struct");
+    if (s->source < DE_EXR_SOURCE_MEAN || s->source > DE_EXR_SOURCE_LOCAL_EXPOSURE) return fail(DE_ERR_INVALID, "de_rgbe.source must be DE_EXR_SOURCE_MEAN, _DENOISED, _HISTORY, _BLOOM or _LOCAL_EXPOSURE");
+    if (s->rle != 0 && s->rle != 1) return fail(DE_ERR_INVALID, "de_rgbe.rle must be 0 or 1");
+    if (s->rounding != DE_RGBE_ROUND_TRUNC && s->rounding != DE_RGBE_ROUND_NEAREST) return fail(DE_ERR_INVALID, "de_rgbe.rounding must be DE_RGBE_ROUND_TRUNC or _NEAREST");
+    if (!(s->scale > 0.0f) || !(s->scale < INFINITY)) return fail(DE_ERR_INVALID, "de_rgbe.scale must be finite and greater than 0");      // NaN fails the first
+    return DE_OK;
+}
+int rg_shape_check(int W, int H) {      // what one conversion can take: the kernels count bytes in 32 bits
+    if (W <= 0 || H <= 0) return fail(DE_ERR_INVALID, "an RGBE frame needs W, H >= 1");
+    if (4ull * (unsigned long long)W * (unsigned long long)H > RGBE_MAX_FLAT) return fail(DE_ERR_INVALID, "the RGBE output takes at most 2^27 flat bytes, 4 W H");
+    return DE_OK;
+}
+RgbeGeometry rg_geometry(int W, int H, const de_rgbe& s) { return rgbe_geometry(W, H, s.rle, s.scale); }
+// The buffers of one conversion of geometry g; `words` holds len[pieces], offset[pieces] and the status word.  Flat rows need the word alone.
+int rg_work_ensure(de_ctx::RgbeWork& w, const RgbeGeometry& g) {
+    int rc = w.planes.ensure(g.rle ? g.pieces * g.plane_stride : 16, "RGBE buffers");
+    if (!rc) rc = w.slots.ensure(g.rle ? g.pieces * g.slot_bytes : 16, "RGBE buffers");
+    if (!rc) rc = w.words.ensure((2 * g.pieces + 4) * sizeof(uint32_t), "RGBE buffers");
+    return rc;
+}
+// src (on this stream) -> the planar bytes -> slots -> the file at `out`; flat rows straight into the file.  `after_convert` runs behind the one
+// kernel that reads `src`.
+template <class AfterConvert>
+int rg_launch(hipStream_t stream, const de_ctx::RgbeWork& w, const RgbeGeometry& g, const DisplaySrc& src, bool flip, int rounding, uint8_t* out, AfterConvert after_convert) {
+    RgbeArgs a;
+    a.src = src; a.flip = flip ? 1 : 0; a.scale = g.scale; a.rounding = rounding; a.rle = g.rle; a.planes = w.planes; a.slots = w.slots;
+    a.len = w.words; a.offset = w.words + g.pieces; a.status = w.words + 2 * g.pieces; a.out = out;
+    a.W = (uint32_t)g.W; a.H = (uint32_t)g.H; a.plane_stride = (uint32_t)g.plane_stride; a.header = (uint32_t)g.header;
+    a.count = (uint32_t)g.pieces; a.slot_bytes = (uint32_t)g.slot_bytes;
+    a.front = (uint32_t)g.front; a.extra = 0u; a.trailer = 0u; a.capacity = (uint32_t)g.capacity;
+    memcpy(a.front_bytes, g.text, sizeof(a.front_bytes));
+    const unsigned row_wgs = (unsigned)((((size_t)g.W + 3) / 4 + 255) / 256);      // rgbe_row_workgroups
+    if (src_aligned(src) && (g.W & 3) == 0) hipLaunchKernelGGL(rgbe_convert_kernel<true>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(rgbe_convert_kernel<false>, dim3(row_wgs * (unsigned)g.H), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    { int rc = after_convert(); if (rc) return rc; }
+    if (g.rle) hipLaunchKernelGGL(rgbe_code_kernel, dim3((unsigned)g.pieces), dim3(RGBE_THREADS), g.plane_stride, stream, a);      // the plane is its dynamic LDS
+    hipLaunchKernelGGL(rgbe_scan_kernel, dim3(1), dim3(CS_SCAN_THREADS), 0, stream, a);
+    if (g.rle) hipLaunchKernelGGL(rgbe_compact_kernel, dim3((unsigned)g.pieces), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return DE_OK;
+}
+// of the context's frame, or of the scene-linear panorama while that is what the RGBE calls deliver
+RgbeGeometry rg_ctx_geometry(const de_ctx* c) { return env_active(c) ? rg_geometry(c->pano.width, c->pano.height, c->rg) : rg_geometry(c->W, c->H, c->rg); }
+int rg_ctx_shape_check(const de_ctx* c) { return env_active(c) ? rg_shape_check(c->pano.width, c->pano.height) : rg_shape_check(c->W, c->H); }
+// As ex_pano_refusal: in front of the display a panorama exists only as the six linear slots.
+int rg_pano_refusal(const de_ctx* c) {
+    if (c->pano.on && c->env_mask != 63u) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): the RGBE output reads the frame in front of the display, where a panorama exists only once six linear faces are captured (de_environment_capture)");
+    return DE_OK;
+}
+int rg_length(const void* word, uint64_t* len) {      // its coder raises no range status
+    static const char* const text = "the RGBE encoder met a plane longer than its proven worst case: nothing was written past a buffer";
+    return coded_read_word(word, len, text, text);
+}
+// One conversion of the scene-linear panorama into `dev` (env_active), as ex_render_environment: the six linear slots resampled into env_out, read
+// with its rows flipped and a divisor of 1.  Nothing is waited for.
+int rg_render_environment(de_ctx* c, Dev<uint8_t>& dev) {
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = rg_ctx_shape_check(c);
+    if (rc) return rc;
+    const RgbeGeometry g = rg_ctx_geometry(c);
+    rc = c->env_out.ensure((size_t)g.W * (size_t)g.H * 3 * sizeof(float), "the environment's buffers");      // its size changes with de_set_panorama alone, which waits for the fetches that read it
+    if (rc) return rc;
+    rc = dev.ensure(coded_stream_bytes(g.capacity), "RGBE buffers");
+    if (rc) return rc;
+    rc = rg_work_ensure(c->rg_work, g);
+    if (rc) return rc;
+    if (c->pano.projection == DE_PANO_EQUIRECT) { rc = pano_tables_ensure(c->stream, c->pano_tab, c->pano.width, c->pano.height, c->pano.supersample); if (rc) return rc; }
+    rc = pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->env_faces, c->pano_tab, c->env_out, true);
+    if (rc) return rc;
+    DisplaySrc src;
+    src.hdr = c->env_out; src.tile_spp = nullptr; src.samples = 1; src.W = g.W; src.H = g.H;      // x / 1.0f == x
+    rc = rg_launch(c->stream, c->rg_work, g, src, true, c->rg.rounding, dev, [] { return (int)DE_OK; });
+    if (rc) return rc;
+    c->rg_coded.out.count++;
+    return DE_OK;
+}
+// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
+int rg_render(de_ctx* c, Dev<uint8_t>& dev) {
+    { int rc = rg_pano_refusal(c); if (rc) return rc; }
+    if (env_active(c)) return rg_render_environment(c, dev);
+    HIP_TRY(hipSetDevice(c->device));
+    const RgbeGeometry g = rg_ctx_geometry(c);
+    int rc = rg_ctx_shape_check(c);
+    if (rc) return rc;
+    if (c->rg.source != DE_EXR_SOURCE_MEAN) { rc = display_chain_refusal(c, ex_stop_of[c->rg.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
+    rc = dev.ensure(coded_stream_bytes(g.capacity), "RGBE buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
+    if (rc) return rc;
+    rc = rg_work_ensure(c->rg_work, g);
+    if (rc) return rc;
+    DisplayArgs d;
+    bool per_tile;
+    rc = ex_source(c, c->rg.source, &d, &per_tile);
+    if (rc) return rc;
+    rc = rg_launch(c->stream, c->rg_work, g, display_src(d, per_tile), true, c->rg.rounding, dev, [c]() { return ex_sums_read(c); });      // behind the conversion: it has read the sums
+    if (rc) return rc;
+    c->rg_coded.out.count++;
+    return DE_OK;
+}
 }  // namespace

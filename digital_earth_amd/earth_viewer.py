@@ -290,6 +290,9 @@ class EarthViewer:
         through the PNG ring; finish_png() ends that loop.  It goes with none of the others.
         exr=True (a keyword beside the sliders too): the same for one complete OpenEXR file of the scene-linear frame in the settings of
         Renderer.set_exr() — Renderer.fetch_exr, through the EXR ring; finish_exr() ends that loop.  It goes with none of the others.
+        rgbe=True (a keyword beside the sliders too): the same for one complete Radiance .hdr file (RGBE) of the scene-linear frame in the settings
+        of Renderer.set_rgbe() — Renderer.fetch_rgbe, through the RGBE ring; finish_rgbe() ends that loop.  It goes with none of the others; with
+        panorama=True it is the 360° environment map, as exr=True.
         panorama=True (a keyword beside the sliders too; the viewer was made with panorama=...): step 2 is Renderer.render_panorama(spp) — the six
         cube faces around the camera, `spp` each, never accumulated over iterations — and what is handed out (the float field, or with pixels /
         hdr_pixels / video / jpeg / png = True that output, pipelined or not) is the 360° frame at Renderer.output_size() — so
@@ -302,7 +305,10 @@ class EarthViewer:
         jpeg = bool(sliders.pop("jpeg", False))
         png = bool(sliders.pop("png", False))
         exr = bool(sliders.pop("exr", False))
+        rgbe = bool(sliders.pop("rgbe", False))
         panorama = bool(sliders.pop("panorama", False))
+        if rgbe and (pixels or hdr_pixels or video or jpeg or png or exr):
+            raise ValueError("rgbe=True goes with none of pixels=True, hdr_pixels=True, video=True, jpeg=True, png=True and exr=True")
         if exr and (pixels or hdr_pixels or video or jpeg or png):
             raise ValueError("exr=True goes with none of pixels=True, hdr_pixels=True, video=True, jpeg=True and png=True")
         if png and (pixels or hdr_pixels or video or jpeg):
@@ -319,14 +325,16 @@ class EarthViewer:
             r.set_look_at(*self.camera.look_at)
             r.set_up(*self.camera._up)
             should_reset = True
-        if panorama and exr:
+        if panorama and (exr or rgbe):
             r.render_environment(int(spp))      # the same six renders, captured in front of the display (include/digital_earth_environment.h)
         elif panorama:
             r.render_panorama(int(spp))         # six faces around the camera, `spp` each; the camera is put back and the frame left empty
         else:
             r.accumulate(int(spp))              # == accumulate() x spp, bit for bit
         frame = None
-        if exr:
+        if rgbe:
+            frame = r.fetch_rgbe(copy=copy, lag=int(pipelined))
+        elif exr:
             frame = r.fetch_exr(copy=copy, lag=int(pipelined))
         elif png:
             frame = r.fetch_png(copy=copy, lag=int(pipelined))
@@ -344,7 +352,7 @@ class EarthViewer:
         # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
         # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
         shown = self._pixels if (pixels or hdr_pixels) else self._image
-        if video or jpeg or png or exr:
+        if video or jpeg or png or exr or rgbe:
             pass                                # no picture of save()'s changed hands
         elif pipelined:
             self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
@@ -369,7 +377,7 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        if video or jpeg or png or exr:
+        if video or jpeg or png or exr or rgbe:
             return frame
         return self._pixels if (pixels or hdr_pixels) else self._image
 
@@ -392,12 +400,12 @@ class EarthViewer:
             w.close()
         return w.frames
 
-    def _record_png(self, path, n, spp, sliders_per_frame, exr=False):
+    def _record_png(self, path, n, spp, sliders_per_frame, exr=False, rgbe=False):
         """record()'s lossless side: frame(png=True) through the pipelined PNG ring into the numbered files path % 0, path % 1, ...; exr=True: the
-        scene-linear side, frame(exr=True) through the EXR ring."""
+        scene-linear side, frame(exr=True) through the EXR ring; rgbe=True: frame(rgbe=True) through the RGBE ring."""
         r = self.renderer
         written = 0
-        which = {"exr": True} if exr else {"png": True}
+        which = {"rgbe": True} if rgbe else {"exr": True} if exr else {"png": True}
 
         def write(got):
             nonlocal written
@@ -410,7 +418,7 @@ class EarthViewer:
             if got is not None:
                 write(got)
             del got
-        for got in (r.fetch_pending_exr if exr else r.fetch_pending_png)(all_images=True):
+        for got in (r.fetch_pending_rgbe if rgbe else r.fetch_pending_exr if exr else r.fetch_pending_png)(all_images=True):
             write(got)
         return written
 
@@ -425,7 +433,9 @@ class EarthViewer:
         A path ending in `.png` is a pattern with one integer field ("frames/%05d.png"): a numbered lossless sequence, one complete PNG file per
         frame from frame(png=True) through the pipelined PNG ring, in the settings of Renderer.set_png() (frames count from 0; `fps` is not used).
         A path ending in `.exr` is such a pattern too ("frames/%05d.exr"): one complete OpenEXR file of the scene-linear frame per iteration, from
-        frame(exr=True) through the pipelined EXR ring, in the settings of Renderer.set_exr()."""
+        frame(exr=True) through the pipelined EXR ring, in the settings of Renderer.set_exr().
+        A path ending in `.hdr` is such a pattern too ("frames/%05d.hdr"): one complete Radiance RGBE file per iteration, from frame(rgbe=True)
+        through the pipelined RGBE ring, in the settings of Renderer.set_rgbe() (the defaults if that was never called)."""
         from . import y4m
         r = self.renderer
         n = int(frames)
@@ -434,7 +444,7 @@ class EarthViewer:
                 raise ValueError("slider %r has %d values for %d frames" % (k, len(v), n))
         if path.endswith((".avi", ".mjpeg")):
             return self._record_jpeg(path, n, spp, fps, sliders_per_frame)
-        if path.endswith((".png", ".exr")):
+        if path.endswith((".png", ".exr", ".hdr")):
             suffix = path[-4:]
             try:
                 numbered = path % 0 != path % 1
@@ -442,7 +452,7 @@ class EarthViewer:
                 numbered = False
             if not numbered:
                 raise ValueError("a %s recording needs a pattern with one integer field, such as frames/%%05d%s" % (suffix, suffix))
-            return self._record_png(path, n, spp, sliders_per_frame, exr=suffix == ".exr")
+            return self._record_png(path, n, spp, sliders_per_frame, exr=suffix == ".exr", rgbe=suffix == ".hdr")
         fmt = r.video()
         w = y4m.Y4MWriter(path, fmt["size"][0], fmt["size"][1], fps=fps, format=fmt["format"], range=fmt["range"], siting=fmt["siting"])
         try:
@@ -466,6 +476,10 @@ class EarthViewer:
     def finish_exr(self, copy=True):
         """End a pipelined frame(exr=True) loop: the file of its last iteration (None when nothing is in flight)."""
         return self.renderer.fetch_pending_exr(copy=copy)
+
+    def finish_rgbe(self, copy=True):
+        """End a pipelined frame(rgbe=True) loop: the file of its last iteration (None when nothing is in flight)."""
+        return self.renderer.fetch_pending_rgbe(copy=copy)
 
     def finish(self, copy=True, pixels=False, video=False, jpeg=False):
         """End a pipelined loop: the image of the last frame() iteration (None when nothing is in flight); pixels=True: of a frame(pixels=True) loop;
@@ -515,8 +529,17 @@ class EarthViewer:
         `.exr`: not a picture held but the scene-linear frame of the CURRENT accumulation, as one OpenEXR file converted and deflated on the GPU
         (Renderer.fetch_exr) in the settings of Renderer.set_exr(), or the defaults (half, ZIP, the mean) if that was never called; a sample is
         rendered first if the frame holds none.  digital_earth_amd.exr.read opens it again.  Behind frame(panorama=True, exr=True) or
-        Renderer.render_environment() the file is whatever fetch_exr() delivers then: the scene-linear panorama."""
+        Renderer.render_environment() the file is whatever fetch_exr() delivers then: the scene-linear panorama.
+        `.hdr` once Renderer.set_rgbe() has been called: the same scene-linear frame as one Radiance RGBE file, converted and run-length coded on the
+        GPU (Renderer.fetch_rgbe) in the settings of set_rgbe(); digital_earth_amd.rgbe.read opens it again.  Without set_rgbe() the extension is
+        what it was before: one the image writer does not know."""
         r = self.renderer
+        if path.endswith(".hdr") and r.rgbe_is_set:
+            if r.current_spp == 0 and not (r.panorama["on"] and len(r.environment["captured"]) == 6):
+                self.render(1)
+            with open(path, "wb") as f:
+                f.write(r.fetch_rgbe())
+            return
         if path.endswith(".exr"):
             if r.current_spp == 0 and not (r.panorama["on"] and len(r.environment["captured"]) == 6):      # the panorama is made of its slots, not of the frame
                 self.render(1)

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DeRgbe, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -218,6 +218,7 @@ class Renderer:
         self._jp_in_flight, self._jp_view_ref = 0, None      # the lagged fetch_jpeg() calls; the last view handed out
         self._pn_in_flight, self._pn_view_ref, self._png_set = 0, None, False      # the same for fetch_png(); set_png() has been called
         self._ex_coded, self._ex_in_flight, self._ex_view_ref = _CodedFetch(self._lib, "exr", "EXR", "_ex"), 0, None      # the same for fetch_exr()
+        self._rg_coded, self._rg_in_flight, self._rg_view_ref, self._rgbe_set = _CodedFetch(self._lib, "rgbe", "RGBE", "_rg"), 0, None, False      # the same for fetch_rgbe(); set_rgbe() has been called
         check(self._lib.de_create(int(device), self.image_res[0], self.image_res[1], ctypes.byref(self._h)))
         _native.apply_env_tuning(self._h)      # experiment overrides (DE_KERNEL, DE_V6_* ...): read HERE, not in the library
         self._params = DeParams()
@@ -265,7 +266,7 @@ class Renderer:
             for ring in (self._image_ring, self._pixel_ring, self._vd_ring):
                 if ring.referenced():
                     raise RuntimeError("a %s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % ring.name)
-            for coded in (self._jp_coded, self._pn_coded, self._ex_coded):
+            for coded in (self._jp_coded, self._pn_coded, self._ex_coded, self._rg_coded):
                 if coded.referenced(self):
                     raise RuntimeError("a fetch_%s(copy=False) view of this Renderer is still referenced: drop it (or copy it) before close()" % coded.stem)
             check(self._lib.de_destroy(self._h))
@@ -1436,6 +1437,88 @@ class Renderer:
         if out.raw[int(cap.value):] != b"\xA5" * sentinel or out.raw[int(n.value):int(cap.value)] != b"\xA5" * (int(cap.value) - int(n.value)):
             raise RuntimeError("de_debug_exr_aovs wrote behind the file's length")
         return out.raw[:int(n.value)]
+
+    # ------------------------------------------------------------------ Radiance HDR output (include/digital_earth_rgbe.h)
+    def _rg_settings(self, source, rle, rounding, scale):
+        if source not in _native.EXR_SOURCES:
+            raise ValueError("source must be one of %s" % (_native.EXR_SOURCES,))
+        if rounding not in _native.RGBE_ROUNDINGS:
+            raise ValueError("rounding must be one of %s" % (tuple(_native.RGBE_ROUNDINGS),))
+        s = DeRgbe()
+        s.struct_bytes = ctypes.sizeof(DeRgbe)
+        s.source, s.rle, s.rounding, s.scale = _native.EXR_SOURCES.index(source), 1 if rle else 0, _native.RGBE_ROUNDINGS[rounding], float(scale)
+        return s
+
+    def set_rgbe(self, source="mean", rle=True, rounding="trunc", scale=1.0):
+        """The settings of fetch_rgbe(): one complete Radiance picture file (.hdr, RGBE) of the SCENE-LINEAR frame, converted and run-length coded
+        on the GPU in front of the display transform — the format environment maps are traded in.  source: as set_exr's, with its refusals.
+        rle: new-style run-length coded rows (where the format allows them: 8 <= W <= 32767), else flat rows.  rounding "trunc" is Radiance's own
+        float2rgbe and suits decoders that add half a step (digital_earth_amd.rgbe.read(half_step=True)); "round" suits those that do not.
+        scale: finite, > 0, multiplied into every sample and written as EXPOSURE.  The file is always the context's size: output scaling and the
+        look do not apply.  Refused (DE_ERR_STATE) while lagged RGBE fetches are in flight.  No other fetch is affected."""
+        s = self._rg_settings(source, rle, rounding, scale)
+        check(self._lib.de_set_rgbe(self._h, ctypes.byref(s)))
+        self._rgbe_set = True
+
+    @property
+    def rgbe_is_set(self):
+        """True once set_rgbe() has been called: EarthViewer.save("x.hdr") then writes the GPU's file."""
+        return self._rgbe_set
+
+    def rgbe(self):
+        """The RGBE settings as a dict (set_rgbe's keywords) plus size = (width, height) and capacity, the proven bound of any frame's length — of
+        the panorama's size while fetch_rgbe() delivers the scene-linear panorama (render_environment)."""
+        s, n = DeRgbe(), ctypes.c_uint64()
+        check(self._lib.de_get_rgbe(self._h, ctypes.byref(s)))
+        check(self._lib.de_rgbe_capacity(self._h, ctypes.byref(n)))
+        return dict(source=_native.EXR_SOURCES[s.source], rle=bool(s.rle), rounding=next(k for k, x in _native.RGBE_ROUNDINGS.items() if x == s.rounding),
+                    scale=float(s.scale), size=self._exr_size(), capacity=int(n.value))
+
+    def fetch_rgbe(self, copy=True, lag=0):
+        """The scene-linear frame as one complete Radiance .hdr file: `bytes` that open(path, "wb").write() takes as they are
+        (digital_earth_amd.rgbe.read opens them again).  Only the file's own bytes cross the link.  copy=False, lag: as fetch_exr's, through a ring
+        of its own; fetch_pending_rgbe() hands out the rest.  Behind render_environment() with the panorama on: the 360° environment map."""
+        return self._rg_coded.fetch(self, copy, lag)
+
+    def fetch_pending_rgbe(self, copy=True, all_images=False):
+        """fetch_pending() for the lagged fetch_rgbe() calls and their ring."""
+        return self._rg_coded.pending(self, copy, all_images)
+
+    def render_to_rgbe(self):
+        """Run the stages up to the source's and the encoder and leave the file on the device (de_render_to_rgbe); returns (address of the file,
+        address of its uint64 length).  Nothing is waited for."""
+        return self._rg_coded.render_to(self)
+
+    def _rg_debug(self, s, W, H, call):
+        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.de_debug_rgbe_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
+        sentinel = 64
+        out = ctypes.create_string_buffer(b"\xA5" * (int(cap.value) + sentinel), int(cap.value) + sentinel)
+        check(call(out, ctypes.c_uint64(int(cap.value)), ctypes.byref(n)))
+        if out.raw[int(n.value):] != b"\xA5" * (int(cap.value) + sentinel - int(n.value)):
+            raise RuntimeError("the RGBE encoder wrote behind the file's length")
+        return out.raw[:int(n.value)]
+
+    def debug_rgbe(self, image, rle=True, rounding="trunc", scale=1.0):
+        """The encoder once on a given (H, W, 3) float32 image in R, G, B order, rows top-down, of any size (de_debug_rgbe); returns the file as
+        bytes.  The renderer's own settings and streams are not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (H, W, 3)")
+        H, W = image.shape[:2]
+        s = self._rg_settings("mean", rle, rounding, scale)
+        return self._rg_debug(s, W, H, lambda out, size, n: self._lib.de_debug_rgbe(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, size, n))
+
+    def debug_environment_rgbe(self, faces, size, projection="equirect", aperture=180.0, apron=1, supersample=2, basis=None, rle=True, rounding="trunc", scale=1.0):
+        """The resampling and the RGBE conversion once on given LINEAR faces, (6, n, n, 3) float32 as debug_panorama takes them
+        (de_debug_environment_rgbe); returns the file as bytes.  The renderer's own settings and faces are not touched."""
+        faces = np.ascontiguousarray(faces, dtype=np.float32)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 3:
+            raise ValueError("faces must have shape (6, n, n, 3)")
+        p = self._panorama_settings(size, projection, aperture, apron, supersample, basis, True)
+        s = self._rg_settings("mean", rle, rounding, scale)
+        return self._rg_debug(s, int(size[0]), int(size[1]), lambda out, n_bytes, n: self._lib.de_debug_environment_rgbe(
+            self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), out, n_bytes, n))
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)
     LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
