@@ -7,6 +7,7 @@
 //   synth_kernel        procedural stand-in Earth maps (the reference ships none)
 //   math_kernel         de_debug_math
 #include "de_kernels.h"
+#include "pt_leaves.h"      // math_kernel: the gas stage's density read
 
 // ------------------------------------------------------------------------------------------------ setup
 __global__ void setup_kernel(SetupArgs s) {
@@ -511,7 +512,7 @@ __global__ void __launch_bounds__(256) synth_kernel(uint8_t* dst, int slot, int 
 }
 
 // ------------------------------------------------------------------------------------------------ debug math
-__global__ void math_kernel(int fn, const float* a, const float* b, float* out, size_t n) {
+__global__ void math_kernel(int fn, const float* a, const float* b, float* out, size_t n, const float* dens_table) {
     const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     float x = a[k], y = b ? b[k] : 0.0f, r;
@@ -531,6 +532,14 @@ __global__ void math_kernel(int fn, const float* a, const float* b, float* out, 
         case 12: r = de_log_unit(x); break;
         case 13: r = de_rcp_nr(x); break;
         case 14: r = de_exp_nonpos(x); break;
+        // the gas densities at altitude x: 17-19 the profiles evaluated (Rayleigh, Mie, ozone), 20-22 what the gas stage's look-ahead reads (pt_leaves.h: the
+        // altitude table's entry, or the profiles off the table; y != 0: the lane is inside its segment)
+        case 17: r = get_density(x).x; break;
+        case 18: r = get_density(x).y; break;
+        case 19: r = get_density(x).z; break;
+        case 20: r = pt::density_ahead(dens_table, x, y != 0.0f).x; break;
+        case 21: r = pt::density_ahead(dens_table, x, y != 0.0f).y; break;
+        case 22: r = pt::density_ahead(dens_table, x, y != 0.0f).z; break;
         default: r = 0.0f;
     }
     out[k] = r;

@@ -830,7 +830,7 @@ static int debug_math(de_ctx* c, int fn, const float* a, const float* b, float* 
     const void* const in[3] = {a, b, nullptr};
     return debug_round_trip(c->stream, bytes, in, 2, out, [&](void* const* m) -> hipError_t {
         if (fast) return de_fast_launch_math(fn, (const float*)m[0], (const float*)m[1], (float*)m[2], (size_t)n, c->stream);
-        hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m[0], (const float*)m[1], (float*)m[2], (size_t)n);
+        hipLaunchKernelGGL(math_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, fn, (const float*)m[0], (const float*)m[1], (float*)m[2], (size_t)n, (const float*)c->d_dens_table);
         return hipSuccess;
     });
 }

@@ -54,7 +54,8 @@ DE_DEV uint32_t asu(float f) { return __builtin_bit_cast(uint32_t, f); }
 
 // ---- stage glue (pathtracer.py:180-205, 219-232): the same statements v2 executes "in place" when a loop ends
 // enter the cloud-shell segment of the ray in p (kind in meta).  aux = rmo_t (kind 0) or trg (kinds 1, 2); X = isect / li.
-// Returns the queue the record goes to, with p.x laid out for it.
+// Returns the queue the record goes to, with p.x laid out for it.  Writes p.x[0..3] and nothing else of the record: render_kernel_v6 relies on it
+// for the gas stage (GasStageT::kSlotKept: P, W.xy stay in the slot unwritten).
 DE_DEV int enter_cloud(Path& p, float c_ts, float c_tm, float aux, float X) {
     const int kind = m_kind(p.meta);
     const float t_start = c_ts;
@@ -340,10 +341,12 @@ DE_DEV int surffin_body(const RenderArgs& a, const ColdT& cold, Path& p) {
 // intersect_land's loop (pathtracer.py:37-44), one step per trip; p.x = (t0, atm_x, atm_y, c_ts, c_tm)
 template <bool CLAMP>
 struct StStage {
+    static constexpr bool kSlotKept = false; // render_kernel_v6 writes the whole record back (see GasStageT)
     const TexR8 topo;                        // by value: what the loop reads stays in scalar registers for the stage's duration only
     float land_height_scale, escape_r, max_ray_dist;
     float t; int cnt;
     DE_DEV void begin(wf::Path& p) { t = p.x[0]; cnt = 0; }
+    DE_DEV void start(wf::Path&) {}                                          // (the gas stage's hook: what a record that is not resumed does before its first step)
     // A step in two halves — `issue` up to the map tap's load, `resolve` from the texel on — so that a caller holding two records per lane
     // can have both loads in flight before it consumes either (render_kernel_v5.hip: run_loop2).  step() = the two in a row.
     struct Tok { uint32_t q; float fx, fy, len; };
@@ -379,52 +382,80 @@ struct StStage {
 
 // ------------------------------------------------------------------------------------------------ GAS: delta / ratio tracking
 // pathtracer.py:91-112 (delta) and :130-141 (ratio) through the Rayleigh / Mie / ozone profiles; p.x = (t, tmax, c_ts, c_tm, X)
-struct GasStage {
+//
+// Two forms of one step, the same arithmetic on the same draws in the same order:
+//   AHEAD = false  the profiles evaluated at the step's point (four exponentials).  The legacy kernel families and the fast-math unit (whose
+//                  exponentials are not the table's) run this one; -DDE_GAS_EVAL builds render_kernel_v6 with it (A/B).
+//   AHEAD = true   (render_kernel_v6) the densities come from the altitude table — get_density(h) bit for bit at every altitude a step can see:
+//                  aux_kernels.hip, dens_table_kernel; h2 / 2 is the entry's altitude exactly — and the read is issued ONE STEP AHEAD.  Read at
+//                  the point it is used, the table took 7.8 % of the frame's vector instructions away and no time: a dependent load in the
+//                  middle of a step that has no other, which a gas wave can only wait for (profiles/experiments/README.md, round 5).  But a
+//                  step's draws do not depend on the density, the rare collision aside: free flight, then (delta tracking) the collision draw.
+//                  So a trip of the wave loop, holding point n with its read in flight, makes the collision draw of point n, then `advance`s to
+//                  point n+1 (free-flight draw, C, t, altitude), consumes the densities of point n, issues the read for point n+1 into the
+//                  registers just freed and `resolve`s point n: a whole trip of this wave and of the SIMD's other waves lies between a read
+//                  and its use.  (The read goes into the SAME registers, after their last use: read earlier into other registers, the copy at
+//                  the loop's back edge waits for it on the spot.)
+// Why AHEAD changes no bit.  The generator: step n draws (free flight n), then — delta lanes — (collision n), then — colliding lanes — (scatter /
+// absorb).  AHEAD draws (collision n) before (free flight n+1) as well, and keeps the generator as it was BETWEEN the two (gr): the colliding lane
+// draws from gr, and every lane whose record ends at point n (collision, trn < 1e-5, a NaN t) leaves with gr and with point n's t (tr).  Nothing is
+// undone: the look-ahead's draw was made on a state such a lane does not keep.  A lane that does not end at point n goes on from the advanced
+// state, which is what step n+1 would have computed first; if point n+1 lies past the segment's end the record ends in THIS trip (the
+// reference's step n+1 returns before it looks at a density), one trip earlier than without the look-ahead and in the same state.  The
+// densities: the table's entry where h2 < DE_DENS_TABLE_N, the evaluated profiles elsewhere (the atmosphere ends below the table's top, so only a
+// NaN gets there) — what the state machine reads.  A lane past its segment's end reads a clamped entry that nothing consumes.
+// The look-ahead is the three density words, a per-lane cache that is never part of the record.  A STORED record (suspend(): a yield, or the
+// tail's export, which moves stored records as they are) holds t (p.x[0]), trn, C and the generator of the point the lane has FLOWN TO and not yet
+// resolved: the state between `advance` and `resolve`, which is what the loop carries; restore() issues that point's read again and draws nothing.
+// (The last resolved point would be the evaluated form's record, but costs the loop six more registers — its C, t and generator, kept beside the
+// advanced ones for the one trip in thousands that yields — and the stage function has none to spare at 80: built so, it spilled in every service.)
+// A record that enters the stage flies to its first point in start(); a resuming one has that point already (begin() draws nothing).
+template <bool AHEAD>
+struct GasStageT {
+    static constexpr bool kSlotKept = AHEAD;     // the stage changes meta, the generator and x[0..3] only and reads x[2..4] in finish() alone: render_kernel_v6 leaves the rest in the record's slot (its loop carries neither P nor x[2..4])
     const LambdaNode* nodes;
     const float* dens_table;
     float ext_r, ext_m, ext_o, rmaxr, t, tmax, trn;
     vec3 C;
-    int kind, event, ev_id;
+    uint32_t ev;                 // rmo_event and ev_id where finish() puts them in the record's meta word (set by the colliding step only)
+    pt::f3v dens;                    // AHEAD: the densities at C (in flight from `fetch` to the next trip's `step`); ONE 96-bit value, so that the read's three registers ARE the loop's (as three floats the third got a copy, and the copy a wait next to the read)
     DE_DEV void begin(wf::Path& p) {
         const LambdaNode& L = nodes[wf::m_node(p.meta)];
         ext_r = L.ext_r; ext_m = L.ext_m; ext_o = L.ext_o; rmaxr = L.inv_max_ext_rmo;
-        kind = wf::m_kind(p.meta);
         t = p.x[0]; tmax = p.x[1];
         C = p.P + t * p.W;
-        trn = 1.0f; event = pt::EV_NULL; ev_id = 0;
+        trn = 1.0f; ev = (uint32_t)pt::EV_NULL << 20;
     }
-    DE_DEV bool step(wf::Path& p) {
+    // AHEAD: a record that is not resumed flies to its first point (render_kernel_v6's run_loop: begin(), then start() or restore())
+    DE_DEV void start(wf::Path& p) { if constexpr (AHEAD) fetch(advance(p)); }
+    // the free flight to the next point: the first statements of a step
+    DE_DEV void flight(wf::Path& p) {
         const float neg_log = -de_log_unit(rng_next(p.rng));
         const float t_step = neg_log * rmaxr;
         C = C + t_step * p.W;
         t += t_step;
-        if (t >= tmax) return true;                                          // the segment ends without an event
-        const float len = length_nr(C);
-        const float h2 = de_max(len - DE_PLANET_R, 0.0f) * 2.0f;
-        vec3 dens;
-#ifndef DE_GAS_TABLE
-        // The profiles evaluated — what the altitude table holds, entry by entry (aux_kernels.hip: dens_table_kernel; h2 / 2 is the
-        // entry's altitude exactly), so the bits are the table's.  The state machine reads the table because it is issue-bound; a
-        // single-class gas wave is latency-bound on that read (one dependent load per 60 instructions) and four exponentials cost it
-        // less than the wait: the persistent scheduler 220 -> 194 ms per frame, the pipeline's gas kernel -1 ms (round 4).
-        (void)h2;
-        dens = get_density(de_max(len - DE_PLANET_R, 0.0f));
-#else
-        if (h2 < (float)DE_DENS_TABLE_N) {
-            dens = dens_table_read(dens_table, (uint32_t)(int)h2);
-        } else {
-            dens = get_density(len - DE_PLANET_R);
-        }
-#endif
-        const vec3 es = v3(ext_r, ext_m, ext_o) * dens;
+    }
+    // delta tracking's collision draw, made on a copy of the generator and committed for kind-0 lanes only (see `resolve`)
+    DE_DEV float collision_draw(wf::Path& p) const {
+        const bool delta = wf::m_kind(p.meta) == 0;
+        Rng g = p.rng;
+        const float rand = rng_next(g);
+        p.rng.s0 = delta ? g.s0 : p.rng.s0; p.rng.s1 = delta ? g.s1 : p.rng.s1;
+        return rand;
+    }
+    // AHEAD: fly to the next point; its altitude
+    struct Tok { float h; };
+    DE_DEV Tok altitude() const { return Tok{de_max(length_nr(C) - DE_PLANET_R, 0.0f)}; }
+    DE_DEV Tok advance(wf::Path& p) { flight(p); return altitude(); }
+    // AHEAD: issue the read of the densities at C (pt::density_ahead: every lane reads; off the table only a lane still inside its segment evaluates)
+    DE_DEV void fetch(const Tok& k) { dens = pt::density_ahead(dens_table, k.h, t < tmax); }
+    // the extinctions at a point to the step's outcome; r: the generator a collision's scatter / absorb draw is taken from
+    DE_DEV bool resolve(Rng& r, const int kind, const vec3 es, const float rand) {
         const float sum = (es.x + es.y) + es.z;
         // delta tracking (kind 0) draws, ratio tracking (kinds 1, 2) multiplies — as selects, for the reason given in CloudStage::resolve: the draw is made
         // on a copy of the generator and committed for kind-0 lanes only; the rare collision (species walk, scatter / absorb draw) keeps its branch
         const float pr = sum * rmaxr;
         const bool delta = kind == 0;
-        Rng g = p.rng;
-        const float rand = rng_next(g);
-        p.rng.s0 = delta ? g.s0 : p.rng.s0; p.rng.s1 = delta ? g.s1 : p.rng.s1;
         const float trn_r = trn * (1.0f - pr);
         trn = delta ? trn : trn_r;
         bool done = !delta & (trn_r < 1e-5f);
@@ -441,21 +472,48 @@ struct GasStage {
                 }
             }
             const float albedo = (id == 0) ? 1.0f : ((id == 1) ? 0.95f : ((id == 2) ? 0.0f : 0.99f));
-            event = (rng_next(p.rng) < albedo) ? pt::EV_SCATTER : pt::EV_ABSORB;
-            ev_id = id;
+            ev = ((uint32_t)id << 17) | ((uint32_t)((rng_next(r) < albedo) ? pt::EV_SCATTER : pt::EV_ABSORB) << 20);
             done = true;
         }
-        return done | !(t < tmax);                                           // loop-head test (differs from "no event" only for NaN)
+        return done;
+    }
+    DE_DEV bool step(wf::Path& p) {
+        if constexpr (!AHEAD) {
+            flight(p);
+            if (t >= tmax) return true;                                      // the segment ends without an event
+            const vec3 es = v3(ext_r, ext_m, ext_o) * get_density(de_max(length_nr(C) - DE_PLANET_R, 0.0f));
+            const float rand = collision_draw(p);
+            return resolve(p.rng, wf::m_kind(p.meta), es, rand) | !(t < tmax);                   // loop-head test (differs from "no event" only for NaN)
+        }
+        if (t >= tmax) return true;                                          // a record's FIRST point past the segment's end (start() flew there); later ones end the trip that flies to them
+        const float rand = collision_draw(p);
+        const float tr = t; Rng gr = p.rng;                                  // point n's t, and the generator as step n leaves it short of a collision
+        Tok k = advance(p);
+        asm volatile("" : "+v"(dens), "+v"(k.h));      // the densities are not touched before the flight is through: the wait for the read issued a trip ago is HERE
+        vec3 es = v3(ext_r, ext_m, ext_o) * v3(dens.x, dens.y, dens.z);
+        asm volatile("" : "+v"(es.x), "+v"(es.y), "+v"(es.z), "+v"(k.h));    // ... and the next read's address is not formed before these: it goes into the registers the three products free
+        fetch(k);
+        const bool done = resolve(gr, wf::m_kind(p.meta), es, rand) | !(tr < tmax);              // loop-head test on the resolved point
+        t = done ? tr : t; p.rng.s0 = done ? gr.s0 : p.rng.s0; p.rng.s1 = done ? gr.s1 : p.rng.s1;      // the record ends at point n: the look-ahead is dropped
+        return done | (t >= tmax);
     }
     DE_DEV int finish(wf::Path& p) {
         // rmo_event / rmo_t / ev_id (delta) or trg = trn (ratio), then the cloud-shell segment of the same ray
-        if (kind == 0) p.meta = (p.meta & ~((7u << 17) | (63u << 20))) | ((uint32_t)ev_id << 17) | ((uint32_t)event << 20);
+        // (kSlotKept: this may change meta and x[0..4] only — never P or W, which render_kernel_v6 does not write back for this stage)
+        const int kind = wf::m_kind(p.meta);
+        if (kind == 0) p.meta = (p.meta & ~((7u << 17) | (63u << 20))) | ev;
         return wf::enter_cloud(p, p.x[2], p.x[3], (kind == 0) ? t : trn, p.x[4]);
     }
-    // as StStage's: the running point C is accumulated step by step, so it travels with t and trn (event / ev_id are set by the last step only)
+    // as StStage's: the running point C is accumulated step by step, so it travels with t and trn (event / ev_id are set by the last step only).
+    // AHEAD: the point is the one flown to, its density not yet consumed (see above); the generator in the record is the one after that flight.
     DE_DEV void suspend(wf::Path& p, wf::Cold* c) const { p.x[0] = t; c->pad1 = trn; c->pad2 = C.x; c->pad3 = C.y; c->pad4 = C.z; }
-    DE_DEV void restore(const wf::Cold* c) { trn = c->pad1; C = v3(c->pad2, c->pad3, c->pad4); }
+    DE_DEV void restore(const wf::Cold* c) {
+        trn = c->pad1; C = v3(c->pad2, c->pad3, c->pad4);
+        if constexpr (AHEAD) fetch(altitude());
+    }
 };
+using GasStage = GasStageT<false>;
+using GasStageAhead = GasStageT<true>;
 
 // ------------------------------------------------------------------------------------------------ CLOUD: tracking through the cloud shell
 // the same loops with get_clouds_density (pathtracer.py:48-65); p.x = (t, tmax, aux = rmo_t | trg, X = isect | li)
@@ -481,6 +539,7 @@ struct GasStage {
 template <bool CLAMP, bool BOUND = false>
 struct CloudStage {
     static constexpr bool kBound = BOUND;
+    static constexpr bool kSlotKept = false;
     const TexR8 clouds;
     const uint8_t* bound;
     float ext_w, rmaxc, t, tmax, trn;
@@ -501,6 +560,7 @@ struct CloudStage {
         trn = 1.0f; cloud_event = 0;
         bnd = 0xffffffffu;
     }
+    DE_DEV void start(wf::Path&) {}
     // issue / resolve: as in StStage (the draws keep their order: free flight in `issue`; collision test and event in `resolve`)
     struct Tok { uint32_t q; float fx, fy, h; bool shell; };
     DE_DEV bool issue(wf::Path& p, Tok& k) {                                 // true: the segment ended without a further point

@@ -10,6 +10,27 @@ namespace pt {
 // what a tracking loop reports (pathtracer.py:73-75)
 enum { EV_NULL = 0, EV_ABSORB = 1, EV_SCATTER = 2 };
 
+// get_density(h) for the gas stage's look-ahead (de_stages.h: GasStageT<true>), h = max(|C| - R, 0) — or a NaN.  The altitude table's entry 2h where
+// the table has one (aux_kernels.hip, dens_table_kernel: entry i IS get_density(i / 2), and a step's altitude is a multiple of 0.5 m), the profiles
+// evaluated elsewhere: what the state machine reads.  `live` = the lane is still inside its segment; one that is not reads a clamped entry, which
+// nothing consumes (its point may lie anywhere above the table: evaluating there would send the whole wave through four exponentials).
+// Every lane reads, live or not: a load under a lane condition is a select on its result, and the select waits next to the load.  The result is ONE
+// 96-bit value, read through a pointer known to be global memory (a global_load counts on the vector-memory counter alone; dens_table_read's
+// flat_load counts on the LDS counter too) at a 32-bit byte offset (index < 2^18: the full-rate multiply) from a base that can stay in scalar registers.
+// de_debug_math evaluates it as functions 20-22 (tests/test_gpu_gas_lookahead.py: the index boundary).
+typedef float f3v __attribute__((ext_vector_type(3)));
+DE_DEV f3v density_ahead(const float* table, float h, bool live) {
+    typedef const __attribute__((address_space(1))) char* de_gbytes;
+    typedef f3v f3v_entry __attribute__((aligned(4)));      // an entry is 12 bytes at a multiple of 12
+    typedef const __attribute__((address_space(1))) f3v_entry* de_gf3;
+    static_assert(DE_DENS_STRIDE == 3, "one 96-bit read per entry");
+    const float h2 = h * 2.0f;
+    const uint32_t off = (uint32_t)__umul24((uint32_t)(int)__builtin_fminf(h2, (float)(DE_DENS_TABLE_N - 1)), (uint32_t)(DE_DENS_STRIDE * sizeof(float)));
+    f3v dens = *(de_gf3)((de_gbytes)table + off);
+    if (live & !(h2 < (float)DE_DENS_TABLE_N)) { const vec3 d = get_density(h); dens = f3v{d.x, d.y, d.z}; }
+    return dens;
+}
+
 // pathtracer.py:145-169
 DE_DEV void intersect_cloud_limits(vec3 ray_pos, vec3 ray_dir, float land_isection, float* t_start_out, float* t_max_out) {
     float t_start = 0.0f, t_max = 0.0f;

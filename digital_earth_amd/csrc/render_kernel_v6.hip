@@ -211,6 +211,24 @@ DE_DEV void store_rec(uint4* rec, uint32_t s, const Path& p) {
     rec[2u * DE_V6_P + s] = make_uint4(wf::asu(p.W.z), wf::asu(p.x[0]), wf::asu(p.x[1]), wf::asu(p.x[2]));
     s_rec2[s] = make_uint2(wf::asu(p.x[3]), wf::asu(p.x[4]));
 }
+// ... of a stage that changes only meta, the generator and x of its record, and reads x[2..4] in its finish() alone (Stage::kSlotKept: the gas
+// stage).  What it does not change stays in the slot, and what only finish() reads is read again for it: the stage's loop carries neither P nor
+// x[2..4] — six registers it has no room for beside its look-ahead (de_stages.h: GasStageT).
+DE_DEV void reload_rec_tail(const uint4* rec, uint32_t s, Path& p) {
+    const uint2 d = s_rec2[s];
+    p.x[2] = wf::asf(reinterpret_cast<const uint32_t*>(rec + 2u * DE_V6_P + s)[3]); p.x[3] = wf::asf(d.x); p.x[4] = wf::asf(d.y);
+}
+DE_DEV void store_rec_finished(uint4* rec, uint32_t s, const Path& p) {
+    uint32_t* a = reinterpret_cast<uint32_t*>(rec + s);
+    a[0] = p.meta; a[1] = p.rng.s0; a[2] = p.rng.s1;
+    rec[2u * DE_V6_P + s] = make_uint4(wf::asu(p.W.z), wf::asu(p.x[0]), wf::asu(p.x[1]), wf::asu(p.x[2]));
+    s_rec2[s] = make_uint2(wf::asu(p.x[3]), wf::asu(p.x[4]));
+}
+DE_DEV void store_rec_suspended(uint4* rec, uint32_t s, const Path& p) {      // suspend() changes x[0] only
+    uint32_t* a = reinterpret_cast<uint32_t*>(rec + s);
+    a[0] = p.meta; a[1] = p.rng.s0; a[2] = p.rng.s1;
+    reinterpret_cast<uint32_t*>(rec + 2u * DE_V6_P + s)[1] = wf::asu(p.x[0]);
+}
 
 // the cold record of the path in THIS lane's slot (the stage bodies index by path id; here the slot decides)
 struct ColdAt {
@@ -512,7 +530,10 @@ struct Wave {
                     // the stage's epilogue for all the lanes that finished since the last service at once (run where a lane finishes it
                     // would execute for two or three lanes of 64 in most trips)
                     const unsigned long long n_fin = STATS ? (unsigned long long)__popcll(__ballot(fin)) : 0ull;
-                    if (fin) { target = st.finish(p); store_rec(rec, slot, p); }
+                    if (fin) {
+                        if constexpr (Stage::kSlotKept) { reload_rec_tail(rec, slot, p); target = st.finish(p); store_rec_finished(rec, slot, p); }
+                        else { target = st.finish(p); store_rec(rec, slot, p); }
+                    }
                     tick<R_EPI>(n_fin);
                     release_wg();
                     (push<TARGETS>(slot, fin && target == TARGETS), ...);
@@ -535,7 +556,8 @@ struct Wave {
                             if (busy) {
                                 st.suspend(p, cold + slot);
                                 p.meta |= 0x80000000u;
-                                store_rec(rec, slot, p);
+                                if constexpr (Stage::kSlotKept) store_rec_suspended(rec, slot, p);
+                                else store_rec(rec, slot, p);
                             }
                             release_wg();
                             push<Q>(slot, busy);
@@ -556,7 +578,7 @@ struct Wave {
                             const bool resumed = (p.meta & 0x80000000u) != 0u;
                             p.meta &= 0x7fffffffu;
                             st.begin(p);
-                            if (resumed) st.restore(cold + slot);
+                            if (resumed) st.restore(cold + slot); else st.start(p);
                             busy = true;
                         }
                         stat(ST_RECS + Q, got);
@@ -791,7 +813,11 @@ DE_V6_STAGE v6_stage_gas() {
     using namespace bs;
     Wave<CLAMP, STATS> W = Wave<CLAMP, STATS>::enter();
     const RenderArgs& a = *W.A.ra;
-    GasStage st{uni_ptr(a.nodes), uni_ptr(a.dens_table)};
+#if defined(DE_GAS_EVAL) || defined(DE_FAST_MATH)
+    GasStage st{uni_ptr(a.nodes), uni_ptr(a.dens_table)};           // the profiles evaluated: A/B (tools/ab_build.sh), and the fast-math unit, whose exponentials are not the altitude table's
+#else
+    GasStageAhead st{uni_ptr(a.nodes), uni_ptr(a.dens_table)};      // densities from the context's altitude table, read one step ahead (de_stages.h)
+#endif
     W.template run_loop<Q_GAS>(st, Targets<Q_CLOUD, Q_EVENT, Q_SCFIN, Q_SURFFIN>{});
 }
 DE_V6_STAGE v6_stage_cloud() {

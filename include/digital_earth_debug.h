@@ -63,7 +63,9 @@ int de_debug_cloud_bound(de_ctx* ctx, uint8_t* out, uint64_t out_bytes, int* cel
  * de_debug_math: evaluate a deterministic f32 elementary function on the GPU (fn: 0 exp, 1 log, 2 sin, 3 cos,
  * 4 atan2(a,b), 5 asin, 6 pow(a,b), 7 a/b, 8 sqrt, 9 the short sqrt de_sqrt_nr, 10 the 3-operation a/b for literal divisors, 11 a * RN(1/b) (contract-2 quotient),
  * 12 log of a random draw de_log_unit, 13 the 3-operation reciprocal de_rcp_nr,
- * 14 exp of a non-positive argument de_exp_nonpos), for bit-exact comparison against the oracle.
+ * 14 exp of a non-positive argument de_exp_nonpos), for bit-exact comparison against the oracle; 17 / 18 / 19 the Rayleigh / Mie / ozone density profile at
+ * altitude a in metres, 20 / 21 / 22 the same as the gas stage of render_kernel_v6 reads them (the altitude table's entry, the profile off the table; b != 0:
+ * a point inside its segment, b == 0: one that has left it and reads a clamped entry) — de_debug_math only.
  * de_debug_math_fast: the same function numbers evaluated by the DE_FLAG_FAST_MATH kernel's translation unit — the hardware's transcendental units and
  * the shorter polynomials — plus 15 / 16, the sine / cosine output of its de_sincos; for comparison against float64 (tests/test_gpu_fast_math_leaves.py). */
 int de_debug_samples(de_ctx* ctx, uint64_t seed, int sample_index, float* out);
