@@ -1,6 +1,6 @@
 // de_api.hip — the C ABI of libdigitalearth_hip.so (include/digital_earth.h): context life cycle, uploads, parameters, the frame loop, fetches.
 // No CPU fallback exists: every entry point needs a HIP device.  The launches are in de_launch.h, the collectives in de_rccl.h, the display path's stages
-// and their one chain in de_display.h, how an output leaves the GPU (staging, rings, the packed outputs' frame) in de_fetch.h, the context in
+// and their one chain in de_display.h, how an output leaves the GPU (staging, rings, the packed outputs' frame, the coded outputs' entry points over a format's descriptor and their debug frame) in de_fetch.h, the context in
 // de_context.h, the owner of all its memory (Dev<T>, Pinned<T>: nothing here allocates or frees by hand) in de_memory.h; the kernel families the product no longer runs hang in under -DDE_LEGACY_VARIANTS (legacy/).  This file holds entry points only.
 #include "de_rccl.h"
 #include "de_display.h"
@@ -1227,10 +1227,9 @@ int de_set_panorama(de_ctx* c, const de_panorama* s) {
     if (c->W != c->H) return fail(DE_ERR_INVALID, "a panorama's face camera is square: the context needs W == H");
     { int rc = pano_settings_check(s, c->W); if (rc) return rc; }
     if (s->on && c->os.enabled) return fail(DE_ERR_STATE, "output scaling is on (de_set_output_scale): it makes the shown image, and a context has one");
-    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring, &c->jp_coded.ring, &c->pn_coded.ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
-    // an EXR fetch of the scene-linear panorama reads the linear slots and the tables (include/digital_earth_environment.h); one of the pinhole frame reads nothing of this stage
-    if (ring_any_in_flight(c->ex_coded.ring, [c](int k) { return c->ex_cell_env[k]; })) return refuse_in_flight(c->ex_coded.ring);
-    if (ring_any_in_flight(c->rg_coded.ring, [c](int k) { return c->rg_cell_env[k]; })) return refuse_in_flight(c->rg_coded.ring);      // the same of an RGBE fetch (include/digital_earth_rgbe.h)
+    for (const FetchRing* r : {&c->img, &c->px_ring, &c->vd_ring}) { int rc = refuse_in_flight(*r); if (rc) return rc; }
+    // an EXR or RGBE fetch of the scene-linear panorama reads the linear slots and the tables (include/digital_earth_environment.h); one of the pinhole frame reads nothing of this stage
+    for (const CodedOut* o : {&c->jp_coded, &c->pn_coded, &c->ex_coded, &c->rg_coded}) { int rc = refuse_panorama_readers(*o); if (rc) return rc; }
     HIP_TRY(hipSetDevice(c->device));
     { int rc = c->pano_faces.ensure((size_t)DE_PANO_FACES * (size_t)c->W * (size_t)c->W * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
     { int rc = c->pano_out.ensure((size_t)s->width * (size_t)s->height * 3 * sizeof(float), "the panorama's buffers"); if (rc) return rc; }
@@ -1305,16 +1304,16 @@ int de_environment_capture(de_ctx* c, int face) {
     if (source == DE_EXR_SOURCE_HISTORY) return fail(DE_ERR_STATE, "a linear panorama face cannot be captured from the history (de_exr.source): the history belongs to another face's camera");
     if (source == DE_EXR_SOURCE_BLOOM) return fail(DE_ERR_STATE, "a linear panorama face cannot be captured from the bloom (de_exr.source): its pyramid ends at the face's border");
     if (source == DE_EXR_SOURCE_LOCAL_EXPOSURE) return fail(DE_ERR_STATE, "a linear panorama face cannot be captured from local exposure (de_exr.source): its pyramid ends at the face's border");
-    if (source != DE_EXR_SOURCE_MEAN) { int rc = display_chain_refusal(c, ex_stop_of[source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
+    if (source != DE_EXR_SOURCE_MEAN) { int rc = display_chain_refusal(c, linear_stop_of[source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
     HIP_TRY(hipSetDevice(c->device));
     { int rc = c->env_faces.ensure((size_t)DE_PANO_FACES * env_face_floats(c) * sizeof(float), "the environment's buffers"); if (rc) return rc; }
     DisplayArgs d;
     bool per_tile;
-    int rc = ex_source(c, source, &d, &per_tile);
+    int rc = linear_source(c, source, &d, &per_tile);
     if (rc) return rc;
     rc = env_capture_launch(c->stream, display_src(d, per_tile), c->env_faces + (size_t)face * env_face_floats(c));
     if (rc) return rc;
-    rc = ex_sums_read(c);      // behind the capture: it has read the sums
+    rc = linear_sums_read(c);      // behind the capture: it has read the sums
     if (rc) return rc;
     c->env_mask |= 1u << face;
     return DE_OK;
@@ -1339,30 +1338,16 @@ int de_debug_environment_exr(de_ctx* c, const float* faces, int n, const de_pano
     { int rc = ex_settings_check(s); if (rc) return rc; }
     { int rc = ex_shape_check(p->width, p->height, s->pixel_type); if (rc) return rc; }
     const ExrGeometry g = ex_geometry(p->width, p->height, *s);
-    HIP_TRY(hipSetDevice(c->device));
-    Dev<float> d_faces, d_image;
-    Dev<uint8_t> d_out;
-    de_ctx::PanoTab tab;
+    EnvDebug env;
     de_ctx::ExrWork work;
-    PanoArgs k = {};
-    pano_make_consts(*p, n, &k);
-    const size_t in_bytes = (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float), image_bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
-    { int rc = ex_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_faces.ensure(in_bytes));
-    HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    if (p->projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, tab, p->width, p->height, p->supersample); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(d_faces, faces, in_bytes, hipMemcpyHostToDevice, c->stream));      // behind it every way out waits for the stream: the copy reads the caller's array
-    hipError_t e = ex_tables_upload(c->stream, work);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); HIP_TRY(e); }
-    int rc = pano_launch(c->stream, *p, k, n, d_faces, tab, d_image, true);
-    if (!rc) {
+    return coded_debug(c, g.capacity, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
         DisplaySrc src;
-        src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = p->width; src.H = p->height;      // x / 1.0f == x
-        rc = ex_launch(c->stream, work, g, src, true, s->scale, d_out, [] { return (int)DE_OK; });
-    }
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    return coded_debug_out(c->stream, d_out, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+        int rc = ex_work_ensure(work, g);
+        if (!rc) rc = env_debug_source(stream, env, faces, n, *p, &src);
+        if (rc) return rc;
+        HIP_TRY(ex_tables_upload(stream, work));
+        return ex_launch(stream, work, g, src, true, s->scale, d_out, no_hook);
+    });
 }
 
 /* include/digital_earth_debug.h: the stage once on a host-given image.  Buffers and tables of its own; the context's setting is not touched. */
@@ -1531,44 +1516,12 @@ int de_get_jpeg(de_ctx* c, de_jpeg* out) {
     *out = c->jp;
     return DE_OK;
 }
-int de_jpeg_capacity(de_ctx* c, uint64_t* bytes) {
-    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
-    { int rc = vd_even_check(c); if (rc) return rc; }
-    *bytes = (uint64_t)jp_ctx_geometry(c).capacity;
-    return DE_OK;
-}
-int de_render_to_jpeg(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    { int rc = vd_even_check(c); if (rc) return rc; }
-    int rc = jp_render(c, c->jp_coded.out.dev, c->jp_out_framed);
-    if (rc) return rc;
-    if (device_stream) *device_stream = c->jp_coded.out.dev + CS_WORD_BYTES;
-    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->jp_coded.out.dev.get());
-    return DE_OK;
-}
-int de_fetch_jpeg_view(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    int rc = de_render_to_jpeg(c, nullptr, nullptr);
-    if (rc) return rc;
-    return coded_view(c, c->jp_coded, jp_length, host, len);
-}
-int de_fetch_jpeg(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
-    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
-    const void* host = nullptr;
-    int rc = de_fetch_jpeg_view(c, &host, len);
-    if (rc) return rc;
-    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the frame (*len; de_jpeg_capacity bounds every frame)");
-}
-int de_fetch_jpeg_begin(de_ctx* c) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    { int rc = vd_even_check(c); if (rc) return rc; }
-    const JpegGeometry g = jp_ctx_geometry(c);
-    return coded_begin(c, c->jp_coded, JP_FRAMING_BYTES + (size_t)g.W * (size_t)g.H / 4, g.capacity, [c](int k) { return jp_render(c, c->jp_coded.cell[k], c->jp_cell_framed[k]); });      // the first: two bits per pixel
-}
-int de_fetch_jpeg_end(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    return coded_end(c, c->jp_coded, jp_length, host, len);
-}
+int de_jpeg_capacity(de_ctx* c, uint64_t* bytes) { return coded_capacity<JpegOut>(c, bytes); }
+int de_render_to_jpeg(de_ctx* c, const void** device_stream, const uint64_t** device_len) { return coded_render_to<JpegOut>(c, device_stream, device_len); }
+int de_fetch_jpeg_view(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_view<JpegOut>(c, host, len); }
+int de_fetch_jpeg(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) { return coded_fetch<JpegOut>(c, out, out_bytes, len); }
+int de_fetch_jpeg_begin(de_ctx* c) { return coded_fetch_begin<JpegOut>(c); }
+int de_fetch_jpeg_end(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_end<JpegOut>(c, host, len); }
 /* the conversion once on a host-given image of any even size.  Buffers of its own; the context's settings and streams are not touched. */
 int de_debug_jpeg(de_ctx* c, const float* image, int W, int H, const de_jpeg* s, void* out, uint64_t out_bytes, uint64_t* len) {
     if (!c || !image || !s || !out || !len || W <= 0 || H <= 0 || (W & 1) || (H & 1) || (long long)W * H > (1ll << 24))
@@ -1576,23 +1529,21 @@ int de_debug_jpeg(de_ctx* c, const float* image, int W, int H, const de_jpeg* s,
     { int rc = jp_settings_check(s); if (rc) return rc; }
     const JpegGeometry g = jp_geometry(W, H, s->restart_mcus);
     { int rc = jp_geometry_check(g); if (rc) return rc; }
-    HIP_TRY(hipSetDevice(c->device));
     JpegTables tab;
     jp_make_tables(s->quality, &tab);
     uint8_t framing[JP_FRAMING_BYTES];
     jp_write_framing(tab, W, H, s->restart_mcus, framing);
     de_ctx::JpegWork work;
     Dev<float> d_image;
-    Dev<uint8_t> d_out;
-    const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
-    { int rc = jp_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(work.tab, &tab, sizeof(tab), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_out + CS_WORD_BYTES, framing, sizeof(framing), hipMemcpyHostToDevice, c->stream));
-    jp_launch(c->stream, d_image, work, g, d_out);
-    return coded_debug_out(c->stream, d_out, jp_length, out, out_bytes, len, "out_bytes is smaller than the frame (*len)");
+    return coded_debug(c, g.capacity, jp_length, out, out_bytes, len, "out_bytes is smaller than the frame (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
+        int rc = jp_work_ensure(work, g);
+        if (!rc) rc = debug_upload(stream, d_image, image, (size_t)W * H * 3 * sizeof(float));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(work.tab, &tab, sizeof(tab), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_out + CS_WORD_BYTES, framing, sizeof(framing), hipMemcpyHostToDevice, stream));
+        jp_launch(stream, d_image, work, g, d_out);
+        return DE_OK;
+    });
 }
 /* the host's part alone: no device, no context */
 int de_debug_jpeg_framing(const de_jpeg* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
@@ -1615,8 +1566,7 @@ int de_set_png(de_ctx* c, const de_png* s) {
     { int rc = pn_settings_check(s); if (rc) return rc; }
     { int rc = refuse_in_flight(c->pn_coded.ring); if (rc) return rc; }
     c->pn = *s;
-    c->pn_coded.guess = 0;
-    packed_reset(c->pn_coded.out);
+    coded_reset(c->pn_coded);
     return DE_OK;
 }
 int de_get_png(de_ctx* c, de_png* out) {
@@ -1624,59 +1574,28 @@ int de_get_png(de_ctx* c, de_png* out) {
     *out = c->pn;
     return DE_OK;
 }
-int de_png_capacity(de_ctx* c, uint64_t* bytes) {
-    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
-    { int rc = pn_source_check(c); if (rc) return rc; }
-    *bytes = (uint64_t)pn_ctx_geometry(c).capacity;
-    return DE_OK;
-}
-int de_render_to_png(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    int rc = pn_render(c, c->pn_coded.out.dev);
-    if (rc) return rc;
-    if (device_stream) *device_stream = c->pn_coded.out.dev + CS_WORD_BYTES;
-    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->pn_coded.out.dev.get());
-    return DE_OK;
-}
-int de_fetch_png_view(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    int rc = de_render_to_png(c, nullptr, nullptr);
-    if (rc) return rc;
-    return coded_view(c, c->pn_coded, pn_length, host, len);
-}
-int de_fetch_png(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
-    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
-    const void* host = nullptr;
-    int rc = de_fetch_png_view(c, &host, len);
-    if (rc) return rc;
-    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the file (*len; de_png_capacity bounds every frame)");
-}
-int de_fetch_png_begin(de_ctx* c) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    { int rc = pn_source_check(c); if (rc) return rc; }
-    const PngGeometry g = pn_ctx_geometry(c);
-    return coded_begin(c, c->pn_coded, g.front + g.filtered / 4, g.capacity, [c](int k) { return pn_render(c, c->pn_coded.cell[k]); });      // the first: a quarter of the filtered bytes
-}
-int de_fetch_png_end(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    return coded_end(c, c->pn_coded, pn_length, host, len);
-}
+int de_png_capacity(de_ctx* c, uint64_t* bytes) { return coded_capacity<PngOut>(c, bytes); }
+int de_render_to_png(de_ctx* c, const void** device_stream, const uint64_t** device_len) { return coded_render_to<PngOut>(c, device_stream, device_len); }
+int de_fetch_png_view(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_view<PngOut>(c, host, len); }
+int de_fetch_png(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) { return coded_fetch<PngOut>(c, out, out_bytes, len); }
+int de_fetch_png_begin(de_ctx* c) { return coded_fetch_begin<PngOut>(c); }
+int de_fetch_png_end(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_end<PngOut>(c, host, len); }
 /* the conversion once on host-given packed pixels of any size.  Buffers of its own; the context's settings and streams are not touched. */
 int de_debug_png(de_ctx* c, const void* pixels, int W, int H, int channels, int depth, const de_png* s, void* out, uint64_t out_bytes, uint64_t* len) {
     if (!c || !pixels || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
     { int rc = pn_shape_check(W, H, channels, depth); if (rc) return rc; }
     { int rc = pn_settings_check(s); if (rc) return rc; }
     const PngGeometry g = png_geometry(W, H, channels, depth, s->chunk_bytes);
-    HIP_TRY(hipSetDevice(c->device));
     de_ctx::PngWork work;
-    Dev<uint8_t> d_out;
-    { int rc = pn_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    HIP_TRY(hipMemcpyAsync(work.pixels, pixels, (size_t)g.H * g.row_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(pn_tables_upload(c->stream, work));
-    const uint8_t cicp[4] = {1, 8, 0, 1};
-    pn_launch(c->stream, work, g, s->filter, cicp, d_out);
-    return coded_debug_out(c->stream, d_out, pn_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+    return coded_debug(c, g.capacity, pn_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
+        int rc = pn_work_ensure(work, g);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(work.pixels, pixels, (size_t)g.H * g.row_bytes, hipMemcpyHostToDevice, stream));
+        HIP_TRY(pn_tables_upload(stream, work));
+        const uint8_t cicp[4] = {1, 8, 0, 1};
+        pn_launch(stream, work, g, s->filter, cicp, d_out);
+        return DE_OK;
+    });
 }
 /* the host's part alone: no device, no context */
 int de_debug_png_framing(const de_png* s, int W, int H, int channels, int depth, const uint8_t* cicp, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
@@ -1703,8 +1622,7 @@ int de_set_exr(de_ctx* c, const de_exr* s) {
     if (c->ex_aovs) { int rc = ex_shape_check(c->W, c->H, s->pixel_type, c->ex_aovs); if (rc) return rc; }      // the AOV channels in force count at the new pixel type
     { int rc = refuse_in_flight(c->ex_coded.ring); if (rc) return rc; }
     c->ex = *s;
-    c->ex_coded.guess = 0;
-    packed_reset(c->ex_coded.out);
+    coded_reset(c->ex_coded);
     return DE_OK;
 }
 int de_get_exr(de_ctx* c, de_exr* out) {
@@ -1712,67 +1630,27 @@ int de_get_exr(de_ctx* c, de_exr* out) {
     *out = c->ex;
     return DE_OK;
 }
-int de_exr_capacity(de_ctx* c, uint64_t* bytes) {
-    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
-    { int rc = ex_ctx_shape_check(c); if (rc) return rc; }
-    *bytes = (uint64_t)ex_ctx_geometry(c).capacity;
-    return DE_OK;
-}
-int de_render_to_exr(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    int rc = ex_render(c, c->ex_coded.out.dev);
-    if (rc) return rc;
-    if (device_stream) *device_stream = c->ex_coded.out.dev + CS_WORD_BYTES;
-    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->ex_coded.out.dev.get());
-    return DE_OK;
-}
-int de_fetch_exr_view(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    int rc = de_render_to_exr(c, nullptr, nullptr);
-    if (rc) return rc;
-    return coded_view(c, c->ex_coded, ex_length, host, len);
-}
-int de_fetch_exr(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
-    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
-    const void* host = nullptr;
-    int rc = de_fetch_exr_view(c, &host, len);
-    if (rc) return rc;
-    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the file (*len; de_exr_capacity bounds every frame)");
-}
-int de_fetch_exr_begin(de_ctx* c) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    { int rc = ex_pano_refusal(c); if (rc) return rc; }
-    { int rc = ex_ctx_shape_check(c); if (rc) return rc; }
-    const ExrGeometry g = ex_ctx_geometry(c);
-    const int cell = ring_next_cell(c->ex_coded.ring);
-    int rc = coded_begin(c, c->ex_coded, g.front + g.raw / 2, g.capacity, [c](int k) { return ex_render(c, c->ex_coded.cell[k]); });      // the first: the front and half the raw bytes
-    if (!rc) c->ex_cell_env[cell] = env_active(c);      // de_set_panorama waits for a fetch of the scene-linear panorama
-    return rc;
-}
-int de_fetch_exr_end(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    return coded_end(c, c->ex_coded, ex_length, host, len);
-}
+int de_exr_capacity(de_ctx* c, uint64_t* bytes) { return coded_capacity<ExrOut>(c, bytes); }
+int de_render_to_exr(de_ctx* c, const void** device_stream, const uint64_t** device_len) { return coded_render_to<ExrOut>(c, device_stream, device_len); }
+int de_fetch_exr_view(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_view<ExrOut>(c, host, len); }
+int de_fetch_exr(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) { return coded_fetch<ExrOut>(c, out, out_bytes, len); }
+int de_fetch_exr_begin(de_ctx* c) { return coded_fetch_begin<ExrOut>(c); }
+int de_fetch_exr_end(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_end<ExrOut>(c, host, len); }
 /* the conversion once on a host-given image of any size, rows top-down.  Buffers of its own; the context's settings and streams are not touched. */
 int de_debug_exr(de_ctx* c, const float* image, int W, int H, const de_exr* s, void* out, uint64_t out_bytes, uint64_t* len) {
     if (!c || !image || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
     { int rc = ex_settings_check(s); if (rc) return rc; }
     { int rc = ex_shape_check(W, H, s->pixel_type); if (rc) return rc; }
     const ExrGeometry g = ex_geometry(W, H, *s);
-    HIP_TRY(hipSetDevice(c->device));
     de_ctx::ExrWork work;
     Dev<float> d_image;
-    Dev<uint8_t> d_out;
-    const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
-    { int rc = ex_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(ex_tables_upload(c->stream, work));
-    DisplaySrc src;
-    src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;      // x / 1.0f == x
-    { int rc = ex_launch(c->stream, work, g, src, false, s->scale, d_out, [] { return (int)DE_OK; }); if (rc) return rc; }
-    return coded_debug_out(c->stream, d_out, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+    return coded_debug(c, g.capacity, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
+        int rc = ex_work_ensure(work, g);
+        if (!rc) rc = debug_upload(stream, d_image, image, (size_t)W * H * 3 * sizeof(float));
+        if (rc) return rc;
+        HIP_TRY(ex_tables_upload(stream, work));
+        return ex_launch(stream, work, g, linear_src(d_image, W, H), false, s->scale, d_out, no_hook);
+    });
 }
 /* the host's part alone: no device, no context */
 int de_debug_exr_framing(const de_exr* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
@@ -1817,54 +1695,45 @@ int de_debug_exr_aovs(de_ctx* c, const float* image, const float* guides, const 
     const ExrGeometry g = ex_geometry(W, H, *s, mask);
     uint32_t need = 0u;
     for (int k = 0; k < g.channels; ++k) need |= exr_slot_need(g.ch[k].slot);
-    if ((need & (EXR_NEED_NC | EXR_NEED_AT | EXR_NEED_DIST)) && !guides) return fail(DE_ERR_INVALID, "the mask selects guide channels: `guides` is null");
+    const bool need_guides = (need & (EXR_NEED_NC | EXR_NEED_AT | EXR_NEED_DIST)) != 0u;
+    if (need_guides && !guides) return fail(DE_ERR_INVALID, "the mask selects guide channels: `guides` is null");
     if ((need & EXR_NEED_MOMENTS) && !s2) return fail(DE_ERR_INVALID, "the mask selects the variance: `s2` is null");
     if ((need & EXR_NEED_DIVISOR) && !counts) return fail(DE_ERR_INVALID, "the mask selects the variance or the samples: `counts` is null");
-    HIP_TRY(hipSetDevice(c->device));
-    // behind the first enqueued copy every way out waits for the stream: the copies read the caller's arrays and the local vectors below
-    #define SYNC_TRY(expr) do { hipError_t se_ = (expr); if (se_ != hipSuccess) { (void)hipStreamSynchronize(c->stream); HIP_TRY(se_); } } while (0)
-    de_ctx::ExrWork work;
-    Dev<float> d_image, d_s2, d_counts, d_dist;
-    Dev<float4> d_nc, d_at;
-    Dev<uint8_t> d_out;
     const size_t npx = (size_t)W * H, image_bytes = npx * 3 * sizeof(float);
-    { int rc = ex_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    SYNC_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));
-    std::vector<float4> nc, at;      // alive until the copies have been waited for
+    std::vector<float4> nc, at;      // the uploads read them: alive until coded_debug has waited
     std::vector<float> dist;
-    ExrAovSrc av;
-    if (need & (EXR_NEED_NC | EXR_NEED_AT | EXR_NEED_DIST)) {      // the nine guides of a pixel side by side, in de_fetch_guides' order, into the device's three buffers
+    if (need_guides) {      // the nine guides of a pixel side by side, in de_fetch_guides' order, into the device's three buffers
         nc.resize(npx); at.resize(npx); dist.resize(npx);
         for (size_t p = 0; p < npx; ++p) {
             const float* q = guides + p * 9;
             nc[p] = make_float4(q[2], q[3], q[4], q[0]); at[p] = make_float4(q[5], q[6], q[7], q[8]); dist[p] = q[1];
         }
-        SYNC_TRY(d_nc.ensure(npx * sizeof(float4)));
-        SYNC_TRY(d_at.ensure(npx * sizeof(float4)));
-        SYNC_TRY(d_dist.ensure(npx * sizeof(float)));
-        SYNC_TRY(hipMemcpyAsync(d_nc, nc.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        SYNC_TRY(hipMemcpyAsync(d_at, at.data(), npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        SYNC_TRY(hipMemcpyAsync(d_dist, dist.data(), npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        av.nc = d_nc; av.at = d_at; av.dist = d_dist;
     }
-    if (need & EXR_NEED_MOMENTS) {
-        SYNC_TRY(d_s2.ensure(image_bytes));
-        SYNC_TRY(hipMemcpyAsync(d_s2, s2, image_bytes, hipMemcpyHostToDevice, c->stream));
-        av.s1 = d_image; av.s2 = d_s2;
-    }
-    if (counts) {      // the divisor of B, G, R too: `image` is read as the sums
-        SYNC_TRY(d_counts.ensure(npx * sizeof(float)));
-        SYNC_TRY(hipMemcpyAsync(d_counts, counts, npx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        av.counts = d_counts;
-    }
-    SYNC_TRY(ex_tables_upload(c->stream, work));
-    DisplaySrc src;
-    src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;      // without counts: x / 1.0f == x
-    { int rc = ex_launch(c->stream, work, g, src, false, s->scale, d_out, [] { return (int)DE_OK; }, av); if (rc) { (void)hipStreamSynchronize(c->stream); return rc; } }
-    #undef SYNC_TRY
-    return coded_debug_out(c->stream, d_out, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+    de_ctx::ExrWork work;
+    Dev<float> d_image, d_s2, d_counts, d_dist;
+    Dev<float4> d_nc, d_at;
+    return coded_debug(c, g.capacity, ex_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
+        ExrAovSrc av;
+        int rc = ex_work_ensure(work, g);
+        if (!rc) rc = debug_upload(stream, d_image, image, image_bytes);
+        if (!rc && need_guides) {
+            rc = debug_upload(stream, d_nc, nc.data(), npx * sizeof(float4));
+            if (!rc) rc = debug_upload(stream, d_at, at.data(), npx * sizeof(float4));
+            if (!rc) rc = debug_upload(stream, d_dist, dist.data(), npx * sizeof(float));
+            av.nc = d_nc; av.at = d_at; av.dist = d_dist;
+        }
+        if (!rc && (need & EXR_NEED_MOMENTS)) {
+            rc = debug_upload(stream, d_s2, s2, image_bytes);
+            av.s1 = d_image; av.s2 = d_s2;
+        }
+        if (!rc && counts) {      // the divisor of B, G, R too: `image` is read as the sums
+            rc = debug_upload(stream, d_counts, counts, npx * sizeof(float));
+            av.counts = d_counts;
+        }
+        if (rc) return rc;
+        HIP_TRY(ex_tables_upload(stream, work));
+        return ex_launch(stream, work, g, linear_src(d_image, W, H), false, s->scale, d_out, no_hook, av);      // without counts: x / 1.0f == x
+    });
 }
 /* the host's part alone: no device, no context */
 int de_debug_exr_aov_framing(const de_exr* s, uint32_t mask, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
@@ -1892,8 +1761,7 @@ int de_set_rgbe(de_ctx* c, const de_rgbe* s) {
     { int rc = rg_settings_check(s); if (rc) return rc; }
     { int rc = refuse_in_flight(c->rg_coded.ring); if (rc) return rc; }
     c->rg = *s;
-    c->rg_coded.guess = 0;
-    packed_reset(c->rg_coded.out);
+    coded_reset(c->rg_coded);
     return DE_OK;
 }
 int de_get_rgbe(de_ctx* c, de_rgbe* out) {
@@ -1901,66 +1769,26 @@ int de_get_rgbe(de_ctx* c, de_rgbe* out) {
     *out = c->rg;
     return DE_OK;
 }
-int de_rgbe_capacity(de_ctx* c, uint64_t* bytes) {
-    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
-    { int rc = rg_ctx_shape_check(c); if (rc) return rc; }
-    *bytes = (uint64_t)rg_ctx_geometry(c).capacity;
-    return DE_OK;
-}
-int de_render_to_rgbe(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    int rc = rg_render(c, c->rg_coded.out.dev);
-    if (rc) return rc;
-    if (device_stream) *device_stream = c->rg_coded.out.dev + CS_WORD_BYTES;
-    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(c->rg_coded.out.dev.get());
-    return DE_OK;
-}
-int de_fetch_rgbe_view(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    int rc = de_render_to_rgbe(c, nullptr, nullptr);
-    if (rc) return rc;
-    return coded_view(c, c->rg_coded, rg_length, host, len);
-}
-int de_fetch_rgbe(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
-    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
-    const void* host = nullptr;
-    int rc = de_fetch_rgbe_view(c, &host, len);
-    if (rc) return rc;
-    return coded_copy_out(host, *len, out, out_bytes, "out_bytes is smaller than the file (*len; de_rgbe_capacity bounds every frame)");
-}
-int de_fetch_rgbe_begin(de_ctx* c) {
-    if (!c) return fail(DE_ERR_INVALID, "null context");
-    { int rc = rg_pano_refusal(c); if (rc) return rc; }
-    { int rc = rg_ctx_shape_check(c); if (rc) return rc; }
-    const RgbeGeometry g = rg_ctx_geometry(c);
-    const int cell = ring_next_cell(c->rg_coded.ring);
-    int rc = coded_begin(c, c->rg_coded, g.header + 2 * (size_t)g.W * (size_t)g.H, g.capacity, [c](int k) { return rg_render(c, c->rg_coded.cell[k]); });      // the first: the front and half the flat bytes
-    if (!rc) c->rg_cell_env[cell] = env_active(c);      // de_set_panorama waits for a fetch of the scene-linear panorama
-    return rc;
-}
-int de_fetch_rgbe_end(de_ctx* c, const void** host, uint64_t* len) {
-    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
-    return coded_end(c, c->rg_coded, rg_length, host, len);
-}
+int de_rgbe_capacity(de_ctx* c, uint64_t* bytes) { return coded_capacity<RgbeOut>(c, bytes); }
+int de_render_to_rgbe(de_ctx* c, const void** device_stream, const uint64_t** device_len) { return coded_render_to<RgbeOut>(c, device_stream, device_len); }
+int de_fetch_rgbe_view(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_view<RgbeOut>(c, host, len); }
+int de_fetch_rgbe(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) { return coded_fetch<RgbeOut>(c, out, out_bytes, len); }
+int de_fetch_rgbe_begin(de_ctx* c) { return coded_fetch_begin<RgbeOut>(c); }
+int de_fetch_rgbe_end(de_ctx* c, const void** host, uint64_t* len) { return coded_fetch_end<RgbeOut>(c, host, len); }
 /* the conversion once on a host-given image of any size, rows top-down.  Buffers of its own; the context's settings and streams are not touched. */
 int de_debug_rgbe(de_ctx* c, const float* image, int W, int H, const de_rgbe* s, void* out, uint64_t out_bytes, uint64_t* len) {
     if (!c || !image || !s || !out || !len) return fail(DE_ERR_INVALID, "null argument");
     { int rc = rg_settings_check(s); if (rc) return rc; }
     { int rc = rg_shape_check(W, H); if (rc) return rc; }
     const RgbeGeometry g = rg_geometry(W, H, *s);
-    HIP_TRY(hipSetDevice(c->device));
     de_ctx::RgbeWork work;
     Dev<float> d_image;
-    Dev<uint8_t> d_out;
-    const size_t image_bytes = (size_t)W * H * 3 * sizeof(float);
-    { int rc = rg_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    HIP_TRY(hipMemcpyAsync(d_image, image, image_bytes, hipMemcpyHostToDevice, c->stream));      // behind it every way out waits for the stream: the copy reads the caller's array
-    DisplaySrc src;
-    src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;      // x / 1.0f == x
-    { int rc = rg_launch(c->stream, work, g, src, false, s->rounding, d_out, [] { return (int)DE_OK; }); if (rc) { (void)hipStreamSynchronize(c->stream); return rc; } }
-    return coded_debug_out(c->stream, d_out, rg_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+    return coded_debug(c, g.capacity, rg_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
+        int rc = rg_work_ensure(work, g);
+        if (!rc) rc = debug_upload(stream, d_image, image, (size_t)W * H * 3 * sizeof(float));
+        if (rc) return rc;
+        return rg_launch(stream, work, g, linear_src(d_image, W, H), false, s->rounding, d_out, no_hook);
+    });
 }
 /* the host's part alone: no device, no context */
 int de_debug_rgbe_framing(const de_rgbe* s, int W, int H, void* out, uint64_t out_bytes, uint64_t* len, uint64_t* capacity) {
@@ -1984,28 +1812,15 @@ int de_debug_environment_rgbe(de_ctx* c, const float* faces, int n, const de_pan
     { int rc = rg_settings_check(s); if (rc) return rc; }
     { int rc = rg_shape_check(p->width, p->height); if (rc) return rc; }
     const RgbeGeometry g = rg_geometry(p->width, p->height, *s);
-    HIP_TRY(hipSetDevice(c->device));
-    Dev<float> d_faces, d_image;
-    Dev<uint8_t> d_out;
-    de_ctx::PanoTab tab;
+    EnvDebug env;
     de_ctx::RgbeWork work;
-    PanoArgs k = {};
-    pano_make_consts(*p, n, &k);
-    const size_t in_bytes = (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float), image_bytes = (size_t)p->width * (size_t)p->height * 3 * sizeof(float);
-    { int rc = rg_work_ensure(work, g); if (rc) return rc; }
-    HIP_TRY(d_faces.ensure(in_bytes));
-    HIP_TRY(d_image.ensure(image_bytes));
-    HIP_TRY(d_out.ensure(coded_stream_bytes(g.capacity)));
-    if (p->projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(c->stream, tab, p->width, p->height, p->supersample); if (rc) return rc; }
-    HIP_TRY(hipMemcpyAsync(d_faces, faces, in_bytes, hipMemcpyHostToDevice, c->stream));      // behind it every way out waits for the stream: the copy reads the caller's array
-    int rc = pano_launch(c->stream, *p, k, n, d_faces, tab, d_image, true);
-    if (!rc) {
+    return coded_debug(c, g.capacity, rg_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)", [&](hipStream_t stream, uint8_t* d_out) -> int {
         DisplaySrc src;
-        src.hdr = d_image; src.tile_spp = nullptr; src.samples = 1; src.W = p->width; src.H = p->height;      // x / 1.0f == x
-        rc = rg_launch(c->stream, work, g, src, true, s->rounding, d_out, [] { return (int)DE_OK; });
-    }
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    return coded_debug_out(c->stream, d_out, rg_length, out, out_bytes, len, "out_bytes is smaller than the file (*len)");
+        int rc = rg_work_ensure(work, g);
+        if (!rc) rc = env_debug_source(stream, env, faces, n, *p, &src);
+        if (rc) return rc;
+        return rg_launch(stream, work, g, src, true, s->rounding, d_out, no_hook);
+    });
 }
 
 /* ---- look LUTs: include/digital_earth_look.h (look_kernels.hip) */

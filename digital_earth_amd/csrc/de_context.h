@@ -107,12 +107,14 @@ struct PackedOut {                       // an output converted from the display
     Pinned<void> stage;                  // where a synchronous fetch lands
     uint32_t count = 0, last_phase = 0;  // conversions since the settings were set; the dither phase of the newest
 };
-struct CodedOut {                        // an output whose length the device decides (the JPEG stream, the PNG file, the OpenEXR file): on the device, the 16-byte word, then the stream
+struct CodedOut {                        // an output whose length the device decides (the JPEG stream, the PNG, OpenEXR and Radiance files): on the device, the 16-byte word, then the stream
     PackedOut out;                       // the stream of the synchronous fetches; its staging buffer grows to the longest frame fetched, not to the capacity
     FetchRing ring;                      // the lagged ones: a fetch copies a prefix at _begin and, should the frame be longer, the whole of it at _end ...
     Dev<uint8_t> cell[DE_FETCH_RING];    // ... from a device stream of its own per ring cell, which the next _begin does not touch
     size_t copied[DE_FETCH_RING] = {};   // bytes of cell k that _begin copied into the pinned cell
     size_t guess = 0;                    // the prefix _begin copies: a quarter more than the newest frame ended; 0: the output's first estimate
+    bool reads_pano[DE_FETCH_RING] = {}; // the lagged fetch in ring cell k reads what de_set_panorama replaces: a displayed output always, a scene-linear
+                                         // one (EXR, RGBE) where it was begun on the scene-linear panorama (env_faces, env_out, the tables)
 };
 
 struct DevTexture {
@@ -317,7 +319,6 @@ struct de_ctx {
     // settings are `pano` and `ex`; the equirect's tables are pano_tab.
     uint32_t env_mask = 0;          // bit k: linear slot k holds a face (cleared by de_set_panorama alone)
     Dev<float> env_faces, env_out;
-    bool ex_cell_env[DE_FETCH_RING] = {};      // lagged EXR fetch in ring cell k was begun with the panorama on: it reads env_faces and env_out
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.
@@ -382,7 +383,6 @@ struct de_ctx {
     de_rgbe rg = {(uint32_t)sizeof(de_rgbe), DE_EXR_SOURCE_MEAN, 1, DE_RGBE_ROUND_TRUNC, 1.0f};
     RgbeWork rg_work;
     CodedOut rg_coded = {{"RGBE"}, {"RGBE", "de_fetch_rgbe"}};
-    bool rg_cell_env[DE_FETCH_RING] = {};      // lagged RGBE fetch in ring cell k was begun with the panorama on: it reads env_faces and env_out
     bool frame_invalid = false;  // a persistent launch left on its abort word since the last de_reset: every fetch / reduce / synchronize reports it until then
     std::string invalid_msg;
     de_ctx* lender = nullptr;    // the context whose maps and LUTs this one reads (de_share_textures)

@@ -480,7 +480,7 @@ int run_panorama(de_ctx* c) {
     return pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->pano_faces, c->pano_tab, c->pano_out);
 }
 // ---- the scene-linear panorama (include/digital_earth_environment.h, environment_kernels.hip, environment_body.h)
-// The EXR output is the panorama's: the stage on and all six LINEAR slots held.  (On with fewer, the EXR calls refuse: ex_pano_refusal.)
+// The scene-linear outputs (EXR, RGBE) are the panorama's: the stage on and all six LINEAR slots held.  (On with fewer, their calls refuse: linear_pano_refusal.)
 bool env_active(const de_ctx* c) { return c->pano.on && c->env_mask == 63u; }
 size_t env_face_floats(const de_ctx* c) { return (size_t)c->W * (size_t)c->W * 3; }
 // src ([N][N][3] and its divisor) -> one linear slot on `stream`: the division and the transposition.
@@ -615,6 +615,17 @@ int jp_render(de_ctx* c, Dev<uint8_t>& dev, uint64_t& framed) {
     c->jp_coded.out.count++;
     return DE_OK;
 }
+struct JpegOut {      // the descriptor of de_fetch.h's entry points
+    static constexpr const char* too_small = "out_bytes is smaller than the frame (*len; de_jpeg_capacity bounds every frame)";
+    static CodedOut& coded(de_ctx* c) { return c->jp_coded; }
+    static int size_refusal(const de_ctx* c) { return vd_even_check(c); }
+    static int refusal(const de_ctx* c) { return vd_even_check(c); }
+    static JpegGeometry geometry(const de_ctx* c) { return jp_ctx_geometry(c); }
+    static size_t first_prefix(const JpegGeometry& g) { return JP_FRAMING_BYTES + (size_t)g.W * (size_t)g.H / 4; }      // two bits per pixel
+    static int render(de_ctx* c, Dev<uint8_t>& dev, int k) { return jp_render(c, dev, k < 0 ? c->jp_out_framed : c->jp_cell_framed[k]); }
+    static bool reads_panorama(const de_ctx*) { return true; }      // the shown image
+    static int length(const void* word, uint64_t* len) { return jp_length(word, len); }
+};
 // ---- PNG output (include/digital_earth_png.h, png_kernels.hip, png_tables.h)
 int pn_settings_check(const de_png* s) {
     if (s->struct_bytes != (uint32_t)sizeof(de_png)) return fail(DE_ERR_INVALID, "de_png.struct_bytes does not match this library's struct");
@@ -684,10 +695,8 @@ int pn_length(const void* word, uint64_t* len) {      // its coders raise no ran
 // One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
 int pn_render(de_ctx* c, Dev<uint8_t>& dev) {
     HIP_TRY(hipSetDevice(c->device));
-    int rc = pn_source_check(c);
-    if (rc) return rc;
     const PngGeometry g = pn_ctx_geometry(c);
-    rc = pn_shape_check(g.W, g.H, g.channels, g.depth);
+    int rc = pn_shape_check(g.W, g.H, g.channels, g.depth);
     if (rc) return rc;
     rc = dev.ensure(coded_stream_bytes(g.capacity), "PNG buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
     if (rc) return rc;
@@ -712,6 +721,17 @@ int pn_render(de_ctx* c, Dev<uint8_t>& dev) {
     c->pn_coded.out.count++;
     return DE_OK;
 }
+struct PngOut {
+    static constexpr const char* too_small = "out_bytes is smaller than the file (*len; de_png_capacity bounds every frame)";
+    static CodedOut& coded(de_ctx* c) { return c->pn_coded; }
+    static int size_refusal(const de_ctx* c) { return pn_source_check(c); }
+    static int refusal(const de_ctx* c) { return pn_source_check(c); }
+    static PngGeometry geometry(const de_ctx* c) { return pn_ctx_geometry(c); }
+    static size_t first_prefix(const PngGeometry& g) { return g.front + g.filtered / 4; }      // a quarter of the filtered bytes
+    static int render(de_ctx* c, Dev<uint8_t>& dev, int) { return pn_render(c, dev); }
+    static bool reads_panorama(const de_ctx*) { return true; }      // the shown image
+    static int length(const void* word, uint64_t* len) { return pn_length(word, len); }
+};
 // ---- look LUTs (include/digital_earth_look.h, look_kernels.hip): in place on the displayed image, directly behind the display launch
 // Everything de_set_look and de_debug_look refuse, in the header's order.
 int lk_settings_check(const de_look* s, const float* t1, const float* t3) {
@@ -839,7 +859,98 @@ int display_chain(de_ctx* c, DisplayStop stop, DisplayArgs* d, bool* per_tile) {
     return DE_OK;
 }
 
-// ---- OpenEXR output (include/digital_earth_exr.h, exr_kernels.hip, exr_tables.h): in FRONT of the display, behind the chain's stages
+// ---- the scene-linear outputs (OpenEXR, Radiance RGBE): in FRONT of the display, behind the chain's stages.  What they share, and
+// with de_environment_capture, which reads the same source.
+static const DisplayStop linear_stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
+// What a scene-linear output of `source` reads of the frame as it stands, on the context stream: MEAN reads what the display launch would read with
+// every stage off; the other sources are the chain left at their stage — its refusals, its side effects.
+int linear_source(de_ctx* c, int source, DisplayArgs* d, bool* per_tile) {
+    if (source != DE_EXR_SOURCE_MEAN) return display_chain(c, linear_stop_of[source], d, per_tile);
+    int rc = join_slots(c);      // the launches in flight first, and the next accumulate_kernel must not overwrite what this reads
+    if (rc) return rc;
+    touched_hdr(c);
+    d->hdr = c->display_src ? c->display_src : c->d_hdr; d->tile_spp = c->d_tile_spp; d->samples = c->current_spp; d->W = c->W; d->H = c->H;
+    *per_tile = c->frame_kind == DE_FRAME_ADAPTIVE;
+    return DE_OK;
+}
+// what the next accumulate_kernel must wait for ends behind the kernel that has read the sums, as behind the display launch in de_render_to_image
+int linear_sums_read(de_ctx* c) {
+    HIP_TRY(hipEventRecord(c->ev_main, c->stream));
+    c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
+    return DE_OK;
+}
+// a host-given or resampled image [H][W][3] as a source: no tile counts and a divisor of 1, x / 1.0f == x
+DisplaySrc linear_src(const float* image, int W, int H) {
+    DisplaySrc src;
+    src.hdr = image; src.tile_spp = nullptr; src.samples = 1; src.W = W; src.H = H;
+    return src;
+}
+// What these outputs deliver: the context's frame, or the scene-linear panorama while that is held (env_active; no AOV channel exists there).
+struct LinearFrame { int W, H; bool env; };
+LinearFrame linear_frame(const de_ctx* c) {
+    const bool env = env_active(c);
+    return {env ? c->pano.width : c->W, env ? c->pano.height : c->H, env};
+}
+// They sit in FRONT of the display: a face's scene-linear frame is not the panorama.  The scene-linear panorama is made of the six LINEAR slots alone
+// (include/digital_earth_environment.h); without all six there is none.
+int linear_pano_refusal(const de_ctx* c, const char* noun) {
+    if (c->pano.on && c->env_mask != 63u) return fail(DE_ERR_STATE, std::string("the panorama is on (de_set_panorama): the ") + noun + " output reads the frame in front of the display, where a panorama exists only once six linear faces are captured (de_environment_capture)");
+    return DE_OK;
+}
+// The environment as a source: six linear faces [6][n][n][3] resampled into `image`, [height][width][3] with row 0 at the bottom, which a layout reads
+// with its rows flipped.  (The context's faces and tables, or a debug call's own.)
+int env_source(hipStream_t stream, const de_panorama& p, const PanoArgs& k, int n, const float* faces, de_ctx::PanoTab& tab, float* image, DisplaySrc* src) {
+    if (p.projection == DE_PANO_EQUIRECT) { int rc = pano_tables_ensure(stream, tab, p.width, p.height, p.supersample); if (rc) return rc; }
+    int rc = pano_launch(stream, p, k, n, faces, tab, image, true);
+    if (rc) return rc;
+    *src = linear_src(image, p.width, p.height);
+    return DE_OK;
+}
+// The resampling half of de_debug_environment_*, inside coded_debug's body: the caller's faces uploaded and resampled on buffers and tables of its own.
+struct EnvDebug { Dev<float> faces, image; de_ctx::PanoTab tab; };
+int env_debug_source(hipStream_t stream, EnvDebug& b, const float* faces, int n, const de_panorama& p, DisplaySrc* src) {
+    PanoArgs k = {};
+    pano_make_consts(p, n, &k);
+    int rc = debug_upload(stream, b.faces, faces, (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float));
+    if (rc) return rc;
+    HIP_TRY(b.image.ensure((size_t)p.width * (size_t)p.height * 3 * sizeof(float)));
+    return env_source(stream, p, k, n, b.faces, b.tab, b.image, src);
+}
+int no_hook() { return DE_OK; }      // a launch's `after` where nothing of the context was read
+// One conversion of what a scene-linear output F (ExrOut, RgbeOut) delivers into `dev`, a file on the device that is (re-)allocated as needed; behind
+// F::refusal.  Nothing is waited for.  The panorama is read from the six linear slots alone: the frame as it stands is not.  F brings its settings'
+// source, its geometry, what it refuses and prepares of the frame ahead of every allocation (frame_prepare), its noun, its work buffers with their
+// tables (work) and its launch, which runs `after` behind the one kernel that reads the source.
+template <class F>
+int linear_render(de_ctx* c, Dev<uint8_t>& dev) {
+    HIP_TRY(hipSetDevice(c->device));
+    const auto g = F::geometry(c);
+    const bool env = env_active(c);
+    const int source = F::source(c);
+    int rc = DE_OK;
+    if (env) rc = c->env_out.ensure((size_t)g.W * (size_t)g.H * 3 * sizeof(float), "the environment's buffers");      // its size changes with de_set_panorama alone, which waits for the fetches that read it
+    else {
+        if (source != DE_EXR_SOURCE_MEAN) rc = display_chain_refusal(c, linear_stop_of[source]);      // ahead of every allocation: a refused call changes nothing
+        if (!rc) rc = F::frame_prepare(c);
+    }
+    if (!rc) rc = dev.ensure(coded_stream_bytes(g.capacity), F::buffers);      // one that is too small is replaced: hipFree waits for the work that reads it
+    if (!rc) rc = F::work(c, g);
+    if (rc) return rc;
+    DisplaySrc src;
+    if (env) rc = env_source(c->stream, c->pano, c->pano_consts, c->W, c->env_faces, c->pano_tab, c->env_out, &src);
+    else {
+        DisplayArgs d;
+        bool per_tile;
+        rc = linear_source(c, source, &d, &per_tile);
+        if (!rc) src = display_src(d, per_tile);
+    }
+    if (!rc) rc = F::launch(c, g, src, dev, [c, env] { return env ? (int)DE_OK : linear_sums_read(c); });      // the frame: the sums have been read
+    if (rc) return rc;
+    F::coded(c).out.count++;
+    return DE_OK;
+}
+
+// ---- OpenEXR output (include/digital_earth_exr.h, exr_kernels.hip, exr_tables.h)
 int ex_settings_check(const de_exr* s) {
     if (s->struct_bytes != (uint32_t)sizeof(de_exr)) return fail(DE_ERR_INVALID, "de_exr.struct_bytes does not match this library's struct");
     if (s->source < DE_EXR_SOURCE_MEAN || s->source > DE_EXR_SOURCE_LOCAL_EXPOSURE) return fail(DE_ERR_INVALID, "de_exr.source must be DE_EXR_SOURCE_MEAN, _DENOISED, _HISTORY, _BLOOM or _LOCAL_EXPOSURE");
@@ -951,9 +1062,6 @@ int ex_launch(hipStream_t stream, const de_ctx::ExrWork& w, const ExrGeometry& g
     HIP_TRY(hipGetLastError());
     return DE_OK;
 }
-// of the context's frame, or of the scene-linear panorama while that is what the EXR calls deliver (B, G, R alone: no AOV channel exists there)
-ExrGeometry ex_ctx_geometry(const de_ctx* c) { return env_active(c) ? ex_geometry(c->pano.width, c->pano.height, c->ex) : ex_geometry(c->W, c->H, c->ex, c->ex_aovs); }
-int ex_ctx_shape_check(const de_ctx* c) { return env_active(c) ? ex_shape_check(c->pano.width, c->pano.height, c->ex.pixel_type) : ex_shape_check(c->W, c->H, c->ex.pixel_type, c->ex_aovs); }
 // What the AOV channels in force refuse before anything is enqueued.  The variance is this context's own sums beside its own S2: not with a display
 // source (the sums shown are another buffer's, S2 is not) and not under a tile or sample partition (this rank's S2 is a part's), as the denoiser,
 // S2's other reader, refuses (denoise_refusal); and not without a complete S2.  The guides' own refusal, before maps and LUTs, is de_fetch_guides'.
@@ -967,97 +1075,51 @@ int ex_aov_refusal(de_ctx* c) {
         return fail(DE_ERR_STATE, "the EXR variance channels need the sums of squares of every sample of this frame: turn the denoiser on (de_set_denoise) before the frame's first sample, or render adaptively");
     return DE_OK;
 }
-// The EXR output sits in FRONT of the display: a face's scene-linear frame is not the panorama.  The scene-linear panorama is made of the six LINEAR
-// slots alone (include/digital_earth_environment.h); without all six there is none, and it has no AOV channels.
-int ex_pano_refusal(const de_ctx* c) {
-    if (!c->pano.on) return DE_OK;
-    if (c->env_mask != 63u) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): the EXR output reads the frame in front of the display, where a panorama exists only once six linear faces are captured (de_environment_capture)");
-    if (c->ex_aovs) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): a scene-linear panorama has no AOV channels (de_set_exr_aovs(ctx, 0) first)");
-    return DE_OK;
-}
 int ex_length(const void* word, uint64_t* len) {      // its coders raise no range status
     static const char* const text = "the EXR encoder met a piece longer than its proven worst case: nothing was written past a buffer";
     return coded_read_word(word, len, text, text);
 }
-static const DisplayStop ex_stop_of[] = {STOP_IMAGE, STOP_DENOISE, STOP_HISTORY, STOP_BLOOM, STOP_LOCAL_EXPOSURE};      // by DE_EXR_SOURCE_*; MEAN runs no chain
-// What a scene-linear output of `source` reads of the frame as it stands, on the context stream: MEAN reads what the display launch would read with
-// every stage off; the other sources are the chain left at their stage — its refusals, its side effects.  (de_environment_capture reads the same.)
-int ex_source(de_ctx* c, int source, DisplayArgs* d, bool* per_tile) {
-    if (source != DE_EXR_SOURCE_MEAN) return display_chain(c, ex_stop_of[source], d, per_tile);
-    int rc = join_slots(c);      // the launches in flight first, and the next accumulate_kernel must not overwrite what this reads
-    if (rc) return rc;
-    touched_hdr(c);
-    d->hdr = c->display_src ? c->display_src : c->d_hdr; d->tile_spp = c->d_tile_spp; d->samples = c->current_spp; d->W = c->W; d->H = c->H;
-    *per_tile = c->frame_kind == DE_FRAME_ADAPTIVE;
-    return DE_OK;
-}
-// what the next accumulate_kernel must wait for ends behind the kernel that has read the sums, as behind the display launch in de_render_to_image
-int ex_sums_read(de_ctx* c) {
-    HIP_TRY(hipEventRecord(c->ev_main, c->stream));
-    c->rec_render = c->gen_render; c->rec_hdr = c->gen_hdr;
-    return DE_OK;
-}
-// One conversion of the scene-linear panorama into `dev` (env_active): the six linear slots resampled into env_out, [height][width][3] with row 0 at
-// the bottom, which the unchanged layout reads with its rows flipped and a divisor of 1.  The frame as it stands is not read.  Nothing is waited for.
-int ex_render_environment(de_ctx* c, Dev<uint8_t>& dev) {
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = ex_ctx_shape_check(c);
-    if (rc) return rc;
-    const ExrGeometry g = ex_ctx_geometry(c);
-    rc = c->env_out.ensure((size_t)g.W * (size_t)g.H * 3 * sizeof(float), "the environment's buffers");      // its size changes with de_set_panorama alone, which waits for the fetches that read it
-    if (rc) return rc;
-    rc = dev.ensure(coded_stream_bytes(g.capacity), "EXR buffers");
-    if (rc) return rc;
-    rc = ex_work_ensure(c->ex_work, g);
-    if (rc) return rc;
-    HIP_TRY(ex_tables_upload(c->stream, c->ex_work));
-    if (c->pano.projection == DE_PANO_EQUIRECT) { rc = pano_tables_ensure(c->stream, c->pano_tab, c->pano.width, c->pano.height, c->pano.supersample); if (rc) return rc; }
-    rc = pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->env_faces, c->pano_tab, c->env_out, true);
-    if (rc) return rc;
-    DisplaySrc src;
-    src.hdr = c->env_out; src.tile_spp = nullptr; src.samples = 1; src.W = g.W; src.H = g.H;      // x / 1.0f == x
-    rc = ex_launch(c->stream, c->ex_work, g, src, true, c->ex.scale, dev, [] { return (int)DE_OK; });
-    if (rc) return rc;
-    c->ex_coded.out.count++;
-    return DE_OK;
-}
-// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
-int ex_render(de_ctx* c, Dev<uint8_t>& dev) {
-    { int rc = ex_pano_refusal(c); if (rc) return rc; }
-    if (env_active(c)) return ex_render_environment(c, dev);
-    HIP_TRY(hipSetDevice(c->device));
-    const ExrGeometry g = ex_ctx_geometry(c);
-    int rc = ex_ctx_shape_check(c);
-    if (rc) return rc;
-    const bool mean = c->ex.source == DE_EXR_SOURCE_MEAN;
-    if (!mean) { rc = display_chain_refusal(c, ex_stop_of[c->ex.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
-    rc = ex_aov_refusal(c);
-    if (rc) return rc;
-    const bool guides = (c->ex_aovs & (DE_EXR_AOV_DEPTH | DE_EXR_AOV_NORMAL | DE_EXR_AOV_ALBEDO | DE_EXR_AOV_COVERAGE | DE_EXR_AOV_TRANSMITTANCE)) != 0u;
-    if (guides) {      // the guides of the frame's geometry, whatever the source: made if stale, as for de_fetch_guides and the denoiser
-        rc = guides_of_the_frame(c);
+struct ExrOut {      // the descriptor of de_fetch.h's entry points and of linear_render
+    static constexpr const char* too_small = "out_bytes is smaller than the file (*len; de_exr_capacity bounds every frame)";
+    static constexpr const char* buffers = "EXR buffers";
+    static CodedOut& coded(de_ctx* c) { return c->ex_coded; }
+    static int source(const de_ctx* c) { return c->ex.source; }
+    static uint32_t aovs(const de_ctx* c, const LinearFrame& f) { return f.env ? 0u : c->ex_aovs; }      // B, G, R alone in the panorama
+    static ExrGeometry geometry(const de_ctx* c) { const LinearFrame f = linear_frame(c); return ex_geometry(f.W, f.H, c->ex, aovs(c, f)); }
+    static int size_refusal(const de_ctx* c) { const LinearFrame f = linear_frame(c); return ex_shape_check(f.W, f.H, c->ex.pixel_type, aovs(c, f)); }
+    static int refusal(const de_ctx* c) {
+        int rc = linear_pano_refusal(c, "EXR");
+        if (!rc && c->pano.on && c->ex_aovs) rc = fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): a scene-linear panorama has no AOV channels (de_set_exr_aovs(ctx, 0) first)");
+        return rc ? rc : size_refusal(c);
+    }
+    static size_t first_prefix(const ExrGeometry& g) { return g.front + g.raw / 2; }      // the front and half the raw bytes
+    static int render(de_ctx* c, Dev<uint8_t>& dev, int) { return linear_render<ExrOut>(c, dev); }
+    static bool reads_panorama(const de_ctx* c) { return env_active(c); }
+    static int length(const void* word, uint64_t* len) { return ex_length(word, len); }
+    // of the frame alone, where the AOV channels live: their refusal, then the guides of the frame's geometry, whatever the source — made if stale, as
+    // for de_fetch_guides and the denoiser
+    static int frame_prepare(de_ctx* c) {
+        int rc = ex_aov_refusal(c);
+        if (!rc && (c->ex_aovs & (DE_EXR_AOV_DEPTH | DE_EXR_AOV_NORMAL | DE_EXR_AOV_ALBEDO | DE_EXR_AOV_COVERAGE | DE_EXR_AOV_TRANSMITTANCE))) rc = guides_of_the_frame(c);
+        return rc;
+    }
+    static int work(de_ctx* c, const ExrGeometry& g) {
+        int rc = ex_work_ensure(c->ex_work, g);
         if (rc) return rc;
+        HIP_TRY(ex_tables_upload(c->stream, c->ex_work));
+        return DE_OK;
     }
-    rc = dev.ensure(coded_stream_bytes(g.capacity), "EXR buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
-    if (rc) return rc;
-    rc = ex_work_ensure(c->ex_work, g);
-    if (rc) return rc;
-    HIP_TRY(ex_tables_upload(c->stream, c->ex_work));
-    DisplayArgs d;
-    bool per_tile;
-    rc = ex_source(c, c->ex.source, &d, &per_tile);
-    if (rc) return rc;
-    ExrAovSrc av;      // the frame's own sums and counts, whatever the source: a stage's mean has no S2
-    if (c->ex_aovs) {
-        av.nc = c->d_dn_nc; av.at = c->d_dn_at; av.dist = c->d_dn_dist;
-        av.s1 = c->d_hdr; av.s2 = c->d_s2;      // the context's own sums beside its own S2 (ex_aov_refusal: no display source)
-        av.tile_spp = c->frame_kind == DE_FRAME_ADAPTIVE ? c->d_tile_spp : nullptr; av.samples = c->current_spp;
+    template <class After>
+    static int launch(de_ctx* c, const ExrGeometry& g, const DisplaySrc& src, uint8_t* out, After after) {
+        ExrAovSrc av;      // the frame's own sums and counts, whatever the source: a stage's mean has no S2
+        if (c->ex_aovs) {
+            av.nc = c->d_dn_nc; av.at = c->d_dn_at; av.dist = c->d_dn_dist;
+            av.s1 = c->d_hdr; av.s2 = c->d_s2;      // the context's own sums beside its own S2 (ex_aov_refusal: no display source)
+            av.tile_spp = c->frame_kind == DE_FRAME_ADAPTIVE ? c->d_tile_spp : nullptr; av.samples = c->current_spp;
+        }
+        return ex_launch(c->stream, c->ex_work, g, src, true, c->ex.scale, out, after, av);
     }
-    rc = ex_launch(c->stream, c->ex_work, g, display_src(d, per_tile), true, c->ex.scale, dev, [c]() { return ex_sums_read(c); }, av);      // behind the layout: it has read the sums
-    if (rc) return rc;
-    c->ex_coded.out.count++;
-    return DE_OK;
-}
+};
 
 // ---- Radiance HDR output (include/digital_earth_rgbe.h, rgbe_kernels.hip, rgbe_tables.h): where the EXR output sits, another file
 int rg_settings_check(const de_rgbe* s) {
@@ -1103,61 +1165,27 @@ int rg_launch(hipStream_t stream, const de_ctx::RgbeWork& w, const RgbeGeometry&
     HIP_TRY(hipGetLastError());
     return DE_OK;
 }
-// of the context's frame, or of the scene-linear panorama while that is what the RGBE calls deliver
-RgbeGeometry rg_ctx_geometry(const de_ctx* c) { return env_active(c) ? rg_geometry(c->pano.width, c->pano.height, c->rg) : rg_geometry(c->W, c->H, c->rg); }
-int rg_ctx_shape_check(const de_ctx* c) { return env_active(c) ? rg_shape_check(c->pano.width, c->pano.height) : rg_shape_check(c->W, c->H); }
-// As ex_pano_refusal: in front of the display a panorama exists only as the six linear slots.
-int rg_pano_refusal(const de_ctx* c) {
-    if (c->pano.on && c->env_mask != 63u) return fail(DE_ERR_STATE, "the panorama is on (de_set_panorama): the RGBE output reads the frame in front of the display, where a panorama exists only once six linear faces are captured (de_environment_capture)");
-    return DE_OK;
-}
 int rg_length(const void* word, uint64_t* len) {      // its coder raises no range status
     static const char* const text = "the RGBE encoder met a plane longer than its proven worst case: nothing was written past a buffer";
     return coded_read_word(word, len, text, text);
 }
-// One conversion of the scene-linear panorama into `dev` (env_active), as ex_render_environment: the six linear slots resampled into env_out, read
-// with its rows flipped and a divisor of 1.  Nothing is waited for.
-int rg_render_environment(de_ctx* c, Dev<uint8_t>& dev) {
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = rg_ctx_shape_check(c);
-    if (rc) return rc;
-    const RgbeGeometry g = rg_ctx_geometry(c);
-    rc = c->env_out.ensure((size_t)g.W * (size_t)g.H * 3 * sizeof(float), "the environment's buffers");      // its size changes with de_set_panorama alone, which waits for the fetches that read it
-    if (rc) return rc;
-    rc = dev.ensure(coded_stream_bytes(g.capacity), "RGBE buffers");
-    if (rc) return rc;
-    rc = rg_work_ensure(c->rg_work, g);
-    if (rc) return rc;
-    if (c->pano.projection == DE_PANO_EQUIRECT) { rc = pano_tables_ensure(c->stream, c->pano_tab, c->pano.width, c->pano.height, c->pano.supersample); if (rc) return rc; }
-    rc = pano_launch(c->stream, c->pano, c->pano_consts, c->W, c->env_faces, c->pano_tab, c->env_out, true);
-    if (rc) return rc;
-    DisplaySrc src;
-    src.hdr = c->env_out; src.tile_spp = nullptr; src.samples = 1; src.W = g.W; src.H = g.H;      // x / 1.0f == x
-    rc = rg_launch(c->stream, c->rg_work, g, src, true, c->rg.rounding, dev, [] { return (int)DE_OK; });
-    if (rc) return rc;
-    c->rg_coded.out.count++;
-    return DE_OK;
-}
-// One conversion of the frame as it stands into `dev`, a file on the device that is (re-)allocated as needed.  Nothing is waited for.
-int rg_render(de_ctx* c, Dev<uint8_t>& dev) {
-    { int rc = rg_pano_refusal(c); if (rc) return rc; }
-    if (env_active(c)) return rg_render_environment(c, dev);
-    HIP_TRY(hipSetDevice(c->device));
-    const RgbeGeometry g = rg_ctx_geometry(c);
-    int rc = rg_ctx_shape_check(c);
-    if (rc) return rc;
-    if (c->rg.source != DE_EXR_SOURCE_MEAN) { rc = display_chain_refusal(c, ex_stop_of[c->rg.source]); if (rc) return rc; }      // ahead of every allocation: a refused call changes nothing
-    rc = dev.ensure(coded_stream_bytes(g.capacity), "RGBE buffers");      // one that is too small is replaced: hipFree waits for the work that reads it
-    if (rc) return rc;
-    rc = rg_work_ensure(c->rg_work, g);
-    if (rc) return rc;
-    DisplayArgs d;
-    bool per_tile;
-    rc = ex_source(c, c->rg.source, &d, &per_tile);
-    if (rc) return rc;
-    rc = rg_launch(c->stream, c->rg_work, g, display_src(d, per_tile), true, c->rg.rounding, dev, [c]() { return ex_sums_read(c); });      // behind the conversion: it has read the sums
-    if (rc) return rc;
-    c->rg_coded.out.count++;
-    return DE_OK;
-}
+struct RgbeOut {      // as ExrOut
+    static constexpr const char* too_small = "out_bytes is smaller than the file (*len; de_rgbe_capacity bounds every frame)";
+    static constexpr const char* buffers = "RGBE buffers";
+    static CodedOut& coded(de_ctx* c) { return c->rg_coded; }
+    static int source(const de_ctx* c) { return c->rg.source; }
+    static RgbeGeometry geometry(const de_ctx* c) { const LinearFrame f = linear_frame(c); return rg_geometry(f.W, f.H, c->rg); }
+    static int size_refusal(const de_ctx* c) { const LinearFrame f = linear_frame(c); return rg_shape_check(f.W, f.H); }
+    static int refusal(const de_ctx* c) { int rc = linear_pano_refusal(c, "RGBE"); return rc ? rc : size_refusal(c); }
+    static size_t first_prefix(const RgbeGeometry& g) { return g.header + 2 * (size_t)g.W * (size_t)g.H; }      // the front and half the flat bytes
+    static int render(de_ctx* c, Dev<uint8_t>& dev, int) { return linear_render<RgbeOut>(c, dev); }
+    static bool reads_panorama(const de_ctx* c) { return env_active(c); }
+    static int length(const void* word, uint64_t* len) { return rg_length(word, len); }
+    static int frame_prepare(de_ctx*) { return DE_OK; }
+    static int work(de_ctx* c, const RgbeGeometry& g) { return rg_work_ensure(c->rg_work, g); }      // no table
+    template <class After>
+    static int launch(de_ctx* c, const RgbeGeometry& g, const DisplaySrc& src, uint8_t* out, After after) {
+        return rg_launch(c->stream, c->rg_work, g, src, true, c->rg.rounding, out, after);
+    }
+};
 }  // namespace

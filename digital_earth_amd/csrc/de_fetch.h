@@ -4,7 +4,9 @@
 //   * copy_out: device -> caller's buffer through the context's staging buffer;
 //   * the conversion frame of the packed outputs (8-bit pixels, HDR pixels, video frames): allocate, display, phase, launch, count;
 //   * the synchronous path (render, copy, wait) and the lagged one (begin: render, copy, record; end: wait, hand out);
-//   * both once more for the outputs whose length the device decides (CodedOut: the JPEG stream, the PNG file), and the debug entry points' tail.
+//   * both once more for the outputs whose length the device decides (CodedOut: the JPEG stream, the PNG, OpenEXR and Radiance files);
+//   * the entry points of those outputs, once over a format's descriptor (coded_capacity ... coded_fetch_end), and the one frame of their debug
+//     conversions (coded_debug).
 // The entry points of de_api.hip check their own arguments and call one of these.
 #pragma once
 
@@ -209,6 +211,90 @@ int coded_debug_out(hipStream_t stream, const uint8_t* d_out, Length length, voi
     HIP_TRY(hipStreamSynchronize(stream));
     return DE_OK;
 }
+// A debug conversion on host-given data, once: the device, the stream's buffer, `body(stream, d_out)` — the format's buffers, its uploads
+// (debug_upload) and its launches — and the tail above.  The rule: from the body's first upload on a copy that reads the caller's memory may be in
+// flight, so every way out behind that point waits for the stream.  `wait`, and nothing else, sees to it; what the copies read and write outlives
+// it: the body's device buffers and host arrays are the caller's locals, declared outside the body.
+struct StreamWait { hipStream_t stream; ~StreamWait() { (void)hipStreamSynchronize(stream); } };
+template <class T>
+int debug_upload(hipStream_t stream, Dev<T>& d, const void* host, size_t bytes) {
+    HIP_TRY(d.ensure(bytes));
+    HIP_TRY(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream));
+    return DE_OK;
+}
+template <class Length, class Body>
+int coded_debug(de_ctx* c, size_t capacity, Length length, void* out, uint64_t out_bytes, uint64_t* len, const char* refusal, Body body) {
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<uint8_t> d_out;
+    HIP_TRY(d_out.ensure(coded_stream_bytes(capacity)));
+    StreamWait wait{c->stream};
+    { int rc = body(c->stream, d_out.get()); if (rc) return rc; }
+    return coded_debug_out(c->stream, d_out, length, out, out_bytes, len, refusal);
+}
+// ---- the entry points of a coded output, once.  A format is a descriptor D (de_display.h: JpegOut, PngOut, ExrOut, RgbeOut) that supplies what differs:
+//   coded(c)                 its CodedOut in the context
+//   size_refusal(c)          what makes its geometry meaningless: all de_*_capacity refuses
+//   refusal(c)               what de_render_to_* and de_fetch_*_begin refuse ahead of everything, size_refusal last
+//   geometry(c)              of the frame as it stands: .capacity bounds every stream;  first_prefix(g): what the first _begin copies
+//   render(c, dev, k)        one conversion into `dev`, the stream of ring cell k or (k < 0) of the synchronous fetches; behind refusal(c)
+//   reads_panorama(c)        whether that conversion reads what de_set_panorama replaces (CodedOut::reads_pano)
+//   length(word, &len)       coded_read_word with its messages;  too_small: de_fetch_*'s refusal of a short `out`
+// A fifth format writes its descriptor and six one-line entry points.
+template <class D>
+int coded_capacity(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = D::size_refusal(c); if (rc) return rc; }
+    *bytes = (uint64_t)D::geometry(c).capacity;
+    return DE_OK;
+}
+template <class D>
+int coded_render_to(de_ctx* c, const void** device_stream, const uint64_t** device_len) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = D::refusal(c); if (rc) return rc; }
+    Dev<uint8_t>& dev = D::coded(c).out.dev;
+    int rc = D::render(c, dev, -1);
+    if (rc) return rc;
+    if (device_stream) *device_stream = dev + CS_WORD_BYTES;
+    if (device_len) *device_len = reinterpret_cast<const uint64_t*>(dev.get());
+    return DE_OK;
+}
+template <class D>
+int coded_fetch_view(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    int rc = coded_render_to<D>(c, nullptr, nullptr);
+    if (rc) return rc;
+    return coded_view(c, D::coded(c), D::length, host, len);
+}
+template <class D>
+int coded_fetch(de_ctx* c, void* out, uint64_t out_bytes, uint64_t* len) {
+    if (!c || !out || !len) return fail(DE_ERR_INVALID, "null argument");
+    const void* host = nullptr;
+    int rc = coded_fetch_view<D>(c, &host, len);
+    if (rc) return rc;
+    return coded_copy_out(host, *len, out, out_bytes, D::too_small);
+}
+template <class D>
+int coded_fetch_begin(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    { int rc = D::refusal(c); if (rc) return rc; }
+    CodedOut& o = D::coded(c);
+    const auto g = D::geometry(c);
+    const int cell = ring_next_cell(o.ring);
+    int rc = coded_begin(c, o, D::first_prefix(g), g.capacity, [c, &o](int k) { return D::render(c, o.cell[k], k); });
+    if (!rc) o.reads_pano[cell] = D::reads_panorama(c);      // de_set_panorama waits for it
+    return rc;
+}
+template <class D>
+int coded_fetch_end(de_ctx* c, const void** host, uint64_t* len) {
+    if (!c || !host || !len) return fail(DE_ERR_INVALID, "null argument");
+    return coded_end(c, D::coded(c), D::length, host, len);
+}
+// what changes the panorama's buffers waits for the lagged fetches that read them
+int refuse_panorama_readers(const CodedOut& o) {
+    if (ring_any_in_flight(o.ring, [&o](int k) { return o.reads_pano[k]; })) return refuse_in_flight(o.ring);
+    return DE_OK;
+}
+void coded_reset(CodedOut& o) { o.guess = 0; packed_reset(o.out); }      // new settings: the first estimate again
 void ring_destroy_events(FetchRing& r) {      // de_destroy; the cells free themselves
     for (hipEvent_t& ev : r.ev) { if (ev) hipEventDestroy(ev); ev = nullptr; }
 }

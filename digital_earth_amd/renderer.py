@@ -122,7 +122,7 @@ class _FetchRing:
 
 
 class _CodedFetch:
-    """One coded output's fetches (fetch_jpeg, fetch_png, fetch_exr; csrc/de_fetch.h's CodedOut is the native side): a whole file whose length the device
+    """One coded output's fetches (fetch_jpeg, fetch_png, fetch_exr, fetch_rgbe; csrc/de_fetch.h's CodedOut is the native side): a whole file whose length the device
     decides, as bytes or as a view of the library's pinned buffer, synchronous or lagged through the output's ring of four.  Parametrised by the
     output: its library functions, its noun, and the names of its two attributes of the Renderer — the lagged fetches in flight (`_jp_in_flight`,
     `_pn_in_flight`) and a weak reference to the last view handed out (close() refuses while it is referenced).  The Renderer is passed in, not kept."""
@@ -1000,10 +1000,20 @@ class Renderer:
             raise ValueError("faces must have shape (6, n, n, 3)")
         p = self._panorama_settings(size, projection, aperture, apron, supersample, basis, True)
         s = self._ex_settings("mean", pixel_type, compression, chunk_bytes, scale)
+        return self._coded_debug(self._lib.de_debug_exr_framing, (ctypes.byref(s), int(size[0]), int(size[1])), lambda out, n_bytes, n: self._lib.de_debug_environment_exr(
+            self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), out, n_bytes, n))
+
+    def _coded_debug(self, framing, shape, call):
+        """The tail of every debug conversion whose length the library decides.  framing(*shape, out, out_bytes, len, capacity) is the format's
+        de_debug_*_framing with its settings and shape: it answers the capacity.  call(out, out_bytes, len) converts into a buffer of that capacity
+        filled, as 64 bytes behind it are, with a sentinel; nothing may be written behind *len.  Returns the file as bytes."""
         cap, n = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.de_debug_exr_framing(ctypes.byref(s), int(size[0]), int(size[1]), None, 0, None, ctypes.byref(cap)))
-        out = ctypes.create_string_buffer(int(cap.value))
-        check(self._lib.de_debug_environment_exr(self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
+        check(framing(*shape, None, 0, None, ctypes.byref(cap)))
+        size = int(cap.value) + 64
+        out = ctypes.create_string_buffer(b"\xA5" * size, size)
+        check(call(out, ctypes.c_uint64(int(cap.value)), ctypes.byref(n)))
+        if out.raw[int(n.value):] != b"\xA5" * (size - int(n.value)):
+            raise RuntimeError("%s: the encoder wrote behind the file's length" % framing.__name__.replace("_framing", ""))
         return out.raw[:int(n.value)]
 
     def _staging_view(self, ptr, _=None):
@@ -1228,11 +1238,8 @@ class Renderer:
             raise ValueError("image must have shape (W, H, 3)")
         W, H = image.shape[:2]
         s = self._jp_settings(quality, restart)
-        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.de_debug_jpeg_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
-        out = ctypes.create_string_buffer(int(cap.value))
-        check(self._lib.de_debug_jpeg(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
-        return out.raw[:int(n.value)]
+        return self._coded_debug(self._lib.de_debug_jpeg_framing, (ctypes.byref(s), W, H), lambda out, size, n: self._lib.de_debug_jpeg(
+            self._h, image.ctypes.data, W, H, ctypes.byref(s), out, size, n))
 
     # ------------------------------------------------------------------ PNG output (include/digital_earth_png.h)
     def _pn_settings(self, source, filter, chunk_bytes):
@@ -1295,11 +1302,8 @@ class Renderer:
         H, W, ch = pixels.shape
         depth = 8 * pixels.dtype.itemsize
         s = self._pn_settings("pixels", filter, chunk_bytes)
-        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.de_debug_png_framing(ctypes.byref(s), W, H, ch, depth, None, None, 0, None, ctypes.byref(cap)))
-        out = ctypes.create_string_buffer(int(cap.value))
-        check(self._lib.de_debug_png(self._h, pixels.ctypes.data, W, H, ch, depth, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
-        data = out.raw[:int(n.value)]
+        data = self._coded_debug(self._lib.de_debug_png_framing, (ctypes.byref(s), W, H, ch, depth, None), lambda out, size, n: self._lib.de_debug_png(
+            self._h, pixels.ctypes.data, W, H, ch, depth, ctypes.byref(s), out, size, n))
         if cicp is not None and depth == 16:
             front, m = ctypes.create_string_buffer(64), ctypes.c_uint64()
             check(self._lib.de_debug_png_framing(ctypes.byref(s), W, H, ch, depth, bytes(bytearray(cicp)), front, ctypes.c_uint64(64), ctypes.byref(m), None))
@@ -1402,11 +1406,8 @@ class Renderer:
             raise ValueError("image must have shape (H, W, 3)")
         H, W = image.shape[:2]
         s = self._ex_settings("mean", pixel_type, compression, chunk_bytes, scale)
-        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.de_debug_exr_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
-        out = ctypes.create_string_buffer(int(cap.value))
-        check(self._lib.de_debug_exr(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, ctypes.c_uint64(len(out)), ctypes.byref(n)))
-        return out.raw[:int(n.value)]
+        return self._coded_debug(self._lib.de_debug_exr_framing, (ctypes.byref(s), W, H), lambda out, size, n: self._lib.de_debug_exr(
+            self._h, image.ctypes.data, W, H, ctypes.byref(s), out, size, n))
 
     def debug_exr_aovs(self, image, guides=None, s2=None, counts=None, aovs=(), pixel_type="half", compression="zip", chunk_bytes=None, scale=1.0):
         """The encoder with AOV channels once on given arrays, rows top-down, of any size (de_debug_exr_aovs): image (H, W, 3) is read as the sums,
@@ -1428,15 +1429,9 @@ class Renderer:
             return a.ctypes.data
         mask = int(aovs) if isinstance(aovs, (int, np.integer)) else self._ex_aov_mask(aovs)
         s = self._ex_settings("mean", pixel_type, compression, chunk_bytes, scale)
-        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.de_debug_exr_aov_framing(ctypes.byref(s), mask, W, H, None, 0, None, ctypes.byref(cap)))
-        sentinel = 64
-        out = ctypes.create_string_buffer(b"\xA5" * (int(cap.value) + sentinel), int(cap.value) + sentinel)
-        check(self._lib.de_debug_exr_aovs(self._h, image.ctypes.data, arg(guides, (H, W, 9), "guides"), arg(s2, (H, W, 3), "s2"), arg(counts, (H, W), "counts"),
-                                          W, H, ctypes.byref(s), mask, out, ctypes.c_uint64(int(cap.value)), ctypes.byref(n)))
-        if out.raw[int(cap.value):] != b"\xA5" * sentinel or out.raw[int(n.value):int(cap.value)] != b"\xA5" * (int(cap.value) - int(n.value)):
-            raise RuntimeError("de_debug_exr_aovs wrote behind the file's length")
-        return out.raw[:int(n.value)]
+        arrays = (arg(guides, (H, W, 9), "guides"), arg(s2, (H, W, 3), "s2"), arg(counts, (H, W), "counts"))
+        return self._coded_debug(self._lib.de_debug_exr_aov_framing, (ctypes.byref(s), mask, W, H), lambda out, size, n: self._lib.de_debug_exr_aovs(
+            self._h, image.ctypes.data, *arrays, W, H, ctypes.byref(s), mask, out, size, n))
 
     # ------------------------------------------------------------------ Radiance HDR output (include/digital_earth_rgbe.h)
     def _rg_settings(self, source, rle, rounding, scale):
@@ -1489,16 +1484,6 @@ class Renderer:
         address of its uint64 length).  Nothing is waited for."""
         return self._rg_coded.render_to(self)
 
-    def _rg_debug(self, s, W, H, call):
-        cap, n = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.de_debug_rgbe_framing(ctypes.byref(s), W, H, None, 0, None, ctypes.byref(cap)))
-        sentinel = 64
-        out = ctypes.create_string_buffer(b"\xA5" * (int(cap.value) + sentinel), int(cap.value) + sentinel)
-        check(call(out, ctypes.c_uint64(int(cap.value)), ctypes.byref(n)))
-        if out.raw[int(n.value):] != b"\xA5" * (int(cap.value) + sentinel - int(n.value)):
-            raise RuntimeError("the RGBE encoder wrote behind the file's length")
-        return out.raw[:int(n.value)]
-
     def debug_rgbe(self, image, rle=True, rounding="trunc", scale=1.0):
         """The encoder once on a given (H, W, 3) float32 image in R, G, B order, rows top-down, of any size (de_debug_rgbe); returns the file as
         bytes.  The renderer's own settings and streams are not touched."""
@@ -1507,7 +1492,8 @@ class Renderer:
             raise ValueError("image must have shape (H, W, 3)")
         H, W = image.shape[:2]
         s = self._rg_settings("mean", rle, rounding, scale)
-        return self._rg_debug(s, W, H, lambda out, size, n: self._lib.de_debug_rgbe(self._h, image.ctypes.data, W, H, ctypes.byref(s), out, size, n))
+        return self._coded_debug(self._lib.de_debug_rgbe_framing, (ctypes.byref(s), W, H), lambda out, size, n: self._lib.de_debug_rgbe(
+            self._h, image.ctypes.data, W, H, ctypes.byref(s), out, size, n))
 
     def debug_environment_rgbe(self, faces, size, projection="equirect", aperture=180.0, apron=1, supersample=2, basis=None, rle=True, rounding="trunc", scale=1.0):
         """The resampling and the RGBE conversion once on given LINEAR faces, (6, n, n, 3) float32 as debug_panorama takes them
@@ -1517,7 +1503,7 @@ class Renderer:
             raise ValueError("faces must have shape (6, n, n, 3)")
         p = self._panorama_settings(size, projection, aperture, apron, supersample, basis, True)
         s = self._rg_settings("mean", rle, rounding, scale)
-        return self._rg_debug(s, int(size[0]), int(size[1]), lambda out, n_bytes, n: self._lib.de_debug_environment_rgbe(
+        return self._coded_debug(self._lib.de_debug_rgbe_framing, (ctypes.byref(s), int(size[0]), int(size[1])), lambda out, n_bytes, n: self._lib.de_debug_environment_rgbe(
             self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), out, n_bytes, n))
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h)
