@@ -391,6 +391,26 @@ RGBE_SYMBOLS = {
     "de_debug_environment_rgbe": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), ctypes.POINTER(DeRgbe), _P, ctypes.c_uint64, _U64P]),
 }
 
+
+class DeIbl(ctypes.Structure):
+    """`de_ibl` (include/digital_earth_ibl.h): the cube edge, the specular levels, the samples per texel, the base level's supersample, the level-of-detail
+    bias and the DDS file's pixel type."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("edge", ctypes.c_int32), ("levels", ctypes.c_int32), ("samples", ctypes.c_int32),
+                ("supersample", ctypes.c_int32), ("lod_bias", ctypes.c_float), ("pixel_type", ctypes.c_int32)]
+
+
+# IBL output: include/digital_earth_ibl.h (same library, additions only; not part of the binder's header)
+IBL_SYMBOLS = {
+    "de_set_ibl": (ctypes.c_int, [_P, ctypes.POINTER(DeIbl)]),
+    "de_get_ibl": (ctypes.c_int, [_P, ctypes.POINTER(DeIbl)]),
+    "de_ibl_build": (ctypes.c_int, [_P]),
+    "de_fetch_ibl_sh": (ctypes.c_int, [_P, _P]),
+    "de_fetch_ibl_face": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P]),
+    "de_ibl_file_bytes": (ctypes.c_int, [_P, _U64P]),
+    "de_fetch_ibl_dds": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
+    "de_debug_ibl": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), ctypes.POINTER(DeIbl), _P, _P, _P, ctypes.c_uint64]),
+}
+
 # look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
 LOOK_SYMBOLS = {
     "de_set_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook), _P, _P]),
@@ -477,7 +497,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()) + list(RGBE_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()) + list(RGBE_SYMBOLS.items()) + list(IBL_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

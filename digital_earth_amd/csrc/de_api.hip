@@ -1823,6 +1823,149 @@ int de_debug_environment_rgbe(de_ctx* c, const float* faces, int n, const de_pan
     });
 }
 
+/* ---- the IBL output: include/digital_earth_ibl.h (ibl_kernels.hip, ibl_body.h, ibl_tables.h) */
+namespace {
+int ibl_settings_check(const de_ibl* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_ibl)) return fail(DE_ERR_INVALID, "de_ibl.struct_bytes does not match this library's struct");
+    if (const char* fault = ibl_settings_fault(s->edge, s->levels, s->samples, s->supersample, s->lod_bias, s->pixel_type)) return fail(DE_ERR_INVALID, fault);
+    return DE_OK;
+}
+unsigned ibl_blocks(int e) { const unsigned tiles = (unsigned)((e + IBL_TILE - 1) / IBL_TILE); return 6u * tiles * tiles; }
+size_t ibl_spec_offset(int E, int l) { return ibl_level_offset(E, l) - ibl_level_offset(E, 1); }      // floats in front of specular level l >= 1
+// The whole bake on `stream`, waited for: faces [6][N][N][3] with the constants of their panorama in `k` -> everything in `w`.
+int ibl_run(hipStream_t stream, de_ctx::IblWork& w, const PanoArgs& k, int N, const float* faces, const de_ibl& s) {
+    const int E = s.edge, L = s.levels, M = ibl_log2(E) + 1, es = E < IBL_SH_EDGE ? E : IBL_SH_EDGE, groups = (6 * es * es + IBL_THREADS - 1) / IBL_THREADS;
+    // the tables, in double on the host, rounded once; they outlive their uploads: this call waits for the stream before it returns
+    std::vector<IblSample> tab, level_tab;
+    std::vector<float> omega;
+    int first[IBL_MAX_LEVELS] = {}, kept[IBL_MAX_LEVELS] = {};
+    for (int l = 1; l < L; ++l) {
+        ibl_build_samples(E, L, s.samples, l, s.lod_bias, &level_tab);
+        first[l] = (int)tab.size(); kept[l] = (int)level_tab.size();
+        tab.insert(tab.end(), level_tab.begin(), level_tab.end());
+    }
+    ibl_build_omega(es, &omega);
+    int rc = w.mips.ensure(ibl_level_offset(E, M) * sizeof(float), "the IBL buffers");
+    if (!rc) rc = w.spec.ensure(ibl_spec_offset(E, L) * sizeof(float), "the IBL buffers");
+    if (!rc) rc = w.tab.ensure((tab.size() + 1) * sizeof(IblSample), "the IBL buffers");
+    if (!rc) rc = w.omega.ensure(omega.size() * sizeof(float), "the IBL buffers");
+    if (!rc) rc = w.partial.ensure((size_t)groups * 27 * sizeof(float), "the IBL buffers");
+    if (!rc) rc = w.sh.ensure(27 * sizeof(float), "the IBL buffers");
+    if (!rc) rc = w.payload.ensure(ibl_payload_bytes(E, L, s.pixel_type), "the IBL buffers");
+    if (rc) return rc;
+    StreamWait wait{stream};
+    if (!tab.empty()) HIP_TRY(hipMemcpyAsync(w.tab, tab.data(), tab.size() * sizeof(IblSample), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(w.omega, omega.data(), omega.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    PanoArgs p = k;
+    p.faces = faces; p.out = nullptr; p.N = N; p.width = 0; p.height = 0; p.S = s.supersample; p.fisheye = 0;
+    p.sin_lon = p.cos_lon = p.sin_lat = p.cos_lat = nullptr;
+    hipLaunchKernelGGL(ibl_base_kernel, dim3(ibl_blocks(E)), dim3(IBL_THREADS), 0, stream, p, w.mips.get(), E, s.supersample);
+    for (int m = 1; m < M; ++m)
+        hipLaunchKernelGGL(ibl_mip_kernel, dim3(ibl_blocks(E >> m)), dim3(IBL_THREADS), 0, stream, w.mips + ibl_level_offset(E, m - 1), w.mips + ibl_level_offset(E, m), E >> m);
+    IblLevelArgs a = {};
+    a.mips = w.mips; a.omega = w.omega; a.E = E; a.M = M;
+    for (int m = 0; m < M; ++m) a.off[m] = (uint32_t)ibl_level_offset(E, m);
+    for (int l = 1; l < L; ++l) {
+        a.out = w.spec + ibl_spec_offset(E, l); a.tab = w.tab + first[l]; a.n = kept[l]; a.e = E >> l;
+        hipLaunchKernelGGL(ibl_spec_kernel, dim3(ibl_blocks(a.e)), dim3(IBL_THREADS), 0, stream, a);
+    }
+    hipLaunchKernelGGL(ibl_sh_kernel, dim3((unsigned)groups), dim3(IBL_THREADS), 0, stream, w.mips + ibl_level_offset(E, ibl_log2(E / es)), w.omega.get(), es, w.partial.get());
+    hipLaunchKernelGGL(ibl_sh_final_kernel, dim3(1), dim3(64), 0, stream, w.partial.get(), groups, w.sh.get());
+    IblPackArgs q = {};
+    q.mips = w.mips; q.spec = w.spec; q.out = w.payload; q.E = E; q.L = L; q.half = s.pixel_type == DE_EXR_PIXEL_HALF ? 1 : 0;
+    q.texels_per_face = (uint32_t)ibl_texels_before(E, L);
+    for (int l = 1; l < L; ++l) q.spec_off[l] = (uint32_t)ibl_spec_offset(E, l);
+    hipLaunchKernelGGL(ibl_pack_kernel, dim3((6u * q.texels_per_face + IBL_THREADS - 1) / IBL_THREADS), dim3(IBL_THREADS), 0, stream, q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DE_OK;
+}
+// device -> the caller's memory on `stream`, waited for
+int ibl_copy_out(hipStream_t stream, void* out, const void* d_src, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(out, d_src, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DE_OK;
+}
+const float* ibl_level_block(const de_ctx::IblWork& w, int E, int level) { return level == 0 ? w.mips.get() : w.spec + ibl_spec_offset(E, level); }
+int ibl_dds_out(hipStream_t stream, const de_ctx::IblWork& w, const de_ibl& s, void* out) {
+    ibl_dds_header(s.edge, s.levels, s.pixel_type, (uint8_t*)out);
+    return ibl_copy_out(stream, (uint8_t*)out + IBL_DDS_HEADER, w.payload, ibl_payload_bytes(s.edge, s.levels, s.pixel_type));
+}
+}  // namespace
+int de_set_ibl(de_ctx* c, const de_ibl* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = ibl_settings_check(s); if (rc) return rc; }
+    c->ibl = *s;
+    c->ibl_built = false;
+    return DE_OK;
+}
+int de_get_ibl(de_ctx* c, de_ibl* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->ibl;
+    return DE_OK;
+}
+int de_ibl_build(de_ctx* c) {
+    if (!c) return fail(DE_ERR_INVALID, "null context");
+    if (!c->pano.on) return fail(DE_ERR_STATE, "the panorama is off (de_set_panorama): the IBL bake reads its six linear faces");
+    if (c->env_mask != 63u) return fail(DE_ERR_STATE, "fewer than six linear faces are captured (de_environment_capture)");
+    HIP_TRY(hipSetDevice(c->device));
+    c->ibl_built = false;
+    int rc = ibl_run(c->stream, c->ibl_work, c->pano_consts, c->W, c->env_faces, c->ibl);
+    if (rc) return rc;
+    c->ibl_built = true;
+    return DE_OK;
+}
+int de_fetch_ibl_sh(de_ctx* c, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (!c->ibl_built) return fail(DE_ERR_STATE, "no IBL product is held (de_ibl_build)");
+    HIP_TRY(hipSetDevice(c->device));
+    return ibl_copy_out(c->stream, out, c->ibl_work.sh, 27 * sizeof(float));
+}
+int de_fetch_ibl_face(de_ctx* c, int level, int face, float* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (level < 0 || level >= c->ibl.levels) return fail(DE_ERR_INVALID, "level must lie in 0 ... de_ibl.levels - 1");
+    if (face < 0 || face >= DE_PANO_FACES) return fail(DE_ERR_INVALID, "face must lie in 0 ... 5");
+    if (!c->ibl_built) return fail(DE_ERR_STATE, "no IBL product is held (de_ibl_build)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t e = (size_t)(c->ibl.edge >> level), floats = e * e * 3;
+    return ibl_copy_out(c->stream, out, ibl_level_block(c->ibl_work, c->ibl.edge, level) + (size_t)face * floats, floats * sizeof(float));
+}
+int de_ibl_file_bytes(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    *bytes = (uint64_t)IBL_DDS_HEADER + (uint64_t)ibl_payload_bytes(c->ibl.edge, c->ibl.levels, c->ibl.pixel_type);
+    return DE_OK;
+}
+int de_fetch_ibl_dds(de_ctx* c, void* out, uint64_t out_bytes) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (out_bytes < (uint64_t)IBL_DDS_HEADER + (uint64_t)ibl_payload_bytes(c->ibl.edge, c->ibl.levels, c->ibl.pixel_type)) return fail(DE_ERR_INVALID, "out_bytes is smaller than the file (de_ibl_file_bytes)");
+    if (!c->ibl_built) return fail(DE_ERR_STATE, "no IBL product is held (de_ibl_build)");
+    HIP_TRY(hipSetDevice(c->device));
+    return ibl_dds_out(c->stream, c->ibl_work, c->ibl, out);
+}
+/* The bake once on host-given linear faces.  Buffers and tables of its own; the context's settings, slots and product are not touched.  The arguments
+ * and both settings are checked before the context is read. */
+int de_debug_ibl(de_ctx* c, const float* faces, int n, const de_panorama* p, const de_ibl* s, float* sh, float* levels, void* dds, uint64_t dds_bytes) {
+    if (!c || !faces || !p || !s || n < 4 || n > 16384) return fail(DE_ERR_INVALID, "bad arguments (faces of 4 ... 16384 pixels a side)");
+    { int rc = pano_settings_check(p, n); if (rc) return rc; }
+    { int rc = ibl_settings_check(s); if (rc) return rc; }
+    if (dds && dds_bytes < (uint64_t)IBL_DDS_HEADER + (uint64_t)ibl_payload_bytes(s->edge, s->levels, s->pixel_type)) return fail(DE_ERR_INVALID, "dds_bytes is smaller than the file");
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<float> d_faces;
+    de_ctx::IblWork work;
+    PanoArgs k = {};
+    pano_make_consts(*p, n, &k);
+    StreamWait wait{c->stream};
+    int rc = debug_upload(c->stream, d_faces, faces, (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float));
+    if (!rc) rc = ibl_run(c->stream, work, k, n, d_faces, *s);
+    if (!rc && sh) rc = ibl_copy_out(c->stream, sh, work.sh, 27 * sizeof(float));
+    for (int l = 0; !rc && levels && l < s->levels; ++l) {
+        const size_t floats = (size_t)(s->edge >> l) * (size_t)(s->edge >> l) * 18;
+        rc = ibl_copy_out(c->stream, levels + ibl_level_offset(s->edge, l), ibl_level_block(work, s->edge, l), floats * sizeof(float));
+    }
+    if (!rc && dds) rc = ibl_dds_out(c->stream, work, *s, dds);
+    return rc;
+}
+
 /* ---- look LUTs: include/digital_earth_look.h (look_kernels.hip) */
 int de_set_look(de_ctx* c, const de_look* s, const float* table_1d, const float* table_3d) {
     if (!c || !s) return fail(DE_ERR_INVALID, "null argument");

@@ -17,6 +17,7 @@
 #include "../../include/digital_earth_exr_aovs.h"
 #include "../../include/digital_earth_environment.h"
 #include "../../include/digital_earth_rgbe.h"
+#include "../../include/digital_earth_ibl.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -56,6 +57,7 @@
 #include "png_kernels.hip"
 #include "exr_kernels.hip"
 #include "rgbe_kernels.hip"
+#include "ibl_kernels.hip"
 
 namespace {
 
@@ -319,6 +321,14 @@ struct de_ctx {
     // settings are `pano` and `ex`; the equirect's tables are pano_tab.
     uint32_t env_mask = 0;          // bit k: linear slot k holds a face (cleared by de_set_panorama alone)
     Dev<float> env_faces, env_out;
+    // IBL output (include/digital_earth_ibl.h).  Everything reaches the device by the first de_ibl_build that succeeds: the mip chain
+    // (level 0 is the base level), the specular levels 1 ... L - 1, the levels' sample tables, the solid angles, the SH partials and result, the DDS payload.
+    struct IblWork {
+        Dev<float> mips, spec, omega, partial, sh; Dev<IblSample> tab; Dev<uint8_t> payload;
+    };
+    de_ibl ibl = {(uint32_t)sizeof(de_ibl), 128, 6, 256, 2, 0.0f, DE_EXR_PIXEL_HALF};
+    bool ibl_built = false;         // ibl_work holds the product of `ibl` (dropped by de_set_ibl)
+    IblWork ibl_work;
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.

@@ -298,7 +298,10 @@ class EarthViewer:
         hdr_pixels / video / jpeg / png = True that output, pipelined or not) is the 360° frame at Renderer.output_size() — so
         record(path, n, panorama=True) writes a 360° Y4M, Motion-JPEG or PNG sequence through the writers as they are.  With exr=True step 2 is
         Renderer.render_environment(spp) instead — the same six renders captured in FRONT of the display — and the file handed out, through the EXR
-        ring when pipelined, is the scene-linear 360° frame, an HDR environment map: record("env/%05d.exr", n, panorama=True) writes a sequence."""
+        ring when pipelined, is the scene-linear 360° frame, an HDR environment map: record("env/%05d.exr", n, panorama=True) writes a sequence.
+        ibl=True with panorama=True (it goes with no other output and not with pipelined): step 2 is Renderer.render_environment(spp) and
+        Renderer.build_ibl() behind it, and what is handed out is Renderer.fetch_ibl_dds(): the GGX-prefiltered cube map as one DDS file, in the
+        settings of Renderer.set_ibl(); Renderer.fetch_ibl_sh() holds the irradiance's SH coefficients of the same bake."""
         r = self.renderer
         hdr_pixels = bool(sliders.pop("hdr_pixels", False))
         video = bool(sliders.pop("video", False))
@@ -307,6 +310,9 @@ class EarthViewer:
         exr = bool(sliders.pop("exr", False))
         rgbe = bool(sliders.pop("rgbe", False))
         panorama = bool(sliders.pop("panorama", False))
+        ibl = bool(sliders.pop("ibl", False))
+        if ibl and (not panorama or pipelined or pixels or hdr_pixels or video or jpeg or png or exr or rgbe):
+            raise ValueError("ibl=True needs panorama=True and goes with no other output and not with pipelined")
         if rgbe and (pixels or hdr_pixels or video or jpeg or png or exr):
             raise ValueError("rgbe=True goes with none of pixels=True, hdr_pixels=True, video=True, jpeg=True, png=True and exr=True")
         if exr and (pixels or hdr_pixels or video or jpeg or png):
@@ -325,14 +331,17 @@ class EarthViewer:
             r.set_look_at(*self.camera.look_at)
             r.set_up(*self.camera._up)
             should_reset = True
-        if panorama and (exr or rgbe):
+        if panorama and (exr or rgbe or ibl):
             r.render_environment(int(spp))      # the same six renders, captured in front of the display (include/digital_earth_environment.h)
         elif panorama:
             r.render_panorama(int(spp))         # six faces around the camera, `spp` each; the camera is put back and the frame left empty
         else:
             r.accumulate(int(spp))              # == accumulate() x spp, bit for bit
         frame = None
-        if rgbe:
+        if ibl:
+            r.build_ibl()
+            frame = r.fetch_ibl_dds()
+        elif rgbe:
             frame = r.fetch_rgbe(copy=copy, lag=int(pipelined))
         elif exr:
             frame = r.fetch_exr(copy=copy, lag=int(pipelined))
@@ -352,7 +361,7 @@ class EarthViewer:
         # The settings this picture was displayed with (read before the sliders below).  A pipelined iteration returns an EARLIER iteration's picture:
         # the settings travel through a queue of their own, one entry per fetch in flight, so that save() labels each picture as it was taken.
         shown = self._pixels if (pixels or hdr_pixels) else self._image
-        if video or jpeg or png or exr or rgbe:
+        if video or jpeg or png or exr or rgbe or ibl:
             pass                                # no picture of save()'s changed hands
         elif pipelined:
             self._hdr_in_flight[bool(pixels)].append(r.hdr_output)
@@ -377,7 +386,7 @@ class EarthViewer:
         r.exposure[None] = cur["exposure"]; r.gamma[None] = cur["gamma"]; r.selected_crf[None] = cur["selected_crf"]
         if should_reset:
             r.reset_framebuffer()
-        if video or jpeg or png or exr or rgbe:
+        if video or jpeg or png or exr or rgbe or ibl:
             return frame
         return self._pixels if (pixels or hdr_pixels) else self._image
 
@@ -532,8 +541,16 @@ class EarthViewer:
         Renderer.render_environment() the file is whatever fetch_exr() delivers then: the scene-linear panorama.
         `.hdr` once Renderer.set_rgbe() has been called: the same scene-linear frame as one Radiance RGBE file, converted and run-length coded on the
         GPU (Renderer.fetch_rgbe) in the settings of set_rgbe(); digital_earth_amd.rgbe.read opens it again.  Without set_rgbe() the extension is
-        what it was before: one the image writer does not know."""
+        what it was before: one the image writer does not know.
+        `.dds` while a panorama with all six linear faces is held (frame(panorama=True, exr / rgbe / ibl = True), Renderer.render_environment()): the
+        IBL bake of those faces in the settings of Renderer.set_ibl() (Renderer.build_ibl, fetch_ibl_dds), a GGX-prefiltered cube map with the DX10
+        header; digital_earth_amd.dds.read opens it again.  Otherwise the extension is one the image writer does not know."""
         r = self.renderer
+        if path.endswith(".dds") and r.panorama["on"] and len(r.environment["captured"]) == 6:
+            r.build_ibl()
+            with open(path, "wb") as f:
+                f.write(r.fetch_ibl_dds())
+            return
         if path.endswith(".hdr") and r.rgbe_is_set:
             if r.current_spp == 0 and not (r.panorama["on"] and len(r.environment["captured"]) == 6):
                 self.render(1)

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DeRgbe, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DeRgbe, DeIbl, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -1505,6 +1505,76 @@ class Renderer:
         s = self._rg_settings("mean", rle, rounding, scale)
         return self._coded_debug(self._lib.de_debug_rgbe_framing, (ctypes.byref(s), int(size[0]), int(size[1])), lambda out, n_bytes, n: self._lib.de_debug_environment_rgbe(
             self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), out, n_bytes, n))
+
+    # ------------------------------------------------------------------ IBL output (include/digital_earth_ibl.h)
+    def _ibl_settings(self, edge, levels, samples, supersample, lod_bias, pixel_type):
+        if pixel_type not in _native.EXR_PIXEL_TYPES:
+            raise ValueError("pixel_type must be one of %s" % (tuple(_native.EXR_PIXEL_TYPES),))
+        s = DeIbl()
+        s.struct_bytes = ctypes.sizeof(DeIbl)
+        s.edge, s.levels, s.samples, s.supersample = int(edge), int(levels), int(samples), int(supersample)
+        s.lod_bias, s.pixel_type = float(lod_bias), _native.EXR_PIXEL_TYPES[pixel_type]
+        return s
+
+    def set_ibl(self, edge=128, levels=6, samples=256, supersample=2, lod_bias=0.0, pixel_type="half"):
+        """The settings of build_ibl(): a cube map of `edge` (a power of two, 8 ... 1024) with `levels` GGX-prefiltered levels (level l: edge >> l,
+        roughness l / (levels - 1)), `samples` per texel (a power of two, 8 ... 1024), the base level's `supersample` (1 ... 4), a bias on every
+        sample's source level of detail, and the DDS file's pixel type, "half" or "float".  Drops the product of an earlier build_ibl()."""
+        s = self._ibl_settings(edge, levels, samples, supersample, lod_bias, pixel_type)
+        check(self._lib.de_set_ibl(self._h, ctypes.byref(s)))
+
+    @property
+    def ibl(self):
+        """The IBL settings as a dict (set_ibl's keywords) plus file_bytes, the DDS file's length."""
+        s, n = DeIbl(), ctypes.c_uint64()
+        check(self._lib.de_get_ibl(self._h, ctypes.byref(s)))
+        check(self._lib.de_ibl_file_bytes(self._h, ctypes.byref(n)))
+        return dict(edge=int(s.edge), levels=int(s.levels), samples=int(s.samples), supersample=int(s.supersample), lod_bias=float(s.lod_bias),
+                    pixel_type=next(k for k, x in _native.EXR_PIXEL_TYPES.items() if x == s.pixel_type), file_bytes=int(n.value))
+
+    def build_ibl(self):
+        """Bake the six linear faces as they stand (behind render_environment(), the panorama on) into the cube map, its GGX-prefiltered levels, the SH
+        coefficients of the irradiance and the DDS payload, on the GPU (de_ibl_build).  The fetch_ibl_* calls hand the product out."""
+        check(self._lib.de_ibl_build(self._h))
+
+    def fetch_ibl_sh(self):
+        """The irradiance's spherical-harmonic coefficients, (3, 9) float32: rows R, G, B; l = 0 ... 2, the cosine lobe applied."""
+        out = np.empty((3, 9), dtype=np.float32)
+        check(self._lib.de_fetch_ibl_sh(self._h, out.ctypes.data))
+        return out
+
+    def fetch_ibl_face(self, level, face):
+        """Face 0 ... 5 (+r, -r, +u, -u, +f, -f: the DDS order) of specular level `level` as (e, e, 3) float32, e = edge >> level, rows top first."""
+        e = self.ibl["edge"] >> max(0, min(int(level), 30))
+        out = np.empty((max(e, 1), max(e, 1), 3), dtype=np.float32)
+        check(self._lib.de_fetch_ibl_face(self._h, int(level), int(face), out.ctypes.data))
+        return out
+
+    def fetch_ibl_dds(self):
+        """The whole product as one DDS cube map file with the DX10 header (`bytes`): digital_earth_amd.dds.read opens it again."""
+        n = self.ibl["file_bytes"]
+        out = ctypes.create_string_buffer(n)
+        check(self._lib.de_fetch_ibl_dds(self._h, out, ctypes.c_uint64(n)))
+        return out.raw
+
+    def debug_ibl(self, faces, apron=1, basis=None, edge=16, levels=5, samples=8, supersample=1, lod_bias=0.0, pixel_type="half"):
+        """The bake once on given LINEAR faces, (6, n, n, 3) float32 as debug_panorama takes them (de_debug_ibl).  Returns (sh (3, 9), levels, dds):
+        levels[l] is (6, e, e, 3) float32.  The renderer's own settings, faces and product are not touched."""
+        faces = np.ascontiguousarray(faces, dtype=np.float32)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 3:
+            raise ValueError("faces must have shape (6, n, n, 3)")
+        p = self._panorama_settings((16, 8), "equirect", 180.0, apron, 1, basis, True)
+        s = self._ibl_settings(edge, levels, samples, supersample, lod_bias, pixel_type)
+        edges = [max(int(edge) >> l, 0) for l in range(max(int(levels), 0))]
+        flat = np.empty(max(sum(18 * e * e for e in edges), 1), dtype=np.float32)
+        n = 148 + sum(6 * e * e for e in edges) * (8 if pixel_type == "half" else 16)
+        sh, dds = np.empty((3, 9), dtype=np.float32), ctypes.create_string_buffer(n)
+        check(self._lib.de_debug_ibl(self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), sh.ctypes.data, flat.ctypes.data, dds, ctypes.c_uint64(n)))
+        out, at = [], 0
+        for e in edges:
+            out.append(flat[at:at + 18 * e * e].reshape(6, e, e, 3).copy())
+            at += 18 * e * e
+        return sh, out, dds.raw
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)
     LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
