@@ -411,6 +411,21 @@ IBL_SYMBOLS = {
     "de_debug_ibl": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), ctypes.POINTER(DeIbl), _P, _P, _P, ctypes.c_uint64]),
 }
 
+class DeIblBc6h(ctypes.Structure):
+    """`de_ibl_bc6h` (include/digital_earth_ibl_bc6h.h): the BC6H stage of the IBL output, off by default, and its quality 0 or 1."""
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("on", ctypes.c_int32), ("quality", ctypes.c_int32)]
+
+
+# IBL output, BC6H-compressed: include/digital_earth_ibl_bc6h.h (same library, additions only; not part of the binder's header)
+IBL_BC6H_SYMBOLS = {
+    "de_set_ibl_bc6h": (ctypes.c_int, [_P, ctypes.POINTER(DeIblBc6h)]),
+    "de_get_ibl_bc6h": (ctypes.c_int, [_P, ctypes.POINTER(DeIblBc6h)]),
+    "de_ibl_bc6h_file_bytes": (ctypes.c_int, [_P, _U64P]),
+    "de_fetch_ibl_bc6h_dds": (ctypes.c_int, [_P, _P, ctypes.c_uint64]),
+    "de_debug_bc6h_encode": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DeIblBc6h), _P, ctypes.c_uint64]),
+    "de_debug_ibl_bc6h": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.POINTER(DePanorama), ctypes.POINTER(DeIbl), ctypes.POINTER(DeIblBc6h), _P, _P, _P, _P, ctypes.c_uint64]),
+}
+
 # look LUTs: include/digital_earth_look.h (same library, additions only; not part of the binder's header)
 LOOK_SYMBOLS = {
     "de_set_look": (ctypes.c_int, [_P, ctypes.POINTER(DeLook), _P, _P]),
@@ -497,7 +512,7 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()) + list(RGBE_SYMBOLS.items()) + list(IBL_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DEBUG_SYMBOLS.items()) + list(DENOISE_SYMBOLS.items()) + list(EXPOSURE_SYMBOLS.items()) + list(BLOOM_SYMBOLS.items()) + list(HISTORY_SYMBOLS.items()) + list(PIXELS_SYMBOLS.items()) + list(LOCAL_EXPOSURE_SYMBOLS.items()) + list(OUTPUT_SCALE_SYMBOLS.items()) + list(HDR_OUTPUT_SYMBOLS.items()) + list(VIDEO_SYMBOLS.items()) + list(LOOK_SYMBOLS.items()) + list(JPEG_SYMBOLS.items()) + list(PNG_SYMBOLS.items()) + list(EXR_SYMBOLS.items()) + list(EXR_AOV_SYMBOLS.items()) + list(PANORAMA_SYMBOLS.items()) + list(ENVIRONMENT_SYMBOLS.items()) + list(RGBE_SYMBOLS.items()) + list(IBL_SYMBOLS.items()) + list(IBL_BC6H_SYMBOLS.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -10,7 +10,7 @@ OUT = os.path.join(_HERE, "libdigitalearth_hip.so")
 OUT_LEGACY = os.path.join(_HERE, "libdigitalearth_hip_legacy.so")
 SOURCES = ["de_api.hip", "de_fast.hip"]   # de_fast.hip: render_kernel_v6 once more, on the hardware transcendentals (DE_FLAG_FAST_MATH).  de_api.hip is one translation unit: de_api.hip -> de_display.h -> de_fetch.h, de_rccl.h -> de_launch.h -> de_host_consts.h -> de_context.h -> de_memory.h, the kernels (each statement of the integrator over pt_leaves.h); de_fast.hip -> de_stages.h -> pt_leaves.h, render_kernel_v6.hip
 DEPS = ["de_api.hip", "de_fast.hip", "de_rccl.h", "de_display.h", "de_fetch.h", "display_source.h", "pyramid.h", "pack.h", "hdr_pack.h", "de_launch.h", "de_host_consts.h", "de_context.h", "de_memory.h", "pt_leaves.h", "render_kernel.hip", "render_kernel_v2.hip", "de_stages.h", "render_kernel_v6.hip",
-        "aux_kernels.hip", "adaptive_kernels.hip", "denoise_kernels.hip", "exposure_kernels.hip", "bloom_kernels.hip", "history_kernels.hip", "pixels_kernels.hip", "local_exposure_kernels.hip", "output_scale_kernels.hip", "panorama_kernels.hip", "panorama_body.h", "environment_kernels.hip", "environment_body.h", "hdr_output_kernels.hip", "videoframe_kernels.hip", "look_kernels.hip", "jpeg_kernels.hip", "jpeg_tables.h", "coded_stream.h", "png_kernels.hip", "png_tables.h", "png_deflate.h", "exr_kernels.hip", "exr_tables.h", "rgbe_kernels.hip", "rgbe_tables.h", "ibl_kernels.hip", "ibl_body.h", "ibl_tables.h", "de_kernels.h", "de_device.h", "de_math.h", os.path.join("..", "..", "include", "digital_earth.h"),
+        "aux_kernels.hip", "adaptive_kernels.hip", "denoise_kernels.hip", "exposure_kernels.hip", "bloom_kernels.hip", "history_kernels.hip", "pixels_kernels.hip", "local_exposure_kernels.hip", "output_scale_kernels.hip", "panorama_kernels.hip", "panorama_body.h", "environment_kernels.hip", "environment_body.h", "hdr_output_kernels.hip", "videoframe_kernels.hip", "look_kernels.hip", "jpeg_kernels.hip", "jpeg_tables.h", "coded_stream.h", "png_kernels.hip", "png_tables.h", "png_deflate.h", "exr_kernels.hip", "exr_tables.h", "rgbe_kernels.hip", "rgbe_tables.h", "ibl_kernels.hip", "ibl_body.h", "ibl_tables.h", "bc6h_kernels.hip", "bc6h_body.h", "bc6h_tables.h", "de_kernels.h", "de_device.h", "de_math.h", os.path.join("..", "..", "include", "digital_earth.h"),
         os.path.join("..", "..", "include", "digital_earth_debug.h"), os.path.join("..", "..", "include", "digital_earth_denoise.h"),
         os.path.join("..", "..", "include", "digital_earth_exposure.h"), os.path.join("..", "..", "include", "digital_earth_bloom.h"),
         os.path.join("..", "..", "include", "digital_earth_history.h"), os.path.join("..", "..", "include", "digital_earth_pixels.h"),
@@ -18,7 +18,7 @@ DEPS = ["de_api.hip", "de_fast.hip", "de_rccl.h", "de_display.h", "de_fetch.h", 
         os.path.join("..", "..", "include", "digital_earth_hdr_output.h"), os.path.join("..", "..", "include", "digital_earth_video.h"),
         os.path.join("..", "..", "include", "digital_earth_look.h"), os.path.join("..", "..", "include", "digital_earth_jpeg.h"),
         os.path.join("..", "..", "include", "digital_earth_png.h"), os.path.join("..", "..", "include", "digital_earth_exr.h"), os.path.join("..", "..", "include", "digital_earth_exr_aovs.h"),
-        os.path.join("..", "..", "include", "digital_earth_panorama.h"), os.path.join("..", "..", "include", "digital_earth_environment.h"), os.path.join("..", "..", "include", "digital_earth_rgbe.h"), os.path.join("..", "..", "include", "digital_earth_ibl.h")]
+        os.path.join("..", "..", "include", "digital_earth_panorama.h"), os.path.join("..", "..", "include", "digital_earth_environment.h"), os.path.join("..", "..", "include", "digital_earth_rgbe.h"), os.path.join("..", "..", "include", "digital_earth_ibl.h"), os.path.join("..", "..", "include", "digital_earth_ibl_bc6h.h")]
 DEPS_LEGACY = DEPS + [os.path.join("legacy", f) for f in ("render_kernel_v1.hip", "render_kernel_v3.hip", "render_kernel_v5.hip", "de_launch_legacy.h", "de_ctx_legacy_members.inc")]
 # -ffp-contract=off is part of the arithmetic contract (de_math.h): fused operations only where written.
 # -fno-slp-vectorize: the SLP vectoriser packs pairs of scalar f32 operations into v_pk_* instructions; on gfx950 the

@@ -1897,6 +1897,7 @@ int de_set_ibl(de_ctx* c, const de_ibl* s) {
     { int rc = ibl_settings_check(s); if (rc) return rc; }
     c->ibl = *s;
     c->ibl_built = false;
+    c->ibl_bc6h_made = false;
     return DE_OK;
 }
 int de_get_ibl(de_ctx* c, de_ibl* out) {
@@ -1910,6 +1911,7 @@ int de_ibl_build(de_ctx* c) {
     if (c->env_mask != 63u) return fail(DE_ERR_STATE, "fewer than six linear faces are captured (de_environment_capture)");
     HIP_TRY(hipSetDevice(c->device));
     c->ibl_built = false;
+    c->ibl_bc6h_made = false;
     int rc = ibl_run(c->stream, c->ibl_work, c->pano_consts, c->W, c->env_faces, c->ibl);
     if (rc) return rc;
     c->ibl_built = true;
@@ -1963,6 +1965,126 @@ int de_debug_ibl(de_ctx* c, const float* faces, int n, const de_panorama* p, con
         rc = ibl_copy_out(c->stream, levels + ibl_level_offset(s->edge, l), ibl_level_block(work, s->edge, l), floats * sizeof(float));
     }
     if (!rc && dds) rc = ibl_dds_out(c->stream, work, *s, dds);
+    return rc;
+}
+
+/* ---- the IBL output, compressed: include/digital_earth_ibl_bc6h.h (bc6h_kernels.hip, bc6h_body.h, bc6h_tables.h) */
+namespace {
+int bc6h_settings_check(const de_ibl_bc6h* s) {
+    if (s->struct_bytes != (uint32_t)sizeof(de_ibl_bc6h)) return fail(DE_ERR_INVALID, "de_ibl_bc6h.struct_bytes does not match this library's struct");
+    if (const char* fault = bc6h_settings_fault(s->on, s->quality)) return fail(DE_ERR_INVALID, fault);
+    return DE_OK;
+}
+// the launch's offset table: `images` images per face, `faces` faces
+void bc6h_args_finish(Bc6hArgs* a, uint32_t images, uint32_t faces, uint8_t* out) {
+    a->images = images; a->first[0] = 0u;
+    for (uint32_t m = 0; m < images; ++m) a->first[m + 1] = a->first[m] + ((a->w[m] + 3u) / 4u) * ((a->h[m] + 3u) / 4u);
+    a->per_face = a->first[images]; a->total = a->per_face * faces; a->out = out;
+}
+// every block of the launch, one launch
+void bc6h_launch(hipStream_t stream, const Bc6hArgs& a, int quality) {
+    if (quality == 0) hipLaunchKernelGGL(bc6h_q0_kernel, dim3((a.total + BC6H_Q0_GROUP_BLOCKS - 1u) / BC6H_Q0_GROUP_BLOCKS), dim3(BC6H_THREADS), 0, stream, a);
+    else hipLaunchKernelGGL(bc6h_q1_kernel, dim3((a.total + BC6H_Q1_GROUP_BLOCKS - 1u) / BC6H_Q1_GROUP_BLOCKS), dim3(BC6H_THREADS), 0, stream, a);
+}
+// the chain held in `w` (after ibl_run) -> w.bc6h, waited for
+int bc6h_run(hipStream_t stream, de_ctx::IblWork& w, const de_ibl& s, int quality) {
+    int rc = w.bc6h.ensure(bc6h_payload_bytes(s.edge, s.levels), "the BC6H blocks");
+    if (rc) return rc;
+    Bc6hArgs a = {};
+    for (int l = 0; l < s.levels; ++l) { a.src[l] = ibl_level_block(w, s.edge, l); a.w[l] = a.h[l] = (uint32_t)(s.edge >> l); }
+    bc6h_args_finish(&a, (uint32_t)s.levels, 6u, w.bc6h.get());
+    bc6h_launch(stream, a, quality);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    return DE_OK;
+}
+int bc6h_dds_out(hipStream_t stream, const de_ctx::IblWork& w, const de_ibl& s, void* out) {
+    bc6h_dds_header(s.edge, s.levels, (uint8_t*)out);
+    return ibl_copy_out(stream, (uint8_t*)out + IBL_DDS_HEADER, w.bc6h, bc6h_payload_bytes(s.edge, s.levels));
+}
+}  // namespace
+int de_set_ibl_bc6h(de_ctx* c, const de_ibl_bc6h* s) {
+    if (!c || !s) return fail(DE_ERR_INVALID, "null argument");
+    { int rc = bc6h_settings_check(s); if (rc) return rc; }
+    c->ibl_bc6h = *s;
+    c->ibl_bc6h_made = false;
+    return DE_OK;
+}
+int de_get_ibl_bc6h(de_ctx* c, de_ibl_bc6h* out) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    *out = c->ibl_bc6h;
+    return DE_OK;
+}
+int de_ibl_bc6h_file_bytes(de_ctx* c, uint64_t* bytes) {
+    if (!c || !bytes) return fail(DE_ERR_INVALID, "null argument");
+    *bytes = (uint64_t)IBL_DDS_HEADER + (uint64_t)bc6h_payload_bytes(c->ibl.edge, c->ibl.levels);
+    return DE_OK;
+}
+int de_fetch_ibl_bc6h_dds(de_ctx* c, void* out, uint64_t out_bytes) {
+    if (!c || !out) return fail(DE_ERR_INVALID, "null argument");
+    if (out_bytes < (uint64_t)IBL_DDS_HEADER + (uint64_t)bc6h_payload_bytes(c->ibl.edge, c->ibl.levels)) return fail(DE_ERR_INVALID, "out_bytes is smaller than the file (de_ibl_bc6h_file_bytes)");
+    if (!c->ibl_bc6h.on) return fail(DE_ERR_STATE, "the BC6H stage is off (de_set_ibl_bc6h)");
+    if (!c->ibl_built) return fail(DE_ERR_STATE, "no IBL product is held (de_ibl_build)");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->ibl_bc6h_made) {
+        int rc = bc6h_run(c->stream, c->ibl_work, c->ibl, c->ibl_bc6h.quality);
+        if (rc) return rc;
+        c->ibl_bc6h_made = true;
+    }
+    return bc6h_dds_out(c->stream, c->ibl_work, c->ibl, out);
+}
+/* The encoder alone on a host-given image.  Buffers of its own; the arguments and the settings are checked before the context is read. */
+int de_debug_bc6h_encode(de_ctx* c, const float* rgb, int w, int h, const de_ibl_bc6h* s, void* blocks, uint64_t bytes) {
+    if (!c || !rgb || !s || !blocks || w < 1 || h < 1 || w > 16384 || h > 16384) return fail(DE_ERR_INVALID, "bad arguments (an image of 1 ... 16384 texels a side)");
+    { int rc = bc6h_settings_check(s); if (rc) return rc; }
+    const size_t need = (size_t)((w + 3) / 4) * (size_t)((h + 3) / 4) * 16;
+    if (bytes < (uint64_t)need) return fail(DE_ERR_INVALID, "bytes is smaller than the blocks (16 ceil(w / 4) ceil(h / 4))");
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<float> d_image;
+    Dev<uint8_t> d_blocks;
+    StreamWait wait{c->stream};
+    int rc = debug_upload(c->stream, d_image, rgb, (size_t)w * (size_t)h * 3 * sizeof(float));
+    if (!rc) rc = d_blocks.ensure(need, "the BC6H blocks");
+    if (rc) return rc;
+    Bc6hArgs a = {};
+    a.src[0] = d_image; a.w[0] = (uint32_t)w; a.h[0] = (uint32_t)h;
+    bc6h_args_finish(&a, 1u, 1u, d_blocks.get());
+    bc6h_launch(c->stream, a, s->quality);
+    HIP_TRY(hipGetLastError());
+    return ibl_copy_out(c->stream, blocks, d_blocks, need);
+}
+/* de_debug_ibl with the compressed file out, and the half integers the blocks encode. */
+int de_debug_ibl_bc6h(de_ctx* c, const float* faces, int n, const de_panorama* p, const de_ibl* s, const de_ibl_bc6h* b, float* sh, float* levels, uint16_t* half_levels, void* dds, uint64_t dds_bytes) {
+    if (!c || !faces || !p || !s || !b || n < 4 || n > 16384) return fail(DE_ERR_INVALID, "bad arguments (faces of 4 ... 16384 pixels a side)");
+    { int rc = pano_settings_check(p, n); if (rc) return rc; }
+    { int rc = ibl_settings_check(s); if (rc) return rc; }
+    { int rc = bc6h_settings_check(b); if (rc) return rc; }
+    if (dds && dds_bytes < (uint64_t)IBL_DDS_HEADER + (uint64_t)bc6h_payload_bytes(s->edge, s->levels)) return fail(DE_ERR_INVALID, "dds_bytes is smaller than the file");
+    HIP_TRY(hipSetDevice(c->device));
+    Dev<float> d_faces;
+    de_ctx::IblWork work;
+    PanoArgs k = {};
+    pano_make_consts(*p, n, &k);
+    StreamWait wait{c->stream};
+    int rc = debug_upload(c->stream, d_faces, faces, (size_t)DE_PANO_FACES * (size_t)n * (size_t)n * 3 * sizeof(float));
+    if (!rc) rc = ibl_run(c->stream, work, k, n, d_faces, *s);
+    if (!rc && sh) rc = ibl_copy_out(c->stream, sh, work.sh, 27 * sizeof(float));
+    const size_t all = ibl_level_offset(s->edge, s->levels);
+    std::vector<float> held;
+    if (!rc && (levels || half_levels)) {
+        float* to = levels;
+        if (!to) { held.resize(all); to = held.data(); }
+        for (int l = 0; !rc && l < s->levels; ++l) {
+            const size_t floats = (size_t)(s->edge >> l) * (size_t)(s->edge >> l) * 18;
+            rc = ibl_copy_out(c->stream, to + ibl_level_offset(s->edge, l), ibl_level_block(work, s->edge, l), floats * sizeof(float));
+        }
+        for (size_t i = 0; !rc && half_levels && i < all; ++i) {      // TEXEL TO HALF, on the host: the same two functions the kernel calls
+            const uint32_t h = exr_half_bits(exr_sample_bits(to[i], 1.0f));
+            half_levels[i] = (uint16_t)((h & 0x8000u) ? 0u : h);
+        }
+    }
+    if (!rc && dds) rc = bc6h_run(c->stream, work, *s, b->quality);
+    if (!rc && dds) rc = bc6h_dds_out(c->stream, work, *s, dds);
     return rc;
 }
 

@@ -18,6 +18,7 @@
 #include "../../include/digital_earth_environment.h"
 #include "../../include/digital_earth_rgbe.h"
 #include "../../include/digital_earth_ibl.h"
+#include "../../include/digital_earth_ibl_bc6h.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -58,6 +59,7 @@
 #include "exr_kernels.hip"
 #include "rgbe_kernels.hip"
 #include "ibl_kernels.hip"
+#include "bc6h_kernels.hip"
 
 namespace {
 
@@ -325,10 +327,13 @@ struct de_ctx {
     // (level 0 is the base level), the specular levels 1 ... L - 1, the levels' sample tables, the solid angles, the SH partials and result, the DDS payload.
     struct IblWork {
         Dev<float> mips, spec, omega, partial, sh; Dev<IblSample> tab; Dev<uint8_t> payload;
+        Dev<uint8_t> bc6h;      // the BC6H blocks of the chain (digital_earth_ibl_bc6h.h): empty until the first de_fetch_ibl_bc6h_dds after a build
     };
     de_ibl ibl = {(uint32_t)sizeof(de_ibl), 128, 6, 256, 2, 0.0f, DE_EXR_PIXEL_HALF};
     bool ibl_built = false;         // ibl_work holds the product of `ibl` (dropped by de_set_ibl)
     IblWork ibl_work;
+    de_ibl_bc6h ibl_bc6h = {(uint32_t)sizeof(de_ibl_bc6h), 0, 0};      // include/digital_earth_ibl_bc6h.h, DESIGN.md §29
+    bool ibl_bc6h_made = false;     // ibl_work.bc6h holds the blocks of the product and of `ibl_bc6h` (dropped by de_ibl_build, de_set_ibl, de_set_ibl_bc6h)
     // HDR display output (include/digital_earth_hdr_output.h).  The constants of the settings are computed by de_set_hdr_output and travel in
     // the kernel's arguments.  Allocated on first use: the packed pixels on the device and one pinned staging buffer, each out_w * out_h * 6 bytes (either
     // format fits: de_set_hdr_output frees nothing); re-allocated when a new output size needs more.  No ring.

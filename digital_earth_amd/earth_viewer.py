@@ -184,7 +184,7 @@ def _rgb_picture(px):
 class EarthViewer:
     """earth_viewer.py:166-318, headless."""
 
-    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, look=None, look_strength=1.0, exr_aovs=(), panorama=None, **renderer_kwargs):
+    def __init__(self, config=None, screen_res=SCREEN_RES, history=None, local_exposure=None, output_res=None, output_filter="lanczos3", hdr_output=None, look=None, look_strength=1.0, exr_aovs=(), panorama=None, ibl_bc6h=None, **renderer_kwargs):
         """history: None / False (off), True (Renderer.set_history's defaults) or a dict of its keywords — the picture then survives camera moves
         in frame()'s loop instead of restarting at one sample per pixel.  local_exposure: the same for Renderer.set_local_exposure — every frame is
         dodged and burned on the GPU ahead of the display transform.  output_res: None, or the (width, height) at which frames are delivered and
@@ -197,7 +197,9 @@ class EarthViewer:
         save("x.exr"), frame(exr=True) and record("f%05d.exr") write beside B, G, R (Renderer.set_exr's aovs).
         panorama: None / False, True (Renderer.set_panorama's defaults: a 4 N x 2 N equirectangular frame) or a dict of its keywords — screen_res must
         be square, (N, N), and the vignette is turned off (it would print every face's border); frame(panorama=True) then renders the six cube faces around the camera and hands out the 360° frame, and save() and
-        record() write it through the writers as they are."""
+        record() write it through the writers as they are.
+        ibl_bc6h: None / False, True (Renderer.set_ibl_bc6h's defaults: quality 0) or a dict of its keywords — save("x.dds") and
+        frame(panorama=True, ibl=True) then deliver the IBL cube map as BC6H_UF16 blocks (Renderer.fetch_ibl_bc6h_dds) instead of half floats."""
         self.window = None
         self.camera = Camera(self.window, up=UP_DIR)
         self.renderer = Renderer(image_res=screen_res, up=UP_DIR, **renderer_kwargs)
@@ -218,6 +220,8 @@ class EarthViewer:
         if panorama:
             self.renderer.vignette_strength = 0.0      # a vignette would darken every face's border: a capture under one is refused
             self.renderer.set_panorama(**(panorama if isinstance(panorama, dict) else {}))
+        if ibl_bc6h:
+            self.renderer.set_ibl_bc6h(True, **(ibl_bc6h if isinstance(ibl_bc6h, dict) else {}))
         self.config = None
         if config is not None:
             self.load_config(config)
@@ -340,7 +344,7 @@ class EarthViewer:
         frame = None
         if ibl:
             r.build_ibl()
-            frame = r.fetch_ibl_dds()
+            frame = r.fetch_ibl_bc6h_dds() if r.ibl_bc6h["on"] else r.fetch_ibl_dds()
         elif rgbe:
             frame = r.fetch_rgbe(copy=copy, lag=int(pipelined))
         elif exr:
@@ -549,7 +553,7 @@ class EarthViewer:
         if path.endswith(".dds") and r.panorama["on"] and len(r.environment["captured"]) == 6:
             r.build_ibl()
             with open(path, "wb") as f:
-                f.write(r.fetch_ibl_dds())
+                f.write(r.fetch_ibl_bc6h_dds() if r.ibl_bc6h["on"] else r.fetch_ibl_dds())
             return
         if path.endswith(".hdr") and r.rgbe_is_set:
             if r.current_spp == 0 and not (r.panorama["on"] and len(r.environment["captured"]) == 6):

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _native, luts, textures as tex
-from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DeRgbe, DeIbl, DigitalEarthError, check
+from ._native import DeParams, DeCounters, DeAdaptive, DeDenoise, DeAutoExposure, DeMetering, DeBloom, DeHistory, DePixels, DeOutputScale, DePanorama, DeLocalExposure, DeHdrOutput, DeVideo, DeLook, DeJpeg, DePng, DeExr, DeRgbe, DeIbl, DeIblBc6h, DigitalEarthError, check
 
 # Default luminance floor of the adaptive noise test (accumulate_adaptive), in HDR units (per-pixel mean of the color_buffer sums).  Measured on the MI355X
 # with tools/adaptive_price.py --luminance (the four BASELINE views at a quarter of their size, 64 spp; profiles/adaptive.md): the Rec.709 luminance of the
@@ -1575,6 +1575,69 @@ class Renderer:
             out.append(flat[at:at + 18 * e * e].reshape(6, e, e, 3).copy())
             at += 18 * e * e
         return sh, out, dds.raw
+
+    # ------------------------------------------------------------------ IBL output, BC6H-compressed (include/digital_earth_ibl_bc6h.h)
+    @staticmethod
+    def _ibl_bc6h_settings(on, quality):
+        s = DeIblBc6h()
+        s.struct_bytes, s.on, s.quality = ctypes.sizeof(DeIblBc6h), 1 if on else 0, int(quality)
+        return s
+
+    def set_ibl_bc6h(self, on=True, quality=0):
+        """The BC6H stage of the IBL output: with it on, fetch_ibl_bc6h_dds() delivers the cube chain as BC6H_UF16 blocks, 1 byte per texel.  quality
+        0: mode 11 alone; 1: the 32 two-region partitions as well.  Every other fetch is unchanged.  Drops the blocks of an earlier fetch."""
+        s = self._ibl_bc6h_settings(on, quality)
+        check(self._lib.de_set_ibl_bc6h(self._h, ctypes.byref(s)))
+
+    @property
+    def ibl_bc6h(self):
+        """The BC6H stage's settings as a dict (set_ibl_bc6h's keywords) plus file_bytes, the compressed file's length under the IBL settings."""
+        s, n = DeIblBc6h(), ctypes.c_uint64()
+        check(self._lib.de_get_ibl_bc6h(self._h, ctypes.byref(s)))
+        check(self._lib.de_ibl_bc6h_file_bytes(self._h, ctypes.byref(n)))
+        return dict(on=bool(s.on), quality=int(s.quality), file_bytes=int(n.value))
+
+    def fetch_ibl_bc6h_dds(self):
+        """The product of build_ibl() as one DDS cube map file of BC6H_UF16 blocks (`bytes`): digital_earth_amd.bc6h.read opens it again."""
+        n = self.ibl_bc6h["file_bytes"]
+        out = ctypes.create_string_buffer(n)
+        check(self._lib.de_fetch_ibl_bc6h_dds(self._h, out, ctypes.c_uint64(n)))
+        return out.raw
+
+    def debug_bc6h_encode(self, image, quality=0):
+        """The encoder alone on an (h, w, 3) float32 image, any h, w >= 1 (de_debug_bc6h_encode): ceil(w / 4) ceil(h / 4) blocks as `bytes`, rows of
+        blocks top first.  The renderer's own settings and product are not touched."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError("image must have shape (h, w, 3)")
+        s = self._ibl_bc6h_settings(True, quality)
+        n = 16 * ((image.shape[1] + 3) // 4) * ((image.shape[0] + 3) // 4)
+        out = ctypes.create_string_buffer(max(n, 1))
+        check(self._lib.de_debug_bc6h_encode(self._h, image.ctypes.data, int(image.shape[1]), int(image.shape[0]), ctypes.byref(s), out, ctypes.c_uint64(n)))
+        return out.raw[:n]
+
+    def debug_ibl_bc6h(self, faces, quality=0, apron=1, basis=None, edge=16, levels=5, samples=8, supersample=1, lod_bias=0.0):
+        """debug_ibl() with the compressed file out (de_debug_ibl_bc6h).  Returns (sh (3, 9), levels, half_levels, dds): levels[l] is (6, e, e, 3)
+        float32, half_levels[l] the same texels as uint16 half integers 0 ... 0x7BFF — what the blocks of dds encode."""
+        faces = np.ascontiguousarray(faces, dtype=np.float32)
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[1] != faces.shape[2] or faces.shape[3] != 3:
+            raise ValueError("faces must have shape (6, n, n, 3)")
+        p = self._panorama_settings((16, 8), "equirect", 180.0, apron, 1, basis, True)
+        s = self._ibl_settings(edge, levels, samples, supersample, lod_bias, "half")
+        b = self._ibl_bc6h_settings(True, quality)
+        edges = [max(int(edge) >> l, 0) for l in range(max(int(levels), 0))]
+        total = max(sum(18 * e * e for e in edges), 1)
+        flat, halves = np.empty(total, dtype=np.float32), np.empty(total, dtype=np.uint16)
+        n = 148 + 96 * sum(max(1, e // 4) ** 2 for e in edges)
+        sh, dds = np.empty((3, 9), dtype=np.float32), ctypes.create_string_buffer(n)
+        check(self._lib.de_debug_ibl_bc6h(self._h, faces.ctypes.data, int(faces.shape[1]), ctypes.byref(p), ctypes.byref(s), ctypes.byref(b), sh.ctypes.data, flat.ctypes.data,
+                                          halves.ctypes.data, dds, ctypes.c_uint64(n)))
+        out, out_half, at = [], [], 0
+        for e in edges:
+            out.append(flat[at:at + 18 * e * e].reshape(6, e, e, 3).copy())
+            out_half.append(halves[at:at + 18 * e * e].reshape(6, e, e, 3).copy())
+            at += 18 * e * e
+        return sh, out, out_half, dds.raw
 
     # ------------------------------------------------------------------ look LUTs (include/digital_earth_look.h, DESIGN.md §19)
     LOOK_INTERPOLATIONS = ("trilinear", "tetrahedral")
